@@ -23,10 +23,15 @@ the observations (k_gram; its cost decides accept/reject), trial sums + decision
 k_reduce_system, [all-reduce], the (12C)^2 reduced camera solve (k_solve_cam).  Every step linearises its trial
 point, accepted or not (never less work than a real iteration).
 
-`value` is the MEDIAN of `--windows` (default 5) timed regions of exactly `--steps` steps each -- every region bracketed by barrier +
-synchronize on both sides and reduced by MAX over the ranks; all of them are printed (`value_windows`).
+Exactly `--steps` steps are timed, split into `--windows` regions (default 1) -- every region bracketed by barrier + synchronize on
+both sides and reduced by MAX over the ranks.  `ms_per_step` = the summed region times / `--steps`; `value` follows from it; every
+region is printed as well (`value_windows`, `ms_per_step_windows`).
 
-Extra objects on the same line: `roofline` (dominant kernel of the timed region, HIP-event timed on the launch stream;
+`--dump-outputs DIR` writes what the last timed step computed -- the current parameter vector (`x.npy`, float64, 12 C + 6 F) and its
+cost (`cost.npy`) -- so that two builds can be compared output for output: the inputs are seeded, identical from run to run.
+
+Extra objects on the same line (the line stays a few KB: the per-config tables and the end-to-end / calibrate() breakdowns go to
+`--details FILE` in full, the line keeps their headline figures): `roofline` (dominant kernel of the timed region, HIP-event timed on the launch stream;
 `bound` names the binding roof), `jacobian_eval` (BASELINE's second figure: ms per materialised Jacobian-eval, with its own
 HBM roofline), `cpu_baseline` (the oracle's scipy path on a bounded sample of the same workload, rank 0 at N = 1 only), `configs` (all
 five BASELINE configs, per iteration), `end_to_end` / `end_to_end_other_shapes` (wall time of the calls users make: `bundle_adjust()`,
@@ -444,6 +449,19 @@ def other_configs(m, headline_ms_per_step):
     return out
 
 
+def result_line(out):
+    """The printed record: `out` without the bulky tables (the driver parses one line of bounded length), their headline figures kept."""
+    line = {k: v for k, v in out.items() if k not in ("configs", "end_to_end", "end_to_end_other_shapes")}
+    if "configs" in out:
+        line["configs_us_per_iteration"] = {k: v["us_per_iteration"] for k, v in out["configs"].items() if isinstance(v, dict)}
+    if "end_to_end" in out:
+        keys = ("ms", "calibrate_ms", "pipeline_ms")
+        line["end_to_end_summary_ms"] = {"%d x %d x %d" % (C, out["config"]["frames_rank0"], ROWS * COLS): {k: out["end_to_end"][k] for k in keys if k in out["end_to_end"]},
+                                         **{shape: {k: o[k] for k in keys if k in o} for shape, o in out.get("end_to_end_other_shapes", {}).items()}}
+    line["details"] = "--details FILE: the full record" if "configs" in out or "end_to_end" in out else None
+    return line
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -473,14 +491,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=5, help="timed regions of --steps steps each; `value` = the median window (all are printed)")
+    ap.add_argument("--windows", type=int, default=1, help="timed regions the --steps steps are split into (each printed); `value` / `ms_per_step` cover all of them")
     ap.add_argument("--frames", type=int, default=F_PER_GPU, help="frames per GPU, weak scaling (default = BASELINE config 3 per GPU)")
     ap.add_argument("--frames-total", type=int, default=0, help="strong scaling: this many frames of ONE rig sharded over the ranks (100000 = BASELINE configs[3])")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the wall-clock measurement of the user-level bundle_adjust() call")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the per-iteration times of BASELINE configs[0] and configs[1]")
     ap.add_argument("--prewarm", type=int, default=300, help="untimed clock-ramp iterations of a throw-away solve before the W warm-up steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (parameter vector, cost) as DIR/<name>.npy")
+    ap.add_argument("--details", metavar="FILE", default=None, help="write the full record (per-config tables, end-to-end and calibrate() breakdowns) as JSON to FILE; "
+                    "the printed line keeps their headline figures only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -561,32 +584,41 @@ def main():
     DOMINANT = "k_gram"
     prob.profile_enable(True, only=[DOMINANT], stride=8)  # every 8th launch: the event records must not pace the stream
     prob.profile_read()
-    # `--windows` timed regions of EXACTLY `--steps` steps each, every one bracketed by barrier + synchronize on both sides and reduced by MAX
-    # over the ranks; `value` comes from the MEDIAN window, all of them are printed (a single 2 ms window at the driver's --steps 20 is one
-    # sample of a box's clock state, not a measurement)
+    # EXACTLY `--steps` timed steps, split into `--windows` regions (default one); every region is bracketed by barrier + synchronize on
+    # both sides and reduced by MAX over the ranks.  `value` / `ms_per_step` = all timed steps over the summed region times; each region
+    # is printed as well.
+    window_steps = [len(w) for w in np.array_split(np.arange(args.steps), max(1, min(args.windows, args.steps)))]
     window_dts, ticks = [], 0
-    for _w in range(max(1, args.windows)):
+    for wsteps in window_steps:
         barrier()
         nfev0 = lm.nfev
         t0 = time.perf_counter()
         wticks = 0
-        while lm.nfev - nfev0 < args.steps:
+        while lm.nfev - nfev0 < wsteps:
             # a step = an LM iteration that evaluated (and linearised) a trial point.  Frame-sharded runs with one collective
             # per iteration occasionally need an extra rebuild-only pass (mispredicted damping): it is timed, not counted.
             status = lm.iterate(always_linearize=True)
             wticks += 1
             assert status is None, f"the LM loop stopped inside the timed region (status {status})"
-            assert wticks <= 2 * args.steps, "too many rebuild-only passes"
+            assert wticks <= 2 * wsteps, "too many rebuild-only passes"
         barrier()
         dtw = time.perf_counter() - t0
-        assert lm.nfev - nfev0 == args.steps, f"{lm.nfev - nfev0} trial evaluations in {args.steps} timed steps"
+        assert lm.nfev - nfev0 == wsteps, f"{lm.nfev - nfev0} trial evaluations in {wsteps} timed steps"
         if dist is not None:
             tmax = torch.tensor([dtw], dtype=torch.float64, device="cpu" if backend == "gloo" else f"cuda:{local_rank}")
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dtw = float(tmax.item())
         window_dts.append(dtw)
         ticks += wticks
-    dt = float(np.median(window_dts))
+    dt = float(sum(window_dts))
+    if args.dump_outputs:
+        # what the last timed step computed: the current point (result.x of the LM loop; the slot the posted state names -- a tick still
+        # in flight writes the other slot) and its cost.  Ranks > 0 hold other frame shards: their vectors get their own file.
+        prob.synchronize()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "x.npy" if world == 1 else f"x_rank{rank}.npy"), np.asarray(prob.get_params(lm.cur), dtype=np.float64))
+        if rank == 0:
+            np.save(os.path.join(args.dump_outputs, "cost.npy"), np.array([lm.cost], dtype=np.float64))
     prof_timed = prob.profile_read()
     prob.profile_enable(True)
     for _ in range(min(args.steps, 50)):
@@ -719,9 +751,10 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": 1e3 * dt / args.steps,
             "windows": len(window_dts),
-            "value_windows": [(args.steps * units / w) if scaling == "weak" else (args.steps / w) for w in window_dts],
-            "ms_per_step_windows": [1e3 * w / args.steps for w in window_dts],
-            "value_is": "the median of the windows",
+            "value_windows": [(n * units / w) if scaling == "weak" else (n / w) for n, w in zip(window_steps, window_dts)],
+            "ms_per_step_windows": [1e3 * w / n for n, w in zip(window_steps, window_dts)],
+            "steps_windows": window_steps,
+            "value_is": "all timed steps over the summed time of the windows",
             "higher_is_better": True,
             "scaling": scaling,
             "vs_baseline": None,
@@ -776,7 +809,10 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
             out["cpu_baseline"]["reference_measured_in_survey_container"] = {"value": 0.0098, "unit": "it/s", "ms_per_jacobian_eval": 68679, "source": "BASELINE.md section 2 (the reference itself, 6x10kx54)"}
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
+        if args.details:
+            with open(args.details, "w") as fh:
+                json.dump(out, fh)
+        os.write(json_fd, (json.dumps(result_line(out)) + "\n").encode())
     prob.close()
     if dist is not None:
         dist.barrier()

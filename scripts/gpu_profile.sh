@@ -11,7 +11,7 @@ OUT=gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ "$PART" = "all" ] || [ "$PART" = "a" ]; then
-python3 bench.py --no-cpu-baseline > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 bench.py --no-cpu-baseline --details $OUT/${TAG}_bench_details.json > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 echo "bench done"
 # (--no-other-configs: the headline tick alone -- configs[0] runs the same k_syrk / k_solve_backsub instances at a tenth of the size and would be averaged in)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -- python3 bench.py --no-cpu-baseline --no-end-to-end --no-other-configs > $OUT/${TAG}_stats_bench.json 2> $OUT/${TAG}_stats.err
