@@ -52,7 +52,7 @@ typedef struct mcba_handle mcba_handle;
 typedef struct mcba_buffer mcba_buffer;   /* a device array that outlives its handle (mcba_residuals_detach) */
 
 /* ---- library ------------------------------------------------------------------------------- */
-int mcba_abi_version(void);            /* 7.  Bumped when this header changes: 7 (round 6) ADDS the mcba_calib_* (incl. mcba_calib_start, mcba_calib_graph) / mcba_pose_* / mcba_create_views block below (calibrate() on the device) and leaves every ABI-6 entry point as it was; 6 (round 5) ADDED mcba_prefilter, mcba_prefilter_subset, mcba_lm_run, mcba_lm_history, mcba_lm_result, mcba_set_bounds / _frozen, mcba_set_loss_table, mcba_set_trial, mcba_calib_normal_equations (and the diagnostics / life-cycle helpers declared below as ABI 6) and leaves every
+int mcba_abi_version(void);            /* 7.  Bumped when this header changes (the mcba_flat_* block at the end is ADDITIVE to ABI 7: new entry points only, none changed): 7 (round 6) ADDS the mcba_calib_* (incl. mcba_calib_start, mcba_calib_graph) / mcba_pose_* / mcba_create_views block below (calibrate() on the device) and leaves every ABI-6 entry point as it was; 6 (round 5) ADDED mcba_prefilter, mcba_prefilter_subset, mcba_lm_run, mcba_lm_history, mcba_lm_result, mcba_set_bounds / _frozen, mcba_set_loss_table, mcba_set_trial, mcba_calib_normal_equations (and the diagnostics / life-cycle helpers declared below as ABI 6) and leaves every
                                         * ABI-5 entry point as it was.  (ABI 5 gave LM-state slots 25 / 26 -- "reserved" before -- their meaning: curvature floor / switch
                                         * fraction; a caller that zeroes them gets the handle's floor, fixed.) */
 const char* mcba_last_error(void);
@@ -468,6 +468,25 @@ const char* mcba_profile_names(void);
  * against it next to the datasheet peak (the reference has no counterpart: its arithmetic is numpy / scipy on the host). */
 int mcba_fp64_issue_rate(int device, double* tflops);
 int mcba_synchronize(mcba_handle* h);
+
+/* ---- floor-plane alignment (reference flatibration.py; additive to ABI 7) -------------------------------
+ * Stateless, like mcba_triangulate: host arrays in and out, one upload per call.  kernel_ms (may be NULL) receives the time of
+ * the call's kernels measured with HIP events. */
+#define MCBA_FLAT_MAX_HYPOTHESES 128   /* RANSAC hypotheses per mcba_flat_ransac call (sklearn's default max_trials is 100) */
+#define MCBA_FLAT_MAX_KEYPOINTS 2048   /* keypoints per frame of mcba_flat_floor_points (a frame is staged whole in LDS) */
+/* keypoints (F, K, 3) -> points_out (F, 3) = per frame the keypoint of smallest z (largest if z_points_down), index_out (F) ints or NULL:
+ * np.argmin / np.argmax semantics (first index on ties, the first NaN wins, an all-NaN frame gives 0). */
+int mcba_flat_floor_points(size_t n_frames, int n_keypoints, const double* keypoints, int z_points_down, int device, double* points_out, int* index_out, double* kernel_ms);
+/* points (n, 3); planes (H, 3) = (a, b, c) of z = a x + b y + c; inlier = |z - (x a + y b + c)| <= threshold.  counts_out (H) = exact inlier
+ * counts; moments_out (H, 9) = over the inliers, with dx = x - shift2[0], dy = y - shift2[1], r = the residual: sums of dx dy r dx^2 dx.dy dy^2
+ * dx.r dy.r r^2, reduced in a fixed order (bitwise reproducible for a given n).  mask_out (n bytes, needs H == 1) or NULL. */
+int mcba_flat_ransac(size_t n_points, const double* points, int n_hypotheses, const double* planes, double threshold, const double* shift2, int device,
+                     unsigned long long* counts_out, double* moments_out, unsigned char* mask_out, double* kernel_ms);
+/* points (n, 3) mapped by rt12 (R row-major 3x3, then t): x' = R p + t.  values_out (2, n_ranks) = the exact order statistics (0-based ranks,
+ * at most 8) of x' and y' (radix select on the device, no sort); sums_out (2) = sums of x' and y'; nans_out (2) = NaN counts of x' and y'
+ * (the order statistics of a coordinate that holds a NaN are meaningless). */
+int mcba_flat_order_stats(size_t n_points, const double* points, const double* rt12, int n_ranks, const long long* ranks, int device, double* values_out, double* sums_out,
+                          unsigned long long* nans_out, double* kernel_ms);
 
 #ifdef __cplusplus
 }

@@ -457,6 +457,11 @@ static int derive_geometry(mcba_handle* h) {
   return MCBA_OK;
 }
 
+// for the other translation units of the library (mcba_flat.hip): set the message mcba_last_error() returns
+namespace mcba {
+int set_error(int code, const std::string& msg) { g_err = msg; return code; }
+}  // namespace mcba
+
 extern "C" {
 
 int mcba_abi_version(void) { return 7; }  // 7 (round 6): calibrate() on the device (mcba_calib_*, mcba_pose_*, mcba_create_views); 6 (round 5): mcba_prefilter, mcba_lm_run / _history / _result -- whole stages of bundle_adjust() per crossing; additions only: every ABI-5 entry point is unchanged
