@@ -16,17 +16,11 @@
 //
 // Moments of the inliers of hypothesis h, in a per-call shift (sx, sy) for x, y and in the hypothesis' own residual r = z - (a x + b y + c)
 // for z (inliers have |r| <= threshold, so nothing cancels): X = sum dx, Y = sum dy, R = sum r, XX, XY, YY, XR, YR, RR.
-#include <hip/hip_runtime.h>
-#include <math.h>
 #include <stdint.h>
-#include <string.h>
-#include <string>
-#include <vector>
 
-#include "../../include/mcba.h"
+#include "mcba_handle.h"
 
 namespace mcba {
-int set_error(int code, const std::string& msg);  // mcba_api.hip: the message mcba_last_error() returns
 
 constexpr int kFlatThreads = 256;
 constexpr int kFloorLdsDoubles = 6144;  // 48 KiB of staged frames per block
@@ -281,133 +275,82 @@ __global__ void k_select_values(const SelState* __restrict__ st, int Q, double* 
 
 }  // namespace mcba
 
-namespace {
-
-int flat_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return mcba::set_error(MCBA_ERR_NODEVICE, "no HIP device visible");
-  if (device < 0 || device >= ndev) return mcba::set_error(MCBA_ERR_ARG, "device ordinal out of range");
-  if (hipSetDevice(device) != hipSuccess) return mcba::set_error(MCBA_ERR_HIP, "hipSetDevice failed");
-  return MCBA_OK;
-}
-
-// the device buffers and events of one call, released on every path out
-struct FlatCall {
-  std::vector<void*> bufs;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~FlatCall() {
-    for (void* b : bufs) (void)hipFree(b);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-  template <class T>
-  hipError_t alloc(T** p, size_t count) {
-    void* v = nullptr;
-    hipError_t e = hipMalloc(&v, count * sizeof(T) > 0 ? count * sizeof(T) : 16);
-    if (e == hipSuccess) bufs.push_back(v);
-    *p = static_cast<T*>(v);
-    return e;
-  }
-  hipError_t start() {
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
-    return e;
-  }
-  hipError_t stop(double* kernel_ms) {
-    hipError_t e = hipEventRecord(e1, nullptr);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    if (e == hipSuccess && kernel_ms) {
-      float ms = 0.f;
-      e = hipEventElapsedTime(&ms, e0, e1);
-      *kernel_ms = ms;
-    }
-    return e;
-  }
-};
-
-#define FLATCHK(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return mcba::set_error(MCBA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-}  // namespace
+using namespace mcba_internal;
 
 extern "C" {
 
 int mcba_flat_floor_points(size_t n_frames, int n_keypoints, const double* keypoints, int z_points_down, int device, double* points_out, int* index_out, double* kernel_ms) {
   if (n_keypoints < 1 || n_keypoints > MCBA_FLAT_MAX_KEYPOINTS || !keypoints || !points_out)
-    return mcba::set_error(MCBA_ERR_ARG, "mcba_flat_floor_points: 1 .. MCBA_FLAT_MAX_KEYPOINTS keypoints per frame, non-NULL arrays required");
-  if (int rc = flat_device(device)) return rc;
+    return fail(MCBA_ERR_ARG, "mcba_flat_floor_points: 1 .. MCBA_FLAT_MAX_KEYPOINTS keypoints per frame, non-NULL arrays required");
+  if (int rc = stateless_device(device)) return rc;
   if (n_frames == 0) return MCBA_OK;
   const int K = n_keypoints;
   int fpb = mcba::kFloorLdsDoubles / (3 * K);
   fpb = fpb > mcba::kFlatThreads ? mcba::kFlatThreads : fpb;
-  FlatCall call;
+  StatelessCall call;
   double *d_kp = nullptr, *d_out = nullptr;
   int* d_idx = nullptr;
   const size_t nin = n_frames * 3 * (size_t)K;
-  FLATCHK(call.alloc(&d_kp, nin));
-  FLATCHK(call.alloc(&d_out, 3 * n_frames));
-  FLATCHK(call.alloc(&d_idx, n_frames));
-  FLATCHK(hipMemcpy(d_kp, keypoints, nin * sizeof(double), hipMemcpyHostToDevice));
-  FLATCHK(call.start());
+  HIPCHK(call.alloc(&d_kp, nin));
+  HIPCHK(call.alloc(&d_out, 3 * n_frames));
+  HIPCHK(call.alloc(&d_idx, n_frames));
+  HIPCHK(hipMemcpy(d_kp, keypoints, nin * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(call.start());
   const size_t nblk = (n_frames + fpb - 1) / fpb;
   mcba::k_floor_points<<<dim3((unsigned)nblk), dim3(mcba::kFlatThreads), (size_t)fpb * 3 * K * sizeof(double)>>>(d_kp, n_frames, K, fpb, z_points_down ? 1 : 0, d_out, d_idx);
-  FLATCHK(hipGetLastError());
-  FLATCHK(call.stop(kernel_ms));
-  FLATCHK(hipMemcpy(points_out, d_out, 3 * n_frames * sizeof(double), hipMemcpyDeviceToHost));
-  if (index_out) FLATCHK(hipMemcpy(index_out, d_idx, n_frames * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipGetLastError());
+  HIPCHK(call.stop(kernel_ms));
+  HIPCHK(hipMemcpy(points_out, d_out, 3 * n_frames * sizeof(double), hipMemcpyDeviceToHost));
+  if (index_out) HIPCHK(hipMemcpy(index_out, d_idx, n_frames * sizeof(int), hipMemcpyDeviceToHost));
   return MCBA_OK;
 }
 
 int mcba_flat_ransac(size_t n_points, const double* points, int n_hypotheses, const double* planes, double threshold, const double* shift2, int device,
                      unsigned long long* counts_out, double* moments_out, unsigned char* mask_out, double* kernel_ms) {
   if (n_points < 1 || !points || n_hypotheses < 1 || n_hypotheses > MCBA_FLAT_MAX_HYPOTHESES || !planes || !shift2 || !counts_out || !moments_out)
-    return mcba::set_error(MCBA_ERR_ARG, "mcba_flat_ransac: points >= 1, 1 .. MCBA_FLAT_MAX_HYPOTHESES hypotheses, non-NULL arrays required");
-  if (mask_out && n_hypotheses != 1) return mcba::set_error(MCBA_ERR_ARG, "mcba_flat_ransac: the inlier mask needs exactly one hypothesis");
-  if (int rc = flat_device(device)) return rc;
+    return fail(MCBA_ERR_ARG, "mcba_flat_ransac: points >= 1, 1 .. MCBA_FLAT_MAX_HYPOTHESES hypotheses, non-NULL arrays required");
+  if (mask_out && n_hypotheses != 1) return fail(MCBA_ERR_ARG, "mcba_flat_ransac: the inlier mask needs exactly one hypothesis");
+  if (int rc = stateless_device(device)) return rc;
   const int H = n_hypotheses;
   const size_t nblk = (n_points + mcba::kScorePoints - 1) / mcba::kScorePoints;
-  FlatCall call;
+  StatelessCall call;
   double *d_pts = nullptr, *d_planes = nullptr, *d_pm = nullptr, *d_mom = nullptr;
   unsigned* d_pn = nullptr;
   unsigned long long* d_cnt = nullptr;
   unsigned char* d_mask = nullptr;
-  FLATCHK(call.alloc(&d_pts, 3 * n_points));
-  FLATCHK(call.alloc(&d_planes, 3 * (size_t)H));
-  FLATCHK(call.alloc(&d_pm, nblk * H * mcba::kMom));
-  FLATCHK(call.alloc(&d_pn, nblk * H));
-  FLATCHK(call.alloc(&d_mom, (size_t)H * mcba::kMom));
-  FLATCHK(call.alloc(&d_cnt, (size_t)H));
-  if (mask_out) FLATCHK(call.alloc(&d_mask, n_points));
-  FLATCHK(hipMemcpy(d_pts, points, 3 * n_points * sizeof(double), hipMemcpyHostToDevice));
-  FLATCHK(hipMemcpy(d_planes, planes, 3 * (size_t)H * sizeof(double), hipMemcpyHostToDevice));
-  FLATCHK(call.start());
+  HIPCHK(call.alloc(&d_pts, 3 * n_points));
+  HIPCHK(call.alloc(&d_planes, 3 * (size_t)H));
+  HIPCHK(call.alloc(&d_pm, nblk * H * mcba::kMom));
+  HIPCHK(call.alloc(&d_pn, nblk * H));
+  HIPCHK(call.alloc(&d_mom, (size_t)H * mcba::kMom));
+  HIPCHK(call.alloc(&d_cnt, (size_t)H));
+  if (mask_out) HIPCHK(call.alloc(&d_mask, n_points));
+  HIPCHK(hipMemcpy(d_pts, points, 3 * n_points * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_planes, planes, 3 * (size_t)H * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(call.start());
   mcba::k_ransac_score<<<dim3((unsigned)nblk), dim3(mcba::kFlatThreads)>>>(d_pts, n_points, d_planes, H, threshold, shift2[0], shift2[1], d_pm, d_pn);
-  FLATCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   mcba::k_ransac_finish<<<dim3((unsigned)H), dim3(mcba::kFlatThreads)>>>(d_pm, d_pn, (int)nblk, H, d_mom, d_cnt);
-  FLATCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   if (mask_out) {
     mcba::k_ransac_mask<<<dim3((unsigned)((n_points + mcba::kFlatThreads - 1) / mcba::kFlatThreads)), dim3(mcba::kFlatThreads)>>>(d_pts, n_points, planes[0], planes[1], planes[2],
                                                                                                                             threshold, d_mask);
-    FLATCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
-  FLATCHK(call.stop(kernel_ms));
-  FLATCHK(hipMemcpy(counts_out, d_cnt, (size_t)H * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  FLATCHK(hipMemcpy(moments_out, d_mom, (size_t)H * mcba::kMom * sizeof(double), hipMemcpyDeviceToHost));
-  if (mask_out) FLATCHK(hipMemcpy(mask_out, d_mask, n_points, hipMemcpyDeviceToHost));
+  HIPCHK(call.stop(kernel_ms));
+  HIPCHK(hipMemcpy(counts_out, d_cnt, (size_t)H * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(moments_out, d_mom, (size_t)H * mcba::kMom * sizeof(double), hipMemcpyDeviceToHost));
+  if (mask_out) HIPCHK(hipMemcpy(mask_out, d_mask, n_points, hipMemcpyDeviceToHost));
   return MCBA_OK;
 }
 
 int mcba_flat_order_stats(size_t n_points, const double* points, const double* rt12, int n_ranks, const long long* ranks, int device, double* values_out, double* sums_out,
                           unsigned long long* nans_out, double* kernel_ms) {
   if (n_points < 1 || !points || !rt12 || n_ranks < 0 || 2 * n_ranks > mcba::kMaxQueries || (n_ranks && (!ranks || !values_out)) || !sums_out || !nans_out)
-    return mcba::set_error(MCBA_ERR_ARG, "mcba_flat_order_stats: points >= 1, 0 .. 8 ranks, non-NULL arrays required");
+    return fail(MCBA_ERR_ARG, "mcba_flat_order_stats: points >= 1, 0 .. 8 ranks, non-NULL arrays required");
   for (int i = 0; i < n_ranks; ++i)
-    if (ranks[i] < 0 || (unsigned long long)ranks[i] >= n_points) return mcba::set_error(MCBA_ERR_ARG, "mcba_flat_order_stats: rank out of range");
-  if (int rc = flat_device(device)) return rc;
+    if (ranks[i] < 0 || (unsigned long long)ranks[i] >= n_points) return fail(MCBA_ERR_ARG, "mcba_flat_order_stats: rank out of range");
+  if (int rc = stateless_device(device)) return rc;
   const size_t n = n_points;
   const size_t nblk = (n + mcba::kFlatThreads - 1) / mcba::kFlatThreads;
   const int Q = 2 * n_ranks;
@@ -418,43 +361,43 @@ int mcba_flat_order_stats(size_t n_points, const double* points, const double* r
       st.coord[c * n_ranks + i] = c;
       st.rank[c * n_ranks + i] = (unsigned long long)ranks[i];
     }
-  FlatCall call;
+  StatelessCall call;
   double *d_pts = nullptr, *d_rt = nullptr, *d_ps = nullptr, *d_val = nullptr;
   unsigned long long *d_keys = nullptr, *d_nan = nullptr;
   unsigned* d_hist = nullptr;
   mcba::SelState* d_st = nullptr;
-  FLATCHK(call.alloc(&d_pts, 3 * n));
-  FLATCHK(call.alloc(&d_rt, 12));
-  FLATCHK(call.alloc(&d_keys, 2 * n));
-  FLATCHK(call.alloc(&d_ps, 2 * nblk));
-  FLATCHK(call.alloc(&d_nan, 2));
-  FLATCHK(call.alloc(&d_hist, (size_t)mcba::kMaxQueries * 256));
-  FLATCHK(call.alloc(&d_st, 1));
-  FLATCHK(call.alloc(&d_val, (size_t)mcba::kMaxQueries));
-  FLATCHK(hipMemcpy(d_pts, points, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-  FLATCHK(hipMemcpy(d_rt, rt12, 12 * sizeof(double), hipMemcpyHostToDevice));
-  FLATCHK(hipMemcpy(d_st, &st, sizeof(st), hipMemcpyHostToDevice));
-  FLATCHK(hipMemset(d_nan, 0, 2 * sizeof(unsigned long long)));
-  FLATCHK(hipMemset(d_hist, 0, (size_t)mcba::kMaxQueries * 256 * sizeof(unsigned)));
-  FLATCHK(call.start());
+  HIPCHK(call.alloc(&d_pts, 3 * n));
+  HIPCHK(call.alloc(&d_rt, 12));
+  HIPCHK(call.alloc(&d_keys, 2 * n));
+  HIPCHK(call.alloc(&d_ps, 2 * nblk));
+  HIPCHK(call.alloc(&d_nan, 2));
+  HIPCHK(call.alloc(&d_hist, (size_t)mcba::kMaxQueries * 256));
+  HIPCHK(call.alloc(&d_st, 1));
+  HIPCHK(call.alloc(&d_val, (size_t)mcba::kMaxQueries));
+  HIPCHK(hipMemcpy(d_pts, points, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_rt, rt12, 12 * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_st, &st, sizeof(st), hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(d_nan, 0, 2 * sizeof(unsigned long long)));
+  HIPCHK(hipMemset(d_hist, 0, (size_t)mcba::kMaxQueries * 256 * sizeof(unsigned)));
+  HIPCHK(call.start());
   mcba::k_flat_transform<<<dim3((unsigned)nblk), dim3(mcba::kFlatThreads)>>>(d_pts, n, d_rt, d_keys, d_ps, d_nan);
-  FLATCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   if (Q > 0) {
     const unsigned hblk = (unsigned)(nblk < 2048 ? nblk : 2048);  // grid-stride beyond 2048 blocks: fewer global histogram flushes
     for (int pass = 0; pass < 8; ++pass) {
       mcba::k_select_hist<<<dim3(hblk), dim3(mcba::kFlatThreads)>>>(d_keys, n, d_st, Q, pass, d_hist);
-      FLATCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
       mcba::k_select_pick<<<dim3(1), dim3(64)>>>(d_st, Q, d_hist);
-      FLATCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
     }
     mcba::k_select_values<<<dim3(1), dim3(64)>>>(d_st, Q, d_val);
-    FLATCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
-  FLATCHK(call.stop(kernel_ms));
+  HIPCHK(call.stop(kernel_ms));
   std::vector<double> ps(2 * nblk);
-  FLATCHK(hipMemcpy(ps.data(), d_ps, 2 * nblk * sizeof(double), hipMemcpyDeviceToHost));
-  FLATCHK(hipMemcpy(nans_out, d_nan, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  if (Q > 0) FLATCHK(hipMemcpy(values_out, d_val, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ps.data(), d_ps, 2 * nblk * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(nans_out, d_nan, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (Q > 0) HIPCHK(hipMemcpy(values_out, d_val, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost));
   for (int c = 0; c < 2; ++c) {  // the per-block sums, in block order
     double s = 0.0;
     for (size_t b = 0; b < nblk; ++b) s += ps[2 * b + c];

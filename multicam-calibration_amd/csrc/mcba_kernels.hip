@@ -1697,8 +1697,6 @@ void launch_gram(hipStream_t st, int loss, double f_scale, const double* obs_t, 
   if (split == 5) {  // whole rounds of the wavefront slots fused, the short last round point-split
     const int fba5 = gram_round_blocks(C, nfb, slots);
     if (fba5 > 0 && fba5 < nfb) {
-      static const bool two_launches = [] { const char* e = getenv("MCBA_GRAM_MIXED"); return e && atoi(e) == 0; }();  // (0: the two-launch form, for A/B)
-      if (two_launches) { fused(0, fba5); psplit(fba5, nfb); return; }
       const int per = npw == 4 ? 1 : 2, nf = (fba5 + 3) / 4, nt = (nfb - fba5 + per - 1) / per;
       const size_t lds = gram_psplit_lds_bytes(npw == 4 ? 4 : 2, 12);
       const bool fast = planar && f_scale == 1.0;
@@ -1775,13 +1773,12 @@ size_t syrk_lds_bytes(int C, int FS, int cw) {
 #define SYRK_IPT 5  // (12C+1)*FS <= 256*SYRK_IPT is guaranteed by the choice of FS in mcba_create
 #define SYRK_IPT_SMALL 3
 
-static bool g_syrk_xcd_remap = [] { const char* e = getenv("MCBA_SYRK_XCD"); return !e || atoi(e) != 0; }();  // (0: the plain (G, groups) launch, for A/B)
 void launch_syrk(hipStream_t st, Sel s, const SyrkFuse& fz, const double* rec0, const double* rec1, double* fbuf, double* fpart, const int* tile_i, const int* tile_j, double* spart, int C, int F, int Fpad, int NT, int NP, int G, int sq, int sr, int FS, int ppw,
                  const double* dscale, int cw) {
   size_t lds = syrk_lds_bytes(C, FS, cw);
 #define SYRK_GO(PPW, IPT, GY, CWV)                                                                                                                              \
   do {                                                                                                                                                          \
-    const bool remap = (GY) > 1 && g_syrk_xcd_remap;                                                                                                            \
+    const bool remap = (GY) > 1;                                                                                                                                \
     dim3 grid(remap ? 8 * ((G / 8) * (GY) + ((G % 8) * (GY) + 7) / 8) : G, remap ? 1 : (GY));                                                                   \
     const int xg = remap ? G : 0, yg = remap ? (GY) : 0;                                                                                                        \
     if (fz.decide && dscale) k_syrk<PPW, IPT, true, true, CWV><<<grid, dim3(256), lds, st>>>(s, fz, rec0, rec1, fbuf, fpart, tile_i, tile_j, spart, C, F, Fpad, NT, NP, sq, sr, FS, dscale, xg, yg);    \

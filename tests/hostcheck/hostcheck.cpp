@@ -134,7 +134,7 @@ void hc_lm_decide(double* lms, const double* trial8, double lam_min, double lam_
 
 // ---- calibrate()'s per-view arithmetic (csrc/mcba_pnp_math.h, the text k_pnp is made of), one view at a time, as one GPU lane runs it
 // (the kernel's wave-uniform loops "until no lane is left" become plain loops here)
-static void board_norm(const double* obj, int N, double* bn) {   // mcba_api.hip: board_normalisation
+static void board_norm(const double* obj, int N, double* bn) {   // mcba_calib_api.hip: board_normalisation
   bn[0] = bn[1] = 0.0; bn[2] = 1.0;
   for (int p = 0; p < N; ++p) { bn[0] += obj[3 * p]; bn[1] += obj[3 * p + 1]; }
   bn[0] /= N; bn[1] /= N;
