@@ -61,6 +61,20 @@ int mcba_device_count(int* count);
 /* ---- problem life cycle -------------------------------------------------------------------- */
 /* n_cameras C, n_frames F (local shard), n_points N, HIP device ordinal. */
 int mcba_create(mcba_handle** out, int n_cameras, int n_frames, int n_points, int device);
+/* The sparse-Schur handle (ADDITIVE to ABI 7): any number of cameras -- mcba_create refuses more than 40.  The Schur reduction runs over the
+ * camera pairs that share a frame (a visibility index built from the observations on first use after an upload), the reduced system is
+ * factorised by a stream-ordered sequence of multi-workgroup launches, and the reduce buffer keeps the dense layout.  Every entry point of
+ * this header that takes a handle works on it, except: the speculative reduction (mcba_lm_auto_reduce(h, 2, .)) and the solve that decides
+ * (mcba_lm_auto_solve(h, ., 1)) return MCBA_ERR_ARG -- its frame-sharded ticks take two collectives; calibrate()'s mcba_calib_* calls
+ * return MCBA_ERR_ARG on a handle of more than 40 cameras (their kernels hold at most 40).  mcba_is_sparse: 1 for such a handle, 0 otherwise. */
+int mcba_create_sparse(mcba_handle** out, int n_cameras, int n_frames, int n_points, int device);
+int mcba_is_sparse(const mcba_handle* h);
+/* Its visibility index, computed on the host from a (C, F) mask (seen[c * F + f] != 0: camera c has a detection in frame f); needs no
+ * device.  sizes[4]: entries (seen pairs), co-visible camera pairs, pair-frame items, chunks.  out (NULL: sizes only), `capacity` ints:
+ * frame_off (F + 1) | ent_cam (entries, frame-major, cameras ascending) | ent_frame | items (3 per item: entry of camera i, entry of camera
+ * j, frame; pairs (i <= j) in (i, j) order, frames ascending) | chunks (3 per chunk of <= 64 items: first item, count, i == j) |
+ * pair_map (C x C: pair id of (i, j), i <= j, or -1) | pair_chunks (pairs + 1: each pair's first chunk). */
+int mcba_sparse_index(const unsigned char* seen, int n_cameras, int n_frames, int* sizes, int* out, size_t capacity);
 int mcba_destroy(mcba_handle* h);
 /* Device and pinned buffers of destroyed handles are parked in a per-process pool and handed out again (hipMalloc / hipFree are
  * synchronising driver calls: 4 ms of a 16 ms bundle_adjust() at 6 x 10 000 x 54 before the pool).  MCBA_POOL_MB caps what is

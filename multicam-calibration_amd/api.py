@@ -133,7 +133,7 @@ class _JacobianSource:
             if prob is None:   # the handle was released under pressure: a new one from the values it held
                 if self.host_uvs is None:
                     raise RuntimeError("result.jac: the GPU handle of this result was released and no copy of its observations was kept")
-                prob = self.prob = ops.Problem(self.host_uvs, self.obj, device=self.device, loss=self.loss, f_scale=self.f_scale)
+                prob = self.prob = ops.Problem(self.host_uvs, self.obj, device=self.device, loss=self.loss, f_scale=self.f_scale, schur="sparse" if self.host_uvs.shape[0] > 40 else "dense")
                 prob.set_params(0, self.x)
                 slot = 0
             m = self.mask(prob)
@@ -389,6 +389,7 @@ def bundle_adjust(all_calib_uvs, all_extrinsics, all_intrinsics, calib_objpoints
     fix_intrinsics = opt_kwargs.pop("fix_intrinsics", False)
     return_jac = opt_kwargs.pop("return_jac", True)
     lm_kwargs = {k: opt_kwargs.pop(k) for k in ("lam0", "dec_floor", "reduced_solver", "curvature") if k in opt_kwargs}
+    schur = opt_kwargs.pop("schur", None)
 
     kw = dict(verbose=2, x_scale="jac", ftol=1e-4, method="trf", loss="soft_l1")
     kw.update(opt_kwargs)
@@ -401,6 +402,12 @@ def bundle_adjust(all_calib_uvs, all_extrinsics, all_intrinsics, calib_objpoints
     calib_objpoints = np.asarray(calib_objpoints, dtype=np.float64)
     calib_poses = np.asarray(calib_poses, dtype=np.float64)
     n_cameras = all_calib_uvs.shape[0]
+    # the Schur reduction: the dense handle up to 40 cameras, the sparse-Schur handle (co-visible camera pairs, multi-workgroup solve) above;
+    # schur="sparse" forces it at any size, schur="dense" above 40 cameras fails as the dense handle does
+    if schur is None:
+        schur = "sparse" if n_cameras > 40 else "dense"
+    if schur not in ("dense", "sparse"):
+        raise ValueError("schur must be 'dense' or 'sparse'")
     # The kernels' camera model is (fx fy cx cy k1 k2) -- all the reference ever optimises (serialize_params drops the rest:
     # bundle_adjustment.py:149-155) -- but its PRE-FILTER projects with the full matrix (geometry.py:323: K @ p): a skew K[0,1] or a
     # non-trivial third row would select other frames there than here.  Refused rather than silently ignored.
@@ -410,7 +417,7 @@ def bundle_adjust(all_calib_uvs, all_extrinsics, all_intrinsics, calib_objpoints
             raise ValueError(f"camera {c}: the camera matrix must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (skew / a general third row are not supported by the GPU solver; "
                              "the reference's pre-filter would honour them, geometry.py:323)")
 
-    pkw = {}
+    pkw = {"schur": schur} if schur == "sparse" else {}
     if distributed:
         import torch
 

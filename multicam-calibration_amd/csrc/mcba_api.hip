@@ -143,6 +143,12 @@ static int derive_geometry(mcba_handle* h) {
   h->slots = slots;
   h->n = h->cw * C;
   h->nsys = (size_t)h->n * h->n + 3 * h->n + 16;
+  if (h->sparse) {
+    // sparse-Schur handle: no k_syrk tile grid and no one-workgroup solve; the frame factors run one workgroup per 64 frames (fpart pairs)
+    h->NT = h->NP = h->G = h->sq = h->sr = 0;
+    h->FS = 0;
+    h->ppw = 4;
+  } else {
   // k_syrk geometry: (12C + 1) rows of [Y ; z^T] padded to NT tiles of 16, NP tile pairs (ti <= tj);
   // FS frames per LDS stage (a divisor of 64; <= 96 KiB so that two workgroups fit a CU when C is small)
   h->NT = (h->n + 1 + 15) / 16;
@@ -174,6 +180,7 @@ static int derive_geometry(mcba_handle* h) {
       h->sr = 0;
       h->G = (nstage + h->sq - 1) / h->sq;
     }
+  }
   }
   h->nbblocks = h->Fpad / 64;
   // fused k_gram needs >= ~1 wavefront per SIMD (1024) to fill the chip; with fewer (camera, frame-block) pairs the
@@ -232,6 +239,11 @@ static int derive_geometry(mcba_handle* h) {
   h->nfblocks = h->G;  // (kept: k_syrk's workgroups factorise their own frames: one (max |g_f|, #failures) pair each)
   h->npad = 16 * h->NT;
   h->solve_lds = mcba::solve_fits_lds(h->npad, h->lds_optin);
+  if (h->sparse) {
+    h->nfblocks = h->nfb;
+    h->npad = mcba::sp_npad(h->n);
+    h->solve_lds = 0;
+  }
   return MCBA_OK;
 }
 
@@ -275,27 +287,31 @@ int ensure_solver(mcba_handle* h) {
   // 110 of the 116 MB at 6 x 10 000 x 54) sit behind the ones that start from zero and are not filled.
   if (!h->solver_arena) {
     struct Piece { double** p; size_t count; };
-    const size_t n_swork = h->solve_lds ? 16 : 2 * (size_t)h->npad * h->npad + 64 * (size_t)h->npad;  // two sets of 16 x 16 tiles of the lower triangle (mcba_solve.hip, right-looking variant)
+    size_t n_swork = h->solve_lds ? 16 : 2 * (size_t)h->npad * h->npad + 64 * (size_t)h->npad;  // two sets of 16 x 16 tiles of the lower triangle (mcba_solve.hip, right-looking variant)
+    if (h->sparse) n_swork = (size_t)h->npad * h->npad;   // the blocked solve's matrix (mcba_sparse.hip)
     Piece zeroed[] = {{&h->gpart2[0], (size_t)C * h->nfb * MCBA_GP}, {&h->gpart2[1], (size_t)C * h->nfb * MCBA_GP}, {&h->fbuf, (size_t)h->Fpad * MCBA_FB}, {&h->fpart, (size_t)2 * h->nfblocks},
                       {&h->cpart, (size_t)2 * C * h->nfb * h->nch}, {&h->bpart, (size_t)3 * h->nbblocks}, {&h->red_own, h->nsys + 8 + 2 * MCBA_LMS},
                       {&h->dcbuf, (size_t)h->n + 8},  // + the word k_solve_backsub's solve releases, + the poll-timeout stamp
-                      {&h->swork, n_swork}, {&h->dscale, h->nx}, {reinterpret_cast<double**>(&h->fixed), ((size_t)h->n + 7) / 8}};
+                      {&h->swork, n_swork}, {&h->dscale, h->nx}, {reinterpret_cast<double**>(&h->fixed), ((size_t)h->n + 7) / 8},
+                      {&h->sp_damp, h->sparse ? (size_t)h->npad : 0}, {&h->sp_y, h->sparse ? (size_t)h->npad : 0}, {reinterpret_cast<double**>(&h->sp_ctl), h->sparse ? (size_t)1 : 0}};
     Piece plain[] = {{&h->rec2[0], (size_t)h->Fpad * C * MCBA_REC}, {&h->rec2[1], (size_t)h->Fpad * C * MCBA_REC},
                      {&h->spart, (size_t)h->G * h->NP * 256 + 64},
                      {&h->gchunk, h->gram_split == 3 ? mcba::gram_chunk_doubles(C, h->nfb, h->gram_nchunk, h->slots) : 0}};
     auto padded = [](size_t count) { return (std::max<size_t>(count, 1) * sizeof(double) + 255) / 256 * 256; };
     size_t zero_bytes = 0, total = 0;
-    for (auto& pc : zeroed) zero_bytes += padded(pc.count);
+    for (auto& pc : zeroed) if (pc.count) zero_bytes += padded(pc.count);   // (the sparse-Schur pieces have count 0 on a dense handle: no bytes)
     total = zero_bytes;
     for (auto& pc : plain) if (pc.count) total += padded(pc.count);
     if ((rc = dalloc(h, &h->solver_arena, total, false)) != MCBA_OK) return rc;
     HIPCHK(hipMemsetAsync(h->solver_arena, 0, zero_bytes, h->stream));
     if (poison_byte()) HIPCHK(hipMemsetAsync(h->solver_arena + zero_bytes, poison_byte(), total - zero_bytes, h->stream));
     size_t off = 0;
-    for (auto& pc : zeroed) { *pc.p = reinterpret_cast<double*>(h->solver_arena + off); off += padded(pc.count); }
+    for (auto& pc : zeroed) if (pc.count) { *pc.p = reinterpret_cast<double*>(h->solver_arena + off); off += padded(pc.count); }
     for (auto& pc : plain) if (pc.count) { *pc.p = reinterpret_cast<double*>(h->solver_arena + off); off += padded(pc.count); }
   }
-  if (mcba::solve_set_lds_limit(h->npad, h->solve_lds) != 0) return fail(MCBA_ERR_HIP, "cannot raise the dynamic LDS limit of k_solve_cam");
+  if (h->sparse) {
+    h->sp_A = h->swork;
+  } else if (mcba::solve_set_lds_limit(h->npad, h->solve_lds) != 0) return fail(MCBA_ERR_HIP, "cannot raise the dynamic LDS limit of k_solve_cam");
   h->fuse_backsub = h->solve_lds != 0;
   if (const char* e = getenv("MCBA_FUSE_BACKSUB")) h->fuse_backsub = h->fuse_backsub && atoi(e) != 0;  // tuning knob
   // (a part whose LDS limit cannot be raised keeps the two-launch k_solve_cam + k_backsub path instead of failing)
@@ -312,12 +328,12 @@ int ensure_solver(mcba_handle* h) {
     if (hipHostGetDevicePointer(reinterpret_cast<void**>(&h->ring_dev), h->ring, 0) != hipSuccess) return fail(MCBA_ERR_HIP, "hipHostGetDevicePointer failed for the LM state ring");
   }
   h->red = h->red_own;
-  if ((rc = tile_tables(h->device, h->NT, &h->tile_i, &h->tile_j)) != MCBA_OK) return rc;
+  if (!h->sparse && (rc = tile_tables(h->device, h->NT, &h->tile_i, &h->tile_j)) != MCBA_OK) return rc;
   if (!h->pinned) {
     h->pinned_bytes = (h->nsys + 8 + MCBA_LMS + h->n) * sizeof(double);
     HIPCHK(pool_host_malloc(reinterpret_cast<void**>(&h->pinned), h->pinned_bytes, hipHostMallocDefault));
   }
-  size_t lds = mcba::syrk_lds_bytes(C, h->FS, h->cw);
+  size_t lds = h->sparse ? 0 : mcba::syrk_lds_bytes(C, h->FS, h->cw);
   if (lds > 64 * 1024) {
     if (mcba::syrk_set_lds_limit(lds) != 0) return fail(MCBA_ERR_HIP, "cannot raise the dynamic LDS limit of k_syrk");
   }
@@ -347,6 +363,7 @@ int upload_impl(mcba_handle* h, const double* uvs, const double* objpoints, bool
   if (const char* e = getenv("MCBA_GRAM_FAST")) { if (atoi(e) == 0) h->planar = 0; }  // development knob: the general instance
   h->have_obs = true;
   h->have_lin = h->have_red = h->have_jac = false;
+  h->sp_ready = false;
   return MCBA_OK;
 }
 
@@ -363,6 +380,10 @@ int trial_sum(mcba_handle* h, mcba::Sel sel, int la, int lb, const mcba::DecideA
 }
 
 int backsub_launch(mcba_handle* h, mcba::Sel sel, int la, int lb, int xa, int xb, const double* delta_cam) {
+  if (h->sparse && delta_cam) {  // (a camera step of more than 480 doubles does not fit the kernel arguments: it goes to the device buffer first)
+    HIPCHK(hipMemcpyAsync(h->dcbuf, delta_cam, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    delta_cam = nullptr;
+  }
   mcba::CamStep cs;
   if (delta_cam) memcpy(cs.v, delta_cam, h->n * sizeof(double));
   {
@@ -374,6 +395,10 @@ int backsub_launch(mcba_handle* h, mcba::Sel sel, int la, int lb, int xa, int xb
 }
 
 int syrk_launch(mcba_handle* h, mcba::Sel sel, const mcba::SyrkFuse& fz) {
+  if (h->sparse) {
+    if (fz.decide) return fail(MCBA_ERR_ARG, "sparse-Schur handle: the decision is not fused into the Schur reduction");
+    return sparse_build(h, sel);
+  }
   { Scope sc(h, K_SYRK); mcba::launch_syrk(h->stream, sel, fz, h->rec2[0], h->rec2[1], h->fbuf, h->fpart, h->tile_i, h->tile_j, h->spart, h->C, h->F, h->Fpad, h->NT, h->NP, h->G, h->sq, h->sr, h->FS, h->ppw, h->have_xscale ? h->dscale : nullptr, h->cw); }
   return check_launch();
 }
@@ -381,6 +406,7 @@ int syrk_launch(mcba_handle* h, mcba::Sel sel, const mcba::SyrkFuse& fz) {
 int reduce_launch(mcba_handle* h, mcba::Sel sel, int rank_slot, bool spec) {
   {
     Scope sc(h, K_REDUCE);
+    // (sparse-Schur handle: NP = 0 -- S0 and rhs were assembled by k_sp_assemble; this launch is the tail: diag U, g_c, the scalars)
     mcba::launch_reduce_system(h->stream, sel, h->gpart2[0], h->gpart2[1], h->spart, h->fpart, h->tile_i, h->tile_j, h->red, h->C, h->nfb, h->G, h->NT, h->NP, h->nfblocks, rank_slot,
                                spec ? h->bpart : nullptr, h->nbblocks, spec ? post_state(h) : nullptr, h->cw, spec ? timeout_word(h) : nullptr, (double)h->last_solve_seq);
   }
@@ -402,12 +428,16 @@ int mcba_device_count(int* count) {
   return MCBA_OK;
 }
 
-int mcba_create(mcba_handle** out, int C, int F, int N, int device) {
-  if (!out || C < 1 || F < 1 || N < 1) return fail(MCBA_ERR_ARG, "mcba_create: need cameras >= 1, frames >= 1, points >= 1");
-  if (C > 40) {
+}  // extern "C"
+
+namespace mcba_internal {
+int create_impl(mcba_handle** out, int C, int F, int N, int device, bool sparse) {
+  const char* who = sparse ? "mcba_create_sparse" : "mcba_create";
+  if (!out || C < 1 || F < 1 || N < 1) { g_err = std::string(who) + ": need cameras >= 1, frames >= 1, points >= 1"; return MCBA_ERR_ARG; }
+  if (!sparse && C > 40) {
     g_err = "mcba_create: " + std::to_string(C) + " cameras -- this build handles at most 40 per handle: the (12 C + 1)-row reduced camera system is factorised by ONE workgroup "
             "(k_solve_cam: tile tables, LDS and scratch are sized for 481 rows) and k_backsub takes the camera step through the kernel arguments (480 doubles); reduced_solver=\"host\" does not "
-            "lift it (the Schur product's tile grid has the same bound).  The reference has no such limit (scipy's sparse LSMR); split the rig, or calibrate the cameras in overlapping groups of <= 40";
+            "lift it (the Schur product's tile grid has the same bound).  The reference has no such limit (scipy's sparse LSMR); the sparse-Schur handle (mcba_create_sparse; ops.Problem(..., schur=\"sparse\"), bundle_adjust's default above 40 cameras) has none";
     return MCBA_ERR_ARG;
   }
   int ndev = 0;
@@ -416,6 +446,8 @@ int mcba_create(mcba_handle** out, int C, int F, int N, int device) {
   HIPCHK(hipSetDevice(device));
   mcba_handle* h = new mcba_handle();
   h->C = C; h->F = F; h->N = N; h->device = device;
+  h->sparse = sparse;
+  h->speculate = !sparse;   // (the sparse handle's frame-sharded ticks take two collectives: no speculative reduction)
   {  // the launch geometry below is derived from the device, not from MI355X constants (a part with fewer CUs or less LDS gets its own deal)
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
@@ -446,6 +478,16 @@ int mcba_create(mcba_handle** out, int C, int F, int N, int device) {
   *out = h;
   return MCBA_OK;
 }
+}  // namespace mcba_internal
+
+extern "C" {
+
+int mcba_create(mcba_handle** out, int C, int F, int N, int device) { return create_impl(out, C, F, N, device, false); }
+
+// The sparse-Schur handle: any number of cameras.  Every entry point of the dense handle that bundle_adjust() reaches works on it; the Schur
+// reduction runs over co-visible camera pairs (mcba_sparse.hip) and the reduced system is factorised by a sequence of multi-workgroup launches.
+int mcba_create_sparse(mcba_handle** out, int C, int F, int N, int device) { return create_impl(out, C, F, N, device, true); }
+int mcba_is_sparse(const mcba_handle* h) { return h && h->sparse ? 1 : 0; }
 
 int mcba_destroy(mcba_handle* h) {
   if (!h) return MCBA_OK;
@@ -498,6 +540,7 @@ int mcba_trim(mcba_handle* h) {
   // the pieces of the solver arena
   h->rec2[0] = h->rec2[1] = h->gpart2[0] = h->gpart2[1] = h->fbuf = h->fpart = h->spart = h->cpart = h->bpart = h->red_own = h->red = h->dcbuf = h->swork = h->dscale = h->gchunk = nullptr;
   h->fixed = nullptr;
+  sparse_forget(h);
   h->cal_out_cap = h->cal_rel_cap = h->cal_sel_cap = h->cal_views_cap = 0;
   h->have_cal_poses = false;
   h->have_solver = h->have_lin = h->have_red = h->have_spec = h->have_jac = h->auto_ready = h->have_xscale = h->have_fixed = h->trial_ready = false;
@@ -586,7 +629,7 @@ int mcba_set_camera_block(mcba_handle* h, int width) {
   if (width == h->cw) return MCBA_OK;
   // (any solver buffer, not just a complete set: a first attempt that ran out of memory part-way leaves buffers sized for the old width behind)
   if (h->have_solver || h->solver_arena) return fail(MCBA_ERR_ARG, "mcba_set_camera_block: call it before the first solver entry point of the handle");
-  if (width == 6) {
+  if (width == 6 && !h->sparse) {
     const int nt = (6 * h->C + 1 + 15) / 16;
     if (nt * (nt + 1) / 2 > 64) return fail(MCBA_ERR_ARG, "mcba_set_camera_block: more than 26 cameras -- hold the intrinsics with the flags of mcba_lm_auto_config instead");
   }

@@ -37,6 +37,9 @@ static void board_normalisation(const double* obj, int N, double* bn) {
 static int calib_ready(mcba_handle* h, const char* who) {
   if (!h) return fail(MCBA_ERR_ARG, "NULL handle");
   if (!h->have_obs || !h->obj_host) { g_err = std::string(who) + ": upload observations first"; return MCBA_ERR_ARG; }
+  // calibrate()'s kernels hold at most 40 cameras (k_pose_chain's LDS tables, the per-view kernels' camera masks); only a sparse-Schur
+  // handle can have more, and it serves bundle_adjust() alone
+  if (h->C > 40) { g_err = std::string(who) + ": " + std::to_string(h->C) + " cameras -- calibrate() on the device handles at most 40 (the sparse-Schur handle serves bundle_adjust only)"; return MCBA_ERR_ARG; }
   for (int p = 0; p < h->N; ++p)
     if (h->obj_host[3 * p + 2] != 0.0) { g_err = std::string(who) + ": the closed-form start needs a planar calibration board (z = 0)"; return MCBA_ERR_ARG; }
   HIPCHK(hipSetDevice(h->device));

@@ -631,8 +631,9 @@ __device__ __forceinline__ bool chol_solve8(double* A, double* b) {
   return ok;
 }
 
-struct DiagCams {   // distortion of every camera (the solver's parameter vector carries k1, k2 only)
+struct DiagCams {   // distortion of the cameras c0 .. c0 + 39 of one launch (the solver's parameter vector carries k1, k2 only)
   double dist[40][5];
+  int c0;
 };
 
 // lane = (camera c, frame f).  obs_t [C][N][Fpad]; x = parameter vector; board = objpoints (N,3), bn = {mean x, mean y, scale}
@@ -647,7 +648,7 @@ __global__ __launch_bounds__(256) void k_reproj_diag(const double2* __restrict__
                                                      double2* __restrict__ und, double* __restrict__ repro, double* __restrict__ trans, double* __restrict__ err, int C, int F, int N, int Fpad, int nfb, int iters,
                                                      int lm_iters) {
   __shared__ CamConst s_cam;
-  const int c = blockIdx.y;
+  const int c = dc.c0 + blockIdx.y;
   if (threadIdx.x == 0) make_cam_const(x + 12 * c, s_cam);
   __syncthreads();
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -661,7 +662,7 @@ __global__ __launch_bounds__(256) void k_reproj_diag(const double2* __restrict__
 #pragma unroll
   for (int i = 0; i < 3; ++i) tc[i] = diag_uni(s_cam.t[i]);
 #pragma unroll
-  for (int i = 0; i < 5; ++i) kd[i] = dc.dist[c][i];
+  for (int i = 0; i < 5; ++i) kd[i] = dc.dist[blockIdx.y][i];
   const double* pose = x + 12 * C + 6 * (size_t)f;
   double pz[6];
 #pragma unroll
@@ -971,11 +972,15 @@ void launch_undistort(hipStream_t st, const double* uv, double* out, size_t n, c
 
 void launch_reproj_diag(hipStream_t st, const double* obs_t, const double* obj, const double* x, const double* dist5, const double* bn, double* und, double* repro, double* trans, double* err, int C, int F, int N,
                         int Fpad, int iters, int lm_iters) {
-  DiagCams dc;
-  for (int c = 0; c < C; ++c)
-    for (int i = 0; i < 5; ++i) dc.dist[c][i] = dist5[5 * c + i];
   const int nfb = Fpad / 64;
-  k_reproj_diag<<<dim3((nfb + 3) / 4, C), dim3(256), 0, st>>>(reinterpret_cast<const double2*>(obs_t), obj, x, dc, bn, reinterpret_cast<double2*>(und), repro, trans, err, C, F, N, Fpad, nfb, iters, lm_iters);
+  for (int c0 = 0; c0 < C; c0 += 40) {   // (more than 40 cameras: the sparse-Schur handle -- one launch per group of 40)
+    const int nc = std::min(40, C - c0);
+    DiagCams dc;
+    dc.c0 = c0;
+    for (int c = 0; c < nc; ++c)
+      for (int i = 0; i < 5; ++i) dc.dist[c][i] = dist5[5 * (c0 + c) + i];
+    k_reproj_diag<<<dim3((nfb + 3) / 4, nc), dim3(256), 0, st>>>(reinterpret_cast<const double2*>(obs_t), obj, x, dc, bn, reinterpret_cast<double2*>(und), repro, trans, err, C, F, N, Fpad, nfb, iters, lm_iters);
+  }
 }
 
 }  // namespace mcba

@@ -19,8 +19,11 @@ namespace mcba_internal {
 
 extern thread_local std::string g_err;  // what mcba_last_error() returns (mcba_api.hip)
 
-enum KernelId { K_TRANSPOSE = 0, K_GRAM, K_COST, K_SYRK, K_REDUCE, K_BACKSUB, K_SUM_TRIAL, K_JACOBIAN, K_DECIDE, K_SOLVE, K_COUNT };
-constexpr const char* kKernelNames = "k_transpose_obs\nk_gram\nk_cost\nk_syrk\nk_reduce_system\nk_backsub\nk_sum_trial\nk_jacobian\nk_decide\nk_solve_cam";
+enum KernelId { K_TRANSPOSE = 0, K_GRAM, K_COST, K_SYRK, K_REDUCE, K_BACKSUB, K_SUM_TRIAL, K_JACOBIAN, K_DECIDE, K_SOLVE,
+                K_SP_FACTOR, K_SP_PAIRS, K_SP_SOLVE_PRE, K_SP_POTRF, K_SP_TRSM, K_SP_UPDATE, K_SP_FINISH, K_COUNT };
+// (sparse-Schur handle: k_sp_factor = k_sp_factor + k_sp_y, k_sp_pairs = k_sp_pairs + k_sp_assemble, k_sp_solve_pre = k_sp_solve_pre + k_sp_load)
+constexpr const char* kKernelNames = "k_transpose_obs\nk_gram\nk_cost\nk_syrk\nk_reduce_system\nk_backsub\nk_sum_trial\nk_jacobian\nk_decide\nk_solve_cam"
+                                     "\nk_sp_factor\nk_sp_pairs\nk_sp_solve_pre\nk_sp_potrf\nk_sp_trsm\nk_sp_update\nk_sp_finish";
 constexpr int kRing = 16;  // host-mapped LM state slots (device-resident loop): the host may run at most kRing - 1 ticks ahead
 
 struct EvRec { int kid; hipEvent_t a, b; };
@@ -115,6 +118,14 @@ struct mcba_handle {
   bool have_solver = false;        // solver buffers are allocated on first use (ensure_solver): a pre-filter handle never needs them
   size_t ring_bytes = 0, pinned_bytes = 0;
   unsigned ring_flags = 0;
+  // sparse-Schur handle (mcba_create_sparse; mcba_sparse_api.hip): the visibility index of the uploaded observations (built on first use
+  // after an upload), Y_cf of every seen (camera, frame), the pair-chunk sums, and the blocked solve's matrix, damping and control words
+  bool sparse = false, sp_ready = false;
+  int sp_nent = 0, sp_npairs = 0, sp_nchunks = 0;
+  int *sp_index = nullptr, *sp_frame_off = nullptr, *sp_ent_cam = nullptr, *sp_ent_frame = nullptr, *sp_items = nullptr, *sp_chunks = nullptr, *sp_pair_map = nullptr, *sp_pair_chunks = nullptr;
+  int* sp_ctl = nullptr;
+  double *sp_Y = nullptr, *sp_part = nullptr, *sp_A = nullptr, *sp_damp = nullptr, *sp_y = nullptr;
+  size_t sp_index_ints = 0, sp_Y_count = 0, sp_part_count = 0;
 };
 
 // a device array that outlives its handle (mcba_residuals_detach, mcba_lm_result)
@@ -249,6 +260,7 @@ struct StatelessCall {
 
 inline int slot_ok(const mcba_handle* h, int slot) { return h && (slot == 0 || slot == 1); }
 
+int create_impl(mcba_handle** out, int C, int F, int N, int device, bool sparse);   // mcba_create / mcba_create_sparse (mcba_api.hip)
 // solver buffers on first use (mcba_api.hip)
 int ensure_solver(mcba_handle* h);
 #define NEED_SOLVER(h) do { int rc_ = mcba_internal::ensure_solver(h); if (rc_) return rc_; } while (0)
@@ -271,5 +283,11 @@ int trial_sum(mcba_handle* h, mcba::Sel sel, int la, int lb, const mcba::DecideA
 int backsub_launch(mcba_handle* h, mcba::Sel sel, int la, int lb, int xa, int xb, const double* delta_cam);  // delta_cam NULL: the camera step on the device (dcbuf)
 int syrk_launch(mcba_handle* h, mcba::Sel sel, const mcba::SyrkFuse& fz);
 int reduce_launch(mcba_handle* h, mcba::Sel sel, int rank_slot, bool spec);   // spec: + the trial scalars and the pre-decision state copy
+
+// ---- the sparse-Schur handle (mcba_sparse_api.hip).  syrk_launch / reduce_launch / backsub_launch and the device-resident solve route here
+// when h->sparse: frame factors + co-visible pairs + assembly, the tail of k_reduce_system, the blocked solve.
+int sparse_build(mcba_handle* h, mcba::Sel sel);      // frame factors, Y, pair chunks, S0 and rhs into h->red
+int sparse_solve(mcba_handle* h, const mcba::SolveArgs& a);
+void sparse_forget(mcba_handle* h);                   // mcba_trim released the buffers
 
 }  // namespace mcba_internal

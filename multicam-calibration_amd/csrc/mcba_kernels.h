@@ -113,6 +113,15 @@ void launch_lm_init(hipStream_t st, const double* red_scal, double* lms, double 
 void launch_pack_result(hipStream_t st, const double* x, const double* gc, const double* fbuf, const unsigned char* fixed, double* out, int C, int F, int cw);  // mcba_lm_result
 void launch_jacobian(hipStream_t st, int loss, double f_scale, const double* obs_raw, const double* obj, const double* x, double* jac, double* res, int C, int F, int N, int Fpad, int robust);
 int syrk_set_lds_limit(size_t bytes);
+// the sparse-Schur handle (mcba_sparse.hip): visibility, frame factors + Y_cf, co-visible pair chunks + assembly of S0 / rhs, the blocked reduced solve
+void launch_sp_seen(hipStream_t st, const double* obs_raw, unsigned char* seen, int C, int F, int N);
+void launch_sp_factor(hipStream_t st, Sel s, const double* rec0, const double* rec1, double* fbuf, double* fpart, const int* frame_off, const int* ent_cam, const int* ent_frame, int nent,
+                      double* Y, const double* dscale, int C, int F, int Fpad, int cw);
+void launch_sp_pairs(hipStream_t st, Sel s, const double* Y, const double* fbuf, const int* items, const int* chunks, int nchunks, double* part, const double* gp0, const double* gp1,
+                     const int* pair_map, const int* pair_chunks, double* red, int C, int nfb, int cw);
+int sp_npad(int n);                // rows of the blocked factorisation: n + 1 rounded up to its block
+// bracket(ctx, stage, begin): profiling hook around each stage (0 prologue + load, 1 diagonal blocks, 2 panels, 3 trailing updates, 4 backward sweep + state)
+void launch_sp_solve(hipStream_t st, const SolveArgs& a, int* ctl, double* damp, double* A, double* y, void (*bracket)(void*, int, int), void* ctx);   // y: npad doubles of scratch
 // pre-filter, frame subsets, undistortion, reprojection diagnostics (mcba_diag.hip)
 void launch_frame_err(hipStream_t st, const double* obs_t, const double* obj, const double* x, double* err, double* mean_cf, double* full_cf, int C, int F, int N, int Fpad,
                       void* prefilter_state = nullptr);   // non-NULL: the launch also zeroes the selection's state (launch_prefilter_select(..., state_cleared = true) follows)

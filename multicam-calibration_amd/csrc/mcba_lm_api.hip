@@ -153,7 +153,7 @@ int mcba_lm_auto_config(mcba_handle* h, double ftol, double xtol, double gtol, d
   h->last_solve_seq = 0;
   h->waited_seq = 0;
   h->auto_ready = true;
-  if (const char* e = getenv("MCBA_SPECULATE")) h->speculate = atoi(e) != 0;
+  if (const char* e = getenv("MCBA_SPECULATE")) h->speculate = atoi(e) != 0 && !h->sparse;
   return MCBA_OK;
 }
 
@@ -176,6 +176,11 @@ static int auto_solve_impl(mcba_handle* h, unsigned long long seq, int decide, b
   a.stage_tag = (double)(++h->solve_launches);
   a.n = h->n; a.npad = h->npad; a.use_lds = h->solve_lds; a.cw = h->cw;
   a.decide = decide ? 1 : 0; a.lam_min = h->lam_min; a.ftol = h->ftol; a.xtol = h->xtol; a.dec_floor = h->dec_floor;
+  if (h->sparse) {   // the blocked multi-workgroup solve (mcba_sparse.hip); its decisions are taken before it (k_sum_trial / k_decide)
+    if (decide) return fail(MCBA_ERR_ARG, "mcba_lm_auto_solve: the sparse-Schur handle takes the accept / reject decision before the solve (decide = 0)");
+    h->trial_ready = false;
+    return sparse_solve(h, a);
+  }
   {
     Scope sc(h, K_SOLVE);
     if (fuse_next)  // + the back-substitution of the next tick's trial step, overlapped with the solve (polls bounded: ~0.5 s)
@@ -230,6 +235,7 @@ int mcba_lm_auto_trial(mcba_handle* h, int decide) { return auto_trial_impl(h, d
 
 int mcba_lm_auto_reduce(mcba_handle* h, int decide, int rank_slot) {
   if (!h || !h->auto_ready || rank_slot < 0 || rank_slot > 11 || decide < 0 || decide > 2) return fail(MCBA_ERR_ARG, "mcba_lm_auto_reduce: bad argument");
+  if (decide == 2 && h->sparse) return fail(MCBA_ERR_ARG, "mcba_lm_auto_reduce: the sparse-Schur handle has no speculative reduction (decide 0 or 1)");
   HIPCHK(hipSetDevice(h->device));
   if (decide == 1) {
     {
@@ -246,6 +252,12 @@ int mcba_lm_auto_tick(mcba_handle* h, unsigned long long seq, int rank_slot) {
   if (!h) return fail(MCBA_ERR_ARG, "NULL handle");
   const bool coll = h->comm != nullptr;
   int rc;
+  if (!coll && h->sparse) {  // sparse-Schur handle, one GPU: k_backsub -> k_gram -> k_sum_trial (+ decision) -> frame factors / pairs / assembly -> tail -> blocked solve
+    if (rank_slot < 0 || rank_slot > 11) return fail(MCBA_ERR_ARG, "mcba_lm_auto_tick: bad rank slot");
+    if ((rc = auto_trial_impl(h, 1, true))) return rc;
+    if ((rc = lm_reduce_chain(h, rank_slot))) return rc;
+    return auto_solve_impl(h, seq, 0, false);
+  }
   if (!coll) {  // one GPU: [k_backsub ->] k_gram -> k_syrk (trial sums + decision + frame factors + SYRK) -> k_reduce_system -> k_solve_backsub
     if (rank_slot < 0 || rank_slot > 11) return fail(MCBA_ERR_ARG, "mcba_lm_auto_tick: bad rank slot");
     if ((rc = auto_trial_impl(h, 0, false))) return rc;
@@ -351,7 +363,7 @@ int mcba_lm_run(mcba_handle* h, const double* x0, const double* opt, const unsig
   h->last_solve_seq = 0;
   h->waited_seq = 0;
   h->auto_ready = true;
-  if (const char* e = getenv("MCBA_SPECULATE")) h->speculate = atoi(e) != 0;
+  if (const char* e = getenv("MCBA_SPECULATE")) h->speculate = atoi(e) != 0 && !h->sparse;
   // (with <= 9 cameras the first solve's launch already carries the back-substitution of the first trial step, like every later one)
   if ((rc = auto_solve_impl(h, 1, 0, false, h->fuse_backsub))) return rc;
 

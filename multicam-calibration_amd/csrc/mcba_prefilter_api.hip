@@ -159,7 +159,7 @@ static int create_subset_impl(mcba_handle** out, mcba_handle* src, const int* fr
   if (!src->have_obs) return fail(MCBA_ERR_ARG, "mcba_create_subset: the source handle has no observations");
   for (int i = 0; i < n_frames; ++i)
     if (frames[i] < 0 || frames[i] >= src->F || (only_cam && (only_cam[i] < 0 || only_cam[i] >= src->C))) return fail(MCBA_ERR_ARG, "mcba_create_subset: frame / camera index out of range");
-  int rc = mcba_create(out, src->C, n_frames, src->N, src->device);
+  int rc = create_impl(out, src->C, n_frames, src->N, src->device, src->sparse);   // (a subset is a handle of the same kind)
   if (rc) return rc;
   mcba_handle* h = *out;
   if (src->stream != h->stream) HIPCHK(hipStreamSynchronize(h->stream));  // mcba_create's zero fills ran on the creation stream

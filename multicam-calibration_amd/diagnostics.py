@@ -48,7 +48,7 @@ def reprojection_errors(all_calib_uvs, all_extrinsics, all_intrinsics, calib_obj
     obj = np.asarray(calib_objpoints, dtype=np.float64)
     if np.ptp(obj[:, 2]) != 0:
         raise NotImplementedError("the board-plane homography needs a planar calibration object (z = const)")
-    prob = ops.Problem(uvs, obj, device=device)
+    prob = ops.Problem(uvs, obj, device=device, schur="sparse" if uvs.shape[0] > 40 else "dense")   # (> 40 cameras: the sparse-Schur handle)
     try:
         prob.set_params(0, serialize_params(all_extrinsics, all_intrinsics, np.asarray(calib_poses, dtype=np.float64)))
         return prob.reprojection_diagnostics(0, _dist5(all_intrinsics), undistort_iterations, arrays)

@@ -22,6 +22,9 @@ SYMBOLS = [
     ("mcba_last_error", ctypes.c_char_p, []),
     ("mcba_device_count", ctypes.c_int, [_ip]),
     ("mcba_create", ctypes.c_int, [ctypes.POINTER(_h), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("mcba_create_sparse", ctypes.c_int, [ctypes.POINTER(_h), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("mcba_is_sparse", ctypes.c_int, [_h]),
+    ("mcba_sparse_index", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, _ip, _ip, ctypes.c_size_t]),
     ("mcba_destroy", ctypes.c_int, [_h]),
     ("mcba_pool_trim", ctypes.c_int, []),
     ("mcba_device_bytes", ctypes.c_size_t, [_h]),
@@ -212,8 +215,10 @@ def pool_trim():
 class Problem:
     """One handle = one GPU = this process's shard of frames."""
 
-    def __init__(self, uvs, objpoints, device=0, loss="soft_l1", f_scale=1.0, stream=None, upload=True):
-        """upload=False: the handle is created, the observations are NOT sent yet -- `prefilter` uploads and scores them in one call."""
+    def __init__(self, uvs, objpoints, device=0, loss="soft_l1", f_scale=1.0, stream=None, upload=True, schur="dense"):
+        """upload=False: the handle is created, the observations are NOT sent yet -- `prefilter` uploads and scores them in one call.
+        schur="sparse": the sparse-Schur handle (include/mcba.h: mcba_create_sparse) -- any number of cameras, the Schur reduction over
+        co-visible camera pairs and a multi-workgroup blocked solve; "dense" (the default) holds at most 40 cameras."""
         self.lib = load_library()
         uvs = _f64(uvs)
         objpoints = _f64(objpoints)
@@ -223,8 +228,11 @@ class Problem:
         self.cw = 12
         self.n = 12 * self.C
         self.nx = 12 * self.C + 6 * self.F
+        if schur not in ("dense", "sparse"):
+            raise ValueError("schur must be 'dense' or 'sparse'")
         self.handle = _h()
-        self._chk(self.lib.mcba_create(ctypes.byref(self.handle), self.C, self.F, self.N, int(device)))
+        create = self.lib.mcba_create_sparse if schur == "sparse" else self.lib.mcba_create
+        self._chk(create(ctypes.byref(self.handle), self.C, self.F, self.N, int(device)))
         if stream is not None:
             self._chk(self.lib.mcba_set_stream(self.handle, ctypes.c_void_p(int(stream))))
         if upload:
@@ -232,6 +240,11 @@ class Problem:
         else:
             self._pending = (uvs, objpoints)
         self.set_loss(loss, f_scale)
+
+    @property
+    def is_sparse(self):
+        """True for a sparse-Schur handle (subsets of one are sparse as well)."""
+        return bool(self.lib.mcba_is_sparse(self.handle))
 
     def prefilter(self, x, outlier_threshold=None):
         """The reference's pre-filter (bundle_adjustment.py:265-285) in one C-ABI crossing and one host synchronisation

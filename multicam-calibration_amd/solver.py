@@ -307,6 +307,8 @@ class LevenbergMarquardt:
         self.device_solve = self.device_decide and reduced_solver == "device" and hasattr(problem, "lm_auto_tick")
         self.depth = max(1, min(int(depth), 12))
         self.speculate = os.environ.get("MCBA_SPECULATE", "1") != "0"  # frame-sharded ticks: one collective instead of two
+        if getattr(problem, "is_sparse", False):
+            self.speculate = False   # (the sparse-Schur handle has no speculative reduction: its sharded ticks take two collectives)
         self.max_nfev = None
         self.max_steps = None
 

@@ -65,7 +65,7 @@ def project(cam12, poses, obj):
     return np.stack(out)
 
 
-def make_problem(n_cameras, n_frames, rows=6, cols=9, pitch=12.5, seed=0, perturb_seed=1, noise=0.2, missing=0.0, outlier_frames=0, scalar_nans=0, frame_seed=None):
+def make_problem(n_cameras, n_frames, rows=6, cols=9, pitch=12.5, seed=0, perturb_seed=1, noise=0.2, missing=0.0, outlier_frames=0, scalar_nans=0, frame_seed=None, visible_k=None):
     """Returns a dict:
       uvs (C,F,N,2) f64 with NaN = missing, obj (N,3),
       true_cam (C,12), true_poses (F,6),
@@ -74,7 +74,10 @@ def make_problem(n_cameras, n_frames, rows=6, cols=9, pitch=12.5, seed=0, pertur
     `outlier_frames` : that many frames get a grossly wrong initial pose (exercise the pre-filter).
     `scalar_nans` : that many single (u or v) scalars are set to NaN (per-coordinate masking).
     `frame_seed` : if given, board poses / noise / pose perturbations come from this seed while the cameras
-                   still come from `seed` and `perturb_seed` -- frame shards of ONE rig for multi-GPU runs."""
+                   still come from `seed` and `perturb_seed` -- frame shards of ONE rig for multi-GPU runs.
+    `visible_k` : if given, each frame is seen by the `visible_k` cameras nearest its board on the ring (by azimuth) and by no
+                  other: the visibility of a wide rig, where a board pose is seen by a handful of the cameras.  Draws nothing from
+                  the generators, so every other output is what the call without it returns."""
     rng = np.random.default_rng(seed)
     obj = board_points(rows, cols, pitch)
     N = obj.shape[0]
@@ -122,6 +125,16 @@ def make_problem(n_cameras, n_frames, rows=6, cols=9, pitch=12.5, seed=0, pertur
     if scalar_nans:
         idx = rng.choice(uvs.size, scalar_nans, replace=False)
         uvs.reshape(-1)[idx] = np.nan
+    if visible_k is not None:
+        k = int(visible_k)
+        if not 1 <= k <= C:
+            raise ValueError("visible_k must be in 1 .. n_cameras")
+        az = np.arctan2(tr[:, 1], tr[:, 0])
+        gap = np.abs(np.angle(np.exp(1j * (phi[None, :] - az[:, None]))))   # (F, C) angular distance board -> camera
+        near = np.argsort(gap, axis=1, kind="stable")[:, :k]
+        keep = np.zeros((F, C), bool)
+        keep[np.arange(F)[:, None], near] = True
+        uvs[~keep.T] = np.nan
 
     prng = np.random.default_rng(perturb_seed)
     cam0 = cam.copy()
