@@ -240,7 +240,7 @@ int mcba_reprojection_diagnostics(mcba_handle* h, int slot, const double* dist5,
   double* d_bn = h->dmean;  // three doubles of scratch (the pre-filter's means are host-side by now)
   HIPCHK(hipMemcpyAsync(d_bn, bn, sizeof(bn), hipMemcpyHostToDevice, h->stream));
   mcba::launch_reproj_diag(h->stream, h->obs_t, h->obj, h->x[slot], d5.data(), d_bn, h->und, reprojections ? h->repro : nullptr, transformed ? h->trans : nullptr, h->err, h->C, h->F, h->N, h->Fpad,
-                           undistort_iterations, 16);
+                           undistort_iterations, 24);
   if ((rc = check_launch())) return rc;
   if ((rc = median_of_err(h, (size_t)h->N * h->Fpad, h->C, false, median_error, nullptr))) return rc;
   if (reprojections) HIPCHK(hipMemcpyAsync(reprojections, h->repro, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));

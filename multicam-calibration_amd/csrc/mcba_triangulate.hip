@@ -78,13 +78,15 @@ __global__ __launch_bounds__(256) void k_triangulate(const double2* __restrict__
     const double k1 = cams.dist[c][0], k2 = cams.dist[c][1], p1 = cams.dist[c][2], p2 = cams.dist[c][3], k3 = cams.dist[c][4];
     const double x0 = (o.x - cx) / fx, y0 = (o.y - cy) / fy;
     double x = x0, y = y0;
+    bool stop = false;   // OpenCV's guard: icdist < 0 -> the unrefined point (mcba_diag.hip, undistort_px)
     for (int it = 0; it < iters; ++it) {
       const double r2 = fma(x, x, y * y);
       const double icdist = 1.0 / fma(fma(fma(k3, r2, k2), r2, k1), r2, 1.0);
+      stop = stop || icdist < 0.0;
       const double dx = fma(2.0 * p1 * x, y, p2 * fma(2.0 * x, x, r2));
       const double dy = fma(p1, fma(2.0 * y, y, r2), 2.0 * p2 * x * y);
-      x = (x0 - dx) * icdist;
-      y = (y0 - dy) * icdist;
+      x = stop ? x0 : (x0 - dx) * icdist;
+      y = stop ? y0 : (y0 - dy) * icdist;
     }
     ux[c] = fma(x, fx, cx);
     uy[c] = fma(y, fy, cy);
@@ -171,13 +173,15 @@ __global__ __launch_bounds__(256) void k_triangulate_wave(const double2* __restr
     const TriCam& cm = cams[c];
     double x0 = (o.x - cm.K[2]) / cm.K[0], y0 = (o.y - cm.K[3]) / cm.K[1];
     double x = x0, y = y0;
+    bool stop = false;   // OpenCV's guard: icdist < 0 -> the unrefined point
     for (int it = 0; it < iters; ++it) {
       const double r2 = fma(x, x, y * y);
       const double icdist = 1.0 / fma(fma(fma(cm.dist[4], r2, cm.dist[1]), r2, cm.dist[0]), r2, 1.0);
+      stop = stop || icdist < 0.0;
       const double dx = fma(2.0 * cm.dist[2] * x, y, cm.dist[3] * fma(2.0 * x, x, r2));
       const double dy = fma(cm.dist[2], fma(2.0 * y, y, r2), 2.0 * cm.dist[3] * x * y);
-      x = (x0 - dx) * icdist;
-      y = (y0 - dy) * icdist;
+      x = stop ? x0 : (x0 - dx) * icdist;
+      y = stop ? y0 : (y0 - dy) * icdist;
     }
     ux[c] = fma(x, cm.K[0], cm.K[2]);
     uy[c] = fma(y, cm.K[1], cm.K[3]);

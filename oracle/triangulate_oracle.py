@@ -40,12 +40,14 @@ def undistort_points(uvs, camera_matrix, dist_coefs, iterations=5):
     x0 = (uvs[..., 0] - K[0, 2]) / K[0, 0]
     y0 = (uvs[..., 1] - K[1, 2]) / K[1, 1]
     x, y = x0.copy(), y0.copy()
+    stop = np.zeros(np.shape(x0), bool)
     for _ in range(iterations):
         r2 = x * x + y * y
         icdist = 1.0 / (1 + ((k3 * r2 + k2) * r2 + k1) * r2)
+        stop |= icdist < 0   # OpenCV (cvUndistortPointsInternal): a point past the model's valid radius stays unrefined
         dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
         dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
-        x, y = (x0 - dx) * icdist, (y0 - dy) * icdist
+        x, y = np.where(stop, x0, (x0 - dx) * icdist), np.where(stop, y0, (y0 - dy) * icdist)
     out = np.stack([x * K[0, 0] + K[0, 2], y * K[1, 1] + K[1, 2]], axis=-1)
     out[np.isnan(uvs).any(-1)] = np.nan
     return out
