@@ -502,6 +502,32 @@ int mcba_flat_ransac(size_t n_points, const double* points, int n_hypotheses, co
 int mcba_flat_order_stats(size_t n_points, const double* points, const double* rt12, int n_ranks, const long long* ranks, int device, double* values_out, double* sums_out,
                           unsigned long long* nans_out, double* kernel_ms);
 
+/* ---- chessboard detection (reference detection.py: detect_chessboard, reorder_chessboard_corners; additive to ABI 7) ----------------
+ * Stateless: host arrays in and out.  Images are 8-bit, (H, W) grey or (H, W, 3) BGR, row-major; BGR is converted with OpenCV's
+ * fixed-point formula.  Coordinates follow the pixel-centre convention (pixel (i, j) covers [j - 1/2, j + 1/2] x [i - 1/2, i + 1/2]).
+ * A board of board_cols x board_rows inner corners (the reference's board_shape = (cols, rows)) is returned row-major: corner k is board
+ * point x = k % board_cols, y = k / board_cols.  kernel_ms (may be NULL) receives the time of the call's kernels (HIP events). */
+#define MCBA_DETECT_MAX_CANDIDATES 1024   /* saddle candidates per frame (more: status 3, the frame is not searched) */
+#define MCBA_DETECT_MAX_CORNERS 512       /* board_cols * board_rows */
+#define MCBA_DETECT_MAX_BOARD_SIDE 30     /* board_cols, board_rows */
+#define MCBA_DETECT_MAX_WINDOW 15         /* cornerSubPix half-window (subpix_winSize) */
+#define MCBA_DETECT_MAX_IMAGE_SIDE 4096   /* image width and height */
+/* The whole pipeline for n_images frames of one size (grey -> saddle candidates -> lattice -> cornerSubPix -> anchor), in chunks whose
+ * device memory stays within memory_budget bytes (0: 256 MiB).  scale_factor in (0, 1]: the search runs on the bilinear downscale, the
+ * refinement on the full image.  Outputs per frame: status_out 0 no board, 1 accepted, 2 rejected (anchor ambiguous: best - second score
+ * < match_score_min_diff), 3 more than MCBA_DETECT_MAX_CANDIDATES candidates; uvs_out (N, 2) float32, NaN unless status 1; scores_out (4)
+ * sorted descending, NaN where no grid was assembled or reorder == 0.  reorder == 0: no anchor, status 1 for every assembled grid. */
+int mcba_detect_chessboards(int n_images, int height, int width, int channels, const unsigned char* images, int board_cols, int board_rows, int win_w, int win_h,
+                            double scale_factor, int reorder, double match_score_min_diff, size_t memory_budget, int device, float* uvs_out, double* scores_out,
+                            signed char* status_out, double* kernel_ms);
+/* cornerSubPix (half-window win_w x win_h, 30 iterations, eps 0.001, no zero zone) of n_corners float32 start points (n, 2) in one image */
+int mcba_detect_subpix(int height, int width, int channels, const unsigned char* image, int n_corners, const float* start, int win_w, int win_h, int device, float* out,
+                       double* kernel_ms);
+/* the anchor test of reorder_chessboard_corners for uvs (N, 2) float32 in the reference's grid layout (board_rows x board_cols):
+ * scores_out (4) unsorted correlations of the four regions, regions_out (4, 40, 40) uint8 or NULL, quads_out (4, 4, 2) float32 or NULL */
+int mcba_detect_anchor(int height, int width, int channels, const unsigned char* image, int board_cols, int board_rows, const float* uvs, int device, double* scores_out,
+                       unsigned char* regions_out, float* quads_out, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ Only what the hot path needs lives here:
   api.py     `bundle_adjust` with the reference's exact signature and return tuple
   diagnostics.py  reprojection_errors (numeric core of plot_residuals), undistort_points -- SURVEY.md section 8f-2
   flatibration.py  get_floor_points / flatibrate / center_arena / flip_z_axis (floor-plane alignment) -- SURVEY.md section 8f-5
+  detection.py  detect_chessboard / detect_chessboards / reorder_chessboard_corners and the reference's host helpers -- SURVEY.md section 8f-7
   io.py      save_calibration / load_calibration (json, jarvis; gimbal needs h5py) -- SURVEY.md section 8f-3
   synth.py   deterministic synthetic board detections for tests and bench
 """
@@ -19,8 +20,10 @@ from .triangulation import triangulate  # noqa: F401
 from .io import save_calibration, load_calibration  # noqa: F401
 from .diagnostics import reprojection_errors, undistort_points  # noqa: F401
 from .flatibration import get_floor_points, flatibrate, center_arena, flip_z_axis  # noqa: F401
+from .detection import detect_chessboard, detect_chessboards, reorder_chessboard_corners, generate_chessboard_objpoints, extend_grid, summarize_detections  # noqa: F401
 from .calibration import calibrate, get_intrinsics, estimate_pose, estimate_all_extrinsics, consensus_calib_poses, get_camera_spanning_tree, estimate_pairwise_camera_transform  # noqa: F401
 
 __all__ = ["bundle_adjust", "bundle_adjustment", "serialize_params", "deserialize_params", "ops", "solver", "synth", "calibration", "calibrate", "triangulate", "get_intrinsics",
            "save_calibration", "load_calibration", "reprojection_errors", "undistort_points", "estimate_pose", "estimate_all_extrinsics", "consensus_calib_poses", "get_camera_spanning_tree", "estimate_pairwise_camera_transform",
-           "get_floor_points", "flatibrate", "center_arena", "flip_z_axis"]
+           "get_floor_points", "flatibrate", "center_arena", "flip_z_axis",
+           "detect_chessboard", "detect_chessboards", "reorder_chessboard_corners", "generate_chessboard_objpoints", "extend_grid", "summarize_detections"]

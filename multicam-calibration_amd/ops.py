@@ -123,6 +123,10 @@ SYMBOLS = [
     ("mcba_flat_floor_points", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp]),
     ("mcba_flat_ransac", ctypes.c_int, [ctypes.c_size_t, _dp, ctypes.c_int, _dp, ctypes.c_double, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),
     ("mcba_flat_order_stats", ctypes.c_int, [ctypes.c_size_t, _dp, _dp, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),
+    ("mcba_detect_chessboards", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_int, _dp, _dp, _dp, _dp]),
+    ("mcba_detect_subpix", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, _dp]),
+    ("mcba_detect_anchor", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),
 ]
 
 LM_STATE = 32  # MCBA_LM_STATE of include/mcba.h
