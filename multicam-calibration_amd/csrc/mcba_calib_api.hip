@@ -59,23 +59,18 @@ static int upload_intr(mcba_handle* h, const double* intr9) {
   HIPCHK(hipMemcpyAsync(h->cal_intr, intr9, (size_t)9 * h->C * sizeof(double), hipMemcpyHostToDevice, h->stream));
   return MCBA_OK;
 }
-struct SelRecord { unsigned long long prefix, rank, count, value; unsigned int hist[256]; };   // = SelState of mcba_diag.hip
-
 // medians of the pairwise transforms (calibration.py:143): rel [E][6][Fpad] -> out (E, 6), counts (E) = frames the pair shares
-static int pairwise_medians(hipStream_t st, const double* rel, int n_edges, int Fpad, unsigned char* sel_dev, double* out, double* counts) {
+static int pairwise_medians(hipStream_t st, const double* rel, int n_edges, int Fpad, mcba::SelState* sel_dev, double* out, double* counts) {
   const int groups = 6 * n_edges;
-  mcba::launch_select(st, rel, nullptr, (size_t)Fpad, groups, Fpad, sel_dev, 2, 1);
+  mcba::launch_select(st, rel, nullptr, (size_t)Fpad, groups, Fpad, sel_dev, 1);
   int rc = check_launch();
   if (rc) return rc;
-  std::vector<unsigned long long> head((size_t)4 * 2 * groups);   // prefix rank count value of every state
-  HIPCHK(hipMemcpy2DAsync(head.data(), 32, sel_dev, sizeof(SelRecord), 32, (size_t)2 * groups, hipMemcpyDeviceToHost, st));
+  std::vector<mcba::SelState> sel((size_t)2 * groups);
+  HIPCHK(hipMemcpyAsync(sel.data(), sel_dev, sel.size() * sizeof(mcba::SelState), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   for (int g = 0; g < groups; ++g) {
-    double a, b;
-    memcpy(&a, &head[4 * (2 * g) + 3], 8);
-    memcpy(&b, &head[4 * (2 * g + 1) + 3], 8);
-    out[g] = head[4 * (2 * g) + 2] ? 0.5 * (a + b) : NAN;   // np.median: the mean of the two middle values; no common frame: NaN
-    if (counts && g % 6 == 0) counts[g / 6] = (double)head[4 * (2 * g) + 2];
+    out[g] = mcba::sel_median(sel[2 * g], sel[2 * g + 1]);   // no common frame: NaN
+    if (counts && g % 6 == 0) counts[g / 6] = (double)sel[2 * g].count;
   }
   return MCBA_OK;
 }
@@ -206,7 +201,7 @@ int mcba_calib_pairwise(mcba_handle* h, const int* edges, int n_edges, double* t
     if (edges[i] < 0 || edges[i] >= h->C) return fail(MCBA_ERR_ARG, "mcba_calib_pairwise: camera index out of range");
   if ((rc = dgrow(h, &h->cal_views, &h->cal_views_cap, (size_t)2 * n_edges))) return rc;
   if ((rc = dgrow(h, &h->cal_rel, &h->cal_rel_cap, (size_t)6 * n_edges * h->Fpad))) return rc;
-  if ((rc = dgrow(h, &h->cal_sel, &h->cal_sel_cap, mcba::select_state_bytes(12 * n_edges)))) return rc;
+  if ((rc = dgrow(h, &h->cal_sel, &h->cal_sel_cap, (size_t)12 * n_edges))) return rc;
   HIPCHK(hipMemcpyAsync(h->cal_views, edges, (size_t)2 * n_edges * sizeof(int), hipMemcpyHostToDevice, h->stream));
   mcba::launch_pose_pairs(h->stream, h->cal_poses_t, (size_t)6 * h->Fpad, 1, (size_t)h->Fpad, h->cal_views, n_edges, h->F, h->Fpad, h->cal_rel);
   if ((rc = check_launch())) return rc;
@@ -261,12 +256,12 @@ int mcba_calib_graph(mcba_handle* h, const int* edges, int n_edges, int root, do
   if (E > 0) {
     if ((rc = dgrow(h, &h->cal_views, &h->cal_views_cap, (size_t)2 * E))) return rc;
     if ((rc = dgrow(h, &h->cal_rel, &h->cal_rel_cap, (size_t)6 * E * h->Fpad))) return rc;
-    if ((rc = dgrow(h, &h->cal_sel, &h->cal_sel_cap, mcba::select_state_bytes(12 * E)))) return rc;
+    if ((rc = dgrow(h, &h->cal_sel, &h->cal_sel_cap, (size_t)12 * E))) return rc;
     HIPCHK(hipMemcpyAsync(h->cal_views, edges, (size_t)2 * E * sizeof(int), hipMemcpyHostToDevice, h->stream));
     mcba::launch_pose_pairs(h->stream, h->cal_poses_t, (size_t)6 * h->Fpad, 1, (size_t)h->Fpad, h->cal_views, E, h->F, h->Fpad, h->cal_rel);
-    mcba::launch_select(h->stream, h->cal_rel, nullptr, (size_t)h->Fpad, 6 * E, h->Fpad, h->cal_sel, 2, 1);
+    mcba::launch_select(h->stream, h->cal_rel, nullptr, (size_t)h->Fpad, 6 * E, h->Fpad, h->cal_sel, 1);
   }
-  mcba::launch_pose_chain(h->stream, h->cal_sel, mcba::select_state_bytes(1), h->cal_views, E, root, h->C, d_ext, d_tr, d_cnt);
+  mcba::launch_pose_chain(h->stream, h->cal_sel, h->cal_views, E, root, h->C, d_ext, d_tr, d_cnt);
   mcba::launch_pose_consensus(h->stream, h->cal_poses_t, (size_t)6 * h->Fpad, 1, (size_t)h->Fpad, d_ext, h->C, h->F, h->Fpad, h->cal_world, h->cal_out);
   if ((rc = check_launch())) return rc;
   HIPCHK(hipMemcpyAsync(extrinsics_out, d_ext, (size_t)6 * h->C * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -287,14 +282,14 @@ int mcba_pose_pairwise(int n_cameras, int n_frames, const double* poses, const i
   if (rc) return rc;
   const int Fpad = (n_frames + 63) / 64 * 64;
   const size_t b_pose = up256((size_t)6 * n_cameras * n_frames * sizeof(double)), b_edge = up256((size_t)2 * n_edges * sizeof(int)), b_rel = up256((size_t)6 * n_edges * Fpad * sizeof(double)),
-               b_sel = up256(mcba::select_state_bytes(12 * n_edges));
+               b_sel = up256((size_t)12 * n_edges * sizeof(mcba::SelState));
   StatelessCall call;
   unsigned char* t = nullptr;
   HIPCHK(call.alloc(&t, b_pose + b_edge + b_rel + b_sel));
   double* d_pose = reinterpret_cast<double*>(t);
   int* d_edge = reinterpret_cast<int*>(t + b_pose);
   double* d_rel = reinterpret_cast<double*>(t + b_pose + b_edge);
-  unsigned char* d_sel = t + b_pose + b_edge + b_rel;
+  mcba::SelState* d_sel = reinterpret_cast<mcba::SelState*>(t + b_pose + b_edge + b_rel);
   HIPCHK(hipMemcpyAsync(d_pose, poses, (size_t)6 * n_cameras * n_frames * sizeof(double), hipMemcpyHostToDevice, nullptr));
   HIPCHK(hipMemcpyAsync(d_edge, edges, (size_t)2 * n_edges * sizeof(int), hipMemcpyHostToDevice, nullptr));
   mcba::launch_pose_pairs(nullptr, d_pose, (size_t)6 * n_frames, 6, 1, d_edge, n_edges, n_frames, Fpad, d_rel);

@@ -8,9 +8,15 @@
 namespace mcba {
 
 // ---------------------------------------------------------------- small device helpers
-__device__ __forceinline__ double wave_sum(double v) {
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
   return v;
 }
 // Sum over the 64 lanes, result valid in lane 63 only.  DPP moves (pure VALU, no LDS round trip):

@@ -5,9 +5,10 @@
 //                    reprojection error |observed - predicted| (NaN where a coordinate is missing), per (camera, frame) its
 //                    nan-mean over the board points and the number of complete points.  Same mapping as k_cost: lane = frame,
 //                    64 consecutive frames per wavefront, loop over the points -> the means are lane-local.
-//   k_sel_hist/pick  exact nan-median of the errors of the selected frames (`5 * np.nanmedian(err)`, :281) without sorting:
-//                    radix select on the bit patterns of the (non-negative) doubles, 8 passes of one byte; histogram in LDS,
-//                    integer atomics only -> the result is the exact order statistic, bit for bit.
+//   k_sel_hist/pick  exact order statistics without sorting -- the nan-median of the errors of the selected frames (`5 * np.nanmedian(err)`,
+//                    :281), calibrate()'s medians of the pairwise transforms, center_arena's percentiles (mcba_flat.hip): radix select
+//                    on the bit patterns of the doubles, 8 passes of one byte; histograms in LDS, integer atomics only -> the result is
+//                    the exact order statistic, bit for bit.
 //   k_gather_frames  observations of a frame subset, device to device, for the handle the solver then runs on.
 //   k_seen_bits      which observation scalars are present, one bit each in numpy.packbits order: the row selection of the
 //                    reference's residual vector and Jacobian (bundle_adjustment.py:68-69, 101) taken from the GPU's own copy.
@@ -103,40 +104,43 @@ __global__ __launch_bounds__(256) void k_frame_err(const double2* __restrict__ o
   }
 }
 
-// ---------------------------------------------------------------- exact order statistic by radix select
-// st: [0] prefix  [1] rank  [2] count of candidates  [3] result bits ; hist 256 x u32 behind it
-struct SelState {
-  unsigned long long prefix, rank, count, value;
-  unsigned int hist[256];
-};
-
-// values: [groups][stride] doubles with the frame index = i % Fpad; mask (per frame) may be nullptr; group g selects the
-// slice [g * per_group, (g + 1) * per_group) (per-camera medians) -- blockIdx.y = group, one SelState per group
-// dual != 0: two states per group (2 g: the lower middle rank, 2 g + 1: the upper one) walk the same slice in the same passes
+// ---------------------------------------------------------------- exact order statistic by radix select (SelState: mcba_kernels.h)
+// values: [groups][per_group] doubles with the frame index = i % Fpad; mask (per frame) may be nullptr; group g selects in the slice
+// [g * per_group, (g + 1) * per_group) (per-camera medians) -- blockIdx.y = group, whose `spg` states are sts[g * spg .. (g + 1) * spg)
+// and walk the slice in the same passes: one read of it per pass, one LDS histogram per state (pass 0: one for all, nothing is fixed yet)
 // skey != 0: the values may be negative -- they are compared through an order-preserving key (sign bit flipped for values >= +0, every bit
-// for negative ones: unsigned order of the keys = numeric order of the values); the errors of the pre-filter are >= +0 and need none
+// for negative ones: unsigned order of the keys = numeric order of the values, -0 < +0); the errors of the pre-filter are >= +0 and need none
 __device__ __forceinline__ unsigned long long sel_key(unsigned long long k, int skey) {
   return skey ? ((k >> 63) ? ~k : (k | 0x8000000000000000ull)) : k;
 }
-__global__ __launch_bounds__(256) void k_sel_hist(const double* __restrict__ v, const unsigned char* __restrict__ fmask, size_t per_group, int Fpad, SelState* __restrict__ sts, int pass, int dual, int skey) {
-  __shared__ unsigned int s_h[256];
-  SelState* st = sts + blockIdx.y;
-  s_h[threadIdx.x] = 0;
+__global__ __launch_bounds__(256) void k_sel_hist(const double* __restrict__ v, const unsigned char* __restrict__ fmask, size_t per_group, int Fpad, SelState* __restrict__ sts, int spg,
+                                                  int pass, int skey) {
+  __shared__ unsigned int s_h[kSelMaxRanks][256];
+  SelState* st = sts + (size_t)blockIdx.y * spg;
+  const int nh = pass == 0 ? 1 : spg;
+  unsigned long long prefix[kSelMaxRanks];
+#pragma unroll
+  for (int j = 0; j < kSelMaxRanks; ++j)
+    if (j < nh) { s_h[j][threadIdx.x] = 0; prefix[j] = st[j].prefix; }
   __syncthreads();
-  const unsigned long long prefix = st->prefix;
   const int shift_hi = 64 - 8 * pass, shift = 56 - 8 * pass;
-  const unsigned long long* keys = reinterpret_cast<const unsigned long long*>(v) + (size_t)(dual ? blockIdx.y >> 1 : blockIdx.y) * per_group;
+  const unsigned long long* keys = reinterpret_cast<const unsigned long long*>(v) + (size_t)blockIdx.y * per_group;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < per_group; i += (size_t)gridDim.x * 256) {
     const unsigned long long kraw = keys[i];
     const double d = __longlong_as_double((long long)kraw);
     const unsigned long long k = sel_key(kraw, skey);
     bool ok = d == d;
     if (fmask) ok = ok && fmask[i % (size_t)Fpad] != 0;
-    if (ok && (pass == 0 || (k >> shift_hi) == prefix)) atomicAdd(&s_h[(unsigned)(k >> shift) & 255u], 1u);
+    const unsigned digit = (unsigned)(k >> shift) & 255u;
+#pragma unroll
+    for (int j = 0; j < kSelMaxRanks; ++j)
+      if (j < nh && ok && (pass == 0 || (k >> shift_hi) == prefix[j])) atomicAdd(&s_h[j][digit], 1u);
   }
   __syncthreads();
-  const unsigned int n = s_h[threadIdx.x];
-  if (n) atomicAdd(&st->hist[threadIdx.x], n);
+  for (int j = 0; j < spg; ++j) {
+    const unsigned int n = s_h[pass == 0 ? 0 : j][threadIdx.x];
+    if (n) atomicAdd(&st[j].hist[threadIdx.x], n);
+  }
 }
 
 // ---------------------------------------------------------------- the pre-filter's frame selection, all of it on the device
@@ -215,24 +219,29 @@ __device__ __forceinline__ void wave_pick_bin(const T* hist, unsigned long long 
   below = __shfl(bl, src, 64);
 }
 
-// one WAVEFRONT per state: which byte holds the wanted rank (wave_pick_bin: four bins per lane, a prefix scan across the lanes); upper == 0
-// selects rank (n-1)/2, upper == 1 rank n/2.  (Round 6: one thread walking the 256 bins with dependent global loads took 15 us per launch,
-// eight launches per median -- 120 us of the 216 us pairwise-median crossing of calibrate().)
-__global__ __launch_bounds__(64) void k_sel_pick(SelState* __restrict__ sts, int pass, int upper, int dual, int skey) {
+// the ranks the states of every group select (state j: r[j]), or -- mid != 0, two states per group -- the lower and the upper middle rank of
+// the group's count, (n - 1) / 2 and n / 2: taken by pass 0
+struct SelRanks {
+  unsigned long long r[kSelMaxRanks];
+  int mid;
+};
+// one WAVEFRONT per state: which byte holds the wanted rank (wave_pick_bin: four bins per lane, a prefix scan across the lanes).
+// (Round 6: one thread walking the 256 bins with dependent global loads took 15 us per launch, eight launches per median -- 120 us of the
+// 216 us pairwise-median crossing of calibrate().)
+__global__ __launch_bounds__(64) void k_sel_pick(SelState* __restrict__ sts, int spg, int pass, SelRanks rk, int skey) {
   SelState* st = sts + blockIdx.x;
-  const int lane = threadIdx.x;
-  if (dual) upper = blockIdx.x & 1;
+  const int lane = threadIdx.x, j = blockIdx.x % spg;
   unsigned long long mine = 0;
 #pragma unroll
   for (int b = 0; b < 4; ++b) mine += st->hist[4 * lane + b];
   unsigned long long total = mine;
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) total += __shfl_xor(total, off, 64);
-  unsigned long long r = pass == 0 ? (total ? (upper ? total / 2 : (total - 1) / 2) : 0) : st->rank;
+  unsigned long long r = pass > 0 ? st->rank : rk.mid ? (total ? (total - 1 + j) / 2 : 0) : rk.r[j];
   unsigned digit;
   unsigned long long below;
   wave_pick_bin<256>(st->hist, r, lane, digit, below);
-  if (total == 0 || r >= total) { digit = 0; below = 0; }   // (an empty group: the value is never used -- count 0 makes the caller report NaN)
+  if (total == 0 || r >= total) { digit = 0; below = 0; }   // (a group without values, or fewer than the rank needs: the value is never used -- the caller reports NaN)
   const unsigned long long prefix = ((pass == 0 ? 0ull : st->prefix) << 8) | (unsigned long long)digit;
   __syncthreads();   // (every lane has read its bins and the old state)
 #pragma unroll
@@ -809,33 +818,27 @@ void launch_frame_err(hipStream_t st, const double* obs_t, const double* obj, co
                                                             static_cast<unsigned long long*>(prefilter_state), (unsigned)(prefilter_state_clear_bytes() / 8));
 }
 
-size_t select_state_bytes(int groups) { return (size_t)groups * sizeof(SelState); }
-
-// median(s) of `groups` equal slices of v (per_group doubles each, frame = index % Fpad): after the call sel[g].count and
-// sel[g].value (bit pattern of the order statistic) are valid.  16 tiny launches per call, no host synchronisation.
-// upper = 0 / 1: one order statistic per group; upper = 2: BOTH middle ranks in the same eight passes (states 2 g and 2 g + 1:
-// `sel` must hold 2 x groups states) -- half the launches and one host synchronisation instead of two for a median
-void launch_select(hipStream_t st, const double* v, const unsigned char* fmask, size_t per_group, int groups, int Fpad, void* sel, int upper, int skey) {
-  SelState* s = static_cast<SelState*>(sel);
-  const int dual = upper == 2 ? 1 : 0, nst = dual ? 2 * groups : groups;
-  (void)hipMemsetAsync(s, 0, select_state_bytes(nst), st);
+void launch_select(hipStream_t st, const double* v, const unsigned char* fmask, size_t per_group, int groups, int Fpad, SelState* sel, int skey, const unsigned long long* ranks, int nranks) {
+  SelRanks rk = {};
+  rk.mid = ranks ? 0 : 1;
+  const int spg = ranks ? nranks : 2;
+  for (int j = 0; ranks && j < nranks; ++j) rk.r[j] = ranks[j];
+  (void)hipMemsetAsync(sel, 0, (size_t)groups * spg * sizeof(SelState), st);
   const unsigned bx = (unsigned)std::min<size_t>((per_group + 255) / 256, 1024);
-  for (int pass = 0; pass < 8; ++pass) {
-    k_sel_hist<<<dim3(bx, nst), dim3(256), 0, st>>>(v, fmask, per_group, Fpad, s, pass, dual, skey);
-    k_sel_pick<<<dim3(nst), dim3(64), 0, st>>>(s, pass, upper, dual, skey);
+  for (int pass = 0; pass < 8; ++pass) {   // 16 small launches, no host synchronisation
+    k_sel_hist<<<dim3(bx, groups), dim3(256), 0, st>>>(v, fmask, per_group, Fpad, sel, spg, pass, skey);
+    k_sel_pick<<<dim3(groups * spg), dim3(64), 0, st>>>(sel, spg, pass, rk, skey);
   }
 }
 
 // one histogram pass with a host-given prefix (sharded select: the caller combines the histograms of several handles)
-int launch_select_hist(hipStream_t st, const double* v, const unsigned char* fmask, size_t per_group, int Fpad, void* sel, unsigned long long prefix, int pass, unsigned int* hist256) {
-  SelState* s = static_cast<SelState*>(sel);
-  SelState init;
-  memset(&init, 0, sizeof(init));
+int launch_select_hist(hipStream_t st, const double* v, const unsigned char* fmask, size_t per_group, int Fpad, SelState* sel, unsigned long long prefix, int pass, unsigned int* hist256) {
+  SelState init = {};
   init.prefix = prefix;
-  if (hipMemcpyAsync(s, &init, sizeof(init), hipMemcpyHostToDevice, st) != hipSuccess) return 1;
+  if (hipMemcpyAsync(sel, &init, sizeof(init), hipMemcpyHostToDevice, st) != hipSuccess) return 1;
   const unsigned bx = (unsigned)std::min<size_t>((per_group + 255) / 256, 1024);
-  k_sel_hist<<<dim3(bx, 1), dim3(256), 0, st>>>(v, fmask, per_group, Fpad, s, pass, 0, 0);
-  if (hipMemcpyAsync(hist256, s->hist, 256 * sizeof(unsigned int), hipMemcpyDeviceToHost, st) != hipSuccess) return 1;
+  k_sel_hist<<<dim3(bx, 1), dim3(256), 0, st>>>(v, fmask, per_group, Fpad, sel, 1, pass, 0);
+  if (hipMemcpyAsync(hist256, sel->hist, 256 * sizeof(unsigned int), hipMemcpyDeviceToHost, st) != hipSuccess) return 1;
   return hipStreamSynchronize(st) == hipSuccess ? 0 : 1;
 }
 

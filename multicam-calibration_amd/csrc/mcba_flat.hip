@@ -9,15 +9,16 @@
 //                           and nine moments of the inliers (below) are reduced lane -> wavefront (xor butterfly) -> workgroup (LDS,
 //                           waves in index order) -> per-block partials, then one block per hypothesis sums the partials in a fixed
 //                           tree.  No floating-point atomics: the result depends on n alone, bit for bit.
-//   mcba_flat_order_stats   transform the points (R p + t), keep x and y as order-preserving 64-bit keys on the device, and find the
-//                           requested order statistics of each by radix select: 8 passes of a 256-bin histogram (integer LDS atomics,
-//                           then integer global atomics: exact) and a one-block pick, all enqueued back to back without a host wait.
-//                           Also the per-coordinate sums (fixed-order per-block partials) and NaN counts.
+//   mcba_flat_order_stats   transform the points (R p + t), keep x and y on the device, and find the requested order statistics of
+//                           each by the radix select of mcba_diag.hip (launch_select: both coordinates, all ranks in the same 8 passes,
+//                           enqueued back to back without a host wait).  Also the per-coordinate sums (fixed-order per-block partials)
+//                           and NaN counts.
 //
 // Moments of the inliers of hypothesis h, in a per-call shift (sx, sy) for x, y and in the hypothesis' own residual r = z - (a x + b y + c)
 // for z (inliers have |r| <= threshold, so nothing cancels): X = sum dx, Y = sum dy, R = sum r, XX, XY, YY, XR, YR, RR.
 #include <stdint.h>
 
+#include "mcba_device.h"
 #include "mcba_handle.h"
 
 namespace mcba {
@@ -27,7 +28,6 @@ constexpr int kFloorLdsDoubles = 6144;  // 48 KiB of staged frames per block
 constexpr int kScorePPT = 4;            // points per lane in the scoring kernel
 constexpr int kScorePoints = kFlatThreads * kScorePPT;
 constexpr int kMom = 9;                 // X Y R XX XY YY XR YR RR
-constexpr int kMaxQueries = 16;         // order statistics per call (both coordinates together)
 
 __global__ __launch_bounds__(kFlatThreads) void k_floor_points(const double* __restrict__ kp, size_t n_frames, int K, int fpb, int down, double* __restrict__ out,
                                                                int* __restrict__ idx) {
@@ -62,17 +62,6 @@ __global__ __launch_bounds__(kFlatThreads) void k_floor_points(const double* __r
     out[3 * g + 1] = fr[3 * bi + 1];
     out[3 * g + 2] = fr[3 * bi + 2];
   }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // the inlier test of RANSAC: |z - (x a + y b + c)| <= threshold (sklearn: absolute_error loss, X @ coef_ + intercept_)
@@ -116,7 +105,7 @@ __global__ __launch_bounds__(kFlatThreads) void k_ransac_score(const double* __r
       m[3] = fma(u, u, m[3]); m[4] = fma(u, v, m[4]); m[5] = fma(v, v, m[5]);
       m[6] = fma(u, w, m[6]); m[7] = fma(v, w, m[7]); m[8] = fma(w, w, m[8]);
     }
-    cnt = wave_sum_u(cnt);
+    cnt = wave_sum(cnt);
 #pragma unroll
     for (int k = 0; k < kMom; ++k) m[k] = wave_sum(m[k]);
     if (lane == 0) {
@@ -180,18 +169,8 @@ __global__ __launch_bounds__(kFlatThreads) void k_ransac_mask(const double* __re
   mask[p] = fabs(plane_residual(pts[3 * p], pts[3 * p + 1], pts[3 * p + 2], a, b, c)) <= thr ? 1 : 0;
 }
 
-// order-preserving key of a double: unsigned order of the keys = numeric order (-0 < +0; NaNs at the two ends, never selected here
-// because the caller reports NaN for a coordinate that holds one)
-__device__ __forceinline__ unsigned long long order_key(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_value(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-// rt12: R row-major (9) + t (3).  keys: 2 x n (x then y).  part_s: blocks x 2 (per-block sums, fixed order); nan2: NaN counts
-__global__ __launch_bounds__(kFlatThreads) void k_flat_transform(const double* __restrict__ pts, size_t n, const double* __restrict__ rt12, unsigned long long* __restrict__ keys,
+// rt12: R row-major (9) + t (3).  xy: 2 x n (x then y).  part_s: blocks x 2 (per-block sums, fixed order); nan2: NaN counts
+__global__ __launch_bounds__(kFlatThreads) void k_flat_transform(const double* __restrict__ pts, size_t n, const double* __restrict__ rt12, double* __restrict__ xy,
                                                                  double* __restrict__ part_s, unsigned long long* __restrict__ nan2) {
   __shared__ double s_s[2][kFlatThreads / 64];
   __shared__ unsigned s_nan[2][kFlatThreads / 64];
@@ -203,15 +182,15 @@ __global__ __launch_bounds__(kFlatThreads) void k_flat_transform(const double* _
     const double px = pts[3 * p], py = pts[3 * p + 1], pz = pts[3 * p + 2];
     X = rt12[0] * px + rt12[1] * py + rt12[2] * pz + rt12[9];
     Y = rt12[3] * px + rt12[4] * py + rt12[5] * pz + rt12[10];
-    keys[p] = order_key(X);
-    keys[n + p] = order_key(Y);
+    xy[p] = X;
+    xy[n + p] = Y;
     nx = X != X ? 1u : 0u;
     ny = Y != Y ? 1u : 0u;
   }
   X = wave_sum(X);
   Y = wave_sum(Y);
-  nx = wave_sum_u(nx);
-  ny = wave_sum_u(ny);
+  nx = wave_sum(nx);
+  ny = wave_sum(ny);
   if (lane == 0) { s_s[0][wave] = X; s_s[1][wave] = Y; s_nan[0][wave] = nx; s_nan[1][wave] = ny; }
   __syncthreads();
   if (tid < 2) {
@@ -222,55 +201,6 @@ __global__ __launch_bounds__(kFlatThreads) void k_flat_transform(const double* _
     part_s[2 * (size_t)blockIdx.x + tid] = v;
     if (c) atomicAdd(nan2 + tid, (unsigned long long)c);
   }
-}
-
-// per query q (coordinate coord[q], wanted rank rank[q]): prefix[q] = the key bits fixed so far (the leading 8 * pass bits)
-struct SelState {
-  unsigned long long prefix[kMaxQueries];
-  unsigned long long rank[kMaxQueries];
-  int coord[kMaxQueries];
-};
-
-__global__ __launch_bounds__(kFlatThreads) void k_select_hist(const unsigned long long* __restrict__ keys, size_t n, const SelState* __restrict__ st, int Q, int pass,
-                                                              unsigned* __restrict__ hist) {
-  __shared__ unsigned s_h[kMaxQueries][256];
-  for (int i = threadIdx.x; i < Q * 256; i += kFlatThreads) s_h[i >> 8][i & 255] = 0;
-  __syncthreads();
-  const int shift = 56 - 8 * pass;
-  for (size_t p = (size_t)blockIdx.x * kFlatThreads + threadIdx.x; p < n; p += (size_t)gridDim.x * kFlatThreads) {
-    const unsigned long long kx = keys[p], ky = keys[n + p];
-    for (int q = 0; q < Q; ++q) {
-      const unsigned long long k = st->coord[q] ? ky : kx;
-      // pass 0 compares nothing (a shift by 64 is undefined: test the pass instead)
-      if (pass == 0 || (k >> (shift + 8)) == st->prefix[q]) atomicAdd(&s_h[q][(k >> shift) & 255], 1u);
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < Q * 256; i += kFlatThreads) {
-    const unsigned v = s_h[i >> 8][i & 255];
-    if (v) atomicAdd(hist + i, v);
-  }
-}
-
-// one lane per query: the bin that holds the wanted rank extends the prefix; the histogram is cleared for the next pass
-__global__ void k_select_pick(SelState* __restrict__ st, int Q, unsigned* __restrict__ hist) {
-  const int q = threadIdx.x;
-  if (q >= Q) return;
-  unsigned* hq = hist + (size_t)q * 256;
-  unsigned long long r = st->rank[q], cum = 0;
-  int bin = 255;
-  for (int b = 0; b < 256; ++b) {
-    if (cum + hq[b] > r) { bin = b; break; }
-    cum += hq[b];
-  }
-  st->prefix[q] = (st->prefix[q] << 8) | (unsigned long long)bin;
-  st->rank[q] = r - cum;
-  for (int b = 0; b < 256; ++b) hq[b] = 0;
-}
-
-__global__ void k_select_values(const SelState* __restrict__ st, int Q, double* __restrict__ out) {
-  const int q = threadIdx.x;
-  if (q < Q) out[q] = key_value(st->prefix[q]);
 }
 
 }  // namespace mcba
@@ -346,58 +276,42 @@ int mcba_flat_ransac(size_t n_points, const double* points, int n_hypotheses, co
 
 int mcba_flat_order_stats(size_t n_points, const double* points, const double* rt12, int n_ranks, const long long* ranks, int device, double* values_out, double* sums_out,
                           unsigned long long* nans_out, double* kernel_ms) {
-  if (n_points < 1 || !points || !rt12 || n_ranks < 0 || 2 * n_ranks > mcba::kMaxQueries || (n_ranks && (!ranks || !values_out)) || !sums_out || !nans_out)
+  if (n_points < 1 || !points || !rt12 || n_ranks < 0 || n_ranks > mcba::kSelMaxRanks || (n_ranks && (!ranks || !values_out)) || !sums_out || !nans_out)
     return fail(MCBA_ERR_ARG, "mcba_flat_order_stats: points >= 1, 0 .. 8 ranks, non-NULL arrays required");
   for (int i = 0; i < n_ranks; ++i)
     if (ranks[i] < 0 || (unsigned long long)ranks[i] >= n_points) return fail(MCBA_ERR_ARG, "mcba_flat_order_stats: rank out of range");
   if (int rc = stateless_device(device)) return rc;
   const size_t n = n_points;
   const size_t nblk = (n + mcba::kFlatThreads - 1) / mcba::kFlatThreads;
-  const int Q = 2 * n_ranks;
-  mcba::SelState st;
-  memset(&st, 0, sizeof(st));
-  for (int c = 0; c < 2; ++c)
-    for (int i = 0; i < n_ranks; ++i) {
-      st.coord[c * n_ranks + i] = c;
-      st.rank[c * n_ranks + i] = (unsigned long long)ranks[i];
-    }
+  const std::vector<unsigned long long> rk(ranks, ranks + n_ranks);
+  std::vector<mcba::SelState> st(2 * (size_t)n_ranks);   // group 0: x, group 1: y
   StatelessCall call;
-  double *d_pts = nullptr, *d_rt = nullptr, *d_ps = nullptr, *d_val = nullptr;
-  unsigned long long *d_keys = nullptr, *d_nan = nullptr;
-  unsigned* d_hist = nullptr;
+  double *d_pts = nullptr, *d_rt = nullptr, *d_xy = nullptr, *d_ps = nullptr;
+  unsigned long long* d_nan = nullptr;
   mcba::SelState* d_st = nullptr;
   HIPCHK(call.alloc(&d_pts, 3 * n));
   HIPCHK(call.alloc(&d_rt, 12));
-  HIPCHK(call.alloc(&d_keys, 2 * n));
+  HIPCHK(call.alloc(&d_xy, 2 * n));
   HIPCHK(call.alloc(&d_ps, 2 * nblk));
   HIPCHK(call.alloc(&d_nan, 2));
-  HIPCHK(call.alloc(&d_hist, (size_t)mcba::kMaxQueries * 256));
-  HIPCHK(call.alloc(&d_st, 1));
-  HIPCHK(call.alloc(&d_val, (size_t)mcba::kMaxQueries));
+  HIPCHK(call.alloc(&d_st, st.size()));
   HIPCHK(hipMemcpy(d_pts, points, 3 * n * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d_rt, rt12, 12 * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_st, &st, sizeof(st), hipMemcpyHostToDevice));
   HIPCHK(hipMemset(d_nan, 0, 2 * sizeof(unsigned long long)));
-  HIPCHK(hipMemset(d_hist, 0, (size_t)mcba::kMaxQueries * 256 * sizeof(unsigned)));
   HIPCHK(call.start());
-  mcba::k_flat_transform<<<dim3((unsigned)nblk), dim3(mcba::kFlatThreads)>>>(d_pts, n, d_rt, d_keys, d_ps, d_nan);
+  mcba::k_flat_transform<<<dim3((unsigned)nblk), dim3(mcba::kFlatThreads)>>>(d_pts, n, d_rt, d_xy, d_ps, d_nan);
   HIPCHK(hipGetLastError());
-  if (Q > 0) {
-    const unsigned hblk = (unsigned)(nblk < 2048 ? nblk : 2048);  // grid-stride beyond 2048 blocks: fewer global histogram flushes
-    for (int pass = 0; pass < 8; ++pass) {
-      mcba::k_select_hist<<<dim3(hblk), dim3(mcba::kFlatThreads)>>>(d_keys, n, d_st, Q, pass, d_hist);
-      HIPCHK(hipGetLastError());
-      mcba::k_select_pick<<<dim3(1), dim3(64)>>>(d_st, Q, d_hist);
-      HIPCHK(hipGetLastError());
-    }
-    mcba::k_select_values<<<dim3(1), dim3(64)>>>(d_st, Q, d_val);
+  if (n_ranks > 0) {
+    // (the select skips NaNs, so a coordinate that holds one has fewer values than a rank may assume: the caller reports NaN for it)
+    mcba::launch_select(nullptr, d_xy, nullptr, n, 2 /* groups: x, y */, 1 /* no frame mask */, d_st, 1 /* either sign */, rk.data(), n_ranks);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(call.stop(kernel_ms));
   std::vector<double> ps(2 * nblk);
   HIPCHK(hipMemcpy(ps.data(), d_ps, 2 * nblk * sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(nans_out, d_nan, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  if (Q > 0) HIPCHK(hipMemcpy(values_out, d_val, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost));
+  if (n_ranks > 0) HIPCHK(hipMemcpy(st.data(), d_st, st.size() * sizeof(mcba::SelState), hipMemcpyDeviceToHost));
+  for (size_t q = 0; q < st.size(); ++q) values_out[q] = mcba::sel_value(st[q]);
   for (int c = 0; c < 2; ++c) {  // the per-block sums, in block order
     double s = 0.0;
     for (size_t b = 0; b < nblk; ++b) s += ps[2 * b + c];

@@ -47,7 +47,8 @@ struct mcba_handle {
   double *red_own = nullptr, *red = nullptr;
   double *jac = nullptr, *res = nullptr;
   double *err = nullptr, *dmean = nullptr, *dfull = nullptr, *repro = nullptr, *trans = nullptr, *und = nullptr;  // pre-filter / diagnostics (lazy)
-  unsigned char *sel = nullptr, *fmask = nullptr;
+  mcba::SelState* sel = nullptr;   // the radix select's states (two per camera: per-camera medians)
+  unsigned char* fmask = nullptr;
   // mcba_prefilter (the selection on the device): scratch state, per-frame status / worst mean error, the packed result and its pinned landing place
   unsigned char *pf_state = nullptr, *pf_status = nullptr, *pf_packed = nullptr, *pf_host = nullptr;
   double* pf_worst = nullptr;
@@ -59,7 +60,8 @@ struct mcba_handle {
   // calibrate() on the device (mcba_calib_*): intrinsics [C][9], every view's board pose [C][6][Fpad] (NaN = none), per-view flags, and
   // scratch that grows with the call (view lists, outputs, pairwise transforms, select states, world-frame poses)
   double *cal_intr = nullptr, *cal_poses_t = nullptr, *cal_out = nullptr, *cal_rel = nullptr, *cal_world = nullptr;
-  unsigned char *cal_valid = nullptr, *cal_nit = nullptr, *cal_sel = nullptr;
+  unsigned char *cal_valid = nullptr, *cal_nit = nullptr;
+  mcba::SelState* cal_sel = nullptr;
   int* cal_views = nullptr;
   size_t cal_out_cap = 0, cal_rel_cap = 0, cal_sel_cap = 0, cal_views_cap = 0;
   bool have_cal_poses = false;

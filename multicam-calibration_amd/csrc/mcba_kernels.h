@@ -8,6 +8,7 @@
 #define MCBA_FB 40    // per frame: L 21 (diagonal slots hold 1 / L_ii) | z 6 | g_f 6 | D_f 6 | pad
 
 #include "mcba_lm_state.h"
+#include "mcba_math.h"
 
 namespace mcba {
 // Double-buffered operands (parameter slots, linearisation records) and the damping are chosen either from host
@@ -125,10 +126,28 @@ void launch_sp_solve(hipStream_t st, const SolveArgs& a, int* ctl, double* damp,
 // pre-filter, frame subsets, undistortion, reprojection diagnostics (mcba_diag.hip)
 void launch_frame_err(hipStream_t st, const double* obs_t, const double* obj, const double* x, double* err, double* mean_cf, double* full_cf, int C, int F, int N, int Fpad,
                       void* prefilter_state = nullptr);   // non-NULL: the launch also zeroes the selection's state (launch_prefilter_select(..., state_cleared = true) follows)
-size_t select_state_bytes(int groups);  // per group: u64 prefix, rank, count, value (bit pattern of the selected double) + a 256-bin histogram
-void launch_select(hipStream_t st, const double* v, const unsigned char* fmask, size_t per_group, int groups, int Fpad, void* sel, int upper,
-                   int skey = 0);   // != 0: values of either sign (compared through an order-preserving key); 0: values >= +0 (the pre-filter's errors)
-int launch_select_hist(hipStream_t st, const double* v, const unsigned char* fmask, size_t per_group, int Fpad, void* sel, unsigned long long prefix, int pass, unsigned int* hist256);
+// exact order statistics by radix select (mcba_diag.hip): one state per wanted rank, eight passes of one byte over the bit patterns
+struct SelState {
+  unsigned long long prefix;   // the leading 8 x pass bits of the selected value's key
+  unsigned long long rank;     // the wanted rank among the group's non-NaN values (set at pass 0), then inside the prefix's bin
+  unsigned long long count;    // non-NaN values of the group
+  unsigned long long value;    // bit pattern of the selected double (after the last pass)
+  unsigned int hist[256];      // the pass' histogram (cleared by the pick)
+};
+constexpr int kSelMaxRanks = 8;   // states per group
+MCBA_HD double sel_value(const SelState& s) { return __builtin_bit_cast(double, s.value); }
+// np.median from the states of the two middle ranks: the mean of the two middle values; NaN for a group without values
+MCBA_HD double sel_median(const SelState& lo, const SelState& hi) {
+  const double m = 0.5 * (sel_value(lo) + sel_value(hi));
+  return lo.count ? m : __builtin_nan("");
+}
+// `groups` equal slices of v (per_group doubles each; frame = index % Fpad for fmask, which may be nullptr), NaNs skipped.  Group g owns
+// the states sel[g * nranks .. (g + 1) * nranks) (nranks <= kSelMaxRanks); state j of a group selects rank ranks[j] -- ranks == nullptr:
+// medians, two states per group for the lower and the upper middle rank.  After the call every state's count and value are valid.
+void launch_select(hipStream_t st, const double* v, const unsigned char* fmask, size_t per_group, int groups, int Fpad, SelState* sel,
+                   int skey,   // != 0: values of either sign (compared through an order-preserving key); 0: values >= +0 (the pre-filter's errors)
+                   const unsigned long long* ranks = nullptr, int nranks = 0);
+int launch_select_hist(hipStream_t st, const double* v, const unsigned char* fmask, size_t per_group, int Fpad, SelState* sel, unsigned long long prefix, int pass, unsigned int* hist256);
 // the pre-filter's selection on the device (mcba_prefilter): see mcba_diag.hip
 size_t prefilter_state_bytes();
 void launch_prefilter_select(hipStream_t st, const double* err, const double* mean_cf, const double* full_cf, unsigned char* fmask, unsigned char* status, double* worst, void* state,
@@ -152,7 +171,7 @@ void launch_pnp(hipStream_t st, int mode, const double* obs_t, const double* obj
 // poses addressed as p[c * sc + f * sf + k * sk]; rel [n_edges][6][Fpad]; world [C][6][Fpad] scratch; out (F, 6)
 void launch_zhang(hipStream_t st, const double* H, const unsigned char* ok, const int* views, int nviews, const double* sizes, int C, double* intr9, unsigned char* closed);
 void launch_pose_pairs(hipStream_t st, const double* poses, size_t sc, size_t sf, size_t sk, const int* edges, int n_edges, int F, int Fpad, double* rel);
-void launch_pose_chain(hipStream_t st, const void* sel, size_t sel_state_bytes, const int* edges, int n_edges, int root, int C, double* ext, double* transforms, double* counts);
+void launch_pose_chain(hipStream_t st, const SelState* sel, const int* edges, int n_edges, int root, int C, double* ext, double* transforms, double* counts);   // sel: the medians of launch_select
 void launch_pose_consensus(hipStream_t st, const double* poses, size_t sc, size_t sf, size_t sk, const double* ext, int C, int F, int Fpad, double* world, double* out);
 // triangulation (mcba_triangulate.hip): up to 8 cameras; P = K [R | t] row-major 3x4, K = (fx, fy, cx, cy), dist = (k1 k2 p1 p2 k3)
 struct TriCams {

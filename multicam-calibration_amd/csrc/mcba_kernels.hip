@@ -94,11 +94,6 @@ __device__ __forceinline__ void wave_reduce_scatter(double* v, double (&out)[3],
     static_assert(LEVEL == 4 || LEVEL == 5, "K must be 48 or 96");
   }
 }
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
 // value known to be wave-uniform -> SGPR pair (frees two VGPRs and a ds_read per use)
 __device__ __forceinline__ double uni(double v) {
   union { double d; int i[2]; } u;

@@ -255,10 +255,10 @@ __global__ __launch_bounds__(64) void k_pose_pairs(PoseView pv, const int* __res
 }
 
 // calibration.py:226-235 on the device: the medians of the tree's pairwise transforms (the two middle order statistics the radix select left in
-// its states: word 2 = count, word 3 = the value's bits, `stride` words per state, two states per component) chained from the root --
+// its states, two states per component) chained from the root --
 // T_world->c2 = T_c1->c2 T_world->c1, edges ordered so that c1 is placed before c2 (the caller checks) -- into ext [C][6]; transforms [E][6] and
 // counts [E] (frames the pair shares) for the caller.  One wavefront; only the C - 1 products of the chain itself run on one lane.
-__global__ __launch_bounds__(64) void k_pose_chain(const unsigned long long* __restrict__ sel, int stride, const int* __restrict__ edges, int n_edges, int root, int C,
+__global__ __launch_bounds__(64) void k_pose_chain(const SelState* __restrict__ sel, const int* __restrict__ edges, int n_edges, int root, int C,
                                                    double* __restrict__ ext, double* __restrict__ transforms, double* __restrict__ counts) {
   __shared__ double Tm[40][12];   // world -> camera: R (9, row-major), t (3)
   __shared__ double Te[39][12];   // the edges' transforms as matrices
@@ -267,12 +267,10 @@ __global__ __launch_bounds__(64) void k_pose_chain(const unsigned long long* __r
   const double nan = __builtin_nan("");
   // the medians: lane = (edge, component) -- every lane's loads in flight together, not 12 E round trips of one lane
   for (int i = lane; i < 6 * n_edges; i += 64) {
-    const unsigned long long cnt = sel[(size_t)(2 * i) * stride + 2];
-    const unsigned long long a = sel[(size_t)(2 * i) * stride + 3], b = sel[(size_t)(2 * i + 1) * stride + 3];
-    const double m = cnt ? 0.5 * (__longlong_as_double((long long)a) + __longlong_as_double((long long)b)) : nan;   // np.median: the mean of the two middle values
+    const double m = sel_median(sel[2 * i], sel[2 * i + 1]);
     med[i] = m;
     transforms[i] = m;
-    if (i % 6 == 0) counts[i / 6] = (double)cnt;
+    if (i % 6 == 0) counts[i / 6] = (double)sel[2 * i].count;
   }
   __syncthreads();
   for (int e = lane; e < n_edges; e += 64) {   // lane = edge: its rotation matrix
@@ -409,8 +407,8 @@ void launch_pose_pairs(hipStream_t st, const double* poses, size_t sc, size_t sf
   k_pose_pairs<<<dim3(Fpad / 64, n_edges), dim3(64), 0, st>>>(PoseView{poses, sc, sf, sk}, edges, F, Fpad, rel);
 }
 
-void launch_pose_chain(hipStream_t st, const void* sel, size_t sel_state_bytes, const int* edges, int n_edges, int root, int C, double* ext, double* transforms, double* counts) {
-  k_pose_chain<<<dim3(1), dim3(64), 0, st>>>(static_cast<const unsigned long long*>(sel), (int)(sel_state_bytes / 8), edges, n_edges, root, C, ext, transforms, counts);
+void launch_pose_chain(hipStream_t st, const SelState* sel, const int* edges, int n_edges, int root, int C, double* ext, double* transforms, double* counts) {
+  k_pose_chain<<<dim3(1), dim3(64), 0, st>>>(sel, edges, n_edges, root, C, ext, transforms, counts);
 }
 
 void launch_pose_consensus(hipStream_t st, const double* poses, size_t sc, size_t sf, size_t sk, const double* ext, int C, int F, int Fpad, double* world, double* out) {

@@ -29,12 +29,6 @@
 
 namespace mcba {
 
-__device__ __forceinline__ double sp_wave_max(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
 // ---------------------------------------------------------------- visibility: seen[c * F + f] = any finite scalar in (c, f)
 __global__ __launch_bounds__(256) void k_sp_seen(const double* __restrict__ obs_raw, unsigned char* __restrict__ seen, int C, int F, int N) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -111,7 +105,7 @@ __global__ __launch_bounds__(64) void k_sp_factor(Sel sl, const double* __restri
 #pragma unroll
     for (int k = 0; k < 40; k += 2) *reinterpret_cast<double2*>(fbp + k) = make_double2(o[k], o[k + 1]);
   }
-  const double wm = sp_wave_max(gmax), wn = wave_sum(nfail);
+  const double wm = wave_max(gmax), wn = wave_sum(nfail);
   if (threadIdx.x == 0) { fpart[2 * blockIdx.x] = wm; fpart[2 * blockIdx.x + 1] = wn; }
 }
 

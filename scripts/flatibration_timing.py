@@ -105,7 +105,7 @@ def main():
         for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
             print("== %d frames: %s" % (N, os.path.relpath(f, out_dir)))
             for line in open(f):
-                if line.startswith('"Name"') or any(k in line for k in ("k_floor", "k_ransac", "k_select", "k_flat")):
+                if line.startswith('"Name"') or any(k in line for k in ("k_floor", "k_ransac", "k_sel_", "k_flat")):
                     print(line.rstrip())
     with open(os.path.join(out_dir, "flatibration_timing.json"), "w") as fh:
         json.dump(results, fh, indent=1)
