@@ -16,13 +16,14 @@
 //   k_reproj_diag    `plot_residuals` (viz.py:166-186) without the plotting: distortion-free reprojection of the board,
 //                    least-squares homography from the undistorted detections to the board plane per (camera, frame),
 //                    reprojections mapped through it, distance to the board points.  Lane = (camera, frame).
+// The per-lane arithmetic of the last two (undistort_px, board_homography_fit) is in mcba_geom_math.h, where the host harness checks the same text.
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <math.h>
 #include <string.h>
 #include <algorithm>
 #include "mcba_kernels.h"
-#include "mcba_math.h"
+#include "mcba_geom_math.h"   // undistort_px, board_homography_fit: the per-lane arithmetic (shared with the host harness tests/hostcheck/hostcheck.cpp)
 
 namespace mcba {
 
@@ -569,24 +570,7 @@ __global__ __launch_bounds__(256) void k_seen_bits(const double* __restrict__ ob
   if ((threadIdx.x & 63) == 0 && i < count) words[i >> 6] = __builtin_bswap64(__brevll(b));  // (the last block's wavefronts past the end own no word)
 }
 
-// ---------------------------------------------------------------- undistortion (cv2.undistortPoints(src, K, dist, None, K))
-__device__ __forceinline__ void undistort_px(double u, double v, double fx, double fy, double cx, double cy, const double* k, int iters, double& uo, double& vo) {
-  const double x0 = (u - cx) / fx, y0 = (v - cy) / fy;
-  double x = x0, y = y0;
-  bool stop = false;   // OpenCV's guard (cvUndistortPointsInternal): icdist < 0 -> the unrefined point, no further iterations
-  for (int it = 0; it < iters; ++it) {
-    const double r2 = fma(x, x, y * y);
-    const double icdist = 1.0 / fma(fma(fma(k[4], r2, k[1]), r2, k[0]), r2, 1.0);
-    stop = stop || icdist < 0.0;
-    const double dx = fma(2.0 * k[2] * x, y, k[3] * fma(2.0 * x, x, r2));
-    const double dy = fma(k[2], fma(2.0 * y, y, r2), 2.0 * k[3] * x * y);
-    x = stop ? x0 : (x0 - dx) * icdist;
-    y = stop ? y0 : (y0 - dy) * icdist;
-  }
-  uo = fma(x, fx, cx);
-  vo = fma(y, fy, cy);
-}
-
+// ---------------------------------------------------------------- undistortion (cv2.undistortPoints(src, K, dist, None, K): undistort_px, mcba_geom_math.h)
 struct UndistCam {
   double K[4];
   double dist[5];
@@ -605,43 +589,6 @@ __global__ __launch_bounds__(256) void k_undistort(const double2* __restrict__ u
 }
 
 // ---------------------------------------------------------------- reprojection diagnostics
-// 8x8 symmetric positive definite solve in registers (upper triangle packed row-major), in place on b
-__device__ __forceinline__ int tri8(int i, int j) { return i * 8 - (i * (i - 1)) / 2 + (j - i); }
-__device__ __forceinline__ bool chol_solve8(double* A, double* b) {
-  bool ok = true;
-  // A = L L^T, L stored over the upper triangle as L^T (row i = column i of L)
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-#pragma unroll
-    for (int j = i; j < 8; ++j) {
-      double s = A[tri8(i, j)];
-#pragma unroll
-      for (int k = 0; k < i; ++k) s = fma(-A[tri8(k, i)], A[tri8(k, j)], s);
-      if (j == i) {
-        ok = ok && s > 0.0;
-        A[tri8(i, i)] = sqrt(s > 0.0 ? s : 1.0);
-      } else {
-        A[tri8(i, j)] = s / A[tri8(i, i)];
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    double s = b[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) s = fma(-A[tri8(k, i)], b[k], s);
-    b[i] = s / A[tri8(i, i)];
-  }
-#pragma unroll
-  for (int i = 7; i >= 0; --i) {
-    double s = b[i];
-#pragma unroll
-    for (int k = i + 1; k < 8; ++k) s = fma(-A[tri8(i, k)], b[k], s);
-    b[i] = s / A[tri8(i, i)];
-  }
-  return ok;
-}
-
 struct DiagCams {   // distortion of the cameras c0 .. c0 + 39 of one launch (the solver's parameter vector carries k1, k2 only)
   double dist[40][5];
   int c0;
@@ -652,9 +599,7 @@ struct DiagCams {   // distortion of the cameras c0 .. c0 + 39 of one launch (th
 // detections.  Outputs (C,F,N,2): repro (distortion-free projection), trans (reprojection mapped to the board plane; NaN for
 // (camera, frame) pairs with an incomplete detection), and err [C][N][Fpad] = |trans - board| (NaN likewise) for the
 // per-camera medians.
-// Homography: normalised inhomogeneous DLT (h33 = 1; 8x8 normal equations) as the start, then Levenberg-Marquardt on the
-// transfer error in the board plane -- the quantity OpenCV's findHomography refines -- with a FIXED number of rounds (every
-// lane runs the same instruction stream; a rejected step only raises that lane's damping).  24 rounds: the large-residual frames converge
+// Homography: board_homography_fit (mcba_geom_math.h) with a FIXED number of rounds.  24 rounds: the large-residual frames converge
 // linearly, and 16 left some 1e-5 mm short of the minimiser.
 __global__ __launch_bounds__(256) void k_reproj_diag(const double2* __restrict__ obs_t, const double* __restrict__ obj, const double* __restrict__ x, DiagCams dc, const double* __restrict__ bn,
                                                      double2* __restrict__ und, double* __restrict__ repro, double* __restrict__ trans, double* __restrict__ err, int C, int F, int N, int Fpad, int nfb, int iters,
@@ -716,78 +661,7 @@ __global__ __launch_bounds__(256) void k_reproj_diag(const double2* __restrict__
     Y = (obj[3 * p + 1] - bmy) * bs;
   };
   double h[8];
-  {  // start: rows [s 1 0 0 0 -X s] h = X, [0 0 0 s 1 -Y s] h = Y  (s = (sx, sy))
-    double A[36], b[8];
-#pragma unroll
-    for (int i = 0; i < 36; ++i) A[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) b[i] = 0.0;
-    for (int p = 0; p < N; ++p) {
-      double sx, sy, X, Y;
-      src(p, sx, sy, X, Y);
-      const double r0[8] = {sx, sy, 1.0, 0.0, 0.0, 0.0, -X * sx, -X * sy};
-      const double r1[8] = {0.0, 0.0, 0.0, sx, sy, 1.0, -Y * sx, -Y * sy};
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-#pragma unroll
-        for (int j = i; j < 8; ++j) A[tri8(i, j)] = fma(r0[i], r0[j], fma(r1[i], r1[j], A[tri8(i, j)]));
-        b[i] = fma(r0[i], X, fma(r1[i], Y, b[i]));
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) A[tri8(i, i)] = complete ? A[tri8(i, i)] : 1.0;
-    const bool ok = chol_solve8(A, b);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) h[i] = ok ? b[i] : ((i == 0 || i == 4) ? 1.0 : 0.0);  // degenerate detection: start from the identity
-  }
-  auto transfer_error = [&](const double* hh) {
-    double e = 0.0;
-    for (int p = 0; p < N; ++p) {
-      double sx, sy, X, Y;
-      src(p, sx, sy, X, Y);
-      const double iw = 1.0 / fma(hh[6], sx, fma(hh[7], sy, 1.0));
-      const double ex = X - fma(hh[0], sx, fma(hh[1], sy, hh[2])) * iw, ey = Y - fma(hh[3], sx, fma(hh[4], sy, hh[5])) * iw;
-      e = fma(ex, ex, fma(ey, ey, e));
-    }
-    return e;
-  };
-  double e_cur = transfer_error(h), mu = 1e-4;
-  for (int it = 0; it < lm_iters; ++it) {
-    double A[36], g[8];
-#pragma unroll
-    for (int i = 0; i < 36; ++i) A[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) g[i] = 0.0;
-    for (int p = 0; p < N; ++p) {
-      double sx, sy, X, Y;
-      src(p, sx, sy, X, Y);
-      const double iw = 1.0 / fma(h[6], sx, fma(h[7], sy, 1.0));
-      const double px = fma(h[0], sx, fma(h[1], sy, h[2])) * iw, py = fma(h[3], sx, fma(h[4], sy, h[5])) * iw;
-      const double r0[8] = {sx * iw, sy * iw, iw, 0.0, 0.0, 0.0, -px * sx * iw, -px * sy * iw};
-      const double r1[8] = {0.0, 0.0, 0.0, sx * iw, sy * iw, iw, -py * sx * iw, -py * sy * iw};
-      const double ex = X - px, ey = Y - py;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-#pragma unroll
-        for (int j = i; j < 8; ++j) A[tri8(i, j)] = fma(r0[i], r0[j], fma(r1[i], r1[j], A[tri8(i, j)]));
-        g[i] = fma(r0[i], ex, fma(r1[i], ey, g[i]));
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) A[tri8(i, i)] = complete ? A[tri8(i, i)] * (1.0 + mu) : 1.0;   // Marquardt damping
-    const bool ok = chol_solve8(A, g);
-    double hn[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) hn[i] = h[i] + (ok ? g[i] : 0.0);
-    const double e_new = transfer_error(hn);
-    // (not worse beyond the round-off of the sum: near the optimum the decrease left is below it, and a strict test stalls each lane
-    //  wherever its round-off says -- up to 1e-5 mm from the minimiser on the board plane; a tolerant one lets the Gauss-Newton steps finish)
-    const bool accept = ok && e_new <= e_cur * (1.0 + 1e-12);   // (NaN compares false)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) h[i] = accept ? hn[i] : h[i];
-    e_cur = accept ? e_new : e_cur;
-    mu = accept ? fmax(mu * 0.1, 1e-15) : fmin(mu * 10.0, 1e8);
-  }
+  board_homography_fit(src, N, complete, lm_iters, h);
   // last pass: distortion-free projection of the board (viz.py:166-168) mapped through the homography, distance to the board
   const double nan = __builtin_nan("");
   double* ep = err + (size_t)c * N * Fpad + f;

@@ -1,9 +1,10 @@
 // mcba_pnp_math.h -- the per-view arithmetic of csrc/mcba_pnp.hip (calibrate()'s homography start, pose start and per-view Levenberg-Marquardt:
 // what the reference asks of cv2.calibrateCamera's closed form and of cv2.solvePnP, calibration.py:68, :108), written once for the GPU kernel
 // (one lane = one view; the kernel owns the wave-uniform loops) and for the host harness (tests/hostcheck/hostcheck.cpp: the same text compiled
-// with g++, also under ASan + UBSan, checked against oracle/calibration_oracle.py in the GPU-less tier).
+// with g++, also under ASan + UBSan, checked against oracle/calibration_oracle.py in the GPU-less tier).  The packed Cholesky solve chol_solve<N> comes
+// from mcba_geom_math.h.
 #pragma once
-#include "mcba_math.h"
+#include "mcba_geom_math.h"   // tri<N>, chol_solve<N>
 
 namespace mcba {
 
@@ -14,6 +15,7 @@ struct Cam9 { double fx, fy, cx, cy, k1, k2, p1, p2, k3; };
 MCBA_HD Cam9 load_cam9(const double* __restrict__ p) { return Cam9{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8]}; }
 
 // pixel -> undistorted normalised coordinates: OpenCV's undistortPoints iteration x <- (x_d - tangential(x)) / radial(x)
+// (undistort_px in mcba_geom_math.h is the other one, separate on purpose: IEEE division, OpenCV's guard against a negative radial factor, pixel output)
 MCBA_HD void undistort_norm(double u, double v, const Cam9& k, double ifx, double ify, int iters, double& x, double& y) {
   // (reciprocals by fast_rcp -- hardware estimate + one cubic step, 1.1e-16: a quarter of the instructions of the two IEEE divisions per round,
   //  which were a fifth of this kernel's instruction stream; ifx / ify are the caller's 1 / fx, 1 / fy)
@@ -55,44 +57,6 @@ MCBA_HD void bwd3(const double* L, const double* z, double* y) {   // L^T y = z
 MCBA_HD double sym3(const double* S, int i, int j) {
   const int a = i < j ? i : j, b = i < j ? j : i;
   return S[a == 0 ? b : (a == 1 ? 2 + b : 5)];
-}
-
-// ---- packed symmetric N x N (upper triangle row-major): Cholesky solve in registers
-template <int N>
-MCBA_HD constexpr int tri(int i, int j) { return i * N - (i * (i - 1)) / 2 + (j - i); }
-template <int N>
-MCBA_HD bool chol_solve(double* A, double* b) {
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-#pragma unroll
-    for (int j = i; j < N; ++j) {
-      double s = A[tri<N>(i, j)];
-#pragma unroll
-      for (int k = 0; k < i; ++k) s = fma(-A[tri<N>(k, i)], A[tri<N>(k, j)], s);
-      if (j == i) {
-        ok = ok && s > 0.0;
-        A[tri<N>(i, i)] = sqrt(s > 0.0 ? s : 1.0);
-      } else {
-        A[tri<N>(i, j)] = s / A[tri<N>(i, i)];
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    double s = b[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) s = fma(-A[tri<N>(k, i)], b[k], s);
-    b[i] = s / A[tri<N>(i, i)];
-  }
-#pragma unroll
-  for (int i = N - 1; i >= 0; --i) {
-    double s = b[i];
-#pragma unroll
-    for (int k = i + 1; k < N; ++k) s = fma(-A[tri<N>(i, k)], b[k], s);
-    b[i] = s / A[tri<N>(i, i)];
-  }
-  return ok;
 }
 
 // rotation matrix -> rotation vector by the reference's formula (geometry.py:38-56: theta = arccos((tr - 1) / 2), axis from the skew part);

@@ -6,62 +6,14 @@
 // nan-median over the pairs.  Everything stays in registers; the only memory traffic is 16 B in per (camera, point) and
 // 24 B out per point, the arithmetic (~3 k FP64 instructions per pair) makes the kernel FP64-VALU bound.
 // The camera count is a template parameter so that the per-camera / per-pair arrays are register arrays.
+// The per-lane arithmetic (undistort_px, null_vector4, triangulate_pair, nan_median) is in mcba_geom_math.h, where the host harness checks the same text.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <algorithm>
 #include "mcba_kernels.h"
-#include "mcba_math.h"
+#include "mcba_geom_math.h"   // undistort_px, null_vector4, triangulate_pair, nan_median: the per-lane arithmetic (shared with the host harness tests/hostcheck/hostcheck.cpp)
 
 namespace mcba {
-
-// right singular vector of the smallest singular value of the 4x4 matrix whose COLUMNS are a[0..3] (each a 4-vector)
-__device__ __forceinline__ void null_vector4(double (&a)[4][4], double (&x)[4]) {
-  double v[4][4];  // v[k] = column k of V
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 7; ++sweep) {  // quadratic convergence: 4-5 sweeps reach FP64 for a 4x4; fixed count, branch-free
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) {
-        double alpha = 0.0, beta = 0.0, gamma = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { alpha = fma(a[p][k], a[p][k], alpha); beta = fma(a[q][k], a[q][k], beta); gamma = fma(a[p][k], a[q][k], gamma); }
-        const bool rot = gamma * gamma > 1e-32 * alpha * beta;  // already orthogonal to FP64: identity
-        const double g = rot ? gamma : 1.0;
-        const double zeta = (beta - alpha) * fast_rcp(2.0 * g);
-        const double az = fabs(zeta);
-        double t = fast_rcp(az + sqrt(fma(zeta, zeta, 1.0)));
-        t = zeta < 0.0 ? -t : t;
-        t = rot ? t : 0.0;
-        const double c = fast_rsqrt(fma(t, t, 1.0)), s = c * t;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const double ap = a[p][k], aq = a[q][k];
-          a[p][k] = fma(c, ap, -(s * aq));
-          a[q][k] = fma(s, ap, c * aq);
-          const double vp = v[p][k], vq = v[q][k];
-          v[p][k] = fma(c, vp, -(s * vq));
-          v[q][k] = fma(s, vp, c * vq);
-        }
-      }
-  }
-  double best = 1e300;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) x[k] = 0.0;
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    double nrm = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) nrm = fma(a[p][k], a[p][k], nrm);
-    const bool take = nrm < best;
-    best = take ? nrm : best;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) x[k] = take ? v[p][k] : x[k];
-  }
-}
 
 template <int C>
 __global__ __launch_bounds__(256) void k_triangulate(const double2* __restrict__ uvs, const TriCams cams, double* __restrict__ out, size_t npts, int iters) {
@@ -74,22 +26,7 @@ __global__ __launch_bounds__(256) void k_triangulate(const double2* __restrict__
   for (int c = 0; c < C; ++c) {
     const double2 o = uvs[(size_t)c * npts + p];  // (C, P) pairs: consecutive lanes, consecutive points
     ok[c] = o.x == o.x && o.y == o.y;
-    const double fx = cams.K[c][0], fy = cams.K[c][1], cx = cams.K[c][2], cy = cams.K[c][3];
-    const double k1 = cams.dist[c][0], k2 = cams.dist[c][1], p1 = cams.dist[c][2], p2 = cams.dist[c][3], k3 = cams.dist[c][4];
-    const double x0 = (o.x - cx) / fx, y0 = (o.y - cy) / fy;
-    double x = x0, y = y0;
-    bool stop = false;   // OpenCV's guard: icdist < 0 -> the unrefined point (mcba_diag.hip, undistort_px)
-    for (int it = 0; it < iters; ++it) {
-      const double r2 = fma(x, x, y * y);
-      const double icdist = 1.0 / fma(fma(fma(k3, r2, k2), r2, k1), r2, 1.0);
-      stop = stop || icdist < 0.0;
-      const double dx = fma(2.0 * p1 * x, y, p2 * fma(2.0 * x, x, r2));
-      const double dy = fma(p1, fma(2.0 * y, y, r2), 2.0 * p2 * x * y);
-      x = stop ? x0 : (x0 - dx) * icdist;
-      y = stop ? y0 : (y0 - dy) * icdist;
-    }
-    ux[c] = fma(x, fx, cx);
-    uy[c] = fma(y, fy, cy);
+    undistort_px(o.x, o.y, cams.K[c][0], cams.K[c][1], cams.K[c][2], cams.K[c][3], cams.dist[c], iters, ux[c], uy[c]);
   }
   double X[NP], Y[NP], Z[NP];
   int n = 0;
@@ -99,6 +36,9 @@ __global__ __launch_bounds__(256) void k_triangulate(const double2* __restrict__
     for (int i = 0; i < C; ++i)
 #pragma unroll
       for (int j = i + 1; j < C; ++j, ++k) {
+        // (triangulate_pair's text, kept inline HERE: called as a function -- even with only the part after the 4x4 system in it -- the same
+        //  operations are scheduled with every pair's registers live at once: C = 4 drops from 3 waves per SIMD to 1, C = 5 spills 636 B per lane.
+        //  k_triangulate_wave and the host harness call the function.)
         double a[4][4];  // a[col][row]
 #pragma unroll
         for (int col = 0; col < 4; ++col) {
@@ -128,22 +68,7 @@ __global__ __launch_bounds__(256) void k_triangulate(const double2* __restrict__
         n += keep ? 1 : 0;
       }
   }
-  // per-coordinate nan-median: sort (odd-even transposition network, NP passes), pick the middle (or the mean of two)
-  auto median = [&](double (&v)[NP]) {
-#pragma unroll
-    for (int pass = 0; pass < NP; ++pass)
-#pragma unroll
-      for (int k = pass & 1; k + 1 < NP; k += 2) {
-        const double lo = fmin(v[k], v[k + 1]), hi = fmax(v[k], v[k + 1]);
-        v[k] = lo; v[k + 1] = hi;
-      }
-    double m0 = 0.0, m1 = 0.0;
-    const int i0 = (n - 1) >> 1, i1 = n >> 1;
-#pragma unroll
-    for (int k = 0; k < NP; ++k) { m0 = k == i0 ? v[k] : m0; m1 = k == i1 ? v[k] : m1; }
-    return n > 0 ? 0.5 * (m0 + m1) : __builtin_nan("");
-  };
-  const double mx = median(X), my = median(Y), mz = median(Z);
+  const double mx = nan_median(X, n), my = nan_median(Y, n), mz = nan_median(Z, n);   // per coordinate
   out[3 * p] = mx; out[3 * p + 1] = my; out[3 * p + 2] = mz;
 }
 
@@ -171,58 +96,19 @@ __global__ __launch_bounds__(256) void k_triangulate_wave(const double2* __restr
   for (int c = lane; c < C; c += 64) {
     const double2 o = uvs[(size_t)c * npts + p];
     const TriCam& cm = cams[c];
-    double x0 = (o.x - cm.K[2]) / cm.K[0], y0 = (o.y - cm.K[3]) / cm.K[1];
-    double x = x0, y = y0;
-    bool stop = false;   // OpenCV's guard: icdist < 0 -> the unrefined point
-    for (int it = 0; it < iters; ++it) {
-      const double r2 = fma(x, x, y * y);
-      const double icdist = 1.0 / fma(fma(fma(cm.dist[4], r2, cm.dist[1]), r2, cm.dist[0]), r2, 1.0);
-      stop = stop || icdist < 0.0;
-      const double dx = fma(2.0 * cm.dist[2] * x, y, cm.dist[3] * fma(2.0 * x, x, r2));
-      const double dy = fma(cm.dist[2], fma(2.0 * y, y, r2), 2.0 * cm.dist[3] * x * y);
-      x = stop ? x0 : (x0 - dx) * icdist;
-      y = stop ? y0 : (y0 - dy) * icdist;
-    }
-    ux[c] = fma(x, cm.K[0], cm.K[2]);
-    uy[c] = fma(y, cm.K[1], cm.K[3]);
+    undistort_px(o.x, o.y, cm.K[0], cm.K[1], cm.K[2], cm.K[3], cm.dist, iters, ux[c], uy[c]);
     okf[c] = (o.x == o.x && o.y == o.y) ? 1.0 : 0.0;
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  const double big = 1e300;  // invalid pairs sort to the end
   int nloc = 0;
   for (int k = lane; k < NP; k += 64) {
     // pair k -> (i, j), i < j, in the order (0,1), (0,2), ..., (0,C-1), (1,2), ...
     int i = 0, rem = k;
     while (rem >= C - 1 - i) { rem -= C - 1 - i; ++i; }
     const int j = i + 1 + rem;
-    const TriCam& ci = cams[i];
-    const TriCam& cj = cams[j];
-    double a[4][4];
-#pragma unroll
-    for (int col = 0; col < 4; ++col) {
-      a[col][0] = fma(ux[i], ci.P[8 + col], -ci.P[col]);
-      a[col][1] = fma(uy[i], ci.P[8 + col], -ci.P[4 + col]);
-      a[col][2] = fma(ux[j], cj.P[8 + col], -cj.P[col]);
-      a[col][3] = fma(uy[j], cj.P[8 + col], -cj.P[4 + col]);
-    }
-    const bool both = okf[i] != 0.0 && okf[j] != 0.0;
-    if (!both) {
-#pragma unroll
-      for (int col = 0; col < 4; ++col)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) a[col][r] = col == r ? 1.0 : 0.0;
-    }
-    double xh[4];
-    null_vector4(a, xh);
-    const double iw = 1.0 / xh[3];
-    const double vx = xh[0] * iw, vy = xh[1] * iw, vz = xh[2] * iw;
-    const bool keep = both && fabs(vx) < big && fabs(vy) < big && fabs(vz) < big;   // (see k_triangulate: NaN / infinite results do not count)
-    XYZ[k] = keep ? vx : big;
-    XYZ[NP + k] = keep ? vy : big;
-    XYZ[2 * NP + k] = keep ? vz : big;
-    nloc += keep ? 1 : 0;
+    nloc += triangulate_pair(ux[i], uy[i], cams[i].P, ux[j], uy[j], cams[j].P, okf[i] != 0.0 && okf[j] != 0.0, XYZ[k], XYZ[NP + k], XYZ[2 * NP + k]) ? 1 : 0;
   }
   int n = nloc;
 #pragma unroll

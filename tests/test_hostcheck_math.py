@@ -22,7 +22,7 @@ def P(a):
 def hc():
     src = os.path.join(HERE, "hostcheck", "hostcheck.cpp")
     lib = os.path.join(HERE, "hostcheck", "libhostcheck.so")
-    hdrs = [os.path.join(HERE, "..", "multicam-calibration_amd", "csrc", h) for h in ("mcba_math.h", "mcba_lm.h", "mcba_lm_state.h", "mcba_pnp_math.h")]
+    hdrs = [os.path.join(HERE, "..", "multicam-calibration_amd", "csrc", h) for h in ("mcba_math.h", "mcba_lm.h", "mcba_lm_state.h", "mcba_geom_math.h", "mcba_pnp_math.h")]
     flags = ["-O2"]
     if os.environ.get("MCBA_HOSTCHECK_SANITIZE") == "1":   # the run test_hostcheck_under_sanitizers starts: AddressSanitizer + UBSan build of the same text
         lib = os.path.join(HERE, "hostcheck", "libhostcheck_san.so")
@@ -234,6 +234,142 @@ def test_rotvec_from_matrix_is_the_references_formula(hc):
         hc.hc_rotvec(P(R), P(w))
         want = np.nan_to_num(co.rodrigues_inv(R))   # (the reference's arccos is unclamped: NaN when rounding pushes the trace past 3 -- the kernels clamp)
         np.testing.assert_allclose(w, want, rtol=0, atol=1e-12)
+
+
+# ---- csrc/mcba_geom_math.h (the text of k_undistort, k_triangulate / k_triangulate_wave and of k_reproj_diag's homography fit) against
+# oracle/triangulate_oracle.py and oracle/diagnostics_oracle.py, on the CPU: the inputs and the gates of the GPU tests of those kernels
+def _hc_undistort(hc, uv, K, dist, iters):
+    uv = np.ascontiguousarray(uv, dtype=np.float64)
+    out = np.empty_like(uv)
+    K4 = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
+    d5 = np.zeros(5)
+    d5[: np.size(dist)] = np.ravel(dist)[:5]
+    hc.hc_undistort(uv.size // 2, P(uv), P(K4), P(d5), int(iters), P(out))
+    return out
+
+
+def test_undistort_px_vs_oracle(hc):
+    """test_gpu_diagnostics.py::test_undistort_points_vs_oracle's camera and points at 0, 1, 5 and 20 rounds (atol 1e-10, NaN pattern equal), and
+    the guard cases of test_triangulate_cpu.py::test_oracle_undistort_icdist_guard, bit for bit."""
+    from oracle import triangulate_oracle as tri
+
+    rng = np.random.default_rng(5)
+    K = np.array([[1150.0, 0, 655.0], [0, 1140.0, 500.0], [0, 0, 1]])
+    dist = np.array([-0.12, 0.03, 1e-3, -5e-4, 0.01])
+    uv = rng.uniform(0, 1280, (7, 33, 2))
+    uv[2, 5] = np.nan
+    uv[4, 9, 1] = np.nan
+    for it in (0, 1, 5, 20):
+        got = _hc_undistort(hc, uv, K, dist, it)
+        want = tri.undistort_points(uv, K, dist, it)
+        assert np.array_equal(np.isnan(got), np.isnan(want))
+        print("undistort, %d rounds: max |diff| %.3g px" % (it, np.nanmax(np.abs(got - want))))
+        np.testing.assert_allclose(got, want, rtol=0, atol=1e-10, equal_nan=True)
+    assert np.isnan(got[4, 9]).all() and np.isnan(got[2, 5]).all()
+    np.testing.assert_allclose(_hc_undistort(hc, uv[0], K, np.zeros(5), 5), uv[0], atol=1e-10)   # no distortion: identity
+    # OpenCV's guard: icdist < 0 -> the unrefined point
+    K = np.array([[1000.0, 0, 640.0], [0, 1000.0, 512.0], [0, 0, 1]])
+    k = np.array([-0.5, 0.0, 0.0, 0.0, 0.0])
+    far = np.array([[640.0 + 1000.0 * 1.6, 512.0 + 1000.0 * 1.2], [640.0 - 1000.0 * 2.0, 512.0]])
+    mid = np.array([[640.0 + 1000.0 * 1.35, 512.0]])   # leaves the valid radius at a later round
+    for it in (1, 5, 20):
+        np.testing.assert_array_equal(_hc_undistort(hc, far, K, k, it), far)
+        np.testing.assert_array_equal(_hc_undistort(hc, mid, K, k, it), tri.undistort_points(mid, K, k, it))
+    np.testing.assert_array_equal(_hc_undistort(hc, mid, K, k, 20), mid)
+
+
+def _hc_triangulate(hc, uvs, ext, intr, iters=5):
+    from oracle import triangulate_oracle as tri
+
+    uv = np.ascontiguousarray(np.stack(uvs), dtype=np.float64)
+    C, npts = uv.shape[:2]
+    P12 = np.ascontiguousarray(np.stack([tri.projection_matrix(e, K) for e, (K, _) in zip(ext, intr)]).reshape(C, 12))
+    K4 = np.ascontiguousarray([[K[0, 0], K[1, 1], K[0, 2], K[1, 2]] for K, _ in intr])
+    d5 = np.zeros((C, 5))
+    for c, (_, d) in enumerate(intr):
+        d5[c, : np.size(d)] = np.ravel(d)[:5]
+    out = np.empty((npts, 3))
+    hc.hc_triangulate(C, npts, P(uv), P(P12), P(K4), P(d5), int(iters), P(out))
+    return out
+
+
+@pytest.mark.parametrize("C", [2, 3, 6, 8, 9, 24, 40])
+def test_triangulation_vs_oracle_with_noise_and_missing_views(hc, C):
+    """The scenes and the gate of test_gpu_triangulate.py::test_matches_oracle_with_noise_and_missing_views."""
+    from oracle import triangulate_oracle as tri
+    from test_triangulate_cpu import scene
+
+    uvs, ext, intr, X = scene(C=C, P=1000 if C <= 8 else 300, seed=10 + C, noise=0.3, p_unseen=0.25 if C <= 8 else 0.6)
+    want = tri.triangulate(uvs, ext, intr)
+    got = _hc_triangulate(hc, uvs, ext, intr)
+    assert np.array_equal(np.isnan(got), np.isnan(want))
+    ok = ~np.isnan(want).any(1)
+    print("triangulation, C = %d: max relative difference %.3g" % (C, np.abs(got[ok] - want[ok]).max() / np.abs(want[ok]).max()))
+    assert np.abs(got[ok] - want[ok]).max() <= 1e-8 * np.abs(want[ok]).max()
+
+
+def test_triangulation_random_rigs_and_occlusion_patterns_vs_oracle(hc):
+    """The 40-case sweep and the gate of test_gpu_triangulate.py::test_random_rigs_and_occlusion_patterns_vs_oracle."""
+    from oracle import triangulate_oracle as tri
+    from test_triangulate_cpu import scene
+
+    rng = np.random.default_rng(404)
+    worst = 0.0
+    for it in range(40):
+        C = int(rng.choice([2, 3, 4, 7, 8, 9, 10, 16, 33, 63, 64]))
+        npts = int(rng.choice([1, 2, 63, 64, 65, 130, 257]))
+        uvs, ext, intr, X = scene(C=C, P=npts, seed=1000 + it, noise=float(rng.choice([0.0, 0.3])), p_unseen=float(rng.choice([0.0, 0.3, 0.7, 0.95])))
+        uvs = [u.copy() for u in uvs]
+        for _ in range(int(rng.integers(0, 4))):
+            uvs[int(rng.integers(C))][int(rng.integers(npts)), int(rng.integers(2))] = np.nan
+        want = tri.triangulate(uvs, ext, intr)
+        got = _hc_triangulate(hc, uvs, ext, intr)
+        tag = f"case {it}: C={C} P={npts}"
+        assert got.shape == want.shape == (npts, 3), tag
+        assert np.array_equal(np.isnan(got), np.isnan(want)), tag
+        ok = ~np.isnan(want).any(1)
+        if ok.any():
+            rel = np.abs(got[ok] - want[ok]).max() / max(1.0, np.abs(want[ok]).max())
+            worst = max(worst, rel)
+            assert rel <= 1e-7, (tag, rel)
+    print("triangulation sweep: worst relative difference %.3g" % worst)
+
+
+def _hc_find_homography(hc, src, dst, lm_iters=24):
+    """diagnostics_oracle.find_homography's frame around the fit: Hartley normalisation (centroid, sqrt(2) / mean distance) as the oracle and
+    k_reproj_diag do it, the fit on the normalised points, de-normalised and scaled to H22 = 1."""
+    def norm(pts):
+        c = pts.mean(0)
+        s = np.sqrt(2.0) / np.mean(np.linalg.norm(pts - c, axis=1))
+        return np.ascontiguousarray((pts - c) * s), np.array([[s, 0, -s * c[0]], [0, s, -s * c[1]], [0, 0, 1.0]])
+
+    sn, Ts = norm(src)
+    dn, Td = norm(dst)
+    h, e = np.zeros(8), np.zeros(1)
+    hc.hc_board_homography(len(src), P(sn), P(dn), int(lm_iters), P(h), P(e))
+    H = np.linalg.inv(Td) @ np.append(h, 1.0).reshape(3, 3) @ Ts
+    return H / H[2, 2]
+
+
+def test_board_homography_fit_vs_oracle(hc):
+    """The known map and the noisy map of test_diagnostics_cpu.py::test_homography_recovers_a_known_map with the kernel's 24 rounds: the known
+    map to that test's 1e-11; on noisy maps the transfer error of the oracle's minimiser to 1e-7 relative (the rtol that
+    test_gpu_diagnostics.py::test_reprojection_errors_vs_oracle puts on the medians)."""
+    from oracle import diagnostics_oracle as dgo
+
+    rng = np.random.default_rng(0)
+    H = np.array([[1.1, 0.05, 3.0], [-0.02, 0.9, -2.0], [1e-4, -2e-4, 1.0]])
+    src = rng.uniform(-100, 100, (30, 2))
+    dst = dgo.perspective_transform(src, H)
+    got = _hc_find_homography(hc, src, dst)
+    print("homography, known map: max |diff| %.3g (oracle: %.3g)" % (np.abs(got - H).max(), np.abs(dgo.find_homography(src, dst) - H).max()))
+    np.testing.assert_allclose(got, H, rtol=0, atol=1e-11)
+    for noise in (0.3, 0.5, 3.0):   # (0.3: that test's own draw)
+        dstn = dst + rng.normal(0, noise, dst.shape)
+        err = lambda Hx: np.sum((dgo.perspective_transform(src, Hx) - dstn) ** 2)
+        mine, want = err(_hc_find_homography(hc, src, dstn)), err(dgo.find_homography(src, dstn))
+        print("homography, noise %.1f: transfer error %.17g, oracle %.17g" % (noise, mine, want))
+        assert abs(mine - want) <= 1e-7 * want, (noise, mine, want)
 
 
 def test_hostcheck_under_sanitizers():
