@@ -346,6 +346,28 @@ int mcba_get_frame_gradient(mcba_handle* h, double* host);
  * receives the kernel time measured with HIP events. */
 int mcba_triangulate(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, int iterations, int device, double* out, double* kernel_ms);
 
+/* ---- keypoints through a calibration (reference geometry.py:128-152, :277-325; additive to ABI 7) -------------
+ * Stateless like mcba_triangulate: host arrays in and out, cam12 (C, 12) camera blocks, kernel_ms (may be NULL) the kernels' time.
+ * No limit on the camera count unless stated: the kernels take the camera table in groups of 64.  n_points == 0 returns at once. */
+/* `project_points` for every camera from one upload of points (P, 3): uvs_out (C, P, 2).  dist5 NULL: the reference's model, k1 and k2 of
+ * cam12 (geometry.py:309); dist5 (C, 5): the forward five-coefficient model (k1 k2 p1 p2 k3), what cv2.undistortPoints inverts.  Nothing
+ * special for points behind a camera; NaN in, NaN out. */
+int mcba_project_points(int n_cameras, size_t n_points, const double* points, const double* cam12, const double* dist5, int device, double* uvs_out, double* kernel_ms);
+/* `apply_rigid_transform`: out (P, 3) = R points + t, T12 = R (9, row-major) then t (3). */
+int mcba_rigid_transform(size_t n_points, const double* points, const double* T12, int device, double* out);
+/* Distance in pixels between each camera's detection uvs (C, P, 2) (raw, distorted; NaN = unseen) and the five-coefficient projection of
+ * points (P, 3) (dist5 NULL: k1, k2 of cam12).  errors_out (C, P) or NULL: NaN where the camera does not see the point or the point has a NaN;
+ * median_out (C): np.nanmedian of each row, exact (radix select on the device; NaN for a camera that sees nothing). */
+int mcba_keypoint_errors(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, int device, double* errors_out, double* median_out,
+                         double* kernel_ms);
+/* Per point, Levenberg-Marquardt on 0.5 sum rho(f^2) over X, f = the raw detections minus the five-coefficient projection in the cameras that
+ * see the point; rho / f_scale as scipy.optimize.least_squares, loss 0 .. 4 = linear soft_l1 huber cauchy arctan.  points_in (P, 3) is the
+ * start, or NULL: the median of pairs of mcba_triangulate (with undistort_iterations), computed from the same upload of uvs.  2 <= C <= 64.
+ * points_out (P, 3): NaN where fewer than two cameras see the point or the start has a NaN; never worse than the start in the robust cost.
+ * info_out (P, 4) or NULL: cost at the result, cost at the start, iterations, status (1 converged, 0 iteration limit, -1 too few views). */
+int mcba_triangulate_refine(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points_in, int undistort_iterations, int loss, double f_scale,
+                            int max_iterations, int device, double* points_out, double* info_out, double* kernel_ms);
+
 /* ---- the wrapper's frame pre-filter (bundle_adjustment.py:265-285) and frame subsets ------------------------ */
 /* Reprojection error |observed - predicted| of every detection at x[slot].  Host outputs, both (C,F) row-major:
  * mean_cf = np.nanmean over the board points (NaN where the camera does not see the frame), full_cf = number of

@@ -9,8 +9,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libmcba.so")
 SOURCES = ["mcba_kernels.hip", "mcba_solve.hip", "mcba_triangulate.hip", "mcba_diag.hip", "mcba_calib.hip", "mcba_pnp.hip", "mcba_flat.hip", "mcba_api.hip", "mcba_lm_api.hip",
-           "mcba_prefilter_api.hip", "mcba_calib_api.hip", "mcba_comm_api.hip", "mcba_sparse.hip", "mcba_sparse_api.hip", "mcba_detect.hip"]
-DEPS = SOURCES + ["mcba_gram_finish.inc", "mcba_math.h", "mcba_geom_math.h", "mcba_pnp_math.h", "mcba_detect_math.h", "mcba_device.h", "mcba_backsub.h", "mcba_kernels.h", "mcba_lm.h", "mcba_lm_state.h", "mcba_handle.h", os.path.join("..", "..", "include", "mcba.h")]
+           "mcba_prefilter_api.hip", "mcba_calib_api.hip", "mcba_comm_api.hip", "mcba_sparse.hip", "mcba_sparse_api.hip", "mcba_detect.hip", "mcba_keypoints.hip"]
+DEPS = SOURCES + ["mcba_gram_finish.inc", "mcba_math.h", "mcba_geom_math.h", "mcba_pnp_math.h", "mcba_keypoint_math.h", "mcba_detect_math.h", "mcba_device.h", "mcba_backsub.h", "mcba_kernels.h", "mcba_lm.h", "mcba_lm_state.h", "mcba_handle.h", os.path.join("..", "..", "include", "mcba.h")]
 
 
 # Register-pressure-bound kernels (k_gram keeps 87 FP64 accumulators per lane): LLVM's "unclustered high register pressure"
@@ -68,7 +68,8 @@ def build(force=False, verbose=False, out=None):
         os.replace(tmp, obj)
         return obj
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 2)) as ex:
+    # (at most 16 compilers at once: os.cpu_count() counts the machine, not what a container or a job slot may use)
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 2, 16)) as ex:
         objs = list(ex.map(compile_one, SOURCES))
     with open(flags_file, "w") as fh:
         fh.write(flags_now)

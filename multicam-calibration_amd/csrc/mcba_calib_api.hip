@@ -1,6 +1,7 @@
 // mcba_calib_api.hip -- calibrate() on the device (include/mcba.h: mcba_calib_*, the pose graph mcba_pose_*), and the stateless geometry
-// calls: undistort_points, robust triangulation, the single-camera normal equations.
+// calls: undistort_points, robust triangulation and its refinement, keypoint projection and reprojection errors, the single-camera normal equations.
 #include "mcba_handle.h"
+#include "mcba_keypoint_math.h"   // KpCam, make_kp_cam: the camera table of the keypoint kernels
 
 using namespace mcba_internal;
 
@@ -342,12 +343,14 @@ int mcba_undistort_points(size_t n_points, const double* uvs, const double* K4, 
 
 // ---------------------------------------------------------------------------------------------------------
 // Robust triangulation (reference geometry.py:361-433): stateless; host arrays in, host array out.
-int mcba_triangulate(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, int iterations, int device, double* out, double* kernel_ms) {
-  if (n_cameras < 2 || n_cameras > 64 || !uvs || !cam12 || !out || iterations < 0) return fail(MCBA_ERR_ARG, "mcba_triangulate: 2..64 cameras, non-NULL arrays, iterations >= 0 required");
-  if (n_points == 0) return MCBA_OK;
-  if (int rc = stateless_device(device)) return rc;
-  // per camera {P = K [R | t] (12), K (4), dist (5)}: kernel arguments for the register path (<= 8 cameras), a device
-  // array for the wavefront-per-point path
+// The median-of-pairs kernels' camera operands: per camera {P = K [R | t] (12), K (4), dist (5)} -- kernel arguments for the register path
+// (<= 8 cameras), a device array for the wavefront-per-point path
+struct TriOperands {
+  bool reg_path = true;
+  mcba::TriCams cams;
+  double* d_cams = nullptr;
+};
+static int tri_operands(StatelessCall& call, int n_cameras, const double* cam12, const double* dist5, TriOperands& op) {
   std::vector<double> cam21((size_t)21 * n_cameras, 0.0);
   for (int c = 0; c < n_cameras; ++c) {
     const double* q = cam12 + 12 * c;
@@ -367,32 +370,170 @@ int mcba_triangulate(int n_cameras, size_t n_points, const double* uvs, const do
     if (dist5) for (int k = 0; k < 5; ++k) P[16 + k] = dist5[5 * c + k];
     else { P[16] = q[4]; P[17] = q[5]; }
   }
-  const bool reg_path = n_cameras <= 8;
-  mcba::TriCams cams;
-  memset(&cams, 0, sizeof(cams));
-  if (reg_path)
+  op.reg_path = n_cameras <= 8;
+  memset(&op.cams, 0, sizeof(op.cams));
+  if (op.reg_path) {
     for (int c = 0; c < n_cameras; ++c) {
-      memcpy(cams.P[c], cam21.data() + (size_t)21 * c, 12 * sizeof(double));
-      memcpy(cams.K[c], cam21.data() + (size_t)21 * c + 12, 4 * sizeof(double));
-      memcpy(cams.dist[c], cam21.data() + (size_t)21 * c + 16, 5 * sizeof(double));
+      memcpy(op.cams.P[c], cam21.data() + (size_t)21 * c, 12 * sizeof(double));
+      memcpy(op.cams.K[c], cam21.data() + (size_t)21 * c + 12, 4 * sizeof(double));
+      memcpy(op.cams.dist[c], cam21.data() + (size_t)21 * c + 16, 5 * sizeof(double));
     }
+  } else {
+    HIPCHK(call.alloc(&op.d_cams, cam21.size()));
+    HIPCHK(hipMemcpy(op.d_cams, cam21.data(), cam21.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  return MCBA_OK;
+}
+static int tri_launch(const TriOperands& op, int n_cameras, const double* d_uv, double* d_out, size_t n_points, int iterations) {
+  return op.reg_path ? mcba::launch_triangulate(nullptr, n_cameras, d_uv, op.cams, d_out, n_points, iterations)
+                     : mcba::launch_triangulate_wave(nullptr, n_cameras, d_uv, op.d_cams, d_out, n_points, iterations);
+}
+
+int mcba_triangulate(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, int iterations, int device, double* out, double* kernel_ms) {
+  if (n_cameras < 2 || n_cameras > 64 || !uvs || !cam12 || !out || iterations < 0) return fail(MCBA_ERR_ARG, "mcba_triangulate: 2..64 cameras, non-NULL arrays, iterations >= 0 required");
+  if (n_points == 0) return MCBA_OK;
+  if (int rc = stateless_device(device)) return rc;
   StatelessCall call;
-  double *d_uv = nullptr, *d_out = nullptr, *d_cams = nullptr;
+  double *d_uv = nullptr, *d_out = nullptr;
   const size_t nin = (size_t)2 * n_cameras * n_points;
   HIPCHK(call.alloc(&d_uv, nin));
   HIPCHK(call.alloc(&d_out, 3 * n_points));
   HIPCHK(hipMemcpy(d_uv, uvs, nin * sizeof(double), hipMemcpyHostToDevice));
-  if (!reg_path) {
-    HIPCHK(call.alloc(&d_cams, cam21.size()));
-    HIPCHK(hipMemcpy(d_cams, cam21.data(), cam21.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
+  TriOperands op;
+  if (int rc = tri_operands(call, n_cameras, cam12, dist5, op)) return rc;
   HIPCHK(call.start());
-  const int lrc = reg_path ? mcba::launch_triangulate(nullptr, n_cameras, d_uv, cams, d_out, n_points, iterations)
-                           : mcba::launch_triangulate_wave(nullptr, n_cameras, d_uv, d_cams, d_out, n_points, iterations);
-  if (lrc != 0) return fail(MCBA_ERR_ARG, "mcba_triangulate: unsupported camera count");
+  if (tri_launch(op, n_cameras, d_uv, d_out, n_points, iterations) != 0) return fail(MCBA_ERR_ARG, "mcba_triangulate: unsupported camera count");
   if (int rc = check_launch()) return rc;
   HIPCHK(call.stop(kernel_ms));
   HIPCHK(hipMemcpy(out, d_out, 3 * n_points * sizeof(double), hipMemcpyDeviceToHost));
+  return MCBA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Keypoints through a calibration (reference geometry.py:128-152 apply_rigid_transform, :277-325 project_points): stateless; host arrays in and out.
+// the camera table of the keypoint kernels (mcba_keypoint_math.h: KpCam) in device memory
+static int kp_table(StatelessCall& call, int n_cameras, const double* cam12, const double* dist5, mcba::KpCam** d_cams) {
+  std::vector<mcba::KpCam> tab((size_t)n_cameras);
+  for (int c = 0; c < n_cameras; ++c) mcba::make_kp_cam(cam12 + 12 * c, dist5 ? dist5 + 5 * c : nullptr, tab[c]);
+  HIPCHK(call.alloc(d_cams, tab.size()));
+  HIPCHK(hipMemcpy(*d_cams, tab.data(), tab.size() * sizeof(mcba::KpCam), hipMemcpyHostToDevice));
+  return MCBA_OK;
+}
+
+int mcba_project_points(int n_cameras, size_t n_points, const double* points, const double* cam12, const double* dist5, int device, double* uvs_out, double* kernel_ms) {
+  if (n_cameras < 1 || !points || !cam12 || !uvs_out) return fail(MCBA_ERR_ARG, "mcba_project_points: cameras >= 1, non-NULL arrays required");
+  if (n_points == 0) return MCBA_OK;
+  if (int rc = stateless_device(device)) return rc;
+  StatelessCall call;
+  double *d_pts = nullptr, *d_out = nullptr;
+  mcba::KpCam* d_cams = nullptr;
+  const size_t nout = (size_t)2 * n_cameras * n_points;
+  HIPCHK(call.alloc(&d_pts, 3 * n_points));
+  HIPCHK(call.alloc(&d_out, nout));
+  HIPCHK(hipMemcpy(d_pts, points, 3 * n_points * sizeof(double), hipMemcpyHostToDevice));
+  if (int rc = kp_table(call, n_cameras, cam12, dist5, &d_cams)) return rc;
+  HIPCHK(call.start());
+  for (int c0 = 0; c0 < n_cameras; c0 += mcba::kKpMaxCams) {   // the table of one launch holds kKpMaxCams cameras
+    const int nc = std::min(mcba::kKpMaxCams, n_cameras - c0);
+    if (mcba::launch_project(nullptr, dist5 ? 1 : 0, d_pts, n_points, d_cams + c0, nc, d_out + (size_t)2 * c0 * n_points) != 0) return fail(MCBA_ERR_ARG, "mcba_project_points: bad launch");
+  }
+  if (int rc = check_launch()) return rc;
+  HIPCHK(call.stop(kernel_ms));
+  HIPCHK(hipMemcpy(uvs_out, d_out, nout * sizeof(double), hipMemcpyDeviceToHost));
+  return MCBA_OK;
+}
+
+int mcba_rigid_transform(size_t n_points, const double* points, const double* T12, int device, double* out) {
+  if (!points || !T12 || !out) return fail(MCBA_ERR_ARG, "mcba_rigid_transform: non-NULL arrays required");
+  if (n_points == 0) return MCBA_OK;
+  if (int rc = stateless_device(device)) return rc;
+  mcba::KpCam kc;
+  memset(&kc, 0, sizeof(kc));
+  memcpy(kc.pc.Rcf, T12, 9 * sizeof(double));
+  memcpy(kc.pc.tcf, T12 + 9, 3 * sizeof(double));
+  StatelessCall call;
+  double *d_pts = nullptr, *d_out = nullptr;
+  mcba::KpCam* d_cams = nullptr;
+  HIPCHK(call.alloc(&d_pts, 3 * n_points));
+  HIPCHK(call.alloc(&d_out, 3 * n_points));
+  HIPCHK(call.alloc(&d_cams, 1));
+  HIPCHK(hipMemcpy(d_pts, points, 3 * n_points * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_cams, &kc, sizeof(kc), hipMemcpyHostToDevice));
+  if (mcba::launch_project(nullptr, 2, d_pts, n_points, d_cams, 1, d_out) != 0) return fail(MCBA_ERR_ARG, "mcba_rigid_transform: bad launch");
+  if (int rc = check_launch()) return rc;
+  HIPCHK(hipMemcpy(out, d_out, 3 * n_points * sizeof(double), hipMemcpyDeviceToHost));
+  return MCBA_OK;
+}
+
+int mcba_keypoint_errors(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, int device, double* errors_out, double* median_out,
+                         double* kernel_ms) {
+  if (n_cameras < 1 || !points || !uvs || !cam12 || !median_out) return fail(MCBA_ERR_ARG, "mcba_keypoint_errors: cameras >= 1, non-NULL arrays required");
+  if (n_points == 0) {
+    for (int c = 0; c < n_cameras; ++c) median_out[c] = __builtin_nan("");
+    return MCBA_OK;
+  }
+  if (int rc = stateless_device(device)) return rc;
+  const size_t npad = (n_points + 63) / 64 * 64, nuv = (size_t)2 * n_cameras * n_points;
+  StatelessCall call;
+  double *d_pts = nullptr, *d_uv = nullptr, *d_err = nullptr;
+  mcba::KpCam* d_cams = nullptr;
+  mcba::SelState* d_sel = nullptr;
+  std::vector<mcba::SelState> sel((size_t)2 * n_cameras);
+  HIPCHK(call.alloc(&d_pts, 3 * n_points));
+  HIPCHK(call.alloc(&d_uv, nuv));
+  HIPCHK(call.alloc(&d_err, (size_t)n_cameras * npad));
+  HIPCHK(call.alloc(&d_sel, sel.size()));
+  HIPCHK(hipMemcpy(d_pts, points, 3 * n_points * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_uv, uvs, nuv * sizeof(double), hipMemcpyHostToDevice));
+  if (int rc = kp_table(call, n_cameras, cam12, dist5, &d_cams)) return rc;
+  HIPCHK(call.start());
+  for (int c0 = 0; c0 < n_cameras; c0 += mcba::kKpMaxCams) {
+    const int nc = std::min(mcba::kKpMaxCams, n_cameras - c0);
+    if (mcba::launch_keypoint_errors(nullptr, d_pts, d_uv + (size_t)2 * c0 * n_points, n_points, npad, d_cams + c0, nc, d_err + (size_t)c0 * npad) != 0)
+      return fail(MCBA_ERR_ARG, "mcba_keypoint_errors: bad launch");
+  }
+  if (int rc = check_launch()) return rc;
+  mcba::launch_select(nullptr, d_err, nullptr, npad, n_cameras, 1 /* no frame mask */, d_sel, 0 /* errors are >= +0 */);   // per-camera medians: two states per camera
+  if (int rc = check_launch()) return rc;
+  HIPCHK(call.stop(kernel_ms));
+  HIPCHK(hipMemcpy(sel.data(), d_sel, sel.size() * sizeof(mcba::SelState), hipMemcpyDeviceToHost));
+  for (int c = 0; c < n_cameras; ++c) median_out[c] = mcba::sel_median(sel[2 * c], sel[2 * c + 1]);
+  if (errors_out)
+    HIPCHK(hipMemcpy2D(errors_out, n_points * sizeof(double), d_err, npad * sizeof(double), n_points * sizeof(double), (size_t)n_cameras, hipMemcpyDeviceToHost));
+  return MCBA_OK;
+}
+
+int mcba_triangulate_refine(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points_in, int undistort_iterations, int loss, double f_scale,
+                            int max_iterations, int device, double* points_out, double* info_out, double* kernel_ms) {
+  if (n_cameras < 2 || n_cameras > 64 || !uvs || !cam12 || !points_out || undistort_iterations < 0 || max_iterations < 0)
+    return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: 2..64 cameras, non-NULL arrays, iterations >= 0 required");
+  if (loss < mcba::LOSS_LINEAR || loss > mcba::LOSS_ARCTAN) return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: loss must be one of linear, soft_l1, huber, cauchy, arctan (0 .. 4)");
+  if (!(f_scale > 0.0)) return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: f_scale must be positive");
+  if (n_points == 0) return MCBA_OK;
+  if (int rc = stateless_device(device)) return rc;
+  StatelessCall call;
+  double *d_uv = nullptr, *d_start = nullptr, *d_out = nullptr, *d_info = nullptr;
+  mcba::KpCam* d_cams = nullptr;
+  const size_t nuv = (size_t)2 * n_cameras * n_points;
+  HIPCHK(call.alloc(&d_uv, nuv));
+  HIPCHK(call.alloc(&d_start, 3 * n_points));
+  HIPCHK(call.alloc(&d_out, 3 * n_points));
+  if (info_out) HIPCHK(call.alloc(&d_info, 4 * n_points));
+  HIPCHK(hipMemcpy(d_uv, uvs, nuv * sizeof(double), hipMemcpyHostToDevice));   // the detections go up once, for the start and for the refinement
+  if (int rc = kp_table(call, n_cameras, cam12, dist5, &d_cams)) return rc;
+  TriOperands op;
+  if (points_in) HIPCHK(hipMemcpy(d_start, points_in, 3 * n_points * sizeof(double), hipMemcpyHostToDevice));
+  else if (int rc = tri_operands(call, n_cameras, cam12, dist5, op)) return rc;
+  HIPCHK(call.start());
+  if (!points_in) {   // start from the median of pairs
+    if (tri_launch(op, n_cameras, d_uv, d_start, n_points, undistort_iterations) != 0) return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: unsupported camera count");
+    if (int rc = check_launch()) return rc;
+  }
+  if (mcba::launch_tri_refine(nullptr, loss, d_uv, d_start, n_points, d_cams, n_cameras, f_scale, max_iterations, d_out, d_info) != 0) return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: bad launch");
+  if (int rc = check_launch()) return rc;
+  HIPCHK(call.stop(kernel_ms));
+  HIPCHK(hipMemcpy(points_out, d_out, 3 * n_points * sizeof(double), hipMemcpyDeviceToHost));
+  if (info_out) HIPCHK(hipMemcpy(info_out, d_info, 4 * n_points * sizeof(double), hipMemcpyDeviceToHost));
   return MCBA_OK;
 }
 

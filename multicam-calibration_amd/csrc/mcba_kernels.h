@@ -184,4 +184,13 @@ void launch_calib_views(hipStream_t st, const double* uvs, const double* obj, co
 int launch_triangulate(hipStream_t st, int C, const double* uvs, const TriCams& cams, double* out, size_t npts, int iters);
 // 9 .. 64 cameras: cams_dev = C x {P[12], K[4], dist[5]} doubles in device memory; one wavefront per point
 int launch_triangulate_wave(hipStream_t st, int C, const double* uvs, const void* cams_dev, double* out, size_t npts, int iters);
+// keypoint projection, reprojection errors and per-point refinement (mcba_keypoints.hip).  cams: C <= kKpMaxCams (64) entries of the camera
+// table (KpCam, mcba_keypoint_math.h) in device memory -- callers with more cameras launch per group.  Non-zero: arguments out of range.
+struct KpCam;
+// mode 0: k1, k2 model, 1: five coefficients -- out (C, P, 2); mode 2: the rigid transform of cams[0] -- out (P, 3)
+int launch_project(hipStream_t st, int mode, const double* pts, size_t npts, const KpCam* cams, int C, double* out);
+// uvs (C, P, 2); err rows (C, npad) doubles, NaN where unseen and in the padding p >= npts
+int launch_keypoint_errors(hipStream_t st, const double* pts, const double* uvs, size_t npts, size_t npad, const KpCam* cams, int C, double* err);
+// start / out (P, 3), info (P, 4) = (cost, cost at the start, iterations, status) or nullptr; loss: enum Loss, LOSS_LINEAR .. LOSS_ARCTAN
+int launch_tri_refine(hipStream_t st, int loss, const double* uvs, const double* start, size_t npts, const KpCam* cams, int C, double f_scale, int max_iterations, double* out, double* info);
 }  // namespace mcba

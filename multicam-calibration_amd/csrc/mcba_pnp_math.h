@@ -352,6 +352,21 @@ MCBA_HD bool zhang_solve(const double* M, int n, double w, double h, double* K4)
   return true;
 }
 
+// ---- the five-coefficient forward model (k1 k2 p1 p2 k3: what undistort_norm inverts) on normalised coordinates (x, y) = (Xc / Zc, Yc / Zc):
+// the distorted point (xd, yd) and the symmetric 2 x 2 derivative d(xd, yd)/d(x, y) = [[axx, axy], [axy, ayy]].  Pixels are (fx xd + cx, fy yd + cy).
+// For the keypoint kernels (mcba_keypoint_math.h).  view_linearise below keeps the same lines inline: calling this from it changes nothing in
+// k_pnp's arithmetic but moves its register allocation (a kernel that lives on the edge of its register budget), so it is left as it was.
+MCBA_HD void distort5(const Cam9& cam, double x, double y, double& xd, double& yd, double& axx, double& axy, double& ayy) {
+  const double r2 = x * x + y * y;
+  const double rad = 1.0 + r2 * (cam.k1 + r2 * (cam.k2 + r2 * cam.k3));
+  const double drad = cam.k1 + r2 * (2.0 * cam.k2 + 3.0 * cam.k3 * r2);
+  xd = x * rad + 2.0 * cam.p1 * x * y + cam.p2 * (r2 + 2.0 * x * x);
+  yd = y * rad + cam.p1 * (r2 + 2.0 * y * y) + 2.0 * cam.p2 * x * y;
+  axx = rad + 2.0 * x * x * drad + 2.0 * cam.p1 * y + 6.0 * cam.p2 * x;
+  axy = 2.0 * x * y * drad + 2.0 * cam.p1 * x + 2.0 * cam.p2 * y;
+  ayy = rad + 2.0 * y * y * drad + 6.0 * cam.p1 * y + 2.0 * cam.p2 * x;
+}
+
 // ---- one linearisation of a view's pixel reprojection error at `trial` (five-coefficient model): Gauss-Newton block (packed upper triangle),
 // gradient J^T e, cost 0.5 sum e^2.  observation(p, u, v) hands out the detection of point p.
 template <class Obs, class Split>

@@ -1,0 +1,175 @@
+"""The reference's `geometry.py` surface: keypoints through a calibration on the GPU, the small matrix helpers on the host.
+
+GPU (`csrc/mcba_keypoints.hip`; no numpy fallback -- without a device every one of them raises `ops.McbaError`):
+  project_points                 geometry.py:277 -- k1, k2 only, any leading shape, nothing special behind the camera, NaN in -> NaN out
+  project_to_cameras             every camera from one upload of the points; distortion="radial2" (the reference's model) or "opencv5"
+                                 (the forward five-coefficient model k1 k2 p1 p2 k3 that undistort_points inverts)
+  apply_rigid_transform          geometry.py:128
+  keypoint_reprojection_errors   |detection - projection| per (camera, point) and the exact per-camera nan-medians
+  refine_triangulation           per point, Levenberg-Marquardt on the robust reprojection cost from a start such as triangulate()'s
+The last two use the five-coefficient forward model on the RAW (distorted) detections: no undistortion iteration, so none of its truncation
+error.  With p1 = p2 = k3 = 0 (all bundle_adjust returns) the model is project_points'.
+
+Host (numpy, the reference's formulas): rigid_transform_from_correspondences (returns (t, rmsd); the one in flatibration.py returns t alone),
+get_projection_matrix, euclidean_to_homogenous, homogeneous_to_euclidean, and rodrigues / rodrigues_inv / get_transformation_matrix /
+get_transformation_vector re-exported from calibration.py.
+"""
+import ctypes
+
+import numpy as np
+
+from . import ops
+from .calibration import rodrigues, rodrigues_inv, get_transformation_matrix, get_transformation_vector  # noqa: F401
+from .triangulation import _cam_blocks, _stack_uvs, DEFAULT_MAX_ITERATIONS
+
+STATUS = {1: "converged", 0: "iteration limit", -1: "too few views"}
+
+
+def _chk(lib, rc):
+    if rc != ops.OK:
+        raise ops.McbaError(rc, lib.mcba_last_error().decode())
+
+
+def _points(points):
+    pts = np.asarray(points, dtype=np.float64)
+    if pts.ndim < 1 or pts.shape[-1] != 3:
+        raise ValueError("points must have shape (..., 3)")
+    return pts.shape[:-1], np.ascontiguousarray(pts.reshape(-1, 3))
+
+
+def _project(flat, cam, dist, device):
+    lib = ops.load_library()
+    C, P = len(cam), len(flat)
+    out = np.empty((C, P, 2))
+    if P:
+        _chk(lib, lib.mcba_project_points(C, P, flat.ctypes.data, cam.ctypes.data, None if dist is None else dist.ctypes.data, int(device), out.ctypes.data, None))
+    return out
+
+
+def project_points(points, extrinsics, camera_matrix, dist_coefs=None, *, device=0):
+    """points (..., 3) in world coordinates -> (..., 2) pixels in the camera (extrinsics (6,), camera_matrix (3, 3)).  Only k1, k2 of
+    dist_coefs are used, as in the reference (geometry.py:309); None = no distortion."""
+    d = np.zeros(2) if dist_coefs is None else np.ravel(np.asarray(dist_coefs, dtype=np.float64))[:2]
+    if d.size < 2:
+        raise ValueError("dist_coefs needs at least k1, k2")
+    cam, _ = _cam_blocks([extrinsics], [(camera_matrix, d)])
+    lead, flat = _points(points)
+    return _project(flat, cam, None, device)[0].reshape(lead + (2,))
+
+
+def project_to_cameras(points, all_extrinsics, all_intrinsics, *, distortion="radial2", device=0):
+    """points (..., 3) -> (C, ..., 2): the points go to the device once, every camera is projected from that copy.
+    distortion "radial2": project_points' model per camera; "opencv5": the forward model with k1 k2 p1 p2 k3."""
+    if distortion not in ("radial2", "opencv5"):
+        raise ValueError("distortion must be 'radial2' or 'opencv5'")
+    if len(all_extrinsics) != len(all_intrinsics) or len(all_extrinsics) < 1:
+        raise ValueError("one (camera_matrix, dist_coefs) per entry of all_extrinsics, at least one camera")
+    cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
+    lead, flat = _points(points)
+    out = _project(flat, cam, dist if distortion == "opencv5" else None, device)
+    return out.reshape((len(cam),) + lead + (2,))
+
+
+def apply_rigid_transform(transform, points, *, device=0):
+    """transform (6,) (rotation vector, translation) or (4, 4); points (..., 3) -> (..., 3)."""
+    T = np.asarray(transform, dtype=np.float64)
+    if T.shape == (6,):
+        T = get_transformation_matrix(T)
+    if T.shape != (4, 4):
+        raise ValueError("transform must have shape (6,) or (4, 4)")
+    lead, flat = _points(points)
+    out = np.empty_like(flat)
+    if len(flat):
+        lib = ops.load_library()
+        T12 = np.ascontiguousarray(np.r_[T[:3, :3].ravel(), T[:3, 3]])
+        _chk(lib, lib.mcba_rigid_transform(len(flat), flat.ctypes.data, T12.ctypes.data, int(device), out.ctypes.data))
+    return out.reshape(lead + (3,))
+
+
+def _keypoint_inputs(points, all_uvs, all_extrinsics, all_intrinsics):
+    uvs = _stack_uvs(all_uvs, all_extrinsics, all_intrinsics)
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.shape != (uvs.shape[1], 3):
+        raise ValueError("points must be (n_points, 3), one row per row of the cameras' uvs")
+    cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
+    return pts, uvs, cam, dist
+
+
+def keypoint_reprojection_errors(points, all_uvs, all_extrinsics, all_intrinsics, *, device=0, arrays=True):
+    """(errors (C, P), median_error (C,)): the distance in pixels between each camera's detection and the reprojection of the 3-D point; NaN
+    where the camera does not see the point (a NaN coordinate in its detection) or the point has a NaN.  median_error[c] is
+    np.nanmedian(errors[c]) bit for bit (an exact select on the device), NaN for a camera that sees nothing.  arrays=False: errors is None
+    (the rows stay on the device, only the medians come back)."""
+    pts, uvs, cam, dist = _keypoint_inputs(points, all_uvs, all_extrinsics, all_intrinsics)
+    C, P = uvs.shape[:2]
+    med = np.full(C, np.nan)
+    err = np.empty((C, P)) if arrays else None
+    if P:
+        lib = ops.load_library()
+        _chk(lib, lib.mcba_keypoint_errors(C, P, pts.ctypes.data, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, int(device), None if err is None else err.ctypes.data, med.ctypes.data, None))
+    return err, med
+
+
+def refine_triangulation(points, all_uvs, all_extrinsics, all_intrinsics, *, loss="soft_l1", f_scale=1.0, max_iterations=DEFAULT_MAX_ITERATIONS, device=0, return_info=False):
+    """Per point, minimise 0.5 sum rho(f^2) over X from the start `points` (P, 3): f = the 2 (cameras that see the point) residuals
+    detection - projection in pixels, rho and f_scale exactly scipy.optimize.least_squares' (loss one of linear, soft_l1, huber, cauchy,
+    arctan).  Points seen by fewer than two cameras, or whose start has a NaN, come back NaN.  A point is never made worse: a step is taken
+    only when the robust cost does not rise, and if none is, the start is returned.  2 to 64 cameras.
+
+    Levenberg-Marquardt per point (Marquardt damping from 1e-4, a tenth on an accepted step, tenfold on a rejected one); it stops when the
+    step is below 1e-12 (1 + |X|), when an accepted step gains less than 1e-15 of the cost, when the gradient is below 1e-12, or after
+    max_iterations (default 100) linearisations -- a point that is done costs nothing further, the others go on.
+
+    return_info=True: (points, info) with per-point arrays info["cost"] (robust cost at the result), info["cost0"] (at the start),
+    info["n_iterations"], info["status"] (1 converged, 0 iteration limit, -1 too few views: `geometry.STATUS`)."""
+    if loss not in ops.LOSSES:
+        raise ValueError(f"loss must be one of {sorted(ops.LOSSES)}")
+    if not f_scale > 0:
+        raise ValueError("`f_scale` must be positive.")
+    if int(max_iterations) < 0:
+        raise ValueError("max_iterations must not be negative")
+    pts, uvs, cam, dist = _keypoint_inputs(points, all_uvs, all_extrinsics, all_intrinsics)
+    C, P = uvs.shape[:2]
+    if not 2 <= C <= 64:
+        raise NotImplementedError("refine_triangulation() supports 2 to 64 cameras")
+    out = np.empty((P, 3))
+    info = np.empty((P, 4))
+    if P:
+        lib = ops.load_library()
+        _chk(lib, lib.mcba_triangulate_refine(C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, 0, ops.LOSSES[loss], float(f_scale), int(max_iterations), int(device),
+                                              out.ctypes.data, info.ctypes.data, None))
+    if not return_info:
+        return out
+    return out, dict(cost=info[:, 0].copy(), cost0=info[:, 1].copy(), n_iterations=info[:, 2].astype(np.int64), status=info[:, 3].astype(np.int64))
+
+
+# ---------------------------------------------------------------- host helpers (numpy; the reference's formulas)
+def euclidean_to_homogenous(x_euclidean):
+    """(..., d) -> (..., d + 1) with a trailing 1 (geometry.py:232)."""
+    x = np.asarray(x_euclidean)
+    return np.concatenate((x, np.ones(x.shape[:-1] + (1,))), axis=-1)
+
+
+def homogeneous_to_euclidean(x_homogenous):
+    """(..., d + 1) -> (..., d): the leading coordinates over the last (geometry.py:255)."""
+    x = np.asarray(x_homogenous)
+    return x[..., :-1] / x[..., -1:]
+
+
+def get_projection_matrix(extrinsics, intrinsics):
+    """P = K [R | t] (3, 4) from extrinsics (6,) and intrinsics (camera_matrix, dist_coefs) (geometry.py:200)."""
+    camera_matrix, _ = intrinsics
+    return np.matmul(camera_matrix, get_transformation_matrix(extrinsics)[:3])
+
+
+def rigid_transform_from_correspondences(source_points, target_points):
+    """(t (6,), rmsd): the rigid transform that takes source_points (..., 3) onto target_points in the least-squares sense (Kabsch: SVD of the
+    centred cross-covariance, a reflection turned back into a rotation) and the root mean square distance left (geometry.py:68)."""
+    from .flatibration import rigid_transform_from_correspondences as fit
+
+    source = np.asarray(source_points, dtype=np.float64).reshape(-1, 3)
+    target = np.asarray(target_points, dtype=np.float64).reshape(-1, 3)
+    t = fit(source, target)
+    T = get_transformation_matrix(t)
+    moved = np.matmul(T, euclidean_to_homogenous(source)[..., np.newaxis])[..., :3, 0]
+    return t, np.sqrt(np.mean(np.sum((moved - target) ** 2, axis=1)))

@@ -112,6 +112,10 @@ SYMBOLS = [
     ("mcba_calib_normal_equations", ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, _dp]),
     ("mcba_reprojection_diagnostics", ctypes.c_int, [_h, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, _dp]),
     ("mcba_triangulate", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
+    ("mcba_project_points", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, ctypes.c_int, _dp, _dp]),
+    ("mcba_rigid_transform", ctypes.c_int, [ctypes.c_size_t, _dp, _dp, ctypes.c_int, _dp]),
+    ("mcba_keypoint_errors", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, ctypes.c_int, _dp, _dp, _dp]),
+    ("mcba_triangulate_refine", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp]),
     ("mcba_profile_enable", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_stride", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_read", ctypes.c_int, [_h, _dp, _ip, ctypes.c_int, _ip]),

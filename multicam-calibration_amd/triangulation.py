@@ -33,22 +33,42 @@ def _cam_blocks(all_extrinsics, all_intrinsics):
     return cam, dist
 
 
-def triangulate(all_uvs, all_extrinsics, all_intrinsics, device=0, undistort_iterations=5, return_kernel_ms=False):
-    """all_uvs: per camera (n_points, 2), NaN = not seen.  Returns (n_points, 3); NaN rows where fewer than two cameras see
-    the point (geometry.py:361-433)."""
-    lib = ops.load_library()
+def _stack_uvs(all_uvs, all_extrinsics, all_intrinsics):
     uvs = np.ascontiguousarray(np.stack([np.asarray(u, dtype=np.float64) for u in all_uvs]))
     if uvs.ndim != 3 or uvs.shape[2] != 2 or uvs.shape[0] != len(all_extrinsics) or len(all_extrinsics) != len(all_intrinsics):
         raise ValueError("all_uvs must be one (n_points, 2) array per camera, matching all_extrinsics / all_intrinsics")
+    return uvs
+
+
+DEFAULT_MAX_ITERATIONS = 100   # linearisations per point of the refinement (geometry.refine_triangulation)
+
+
+def triangulate(all_uvs, all_extrinsics, all_intrinsics, device=0, undistort_iterations=5, return_kernel_ms=False, *, refine=False, loss="soft_l1", f_scale=1.0):
+    """all_uvs: per camera (n_points, 2), NaN = not seen.  Returns (n_points, 3); NaN rows where fewer than two cameras see
+    the point (geometry.py:361-433).
+
+    refine=True: the reference's estimate (the median over the camera pairs) is only the start; every point is then moved to the minimiser
+    of its robust reprojection cost (`geometry.refine_triangulation` with `loss`, `f_scale` and its default iteration limit).  The
+    detections go to the device once; the two kernels run back to back there."""
+    lib = ops.load_library()
+    uvs = _stack_uvs(all_uvs, all_extrinsics, all_intrinsics)
     C, P = uvs.shape[:2]
     if not 2 <= C <= 64:
         raise NotImplementedError("triangulate() supports 2 to 64 cameras")
+    if refine and loss not in ops.LOSSES:
+        raise ValueError(f"loss must be one of {sorted(ops.LOSSES)}")
+    if refine and not f_scale > 0:
+        raise ValueError("`f_scale` must be positive.")
     cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
     out = np.empty((P, 3))
     ms = ctypes.c_double(0.0)
     dp = ctypes.POINTER(ctypes.c_double)
-    rc = lib.mcba_triangulate(C, P, uvs.ctypes.data_as(dp), cam.ctypes.data_as(dp), dist.ctypes.data_as(dp), int(undistort_iterations), int(device),
-                              out.ctypes.data_as(dp), ctypes.cast(ctypes.byref(ms), dp))
+    if refine:
+        rc = lib.mcba_triangulate_refine(C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, None, int(undistort_iterations), ops.LOSSES[loss], float(f_scale), DEFAULT_MAX_ITERATIONS,
+                                         int(device), out.ctypes.data, None, ctypes.addressof(ms))
+    else:
+        rc = lib.mcba_triangulate(C, P, uvs.ctypes.data_as(dp), cam.ctypes.data_as(dp), dist.ctypes.data_as(dp), int(undistort_iterations), int(device),
+                                  out.ctypes.data_as(dp), ctypes.cast(ctypes.byref(ms), dp))
     if rc != ops.OK:
         raise ops.McbaError(rc, lib.mcba_last_error().decode())
     return (out, ms.value) if return_kernel_ms else out
