@@ -367,6 +367,18 @@ int mcba_keypoint_errors(int n_cameras, size_t n_points, const double* points, c
  * info_out (P, 4) or NULL: cost at the result, cost at the start, iterations, status (1 converged, 0 iteration limit, -1 too few views). */
 int mcba_triangulate_refine(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points_in, int undistort_iterations, int loss, double f_scale,
                             int max_iterations, int device, double* points_out, double* info_out, double* kernel_ms);
+/* Consensus triangulation (additive to ABI 7): which camera's detection of a point is wrong, and the point without it.  Per point,
+ * every camera pair that sees it gives a hypothesis (the two-view DLT point of mcba_triangulate, undistort_iterations rounds); a camera that sees
+ * the point is an inlier of a hypothesis when the point lies in front of it and its raw detection is within threshold (pixels, > 0) of the
+ * five-coefficient projection; the hypothesis of lowest truncated cost (sum of e^2 for inliers, threshold^2 otherwise; an exact tie goes to
+ * the first pair in the order (0,1), (0,2), ..., (1,2), ...) wins, and the point is refitted on its inliers alone as mcba_triangulate_refine
+ * does (loss, f_scale, max_iterations; max_iterations 0 returns the hypothesis itself).  The mask is not voted again after the refit.
+ * 2 <= C <= 64, min_views >= 2.  points_out (P, 3); inliers_out (P): bit c of word p set = camera c is an inlier of point p;
+ * info_out (P, 8) or NULL: inlier count, winning pair (i, j), winning cost, refit cost at the result and at the start, iterations, status
+ * (1 converged, 0 iteration limit, -1 too few views: no hypothesis, point NaN, empty mask, pair (-1, -1); -2 no consensus: fewer than min_views
+ * inliers, point NaN, the mask still reported); errors_out (C, P) or NULL: as mcba_keypoint_errors at points_out. */
+int mcba_triangulate_consensus(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, double threshold, int min_views, int undistort_iterations, int loss,
+                               double f_scale, int max_iterations, int device, double* points_out, unsigned long long* inliers_out, double* info_out, double* errors_out, double* kernel_ms);
 
 /* ---- the wrapper's frame pre-filter (bundle_adjustment.py:265-285) and frame subsets ------------------------ */
 /* Reprojection error |observed - predicted| of every detection at x[slot].  Host outputs, both (C,F) row-major:

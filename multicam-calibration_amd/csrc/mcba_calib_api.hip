@@ -537,6 +537,47 @@ int mcba_triangulate_refine(int n_cameras, size_t n_points, const double* uvs, c
   return MCBA_OK;
 }
 
+// Consensus triangulation (csrc/mcba_consensus.hip): the detections go up once; the search, the refit and the optional errors at the
+// final point run on that copy.  The projection matrices of the hypotheses are derived on the device from the one camera table (kp_table).
+int mcba_triangulate_consensus(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, double threshold, int min_views, int undistort_iterations, int loss,
+                               double f_scale, int max_iterations, int device, double* points_out, unsigned long long* inliers_out, double* info_out, double* errors_out, double* kernel_ms) {
+  if (n_cameras < 2 || n_cameras > 64 || !uvs || !cam12 || !points_out || !inliers_out || undistort_iterations < 0 || max_iterations < 0)
+    return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: 2..64 cameras, non-NULL arrays, iterations >= 0 required");
+  if (!(threshold > 0.0)) return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: threshold (pixels) must be positive");
+  if (min_views < 2) return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: min_views must be at least 2");
+  if (loss < mcba::LOSS_LINEAR || loss > mcba::LOSS_ARCTAN) return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: loss must be one of linear, soft_l1, huber, cauchy, arctan (0 .. 4)");
+  if (!(f_scale > 0.0)) return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: f_scale must be positive");
+  if (n_points == 0) return MCBA_OK;
+  if (int rc = stateless_device(device)) return rc;
+  StatelessCall call;
+  double *d_uv = nullptr, *d_out = nullptr, *d_hyp = nullptr, *d_info = nullptr, *d_err = nullptr;
+  unsigned long long* d_mask = nullptr;
+  mcba::KpCam* d_cams = nullptr;
+  const size_t nuv = (size_t)2 * n_cameras * n_points;
+  HIPCHK(call.alloc(&d_uv, nuv));
+  HIPCHK(call.alloc(&d_out, 3 * n_points));
+  HIPCHK(call.alloc(&d_mask, n_points));
+  HIPCHK(call.alloc(&d_hyp, 2 * n_points));
+  if (info_out) HIPCHK(call.alloc(&d_info, 8 * n_points));
+  if (errors_out) HIPCHK(call.alloc(&d_err, (size_t)n_cameras * n_points));
+  HIPCHK(hipMemcpy(d_uv, uvs, nuv * sizeof(double), hipMemcpyHostToDevice));
+  if (int rc = kp_table(call, n_cameras, cam12, dist5, &d_cams)) return rc;
+  HIPCHK(call.start());
+  if (mcba::launch_consensus(nullptr, mcba::CONSENSUS_AUTO, loss, d_uv, n_points, d_cams, n_cameras, threshold, min_views, undistort_iterations, f_scale, max_iterations, d_out, d_mask, d_hyp, d_info) != 0)
+    return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: bad launch (MCBA_CONSENSUS_FORM, if set, must be lane, wave or lane2)");
+  if (int rc = check_launch()) return rc;
+  if (errors_out) {
+    if (mcba::launch_keypoint_errors(nullptr, d_out, d_uv, n_points, n_points, d_cams, n_cameras, d_err) != 0) return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: bad launch");
+    if (int rc = check_launch()) return rc;
+  }
+  HIPCHK(call.stop(kernel_ms));
+  HIPCHK(hipMemcpy(points_out, d_out, 3 * n_points * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(inliers_out, d_mask, n_points * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (info_out) HIPCHK(hipMemcpy(info_out, d_info, 8 * n_points * sizeof(double), hipMemcpyDeviceToHost));
+  if (errors_out) HIPCHK(hipMemcpy(errors_out, d_err, (size_t)n_cameras * n_points * sizeof(double), hipMemcpyDeviceToHost));
+  return MCBA_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Single-camera calibration with OpenCV's five-coefficient model (reference calibration.py:11-71 -> cv2.calibrateCamera without
 // CALIB_FIX_K3 / CALIB_ZERO_TANGENT_DIST; :74-113 -> cv2.solvePnP with such coefficients): stateless; per view the Gauss-Newton block of

@@ -193,4 +193,10 @@ int launch_project(hipStream_t st, int mode, const double* pts, size_t npts, con
 int launch_keypoint_errors(hipStream_t st, const double* pts, const double* uvs, size_t npts, size_t npad, const KpCam* cams, int C, double* err);
 // start / out (P, 3), info (P, 4) = (cost, cost at the start, iterations, status) or nullptr; loss: enum Loss, LOSS_LINEAR .. LOSS_ARCTAN
 int launch_tri_refine(hipStream_t st, int loss, const double* uvs, const double* start, size_t npts, const KpCam* cams, int C, double f_scale, int max_iterations, double* out, double* info);
+// consensus triangulation (mcba_consensus.hip): 2 <= C <= kKpMaxCams.  out (P, 3), mask (P) inlier words, info (P, 8) = (inliers, pair i, pair j,
+// hypothesis cost, refit cost, refit cost at the start, iterations, status) or nullptr; hyp (P, 2): scratch between the search and the refit of
+// the two-launch forms (may be nullptr for CONSENSUS_LANE).  form: CONSENSUS_AUTO picks by camera count.
+enum ConsensusForm { CONSENSUS_AUTO = -1, CONSENSUS_LANE = 0, CONSENSUS_WAVE = 1, CONSENSUS_LANE_SEARCH = 2 };
+int launch_consensus(hipStream_t st, int form, int loss, const double* uvs, size_t npts, const KpCam* cams, int C, double threshold, int min_views, int und_iters, double f_scale,
+                     int max_iterations, double* out, unsigned long long* mask, double* hyp, double* info);
 }  // namespace mcba

@@ -7,7 +7,9 @@ GPU (`csrc/mcba_keypoints.hip`; no numpy fallback -- without a device every one 
   apply_rigid_transform          geometry.py:128
   keypoint_reprojection_errors   |detection - projection| per (camera, point) and the exact per-camera nan-medians
   refine_triangulation           per point, Levenberg-Marquardt on the robust reprojection cost from a start such as triangulate()'s
-The last two use the five-coefficient forward model on the RAW (distorted) detections: no undistortion iteration, so none of its truncation
+  triangulate_consensus          (`csrc/mcba_consensus.hip`; no counterpart in the reference) per point, every camera
+                                 pair's two-view point scored against all detections, the inlier cameras named, the point refitted on them
+The last three use the five-coefficient forward model on the RAW (distorted) detections: no undistortion iteration, so none of its truncation
 error.  With p1 = p2 = k3 = 0 (all bundle_adjust returns) the model is project_points'.
 
 Host (numpy, the reference's formulas): rigid_transform_from_correspondences (returns (t, rmsd); the one in flatibration.py returns t alone),
@@ -141,6 +143,61 @@ def refine_triangulation(points, all_uvs, all_extrinsics, all_intrinsics, *, los
     if not return_info:
         return out
     return out, dict(cost=info[:, 0].copy(), cost0=info[:, 1].copy(), n_iterations=info[:, 2].astype(np.int64), status=info[:, 3].astype(np.int64))
+
+
+CONSENSUS_STATUS = {1: "converged", 0: "iteration limit", -1: "too few views", -2: "no consensus"}
+
+
+def triangulate_consensus(all_uvs, all_extrinsics, all_intrinsics, *, threshold, min_views=2, loss="linear", f_scale=1.0, max_iterations=DEFAULT_MAX_ITERATIONS, undistort_iterations=5,
+                          device=0, return_info=False, return_errors=False):
+    """Which camera's detection of a point is wrong, and the point without it: (points (P, 3), inliers (C, P) bool).
+
+    Per point, every camera pair that sees it (both coordinates of the detection non-NaN) gives a hypothesis: triangulate()'s two-view point
+    (`undistort_iterations` rounds).  A camera that sees the point is an inlier of a hypothesis when the point lies in front of it and its
+    raw detection is within `threshold` pixels of the five-coefficient projection.  The hypothesis of lowest truncated cost -- e^2 per inlier,
+    threshold^2 per other seeing camera -- wins (an exact tie: the first pair in the order (0,1), (0,2), ..., (1,2), ...); the enumeration is
+    exhaustive, nothing is sampled.  The point is then refitted on the winner's inliers alone as refine_triangulation does (`loss`, default
+    plain least squares, `f_scale`, `max_iterations`; max_iterations=0 returns the winning hypothesis itself).  The mask is the winner's: it is
+    not voted again after the refit.  `threshold` has no default: the right value is the detector's noise.  2 to 64 cameras.
+
+    A point no pair sees comes back NaN with an empty mask (status -1); a winner with fewer than `min_views` (>= 2) inliers gives NaN with the
+    mask still reported (status -2).
+
+    return_info=True: also a dict of per-point arrays -- n_inliers, pair (P, 2) (the winning pair, -1 where none), hypothesis_cost, cost and
+    cost0 (the refit's cost at the result and at its start), n_iterations, status (`geometry.CONSENSUS_STATUS`).
+    return_errors=True: also errors (C, P), keypoint_reprojection_errors' at the returned points (computed on the device from the same upload)."""
+    if not threshold > 0:
+        raise ValueError("`threshold` (pixels) must be positive.")
+    if int(min_views) < 2:
+        raise ValueError("min_views must be at least 2")
+    if loss not in ops.LOSSES:
+        raise ValueError(f"loss must be one of {sorted(ops.LOSSES)}")
+    if not f_scale > 0:
+        raise ValueError("`f_scale` must be positive.")
+    if int(max_iterations) < 0 or int(undistort_iterations) < 0:
+        raise ValueError("max_iterations and undistort_iterations must not be negative")
+    uvs = _stack_uvs(all_uvs, all_extrinsics, all_intrinsics)
+    C, P = uvs.shape[:2]
+    if not 2 <= C <= 64:
+        raise NotImplementedError("triangulate_consensus() supports 2 to 64 cameras")
+    cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
+    out = np.empty((P, 3))
+    words = np.zeros(P, dtype=np.uint64)
+    info = np.empty((P, 8)) if return_info else None
+    err = np.empty((C, P)) if return_errors else None
+    if P:
+        lib = ops.load_library()
+        _chk(lib, lib.mcba_triangulate_consensus(C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, float(threshold), int(min_views), int(undistort_iterations), ops.LOSSES[loss],
+                                                 float(f_scale), int(max_iterations), int(device), out.ctypes.data, words.ctypes.data, None if info is None else info.ctypes.data,
+                                                 None if err is None else err.ctypes.data, None))
+    inliers = ((words[None, :] >> np.arange(C, dtype=np.uint64)[:, None]) & np.uint64(1)).astype(bool)
+    res = (out, inliers)
+    if return_info:
+        res += (dict(n_inliers=info[:, 0].astype(np.int64), pair=info[:, 1:3].astype(np.int64), hypothesis_cost=info[:, 3].copy(), cost=info[:, 4].copy(), cost0=info[:, 5].copy(),
+                     n_iterations=info[:, 6].astype(np.int64), status=info[:, 7].astype(np.int64)),)
+    if return_errors:
+        res += (err,)
+    return res
 
 
 # ---------------------------------------------------------------- host helpers (numpy; the reference's formulas)
