@@ -1,7 +1,7 @@
 // mcba_api.hip -- the C ABI of include/mcba.h: handle life cycle and buffer pool, launch geometry, upload, parameters, cost / residuals /
 // Jacobian, the host-driven LM step and the launches of its chain, x_scale / bounds / frozen coordinates, detached buffers, profiling.
-// The device-resident LM loops are in mcba_lm_api.hip, the frame pre-filter in mcba_prefilter_api.hip, calibrate() and the stateless
-// geometry calls in mcba_calib_api.hip, RCCL in mcba_comm_api.hip; what they share is in mcba_handle.h.
+// The device-resident LM loops are in mcba_lm_api.hip, the frame pre-filter in mcba_prefilter_api.hip, calibrate() in mcba_calib_api.hip, the
+// stateless geometry calls in mcba_geom_api.hip, RCCL in mcba_comm_api.hip; what they share is in mcba_handle.h.
 #include <map>
 #include <mutex>
 

@@ -1,7 +1,6 @@
-// mcba_calib_api.hip -- calibrate() on the device (include/mcba.h: mcba_calib_*, the pose graph mcba_pose_*), and the stateless geometry
-// calls: undistort_points, robust triangulation and its refinement, keypoint projection and reprojection errors, the single-camera normal equations.
+// mcba_calib_api.hip -- calibrate() on the device (include/mcba.h: the handle calls mcba_calib_*), the same pose-graph steps for a caller's own
+// pose array (mcba_pose_*, stateless) and the single-camera normal equations (mcba_calib_normal_equations, stateless).
 #include "mcba_handle.h"
-#include "mcba_keypoint_math.h"   // KpCam, make_kp_cam: the camera table of the keypoint kernels
 
 using namespace mcba_internal;
 
@@ -286,7 +285,7 @@ int mcba_pose_pairwise(int n_cameras, int n_frames, const double* poses, const i
                b_sel = up256((size_t)12 * n_edges * sizeof(mcba::SelState));
   StatelessCall call;
   unsigned char* t = nullptr;
-  HIPCHK(call.alloc(&t, b_pose + b_edge + b_rel + b_sel));
+  if ((rc = call.scratch(&t, b_pose + b_edge + b_rel + b_sel))) return rc;   // one slab: the two copies below fill its input slices (d_pose, d_edge)
   double* d_pose = reinterpret_cast<double*>(t);
   int* d_edge = reinterpret_cast<int*>(t + b_pose);
   double* d_rel = reinterpret_cast<double*>(t + b_pose + b_edge);
@@ -307,7 +306,7 @@ int mcba_pose_consensus(int n_cameras, int n_frames, const double* poses, const 
                b_out = up256((size_t)6 * n_frames * sizeof(double));
   StatelessCall call;
   unsigned char* t = nullptr;
-  HIPCHK(call.alloc(&t, b_pose + b_ext + b_world + b_out));
+  if ((rc = call.scratch(&t, b_pose + b_ext + b_world + b_out))) return rc;   // one slab: the two copies below fill its input slices (d_pose, d_ext)
   double* d_pose = reinterpret_cast<double*>(t);
   double* d_ext = reinterpret_cast<double*>(t + b_pose);
   double* d_world = reinterpret_cast<double*>(t + b_pose + b_ext);
@@ -321,263 +320,6 @@ int mcba_pose_consensus(int n_cameras, int n_frames, const double* poses, const 
   return MCBA_OK;
 }
 
-// undistort_points (reference geometry.py:328-358): stateless; host arrays in, host array out
-int mcba_undistort_points(size_t n_points, const double* uvs, const double* K4, const double* dist5, int iterations, int device, double* out) {
-  if (!uvs || !K4 || !out || iterations < 0) return fail(MCBA_ERR_ARG, "mcba_undistort_points: bad argument");
-  if (n_points == 0) return MCBA_OK;
-  if (int rc = stateless_device(device)) return rc;
-  double *d_in = nullptr, *d_out = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_in), 2 * n_points * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_out), 2 * n_points * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(d_in, uvs, 2 * n_points * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    mcba::launch_undistort(nullptr, d_in, d_out, n_points, K4, dist5, iterations);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(out, d_out, 2 * n_points * sizeof(double), hipMemcpyDeviceToHost);
-  if (d_in) (void)hipFree(d_in);
-  if (d_out) (void)hipFree(d_out);
-  if (e != hipSuccess) { g_err = std::string("mcba_undistort_points: ") + hipGetErrorString(e); return MCBA_ERR_HIP; }
-  return MCBA_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Robust triangulation (reference geometry.py:361-433): stateless; host arrays in, host array out.
-// The median-of-pairs kernels' camera operands: per camera {P = K [R | t] (12), K (4), dist (5)} -- kernel arguments for the register path
-// (<= 8 cameras), a device array for the wavefront-per-point path
-struct TriOperands {
-  bool reg_path = true;
-  mcba::TriCams cams;
-  double* d_cams = nullptr;
-};
-static int tri_operands(StatelessCall& call, int n_cameras, const double* cam12, const double* dist5, TriOperands& op) {
-  std::vector<double> cam21((size_t)21 * n_cameras, 0.0);
-  for (int c = 0; c < n_cameras; ++c) {
-    const double* q = cam12 + 12 * c;
-    double* P = cam21.data() + (size_t)21 * c;
-    double R[9];
-    mcba::rot_only(q + 6, R);
-    const double fx = q[0], fy = q[1], cx = q[2], cy = q[3];
-    for (int j = 0; j < 3; ++j) {
-      P[j] = fx * R[j] + cx * R[6 + j];
-      P[4 + j] = fy * R[3 + j] + cy * R[6 + j];
-      P[8 + j] = R[6 + j];
-    }
-    P[3] = fx * q[9] + cx * q[11];
-    P[7] = fy * q[10] + cy * q[11];
-    P[11] = q[11];
-    P[12] = fx; P[13] = fy; P[14] = cx; P[15] = cy;
-    if (dist5) for (int k = 0; k < 5; ++k) P[16 + k] = dist5[5 * c + k];
-    else { P[16] = q[4]; P[17] = q[5]; }
-  }
-  op.reg_path = n_cameras <= 8;
-  memset(&op.cams, 0, sizeof(op.cams));
-  if (op.reg_path) {
-    for (int c = 0; c < n_cameras; ++c) {
-      memcpy(op.cams.P[c], cam21.data() + (size_t)21 * c, 12 * sizeof(double));
-      memcpy(op.cams.K[c], cam21.data() + (size_t)21 * c + 12, 4 * sizeof(double));
-      memcpy(op.cams.dist[c], cam21.data() + (size_t)21 * c + 16, 5 * sizeof(double));
-    }
-  } else {
-    HIPCHK(call.alloc(&op.d_cams, cam21.size()));
-    HIPCHK(hipMemcpy(op.d_cams, cam21.data(), cam21.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
-  return MCBA_OK;
-}
-static int tri_launch(const TriOperands& op, int n_cameras, const double* d_uv, double* d_out, size_t n_points, int iterations) {
-  return op.reg_path ? mcba::launch_triangulate(nullptr, n_cameras, d_uv, op.cams, d_out, n_points, iterations)
-                     : mcba::launch_triangulate_wave(nullptr, n_cameras, d_uv, op.d_cams, d_out, n_points, iterations);
-}
-
-int mcba_triangulate(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, int iterations, int device, double* out, double* kernel_ms) {
-  if (n_cameras < 2 || n_cameras > 64 || !uvs || !cam12 || !out || iterations < 0) return fail(MCBA_ERR_ARG, "mcba_triangulate: 2..64 cameras, non-NULL arrays, iterations >= 0 required");
-  if (n_points == 0) return MCBA_OK;
-  if (int rc = stateless_device(device)) return rc;
-  StatelessCall call;
-  double *d_uv = nullptr, *d_out = nullptr;
-  const size_t nin = (size_t)2 * n_cameras * n_points;
-  HIPCHK(call.alloc(&d_uv, nin));
-  HIPCHK(call.alloc(&d_out, 3 * n_points));
-  HIPCHK(hipMemcpy(d_uv, uvs, nin * sizeof(double), hipMemcpyHostToDevice));
-  TriOperands op;
-  if (int rc = tri_operands(call, n_cameras, cam12, dist5, op)) return rc;
-  HIPCHK(call.start());
-  if (tri_launch(op, n_cameras, d_uv, d_out, n_points, iterations) != 0) return fail(MCBA_ERR_ARG, "mcba_triangulate: unsupported camera count");
-  if (int rc = check_launch()) return rc;
-  HIPCHK(call.stop(kernel_ms));
-  HIPCHK(hipMemcpy(out, d_out, 3 * n_points * sizeof(double), hipMemcpyDeviceToHost));
-  return MCBA_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Keypoints through a calibration (reference geometry.py:128-152 apply_rigid_transform, :277-325 project_points): stateless; host arrays in and out.
-// the camera table of the keypoint kernels (mcba_keypoint_math.h: KpCam) in device memory
-static int kp_table(StatelessCall& call, int n_cameras, const double* cam12, const double* dist5, mcba::KpCam** d_cams) {
-  std::vector<mcba::KpCam> tab((size_t)n_cameras);
-  for (int c = 0; c < n_cameras; ++c) mcba::make_kp_cam(cam12 + 12 * c, dist5 ? dist5 + 5 * c : nullptr, tab[c]);
-  HIPCHK(call.alloc(d_cams, tab.size()));
-  HIPCHK(hipMemcpy(*d_cams, tab.data(), tab.size() * sizeof(mcba::KpCam), hipMemcpyHostToDevice));
-  return MCBA_OK;
-}
-
-int mcba_project_points(int n_cameras, size_t n_points, const double* points, const double* cam12, const double* dist5, int device, double* uvs_out, double* kernel_ms) {
-  if (n_cameras < 1 || !points || !cam12 || !uvs_out) return fail(MCBA_ERR_ARG, "mcba_project_points: cameras >= 1, non-NULL arrays required");
-  if (n_points == 0) return MCBA_OK;
-  if (int rc = stateless_device(device)) return rc;
-  StatelessCall call;
-  double *d_pts = nullptr, *d_out = nullptr;
-  mcba::KpCam* d_cams = nullptr;
-  const size_t nout = (size_t)2 * n_cameras * n_points;
-  HIPCHK(call.alloc(&d_pts, 3 * n_points));
-  HIPCHK(call.alloc(&d_out, nout));
-  HIPCHK(hipMemcpy(d_pts, points, 3 * n_points * sizeof(double), hipMemcpyHostToDevice));
-  if (int rc = kp_table(call, n_cameras, cam12, dist5, &d_cams)) return rc;
-  HIPCHK(call.start());
-  for (int c0 = 0; c0 < n_cameras; c0 += mcba::kKpMaxCams) {   // the table of one launch holds kKpMaxCams cameras
-    const int nc = std::min(mcba::kKpMaxCams, n_cameras - c0);
-    if (mcba::launch_project(nullptr, dist5 ? 1 : 0, d_pts, n_points, d_cams + c0, nc, d_out + (size_t)2 * c0 * n_points) != 0) return fail(MCBA_ERR_ARG, "mcba_project_points: bad launch");
-  }
-  if (int rc = check_launch()) return rc;
-  HIPCHK(call.stop(kernel_ms));
-  HIPCHK(hipMemcpy(uvs_out, d_out, nout * sizeof(double), hipMemcpyDeviceToHost));
-  return MCBA_OK;
-}
-
-int mcba_rigid_transform(size_t n_points, const double* points, const double* T12, int device, double* out) {
-  if (!points || !T12 || !out) return fail(MCBA_ERR_ARG, "mcba_rigid_transform: non-NULL arrays required");
-  if (n_points == 0) return MCBA_OK;
-  if (int rc = stateless_device(device)) return rc;
-  mcba::KpCam kc;
-  memset(&kc, 0, sizeof(kc));
-  memcpy(kc.pc.Rcf, T12, 9 * sizeof(double));
-  memcpy(kc.pc.tcf, T12 + 9, 3 * sizeof(double));
-  StatelessCall call;
-  double *d_pts = nullptr, *d_out = nullptr;
-  mcba::KpCam* d_cams = nullptr;
-  HIPCHK(call.alloc(&d_pts, 3 * n_points));
-  HIPCHK(call.alloc(&d_out, 3 * n_points));
-  HIPCHK(call.alloc(&d_cams, 1));
-  HIPCHK(hipMemcpy(d_pts, points, 3 * n_points * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_cams, &kc, sizeof(kc), hipMemcpyHostToDevice));
-  if (mcba::launch_project(nullptr, 2, d_pts, n_points, d_cams, 1, d_out) != 0) return fail(MCBA_ERR_ARG, "mcba_rigid_transform: bad launch");
-  if (int rc = check_launch()) return rc;
-  HIPCHK(hipMemcpy(out, d_out, 3 * n_points * sizeof(double), hipMemcpyDeviceToHost));
-  return MCBA_OK;
-}
-
-int mcba_keypoint_errors(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, int device, double* errors_out, double* median_out,
-                         double* kernel_ms) {
-  if (n_cameras < 1 || !points || !uvs || !cam12 || !median_out) return fail(MCBA_ERR_ARG, "mcba_keypoint_errors: cameras >= 1, non-NULL arrays required");
-  if (n_points == 0) {
-    for (int c = 0; c < n_cameras; ++c) median_out[c] = __builtin_nan("");
-    return MCBA_OK;
-  }
-  if (int rc = stateless_device(device)) return rc;
-  const size_t npad = (n_points + 63) / 64 * 64, nuv = (size_t)2 * n_cameras * n_points;
-  StatelessCall call;
-  double *d_pts = nullptr, *d_uv = nullptr, *d_err = nullptr;
-  mcba::KpCam* d_cams = nullptr;
-  mcba::SelState* d_sel = nullptr;
-  std::vector<mcba::SelState> sel((size_t)2 * n_cameras);
-  HIPCHK(call.alloc(&d_pts, 3 * n_points));
-  HIPCHK(call.alloc(&d_uv, nuv));
-  HIPCHK(call.alloc(&d_err, (size_t)n_cameras * npad));
-  HIPCHK(call.alloc(&d_sel, sel.size()));
-  HIPCHK(hipMemcpy(d_pts, points, 3 * n_points * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_uv, uvs, nuv * sizeof(double), hipMemcpyHostToDevice));
-  if (int rc = kp_table(call, n_cameras, cam12, dist5, &d_cams)) return rc;
-  HIPCHK(call.start());
-  for (int c0 = 0; c0 < n_cameras; c0 += mcba::kKpMaxCams) {
-    const int nc = std::min(mcba::kKpMaxCams, n_cameras - c0);
-    if (mcba::launch_keypoint_errors(nullptr, d_pts, d_uv + (size_t)2 * c0 * n_points, n_points, npad, d_cams + c0, nc, d_err + (size_t)c0 * npad) != 0)
-      return fail(MCBA_ERR_ARG, "mcba_keypoint_errors: bad launch");
-  }
-  if (int rc = check_launch()) return rc;
-  mcba::launch_select(nullptr, d_err, nullptr, npad, n_cameras, 1 /* no frame mask */, d_sel, 0 /* errors are >= +0 */);   // per-camera medians: two states per camera
-  if (int rc = check_launch()) return rc;
-  HIPCHK(call.stop(kernel_ms));
-  HIPCHK(hipMemcpy(sel.data(), d_sel, sel.size() * sizeof(mcba::SelState), hipMemcpyDeviceToHost));
-  for (int c = 0; c < n_cameras; ++c) median_out[c] = mcba::sel_median(sel[2 * c], sel[2 * c + 1]);
-  if (errors_out)
-    HIPCHK(hipMemcpy2D(errors_out, n_points * sizeof(double), d_err, npad * sizeof(double), n_points * sizeof(double), (size_t)n_cameras, hipMemcpyDeviceToHost));
-  return MCBA_OK;
-}
-
-int mcba_triangulate_refine(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points_in, int undistort_iterations, int loss, double f_scale,
-                            int max_iterations, int device, double* points_out, double* info_out, double* kernel_ms) {
-  if (n_cameras < 2 || n_cameras > 64 || !uvs || !cam12 || !points_out || undistort_iterations < 0 || max_iterations < 0)
-    return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: 2..64 cameras, non-NULL arrays, iterations >= 0 required");
-  if (loss < mcba::LOSS_LINEAR || loss > mcba::LOSS_ARCTAN) return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: loss must be one of linear, soft_l1, huber, cauchy, arctan (0 .. 4)");
-  if (!(f_scale > 0.0)) return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: f_scale must be positive");
-  if (n_points == 0) return MCBA_OK;
-  if (int rc = stateless_device(device)) return rc;
-  StatelessCall call;
-  double *d_uv = nullptr, *d_start = nullptr, *d_out = nullptr, *d_info = nullptr;
-  mcba::KpCam* d_cams = nullptr;
-  const size_t nuv = (size_t)2 * n_cameras * n_points;
-  HIPCHK(call.alloc(&d_uv, nuv));
-  HIPCHK(call.alloc(&d_start, 3 * n_points));
-  HIPCHK(call.alloc(&d_out, 3 * n_points));
-  if (info_out) HIPCHK(call.alloc(&d_info, 4 * n_points));
-  HIPCHK(hipMemcpy(d_uv, uvs, nuv * sizeof(double), hipMemcpyHostToDevice));   // the detections go up once, for the start and for the refinement
-  if (int rc = kp_table(call, n_cameras, cam12, dist5, &d_cams)) return rc;
-  TriOperands op;
-  if (points_in) HIPCHK(hipMemcpy(d_start, points_in, 3 * n_points * sizeof(double), hipMemcpyHostToDevice));
-  else if (int rc = tri_operands(call, n_cameras, cam12, dist5, op)) return rc;
-  HIPCHK(call.start());
-  if (!points_in) {   // start from the median of pairs
-    if (tri_launch(op, n_cameras, d_uv, d_start, n_points, undistort_iterations) != 0) return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: unsupported camera count");
-    if (int rc = check_launch()) return rc;
-  }
-  if (mcba::launch_tri_refine(nullptr, loss, d_uv, d_start, n_points, d_cams, n_cameras, f_scale, max_iterations, d_out, d_info) != 0) return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: bad launch");
-  if (int rc = check_launch()) return rc;
-  HIPCHK(call.stop(kernel_ms));
-  HIPCHK(hipMemcpy(points_out, d_out, 3 * n_points * sizeof(double), hipMemcpyDeviceToHost));
-  if (info_out) HIPCHK(hipMemcpy(info_out, d_info, 4 * n_points * sizeof(double), hipMemcpyDeviceToHost));
-  return MCBA_OK;
-}
-
-// Consensus triangulation (csrc/mcba_consensus.hip): the detections go up once; the search, the refit and the optional errors at the
-// final point run on that copy.  The projection matrices of the hypotheses are derived on the device from the one camera table (kp_table).
-int mcba_triangulate_consensus(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, double threshold, int min_views, int undistort_iterations, int loss,
-                               double f_scale, int max_iterations, int device, double* points_out, unsigned long long* inliers_out, double* info_out, double* errors_out, double* kernel_ms) {
-  if (n_cameras < 2 || n_cameras > 64 || !uvs || !cam12 || !points_out || !inliers_out || undistort_iterations < 0 || max_iterations < 0)
-    return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: 2..64 cameras, non-NULL arrays, iterations >= 0 required");
-  if (!(threshold > 0.0)) return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: threshold (pixels) must be positive");
-  if (min_views < 2) return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: min_views must be at least 2");
-  if (loss < mcba::LOSS_LINEAR || loss > mcba::LOSS_ARCTAN) return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: loss must be one of linear, soft_l1, huber, cauchy, arctan (0 .. 4)");
-  if (!(f_scale > 0.0)) return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: f_scale must be positive");
-  if (n_points == 0) return MCBA_OK;
-  if (int rc = stateless_device(device)) return rc;
-  StatelessCall call;
-  double *d_uv = nullptr, *d_out = nullptr, *d_hyp = nullptr, *d_info = nullptr, *d_err = nullptr;
-  unsigned long long* d_mask = nullptr;
-  mcba::KpCam* d_cams = nullptr;
-  const size_t nuv = (size_t)2 * n_cameras * n_points;
-  HIPCHK(call.alloc(&d_uv, nuv));
-  HIPCHK(call.alloc(&d_out, 3 * n_points));
-  HIPCHK(call.alloc(&d_mask, n_points));
-  HIPCHK(call.alloc(&d_hyp, 2 * n_points));
-  if (info_out) HIPCHK(call.alloc(&d_info, 8 * n_points));
-  if (errors_out) HIPCHK(call.alloc(&d_err, (size_t)n_cameras * n_points));
-  HIPCHK(hipMemcpy(d_uv, uvs, nuv * sizeof(double), hipMemcpyHostToDevice));
-  if (int rc = kp_table(call, n_cameras, cam12, dist5, &d_cams)) return rc;
-  HIPCHK(call.start());
-  if (mcba::launch_consensus(nullptr, mcba::CONSENSUS_AUTO, loss, d_uv, n_points, d_cams, n_cameras, threshold, min_views, undistort_iterations, f_scale, max_iterations, d_out, d_mask, d_hyp, d_info) != 0)
-    return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: bad launch (MCBA_CONSENSUS_FORM, if set, must be lane, wave or lane2)");
-  if (int rc = check_launch()) return rc;
-  if (errors_out) {
-    if (mcba::launch_keypoint_errors(nullptr, d_out, d_uv, n_points, n_points, d_cams, n_cameras, d_err) != 0) return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: bad launch");
-    if (int rc = check_launch()) return rc;
-  }
-  HIPCHK(call.stop(kernel_ms));
-  HIPCHK(hipMemcpy(points_out, d_out, 3 * n_points * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(inliers_out, d_mask, n_points * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  if (info_out) HIPCHK(hipMemcpy(info_out, d_info, 8 * n_points * sizeof(double), hipMemcpyDeviceToHost));
-  if (errors_out) HIPCHK(hipMemcpy(errors_out, d_err, (size_t)n_cameras * n_points * sizeof(double), hipMemcpyDeviceToHost));
-  return MCBA_OK;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // Single-camera calibration with OpenCV's five-coefficient model (reference calibration.py:11-71 -> cv2.calibrateCamera without
 // CALIB_FIX_K3 / CALIB_ZERO_TANGENT_DIST; :74-113 -> cv2.solvePnP with such coefficients): stateless; per view the Gauss-Newton block of
@@ -587,20 +329,16 @@ int mcba_calib_normal_equations(int n_views, int n_points, const double* uvs, co
   if (int rc = stateless_device(device)) return rc;
   const size_t nuv = (size_t)2 * n_views * n_points, nobj = (size_t)3 * n_points, npose = (size_t)6 * n_views, nout = (size_t)136 * n_views;
   const size_t total = nuv + nobj + 9 + npose + nout;
+  StatelessCall call;
   double* d = nullptr;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), total * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(d, uvs, nuv * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + nuv, objpoints, nobj * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + nuv + nobj, intr9, 9 * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d + nuv + nobj + 9, poses, npose * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    mcba::launch_calib_views(nullptr, d, d + nuv, d + nuv + nobj, d + nuv + nobj + 9, n_views, n_points, d + nuv + nobj + 9 + npose);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(out, d + nuv + nobj + 9 + npose, nout * sizeof(double), hipMemcpyDeviceToHost);
-  if (d) (void)hipFree(d);
-  if (e != hipSuccess) { g_err = std::string("mcba_calib_normal_equations: ") + hipGetErrorString(e); return MCBA_ERR_HIP; }
-  return MCBA_OK;
+  if (int rc = call.scratch(&d, total)) return rc;   // one slab: the four put() below fill its input slices, the kernel its last nout
+  if (int rc = call.put(d, uvs, nuv)) return rc;
+  if (int rc = call.put(d + nuv, objpoints, nobj)) return rc;
+  if (int rc = call.put(d + nuv + nobj, intr9, 9)) return rc;
+  if (int rc = call.put(d + nuv + nobj + 9, poses, npose)) return rc;
+  mcba::launch_calib_views(nullptr, d, d + nuv, d + nuv + nobj, d + nuv + nobj + 9, n_views, n_points, d + nuv + nobj + 9 + npose);
+  if (int rc = check_launch()) return rc;
+  return call.download(out, d + nuv + nobj + 9 + npose, nout);
 }
 
 }  // extern "C"

@@ -534,15 +534,6 @@ using namespace mcba_internal;
 
 namespace {
 
-// a buffer nobody fills before a kernel reads what it wrote: filled with the MCBA_POISON byte when that mode is on (tests)
-template <class T>
-int det_alloc(StatelessCall& call, T** p, size_t count) {
-  HIPCHK(call.alloc(p, count));
-  if (int pz = poison_byte()) HIPCHK(hipMemset(*p, pz, count * sizeof(T) > 0 ? count * sizeof(T) : 16));
-  return MCBA_OK;
-}
-#define DALLOC(p, n) do { if (int rc_ = det_alloc(call, p, n)) return rc_; } while (0)
-
 int check_image(int height, int width, int channels) {
   if (height < 8 || width < 8 || height > MCBA_DETECT_MAX_IMAGE_SIDE || width > MCBA_DETECT_MAX_IMAGE_SIDE)
     return fail(MCBA_ERR_ARG, "mcba_detect: image sides must lie in 8 .. MCBA_DETECT_MAX_IMAGE_SIDE");
@@ -599,21 +590,23 @@ int mcba_detect_chessboards(int n_images, int height, int width, int channels, c
   int* d_gstat = nullptr;
   double* d_scores = nullptr;
   int8_t* d_status = nullptr;
-  DALLOC(&d_in, (size_t)chunk * px * channels);
-  if (channels == 3) DALLOC(&d_grey, (size_t)chunk * px);
-  else d_grey = d_in;
-  if (resized) DALLOC(&d_det, (size_t)chunk * pxd);
-  else d_det = d_grey;
-  DALLOC(&d_resp, (size_t)chunk * pxd);
-  DALLOC(&d_rmax, (size_t)chunk);
-  DALLOC(&d_cnt, (size_t)chunk);
-  DALLOC(&d_cand, (size_t)chunk * MCBA_DETECT_MAX_CANDIDATES);
-  DALLOC(&d_start, (size_t)chunk * N);
-  DALLOC(&d_ref, (size_t)chunk * N);
-  DALLOC(&d_out, (size_t)chunk * N);
-  DALLOC(&d_gstat, (size_t)chunk);
-  DALLOC(&d_scores, (size_t)chunk * 4);
-  DALLOC(&d_status, (size_t)chunk);
+  if (int rc = call.scratch(&d_in, (size_t)chunk * px * channels)) return rc;   // staging: every chunk's put() below fills the B images that its kernels read
+  d_grey = d_in;
+  if (channels == 3)
+    if (int rc = call.scratch(&d_grey, (size_t)chunk * px)) return rc;
+  d_det = d_grey;
+  if (resized)
+    if (int rc = call.scratch(&d_det, (size_t)chunk * pxd)) return rc;
+  if (int rc = call.scratch(&d_resp, (size_t)chunk * pxd)) return rc;
+  if (int rc = call.scratch(&d_rmax, (size_t)chunk)) return rc;
+  if (int rc = call.scratch(&d_cnt, (size_t)chunk)) return rc;
+  if (int rc = call.scratch(&d_cand, (size_t)chunk * MCBA_DETECT_MAX_CANDIDATES)) return rc;
+  if (int rc = call.scratch(&d_start, (size_t)chunk * N)) return rc;
+  if (int rc = call.scratch(&d_ref, (size_t)chunk * N)) return rc;
+  if (int rc = call.scratch(&d_out, (size_t)chunk * N)) return rc;
+  if (int rc = call.scratch(&d_gstat, (size_t)chunk)) return rc;
+  if (int rc = call.scratch(&d_scores, (size_t)chunk * 4)) return rc;
+  if (int rc = call.scratch(&d_status, (size_t)chunk)) return rc;
   std::vector<int> gstat(chunk);
   std::vector<int8_t> st(chunk);
   std::vector<float2> uv((size_t)chunk * N);
@@ -623,7 +616,7 @@ int mcba_detect_chessboards(int n_images, int height, int width, int channels, c
   const bool square = board_cols == board_rows;
   for (int f0 = 0; f0 < n_images; f0 += chunk) {
     const int B = std::min(chunk, n_images - f0);
-    HIPCHK(hipMemcpy(d_in, images + (size_t)f0 * px * channels, (size_t)B * px * channels, hipMemcpyHostToDevice));
+    if (int rc = call.put(d_in, images + (size_t)f0 * px * channels, (size_t)B * px * channels)) return rc;
     HIPCHK(hipMemset(d_rmax, 0, (size_t)B * sizeof(unsigned)));
     HIPCHK(hipMemset(d_cnt, 0, (size_t)B * sizeof(unsigned)));
     HIPCHK(hipEventRecord(call.e0, nullptr));
@@ -652,11 +645,11 @@ int mcba_detect_chessboards(int n_images, int height, int width, int channels, c
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, call.e0, call.e1));
     total_ms += ms;
-    HIPCHK(hipMemcpy(gstat.data(), d_gstat, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(uv.data(), reorder ? d_out : d_ref, (size_t)B * N * sizeof(float2), hipMemcpyDeviceToHost));
+    if (int rc = call.download(gstat.data(), d_gstat, (size_t)B)) return rc;
+    if (int rc = call.download(uv.data(), reorder ? d_out : d_ref, (size_t)B * N)) return rc;
     if (reorder) {
-      HIPCHK(hipMemcpy(st.data(), d_status, (size_t)B, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(sc.data(), d_scores, (size_t)B * 4 * sizeof(double), hipMemcpyDeviceToHost));
+      if (int rc = call.download(st.data(), d_status, (size_t)B)) return rc;
+      if (int rc = call.download(sc.data(), d_scores, (size_t)B * 4)) return rc;
     }
     for (int b = 0; b < B; ++b) {
       const size_t f = (size_t)f0 + b;
@@ -687,20 +680,18 @@ int mcba_detect_subpix(int height, int width, int channels, const unsigned char*
   StatelessCall call;
   uint8_t *d_in = nullptr, *d_grey = nullptr;
   float2 *d_start = nullptr, *d_out = nullptr;
-  DALLOC(&d_in, px * channels);
-  if (channels == 3) DALLOC(&d_grey, px);
-  else d_grey = d_in;
-  DALLOC(&d_start, (size_t)n_corners);
-  DALLOC(&d_out, (size_t)n_corners);
-  HIPCHK(hipMemcpy(d_in, image, px * channels, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_start, start, (size_t)n_corners * sizeof(float2), hipMemcpyHostToDevice));
+  if (int rc = call.upload(&d_in, image, px * channels)) return rc;
+  d_grey = d_in;
+  if (channels == 3)
+    if (int rc = call.scratch(&d_grey, px)) return rc;
+  if (int rc = call.upload(&d_start, reinterpret_cast<const float2*>(start), (size_t)n_corners)) return rc;
+  if (int rc = call.scratch(&d_out, (size_t)n_corners)) return rc;
   HIPCHK(call.start());
   if (int rc = launch_prep(d_in, 1, height, width, channels, d_grey)) return rc;
   mcba::k_det_subpix<<<dim3((unsigned)n_corners), dim3(64)>>>(d_grey, width, height, d_start, n_corners, nullptr, win_w, win_h, d_out);
   if (int rc = check_launch()) return rc;
   HIPCHK(call.stop(kernel_ms));
-  HIPCHK(hipMemcpy(out, d_out, (size_t)n_corners * sizeof(float2), hipMemcpyDeviceToHost));
-  return MCBA_OK;
+  return call.download(reinterpret_cast<float2*>(out), d_out, (size_t)n_corners);
 }
 
 int mcba_detect_anchor(int height, int width, int channels, const unsigned char* image, int board_cols, int board_rows, const float* uvs, int device, double* scores_out,
@@ -716,26 +707,25 @@ int mcba_detect_anchor(int height, int width, int channels, const unsigned char*
   float2 *d_uv = nullptr, *d_quad = nullptr;
   double* d_sc = nullptr;
   int8_t* d_st = nullptr;
-  DALLOC(&d_in, px * channels);
-  if (channels == 3) DALLOC(&d_grey, px);
-  else d_grey = d_in;
-  DALLOC(&d_uv, (size_t)N);
-  DALLOC(&d_sc, 4);
-  DALLOC(&d_st, 1);
-  DALLOC(&d_reg, 4 * 1600);
-  DALLOC(&d_quad, 16);
-  HIPCHK(hipMemcpy(d_in, image, px * channels, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_uv, uvs, (size_t)N * sizeof(float2), hipMemcpyHostToDevice));
+  if (int rc = call.upload(&d_in, image, px * channels)) return rc;
+  d_grey = d_in;
+  if (channels == 3)
+    if (int rc = call.scratch(&d_grey, px)) return rc;
+  if (int rc = call.upload(&d_uv, reinterpret_cast<const float2*>(uvs), (size_t)N)) return rc;
+  if (int rc = call.scratch(&d_sc, 4)) return rc;
+  if (int rc = call.scratch(&d_st, 1)) return rc;
+  if (int rc = call.scratch(&d_reg, 4 * 1600)) return rc;
+  if (int rc = call.scratch(&d_quad, 16)) return rc;
   HIPCHK(call.start());
   if (int rc = launch_prep(d_in, 1, height, width, channels, d_grey)) return rc;
   const mcba::AnchorArgs aa{width, height, board_rows, board_cols, 0, 0.0};
   mcba::k_det_anchor<<<dim3(1), dim3(256)>>>(d_grey, d_uv, nullptr, aa, d_sc, 0, d_st, nullptr, d_reg, d_quad);
   if (int rc = check_launch()) return rc;
   HIPCHK(call.stop(kernel_ms));
-  HIPCHK(hipMemcpy(scores_out, d_sc, 4 * sizeof(double), hipMemcpyDeviceToHost));
-  if (regions_out) HIPCHK(hipMemcpy(regions_out, d_reg, 4 * 1600, hipMemcpyDeviceToHost));
-  if (quads_out) HIPCHK(hipMemcpy(quads_out, d_quad, 16 * sizeof(float2), hipMemcpyDeviceToHost));
-  return MCBA_OK;
+  if (int rc = call.download(scores_out, d_sc, 4)) return rc;
+  if (regions_out)
+    if (int rc = call.download(regions_out, d_reg, 4 * 1600)) return rc;
+  return quads_out ? call.download(reinterpret_cast<float2*>(quads_out), d_quad, 16) : MCBA_OK;
 }
 
 }  // extern "C"

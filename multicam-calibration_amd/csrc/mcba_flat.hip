@@ -221,18 +221,16 @@ int mcba_flat_floor_points(size_t n_frames, int n_keypoints, const double* keypo
   double *d_kp = nullptr, *d_out = nullptr;
   int* d_idx = nullptr;
   const size_t nin = n_frames * 3 * (size_t)K;
-  HIPCHK(call.alloc(&d_kp, nin));
-  HIPCHK(call.alloc(&d_out, 3 * n_frames));
-  HIPCHK(call.alloc(&d_idx, n_frames));
-  HIPCHK(hipMemcpy(d_kp, keypoints, nin * sizeof(double), hipMemcpyHostToDevice));
+  if (int rc = call.upload(&d_kp, keypoints, nin)) return rc;
+  if (int rc = call.scratch(&d_out, 3 * n_frames)) return rc;
+  if (int rc = call.scratch(&d_idx, n_frames)) return rc;
   HIPCHK(call.start());
   const size_t nblk = (n_frames + fpb - 1) / fpb;
   mcba::k_floor_points<<<dim3((unsigned)nblk), dim3(mcba::kFlatThreads), (size_t)fpb * 3 * K * sizeof(double)>>>(d_kp, n_frames, K, fpb, z_points_down ? 1 : 0, d_out, d_idx);
-  HIPCHK(hipGetLastError());
+  if (int rc = check_launch()) return rc;
   HIPCHK(call.stop(kernel_ms));
-  HIPCHK(hipMemcpy(points_out, d_out, 3 * n_frames * sizeof(double), hipMemcpyDeviceToHost));
-  if (index_out) HIPCHK(hipMemcpy(index_out, d_idx, n_frames * sizeof(int), hipMemcpyDeviceToHost));
-  return MCBA_OK;
+  if (int rc = call.download(points_out, d_out, 3 * n_frames)) return rc;
+  return index_out ? call.download(index_out, d_idx, n_frames) : MCBA_OK;
 }
 
 int mcba_flat_ransac(size_t n_points, const double* points, int n_hypotheses, const double* planes, double threshold, const double* shift2, int device,
@@ -248,30 +246,28 @@ int mcba_flat_ransac(size_t n_points, const double* points, int n_hypotheses, co
   unsigned* d_pn = nullptr;
   unsigned long long* d_cnt = nullptr;
   unsigned char* d_mask = nullptr;
-  HIPCHK(call.alloc(&d_pts, 3 * n_points));
-  HIPCHK(call.alloc(&d_planes, 3 * (size_t)H));
-  HIPCHK(call.alloc(&d_pm, nblk * H * mcba::kMom));
-  HIPCHK(call.alloc(&d_pn, nblk * H));
-  HIPCHK(call.alloc(&d_mom, (size_t)H * mcba::kMom));
-  HIPCHK(call.alloc(&d_cnt, (size_t)H));
-  if (mask_out) HIPCHK(call.alloc(&d_mask, n_points));
-  HIPCHK(hipMemcpy(d_pts, points, 3 * n_points * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_planes, planes, 3 * (size_t)H * sizeof(double), hipMemcpyHostToDevice));
+  if (int rc = call.upload(&d_pts, points, 3 * n_points)) return rc;
+  if (int rc = call.upload(&d_planes, planes, 3 * (size_t)H)) return rc;
+  if (int rc = call.scratch(&d_pm, nblk * H * mcba::kMom)) return rc;
+  if (int rc = call.scratch(&d_pn, nblk * H)) return rc;
+  if (int rc = call.scratch(&d_mom, (size_t)H * mcba::kMom)) return rc;
+  if (int rc = call.scratch(&d_cnt, (size_t)H)) return rc;
+  if (mask_out)
+    if (int rc = call.scratch(&d_mask, n_points)) return rc;
   HIPCHK(call.start());
   mcba::k_ransac_score<<<dim3((unsigned)nblk), dim3(mcba::kFlatThreads)>>>(d_pts, n_points, d_planes, H, threshold, shift2[0], shift2[1], d_pm, d_pn);
-  HIPCHK(hipGetLastError());
+  if (int rc = check_launch()) return rc;
   mcba::k_ransac_finish<<<dim3((unsigned)H), dim3(mcba::kFlatThreads)>>>(d_pm, d_pn, (int)nblk, H, d_mom, d_cnt);
-  HIPCHK(hipGetLastError());
+  if (int rc = check_launch()) return rc;
   if (mask_out) {
     mcba::k_ransac_mask<<<dim3((unsigned)((n_points + mcba::kFlatThreads - 1) / mcba::kFlatThreads)), dim3(mcba::kFlatThreads)>>>(d_pts, n_points, planes[0], planes[1], planes[2],
                                                                                                                             threshold, d_mask);
-    HIPCHK(hipGetLastError());
+    if (int rc = check_launch()) return rc;
   }
   HIPCHK(call.stop(kernel_ms));
-  HIPCHK(hipMemcpy(counts_out, d_cnt, (size_t)H * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(moments_out, d_mom, (size_t)H * mcba::kMom * sizeof(double), hipMemcpyDeviceToHost));
-  if (mask_out) HIPCHK(hipMemcpy(mask_out, d_mask, n_points, hipMemcpyDeviceToHost));
-  return MCBA_OK;
+  if (int rc = call.download(counts_out, d_cnt, (size_t)H)) return rc;
+  if (int rc = call.download(moments_out, d_mom, (size_t)H * mcba::kMom)) return rc;
+  return mask_out ? call.download(mask_out, d_mask, n_points) : MCBA_OK;
 }
 
 int mcba_flat_order_stats(size_t n_points, const double* points, const double* rt12, int n_ranks, const long long* ranks, int device, double* values_out, double* sums_out,
@@ -289,28 +285,27 @@ int mcba_flat_order_stats(size_t n_points, const double* points, const double* r
   double *d_pts = nullptr, *d_rt = nullptr, *d_xy = nullptr, *d_ps = nullptr;
   unsigned long long* d_nan = nullptr;
   mcba::SelState* d_st = nullptr;
-  HIPCHK(call.alloc(&d_pts, 3 * n));
-  HIPCHK(call.alloc(&d_rt, 12));
-  HIPCHK(call.alloc(&d_xy, 2 * n));
-  HIPCHK(call.alloc(&d_ps, 2 * nblk));
-  HIPCHK(call.alloc(&d_nan, 2));
-  HIPCHK(call.alloc(&d_st, st.size()));
-  HIPCHK(hipMemcpy(d_pts, points, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_rt, rt12, 12 * sizeof(double), hipMemcpyHostToDevice));
+  if (int rc = call.upload(&d_pts, points, 3 * n)) return rc;
+  if (int rc = call.upload(&d_rt, rt12, 12)) return rc;
+  if (int rc = call.scratch(&d_xy, 2 * n)) return rc;
+  if (int rc = call.scratch(&d_ps, 2 * nblk)) return rc;
+  if (int rc = call.scratch(&d_nan, 2)) return rc;
+  if (int rc = call.scratch(&d_st, st.size())) return rc;
   HIPCHK(hipMemset(d_nan, 0, 2 * sizeof(unsigned long long)));
   HIPCHK(call.start());
   mcba::k_flat_transform<<<dim3((unsigned)nblk), dim3(mcba::kFlatThreads)>>>(d_pts, n, d_rt, d_xy, d_ps, d_nan);
-  HIPCHK(hipGetLastError());
+  if (int rc = check_launch()) return rc;
   if (n_ranks > 0) {
     // (the select skips NaNs, so a coordinate that holds one has fewer values than a rank may assume: the caller reports NaN for it)
     mcba::launch_select(nullptr, d_xy, nullptr, n, 2 /* groups: x, y */, 1 /* no frame mask */, d_st, 1 /* either sign */, rk.data(), n_ranks);
-    HIPCHK(hipGetLastError());
+    if (int rc = check_launch()) return rc;
   }
   HIPCHK(call.stop(kernel_ms));
   std::vector<double> ps(2 * nblk);
-  HIPCHK(hipMemcpy(ps.data(), d_ps, 2 * nblk * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(nans_out, d_nan, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  if (n_ranks > 0) HIPCHK(hipMemcpy(st.data(), d_st, st.size() * sizeof(mcba::SelState), hipMemcpyDeviceToHost));
+  if (int rc = call.download(ps.data(), d_ps, 2 * nblk)) return rc;
+  if (int rc = call.download(nans_out, d_nan, 2)) return rc;
+  if (n_ranks > 0)
+    if (int rc = call.download(st.data(), d_st, st.size())) return rc;
   for (size_t q = 0; q < st.size(); ++q) values_out[q] = mcba::sel_value(st[q]);
   for (int c = 0; c < 2; ++c) {  // the per-block sums, in block order
     double s = 0.0;

@@ -1,5 +1,5 @@
 // mcba_handle.h -- what the translation units of the C ABI (mcba_api.hip, mcba_lm_api.hip, mcba_prefilter_api.hip, mcba_calib_api.hip,
-// mcba_comm_api.hip, mcba_flat.hip) share: the handle, the error plumbing, the buffer pool, profiling scopes and the launch helpers of the solver chain.
+// mcba_geom_api.hip, mcba_comm_api.hip, mcba_flat.hip, mcba_detect.hip) share: the handle, the error plumbing, the buffer pool, profiling scopes and the launch helpers of the solver chain.
 // Private to the library: not installed, not part of include/mcba.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -225,7 +225,8 @@ inline int stateless_device(int device, const char* who = nullptr) {
   return MCBA_OK;
 }
 
-// the device buffers and events of one stateless call (null stream), released on every path out; start / stop time its kernels
+// the device buffers and events of one stateless call (null stream), released on every path out.  upload / scratch / put / download return
+// an MCBA_* code with g_err set; counts are elements of T, the type of both the host and the device side; start / stop time the call's kernels
 struct StatelessCall {
   std::vector<void*> bufs;
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -235,12 +236,35 @@ struct StatelessCall {
     if (e1) (void)hipEventDestroy(e1);
   }
   template <class T>
-  hipError_t alloc(T** p, size_t count) {
+  int alloc(T** p, size_t count, bool poison) {
+    const size_t bytes = count * sizeof(T) > 0 ? count * sizeof(T) : 16;
     void* v = nullptr;
-    hipError_t e = hipMalloc(&v, count * sizeof(T) > 0 ? count * sizeof(T) : 16);
-    if (e == hipSuccess) bufs.push_back(v);
+    HIPCHK(hipMalloc(&v, bytes));
+    bufs.push_back(v);
     *p = static_cast<T*>(v);
-    return e;
+    if (int pz = poison ? poison_byte() : 0) HIPCHK(hipMemset(v, pz, bytes));
+    return MCBA_OK;
+  }
+  // a buffer that a kernel writes before anything reads it, outputs included: filled with the MCBA_POISON byte when that mode is on (tests:
+  // whatever reads an element nobody wrote shows).  Inputs go through upload(); only a slab that holds inputs and scratch in one allocation,
+  // or a staging buffer refilled per chunk, is made here and has its input slices filled by put() or the caller's own copies
+  template <class T>
+  int scratch(T** p, size_t count) { return alloc(p, count, true); }
+  template <class T>
+  int put(T* dst, const T* host, size_t count) {
+    HIPCHK(hipMemcpy(dst, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return MCBA_OK;
+  }
+  // a buffer holding `count` elements of a host array
+  template <class T>
+  int upload(T** p, const T* host, size_t count) {
+    if (int rc = alloc(p, count, false)) return rc;
+    return put(*p, host, count);
+  }
+  template <class T>
+  int download(T* host, const T* src, size_t count) {
+    HIPCHK(hipMemcpy(host, src, count * sizeof(T), hipMemcpyDeviceToHost));
+    return MCBA_OK;
   }
   hipError_t start() {
     hipError_t e = hipEventCreate(&e0);

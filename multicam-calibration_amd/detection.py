@@ -44,11 +44,6 @@ STATUS_NONE, STATUS_ACCEPTED, STATUS_AMBIGUOUS = 0, 1, 2
 _STATUS_OVERFLOW = 3
 
 
-def _check(lib, rc):
-    if rc != ops.OK:
-        raise ops.McbaError(rc, lib.mcba_last_error().decode())
-
-
 def _board(board_shape):
     cols, rows = (int(v) for v in board_shape)
     if cols < 2 or rows < 2:
@@ -128,13 +123,12 @@ def detect_chessboards(images, *, board_shape=(7, 10), subpix_winSize=(5, 5), sc
     if not (0.0 < s <= 1.0):
         raise NotImplementedError("scale_factor must lie in (0, 1]")
     N = cols * rows
-    lib = ops.load_library()
     uvs = np.empty((B, N, 2), dtype=np.float32)
     scores = np.empty((B, 4))
     status = np.empty(B, dtype=np.int8)
     ms = np.zeros(1)
-    _check(lib, lib.mcba_detect_chessboards(B, H, W, ch, frames.ctypes.data, cols, rows, w, h, s, int(bool(reorder)), float(match_score_min_diff), int(memory_budget),
-                                            int(device), uvs.ctypes.data, scores.ctypes.data, status.ctypes.data, ms.ctypes.data))
+    ops.call("mcba_detect_chessboards", B, H, W, ch, frames.ctypes.data, cols, rows, w, h, s, int(bool(reorder)), float(match_score_min_diff), int(memory_budget),
+             int(device), uvs.ctypes.data, scores.ctypes.data, status.ctypes.data, ms.ctypes.data)
     over = np.flatnonzero(status == _STATUS_OVERFLOW)
     if len(over):
         warnings.warn("chessboard detection: %d frame(s) had more than %d corner candidates and were not searched: %s"
@@ -169,8 +163,7 @@ def corner_subpix(image, corners, subpix_winSize=(5, 5), *, device=0):
     w, h = _window(subpix_winSize)
     start = np.ascontiguousarray(np.asarray(corners, dtype=np.float32).reshape(-1, 2))
     out = np.empty_like(start)
-    lib = ops.load_library()
-    _check(lib, lib.mcba_detect_subpix(img.shape[0], img.shape[1], ch, img.ctypes.data, start.shape[0], start.ctypes.data, w, h, int(device), out.ctypes.data, None))
+    ops.call("mcba_detect_subpix", img.shape[0], img.shape[1], ch, img.ctypes.data, start.shape[0], start.ctypes.data, w, h, int(device), out.ctypes.data, None)
     return out
 
 
@@ -191,9 +184,8 @@ def reorder_chessboard_corners(image, uvs, board_shape, template_size=40, *, dev
     scores = np.empty(4)
     regions = np.empty((4, TEMPLATE_SIZE, TEMPLATE_SIZE), dtype=np.uint8)
     quads = np.empty((4, 4, 2), dtype=np.float32)
-    lib = ops.load_library()
-    _check(lib, lib.mcba_detect_anchor(img.shape[0], img.shape[1], ch, img.ctypes.data, cols, rows, u.ctypes.data, int(device), scores.ctypes.data, regions.ctypes.data,
-                                       quads.ctypes.data, None))
+    ops.call("mcba_detect_anchor", img.shape[0], img.shape[1], ch, img.ctypes.data, cols, rows, u.ctypes.data, int(device), scores.ctypes.data, regions.ctypes.data,
+             quads.ctypes.data, None)
     uv_grid = np.asarray(uvs).reshape(rows, cols, 2)
     best = int(np.argmax(scores))
     if best in (2, 3):

@@ -31,11 +31,6 @@ def _concat(a):
     return np.concatenate(a) if isinstance(a, list) else a
 
 
-def _check(lib, rc):
-    if rc != ops.OK:
-        raise ops.McbaError(rc, lib.mcba_last_error().decode())
-
-
 # ------------------------------------------------------------------ get_floor_points (flatibration.py:40-60)
 def get_floor_points(keypoints, z_points_down=False, *, device=0, return_index=False):
     """keypoints (n_frames, n_keypoints, 3), or a list of such arrays (concatenated).  Returns (n_frames, 3): per frame the keypoint
@@ -48,11 +43,10 @@ def get_floor_points(keypoints, z_points_down=False, *, device=0, return_index=F
         raise ValueError("attempt to get argmin of an empty sequence")
     if K > MAX_KEYPOINTS:
         raise NotImplementedError("get_floor_points supports at most %d keypoints per frame" % MAX_KEYPOINTS)
-    lib = ops.load_library()
     data = np.ascontiguousarray(kp, dtype=np.float64)
     out = np.empty((F, 3))
     idx = np.empty(F, dtype=np.int32)
-    _check(lib, lib.mcba_flat_floor_points(F, K, data.ctypes.data, int(bool(z_points_down)), int(device), out.ctypes.data, idx.ctypes.data, None))
+    ops.call("mcba_flat_floor_points", F, K, data.ctypes.data, int(bool(z_points_down)), int(device), out.ctypes.data, idx.ctypes.data, None)
     if np.issubdtype(kp.dtype, np.floating) and kp.dtype != np.float64:
         out = out.astype(kp.dtype)  # (exact: the values were widened, compared and copied)
     return (out, idx.astype(np.intp)) if return_index else out
@@ -205,12 +199,11 @@ def ransac_plane(points, residual_threshold=10, *, device=0, forced_trials=None,
     trials = MAX_TRIALS if forced_trials is None else int(forced_trials)
     idx, states = draw_subsets(n, trials)
     planes = np.ascontiguousarray(hypotheses(P, idx))
-    lib = ops.load_library()
     counts = np.empty(trials, dtype=np.uint64)
     moments = np.empty((trials, 9))
     shift = np.ascontiguousarray(P[0, :2])
-    _check(lib, lib.mcba_flat_ransac(n, P.ctypes.data, trials, planes.ctypes.data, float(residual_threshold), shift.ctypes.data, int(device), counts.ctypes.data,
-                                     moments.ctypes.data, None, None))
+    ops.call("mcba_flat_ransac", n, P.ctypes.data, trials, planes.ctypes.data, float(residual_threshold), shift.ctypes.data, int(device), counts.ctypes.data,
+             moments.ctypes.data, None, None)
     scores = r2_scores(planes, counts, moments)
     if forced_trials is not None:
         best, n_trials, margin = int(np.argmax(counts)), trials, np.inf
@@ -229,12 +222,11 @@ def ransac_plane(points, residual_threshold=10, *, device=0, forced_trials=None,
 def inlier_mask(points, plane, residual_threshold, *, device=0):
     """The inliers of one plane on the device (the same test the scoring kernel counts): n bytes -> bool."""
     P = np.ascontiguousarray(points, dtype=np.float64)
-    lib = ops.load_library()
     pl = np.ascontiguousarray(plane, dtype=np.float64)
     mask = np.empty(P.shape[0], dtype=np.uint8)
     counts, moments, shift = np.empty(1, dtype=np.uint64), np.empty((1, 9)), np.ascontiguousarray(P[0, :2])
-    _check(lib, lib.mcba_flat_ransac(P.shape[0], P.ctypes.data, 1, pl.ctypes.data, float(residual_threshold), shift.ctypes.data, int(device), counts.ctypes.data,
-                                     moments.ctypes.data, mask.ctypes.data, None))
+    ops.call("mcba_flat_ransac", P.shape[0], P.ctypes.data, 1, pl.ctypes.data, float(residual_threshold), shift.ctypes.data, int(device), counts.ctypes.data,
+             moments.ctypes.data, mask.ctypes.data, None)
     return mask.astype(bool)
 
 
@@ -309,12 +301,11 @@ def arena_center(transform, floor_points, center_method="midrange", range_pctl=1
         ranks = np.array([(n - 1) // 2, n // 2], dtype=np.int64)
     else:
         ranks = np.zeros(0, dtype=np.int64)
-    lib = ops.load_library()
     values = np.empty((2, max(len(ranks), 1)))
     sums = np.empty(2)
     nans = np.empty(2, dtype=np.uint64)
-    _check(lib, lib.mcba_flat_order_stats(n, P.ctypes.data, rt12.ctypes.data, len(ranks), ranks.ctypes.data, int(device), values.ctypes.data, sums.ctypes.data,
-                                          nans.ctypes.data, None))
+    ops.call("mcba_flat_order_stats", n, P.ctypes.data, rt12.ctypes.data, len(ranks), ranks.ctypes.data, int(device), values.ctypes.data, sums.ctypes.data,
+             nans.ctypes.data, None)
     if center_method == "mean":
         return sums / n
     if center_method == "median":

@@ -16,8 +16,6 @@ Host (numpy, the reference's formulas): rigid_transform_from_correspondences (re
 get_projection_matrix, euclidean_to_homogenous, homogeneous_to_euclidean, and rodrigues / rodrigues_inv / get_transformation_matrix /
 get_transformation_vector re-exported from calibration.py.
 """
-import ctypes
-
 import numpy as np
 
 from . import ops
@@ -25,11 +23,6 @@ from .calibration import rodrigues, rodrigues_inv, get_transformation_matrix, ge
 from .triangulation import _cam_blocks, _stack_uvs, DEFAULT_MAX_ITERATIONS
 
 STATUS = {1: "converged", 0: "iteration limit", -1: "too few views"}
-
-
-def _chk(lib, rc):
-    if rc != ops.OK:
-        raise ops.McbaError(rc, lib.mcba_last_error().decode())
 
 
 def _points(points):
@@ -40,11 +33,10 @@ def _points(points):
 
 
 def _project(flat, cam, dist, device):
-    lib = ops.load_library()
     C, P = len(cam), len(flat)
     out = np.empty((C, P, 2))
     if P:
-        _chk(lib, lib.mcba_project_points(C, P, flat.ctypes.data, cam.ctypes.data, None if dist is None else dist.ctypes.data, int(device), out.ctypes.data, None))
+        ops.call("mcba_project_points", C, P, flat.ctypes.data, cam.ctypes.data, None if dist is None else dist.ctypes.data, int(device), out.ctypes.data, None)
     return out
 
 
@@ -82,9 +74,8 @@ def apply_rigid_transform(transform, points, *, device=0):
     lead, flat = _points(points)
     out = np.empty_like(flat)
     if len(flat):
-        lib = ops.load_library()
         T12 = np.ascontiguousarray(np.r_[T[:3, :3].ravel(), T[:3, 3]])
-        _chk(lib, lib.mcba_rigid_transform(len(flat), flat.ctypes.data, T12.ctypes.data, int(device), out.ctypes.data))
+        ops.call("mcba_rigid_transform", len(flat), flat.ctypes.data, T12.ctypes.data, int(device), out.ctypes.data)
     return out.reshape(lead + (3,))
 
 
@@ -107,8 +98,7 @@ def keypoint_reprojection_errors(points, all_uvs, all_extrinsics, all_intrinsics
     med = np.full(C, np.nan)
     err = np.empty((C, P)) if arrays else None
     if P:
-        lib = ops.load_library()
-        _chk(lib, lib.mcba_keypoint_errors(C, P, pts.ctypes.data, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, int(device), None if err is None else err.ctypes.data, med.ctypes.data, None))
+        ops.call("mcba_keypoint_errors", C, P, pts.ctypes.data, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, int(device), None if err is None else err.ctypes.data, med.ctypes.data, None)
     return err, med
 
 
@@ -137,9 +127,8 @@ def refine_triangulation(points, all_uvs, all_extrinsics, all_intrinsics, *, los
     out = np.empty((P, 3))
     info = np.empty((P, 4))
     if P:
-        lib = ops.load_library()
-        _chk(lib, lib.mcba_triangulate_refine(C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, 0, ops.LOSSES[loss], float(f_scale), int(max_iterations), int(device),
-                                              out.ctypes.data, info.ctypes.data, None))
+        ops.call("mcba_triangulate_refine", C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, 0, ops.LOSSES[loss], float(f_scale), int(max_iterations), int(device),
+                 out.ctypes.data, info.ctypes.data, None)
     if not return_info:
         return out
     return out, dict(cost=info[:, 0].copy(), cost0=info[:, 1].copy(), n_iterations=info[:, 2].astype(np.int64), status=info[:, 3].astype(np.int64))
@@ -186,10 +175,9 @@ def triangulate_consensus(all_uvs, all_extrinsics, all_intrinsics, *, threshold,
     info = np.empty((P, 8)) if return_info else None
     err = np.empty((C, P)) if return_errors else None
     if P:
-        lib = ops.load_library()
-        _chk(lib, lib.mcba_triangulate_consensus(C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, float(threshold), int(min_views), int(undistort_iterations), ops.LOSSES[loss],
-                                                 float(f_scale), int(max_iterations), int(device), out.ctypes.data, words.ctypes.data, None if info is None else info.ctypes.data,
-                                                 None if err is None else err.ctypes.data, None))
+        ops.call("mcba_triangulate_consensus", C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, float(threshold), int(min_views), int(undistort_iterations), ops.LOSSES[loss],
+                 float(f_scale), int(max_iterations), int(device), out.ctypes.data, words.ctypes.data, None if info is None else info.ctypes.data,
+                 None if err is None else err.ctypes.data, None)
     inliers = ((words[None, :] >> np.arange(C, dtype=np.uint64)[:, None]) & np.uint64(1)).astype(bool)
     res = (out, inliers)
     if return_info:

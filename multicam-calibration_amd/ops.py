@@ -169,6 +169,18 @@ def load_library():
     return lib
 
 
+def _raise(lib, rc):
+    raise McbaError(rc, lib.mcba_last_error().decode())
+
+
+def call(name, *args):
+    """Load the library, call its symbol `name`; a non-zero return code raises McbaError with the library's message."""
+    lib = load_library()
+    rc = getattr(lib, name)(*args)
+    if rc:
+        _raise(lib, rc)
+
+
 def _p(a):
     return a.ctypes.data
 
@@ -190,7 +202,7 @@ class DeviceArray:
             out = np.empty(self.shape)
             rc = self.lib.mcba_buffer_download(self.handle, _p(out))
             if rc != OK:
-                raise McbaError(rc, self.lib.mcba_last_error().decode())
+                _raise(self.lib, rc)
             self._host = out
             self.free()
         return self._host
@@ -209,11 +221,8 @@ class DeviceArray:
 
 def fp64_issue_rate(device=0):
     """TFLOP/s of independent v_fma_f64 the device sustains at one wavefront per SIMD (include/mcba.h: mcba_fp64_issue_rate)."""
-    lib = load_library()
     t = ctypes.c_double()
-    rc = lib.mcba_fp64_issue_rate(int(device), ctypes.byref(t))
-    if rc != OK:
-        raise McbaError(rc, lib.mcba_last_error().decode())
+    call("mcba_fp64_issue_rate", int(device), ctypes.byref(t))
     return t.value
 
 
@@ -300,12 +309,7 @@ class Problem:
         self._pending = None
         new = None
         if sub:
-            new = Problem.__new__(Problem)
-            new.lib = self.lib
-            new.C, new.N, new.F = self.C, self.N, int(info[4] - info[5])
-            new.cw, new.n = 12, 12 * self.C
-            new.nx = 12 * new.C + 6 * new.F
-            new.handle = sub
+            new = self._sibling(sub, info[4] - info[5])
             if loss is not None:
                 new.set_loss(loss, 1.0 if f_scale is None else f_scale)
         return status, float(info[0]), info, new
@@ -347,19 +351,15 @@ class Problem:
     def subset(self, frames, loss=None, f_scale=None):
         """A new Problem holding the observations of `frames` (indices into this one), gathered on the GPU."""
         idx = np.ascontiguousarray(frames, dtype=np.int32)
-        new = Problem.__new__(Problem)
-        new.lib = self.lib
-        new.C, new.N, new.F = self.C, self.N, int(idx.size)
-        new.cw, new.n = 12, 12 * self.C
-        new.nx = 12 * new.C + 6 * new.F
-        new.handle = _h()
-        self._chk(self.lib.mcba_create_subset(ctypes.byref(new.handle), self.handle, idx.ctypes.data_as(_ip), int(idx.size)))
+        sub = _h()
+        self._chk(self.lib.mcba_create_subset(ctypes.byref(sub), self.handle, idx.ctypes.data_as(_ip), int(idx.size)))
+        new = self._sibling(sub, idx.size)
         if loss is not None:
             new.set_loss(loss, 1.0 if f_scale is None else f_scale)
         return new
 
-    # ---- calibrate() on the device (include/mcba.h: the mcba_calib_* block; reference calibration.py:11-277)
     def _sibling(self, handle, F):
+        """A Problem around an existing handle of this one's cameras and board, F frames."""
         new = Problem.__new__(Problem)
         new.lib = self.lib
         new.C, new.N, new.F = self.C, self.N, int(F)
@@ -368,6 +368,7 @@ class Problem:
         new.handle = handle
         return new
 
+    # ---- calibrate() on the device (include/mcba.h: the mcba_calib_* block; reference calibration.py:11-277)
     def view_subset(self, views, loss=None, f_scale=None):
         """A new Problem of C cameras x len(views) frames: frame j holds the detection of view j = (camera, frame) in its camera alone."""
         v = np.ascontiguousarray(views, dtype=np.int32).reshape(-1, 2)
@@ -459,7 +460,7 @@ class Problem:
 
     def _chk(self, rc):
         if rc != OK:
-            raise McbaError(rc, self.lib.mcba_last_error().decode())
+            _raise(self.lib, rc)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -979,38 +980,29 @@ class Problem:
 
 def undistort_points(uvs, K4, dist5=None, iterations=5, device=0):
     """(…,2) pixel coordinates -> undistorted pixel coordinates (same camera matrix); NaN rows stay NaN."""
-    lib = load_library()
     a = _f64(uvs)
     out = np.empty_like(a)
     k = _f64(K4)
     d = None if dist5 is None else _f64(dist5)
-    rc = lib.mcba_undistort_points(a.size // 2, _p(a), _p(k), None if d is None else _p(d), int(iterations), int(device), _p(out))
-    if rc != OK:
-        raise McbaError(rc, lib.mcba_last_error().decode())
+    call("mcba_undistort_points", a.size // 2, _p(a), _p(k), None if d is None else _p(d), int(iterations), int(device), _p(out))
     return out
 
 
 def pose_pairwise(poses, edges, device=0):
     """Median relative transforms of camera pairs over a caller's pose array (C,F,6) (include/mcba.h: mcba_pose_pairwise)."""
-    lib = load_library()
     ps = _f64(poses)
     e = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
     out, cnt = np.empty((len(e), 6)), np.empty(len(e))
-    rc = lib.mcba_pose_pairwise(ps.shape[0], ps.shape[1], _p(ps), e.ctypes.data_as(_ip), len(e), int(device), _p(out), _p(cnt))
-    if rc != OK:
-        raise McbaError(rc, lib.mcba_last_error().decode())
+    call("mcba_pose_pairwise", ps.shape[0], ps.shape[1], _p(ps), e.ctypes.data_as(_ip), len(e), int(device), _p(out), _p(cnt))
     return out, cnt
 
 
 def pose_consensus(poses, extrinsics, device=0):
     """Consensus board poses (F,6) of a caller's pose array (C,F,6) under the extrinsics (C,6) (include/mcba.h: mcba_pose_consensus)."""
-    lib = load_library()
     ps = _f64(poses)
     ext = _f64(extrinsics).reshape(ps.shape[0], 6)
     out = np.empty((ps.shape[1], 6))
-    rc = lib.mcba_pose_consensus(ps.shape[0], ps.shape[1], _p(ps), _p(ext), int(device), _p(out))
-    if rc != OK:
-        raise McbaError(rc, lib.mcba_last_error().decode())
+    call("mcba_pose_consensus", ps.shape[0], ps.shape[1], _p(ps), _p(ext), int(device), _p(out))
     return out
 
 
@@ -1018,15 +1010,12 @@ def calib_normal_equations(uvs, objpoints, intr9, poses, device=0):
     """Single-camera calibration with the five-coefficient model (include/mcba.h: mcba_calib_normal_equations): uvs (V,N,2), objpoints (N,3),
     intr9 = fx fy cx cy k1 k2 p1 p2 k3, poses (V,6) -> (H (V,15,15) symmetric Gauss-Newton blocks over [intr9 | pose6], g (V,15), cost (V,)),
     residuals observed - predicted."""
-    lib = load_library()
     uvs, obj, k, ps = _f64(uvs), _f64(objpoints), _f64(intr9), _f64(poses)
     V, N = uvs.shape[:2]
     if uvs.shape != (V, N, 2) or obj.shape != (N, 3) or k.shape != (9,) or ps.shape != (V, 6):
         raise ValueError("uvs (V,N,2), objpoints (N,3), intr9 (9,), poses (V,6) required")
     out = np.empty((V, 136))
-    rc = lib.mcba_calib_normal_equations(V, N, _p(uvs), _p(obj), _p(k), _p(ps), int(device), _p(out))
-    if rc != OK:
-        raise McbaError(rc, lib.mcba_last_error().decode())
+    call("mcba_calib_normal_equations", V, N, _p(uvs), _p(obj), _p(k), _p(ps), int(device), _p(out))
     H = np.zeros((V, 15, 15))
     iu = np.triu_indices(15)
     H[:, iu[0], iu[1]] = out[:, :120]

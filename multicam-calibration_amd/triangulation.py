@@ -50,7 +50,6 @@ def triangulate(all_uvs, all_extrinsics, all_intrinsics, device=0, undistort_ite
     refine=True: the reference's estimate (the median over the camera pairs) is only the start; every point is then moved to the minimiser
     of its robust reprojection cost (`geometry.refine_triangulation` with `loss`, `f_scale` and its default iteration limit).  The
     detections go to the device once; the two kernels run back to back there."""
-    lib = ops.load_library()
     uvs = _stack_uvs(all_uvs, all_extrinsics, all_intrinsics)
     C, P = uvs.shape[:2]
     if not 2 <= C <= 64:
@@ -62,13 +61,9 @@ def triangulate(all_uvs, all_extrinsics, all_intrinsics, device=0, undistort_ite
     cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
     out = np.empty((P, 3))
     ms = ctypes.c_double(0.0)
-    dp = ctypes.POINTER(ctypes.c_double)
     if refine:
-        rc = lib.mcba_triangulate_refine(C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, None, int(undistort_iterations), ops.LOSSES[loss], float(f_scale), DEFAULT_MAX_ITERATIONS,
-                                         int(device), out.ctypes.data, None, ctypes.addressof(ms))
+        ops.call("mcba_triangulate_refine", C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, None, int(undistort_iterations), ops.LOSSES[loss], float(f_scale), DEFAULT_MAX_ITERATIONS,
+                 int(device), out.ctypes.data, None, ctypes.addressof(ms))
     else:
-        rc = lib.mcba_triangulate(C, P, uvs.ctypes.data_as(dp), cam.ctypes.data_as(dp), dist.ctypes.data_as(dp), int(undistort_iterations), int(device),
-                                  out.ctypes.data_as(dp), ctypes.cast(ctypes.byref(ms), dp))
-    if rc != ops.OK:
-        raise ops.McbaError(rc, lib.mcba_last_error().decode())
+        ops.call("mcba_triangulate", C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, int(undistort_iterations), int(device), out.ctypes.data, ctypes.addressof(ms))
     return (out, ms.value) if return_kernel_ms else out
