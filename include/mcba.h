@@ -562,6 +562,21 @@ int mcba_detect_subpix(int height, int width, int channels, const unsigned char*
 int mcba_detect_anchor(int height, int width, int channels, const unsigned char* image, int board_cols, int board_rows, const float* uvs, int device, double* scores_out,
                        unsigned char* regions_out, float* quads_out, double* kernel_ms);
 
+/* ---- calibration uncertainty (no reference counterpart; additive to ABI 7) -----------------------------------------------------------
+ * The Gauss-Newton (IRLS-weighted) covariance at x[slot], with the handle's loss, f_scale and camera block (mcba_set_camera_block):
+ *   H = J^T diag(rho') J in blocks U_c, V_f, W_cf;  S = blockdiag(U) - sum_f W_f V_f^-1 W_f^T;  S_g = S with the six extrinsics of
+ *   gauge_camera held (their rows and columns leave the system and are reported as exact zeros);
+ *   cam_cov (n x n, n = 12 C, or 6 C with the 6-wide block; row i = the i-th variable of the camera system) = sigma2 S_g^-1;
+ *   frame_cov (F x 6 x 6) = sigma2 V_f^-1 + Y_f cam_cov Y_f^T, Y_f = V_f^-1 W_f^T.  A frame without data gets a NaN block and leaves the
+ *   count p; frames that hold data but whose V_f is not positive definite are refused (MCBA_ERR_ARG: leave them out).
+ *   sigma2 = sigma2_in, or -- NaN -- sum rho' f^2 / (m - p) with m present scalars and p free parameters (NaN if m <= p).
+ * The call linearises x[slot] with curvature floor 1 into the handle's own buffers and reduces with lambda = 0: a linearisation or reduced
+ * system the caller had is gone afterwards (call mcba_linearize again); the handle's curvature floor, loss and parameters are untouched.
+ * Either output may be NULL.  info8 = {sigma2, m, p, frames without data, failing pivot (-1 = none), kernel_ms of the covariance kernels,
+ * 0, 0}.  MCBA_ERR_NONFINITE with info8[4] >= 0: S_g is not positive definite at that pivot (the message names camera and parameter).
+ * MCBA_ERR_ARG: a sparse-Schur handle, a tabulated loss, a numeric x_scale or frozen coordinates, gauge_camera out of range. */
+int mcba_covariance(mcba_handle* h, int slot, int gauge_camera, double sigma2_in, double* cam_cov, double* frame_cov, double* info8);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 // mcba_handle.h -- what the translation units of the C ABI (mcba_api.hip, mcba_lm_api.hip, mcba_prefilter_api.hip, mcba_calib_api.hip,
-// mcba_geom_api.hip, mcba_comm_api.hip, mcba_flat.hip, mcba_detect.hip) share: the handle, the error plumbing, the buffer pool, profiling scopes and the launch helpers of the solver chain.
+// mcba_geom_api.hip, mcba_comm_api.hip, mcba_cov_api.hip, mcba_flat.hip, mcba_detect.hip) share: the handle, the error plumbing, the buffer pool, profiling scopes and the launch helpers of the solver chain.
 // Private to the library: not installed, not part of include/mcba.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -56,6 +56,7 @@ struct mcba_handle {
   double* core_arena = nullptr;            // mcba_create: x[0] | x[1] | obj
   unsigned char* solver_arena = nullptr;   // ensure_solver: the one allocation the solver buffers below are pieces of
   int* sub_frames = nullptr;   // mcba_create_subset: the frame indices on the device (kept with the handle: no synchronisation to free them)
+  double* cov_work = nullptr;  // mcba_covariance: factor, inverse factor and Sigma_cc (ld x ld each), scales, sums, flags, the frame blocks [F][36] (lazy)
   double* outbuf = nullptr;    // mcba_lm_result: [x | gradient] packed for one device-to-host copy
   // calibrate() on the device (mcba_calib_*): intrinsics [C][9], every view's board pose [C][6][Fpad] (NaN = none), per-view flags, and
   // scratch that grows with the call (view lists, outputs, pairwise transforms, select states, world-frame poses)

@@ -199,4 +199,13 @@ int launch_tri_refine(hipStream_t st, int loss, const double* uvs, const double*
 enum ConsensusForm { CONSENSUS_AUTO = -1, CONSENSUS_LANE = 0, CONSENSUS_WAVE = 1, CONSENSUS_LANE_SEARCH = 2 };
 int launch_consensus(hipStream_t st, int form, int loss, const double* uvs, size_t npts, const KpCam* cams, int C, double threshold, int min_views, int und_iters, double f_scale,
                      int max_iterations, double* out, unsigned long long* mask, double* hyp, double* info);
+// calibration uncertainty (mcba_cov.hip).  Non-zero: arguments out of range.
+// part: 2 x 1024 doubles of scratch; out[0] = sum rho' f^2, out[1] = present scalars of the residual vector res (NaN = missing)
+int launch_cov_wss(hipStream_t st, int loss, double f_scale, const double* res, size_t count, double* part, double* out);
+// flag[f]: 0 = V_f positive definite, 1 = a frame without data, 2 = not positive definite with data; counts[0] += flags != 0, counts[1] += flags == 2
+void launch_cov_check(hipStream_t st, const double* rec, unsigned char* flag, int* counts, int C, int F, int Fpad);
+// S0 (n x n) -> Sig (ld x ld, ld = ceil(n / 64) 64, zero outside the free n x n) = sigma2 S_g^-1; R, M: ld x ld scratch, isd: n; *pivot (preset to -1) = the first failing pivot
+void launch_cov_cam(hipStream_t st, const double* S0, int n, int cw, int gauge, double sigma2, double* R, double* M, double* isd, double* Sig, int ld, int* pivot);
+int cov_frames_group(int n, int lds_limit, int force_g);   // frames per workgroup of k_cov_frames (8 or 4; 0: no shape fits)
+int launch_cov_frames(hipStream_t st, const double* rec, const double* fbuf, const unsigned char* flag, const double* Sig, int ld, double sigma2, double* out, int C, int F, int Fpad, int cw, int G);
 }  // namespace mcba

@@ -68,6 +68,7 @@ SYMBOLS = [
     ("mcba_accept_linearization", ctypes.c_int, [_h]),
     ("mcba_get_trial", ctypes.c_int, [_h, _dp]),
     ("mcba_reduce_fetch", ctypes.c_int, [_h, ctypes.c_double, ctypes.c_int, _dp]),
+    ("mcba_covariance", ctypes.c_int, [_h, ctypes.c_int, ctypes.c_int, ctypes.c_double, _dp, _dp, _dp]),
     ("mcba_step_fetch", ctypes.c_int, [_h, _dp, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, _dp]),
     ("mcba_lm_set_state", ctypes.c_int, [_h, _dp]),
     ("mcba_lm_trial", ctypes.c_int, [_h, _dp]),
@@ -737,6 +738,22 @@ class Problem:
         if rc:
             self._chk(rc)
         return self._red_views
+
+    def covariance(self, slot, gauge_camera, sigma2=None, frames=True):
+        """Covariance of the camera system and of every frame pose at x[slot] (include/mcba.h: mcba_covariance).  Returns (cam_cov (n, n) in the
+        order of `cam_index`, frame_cov (F, 6, 6) or None, info (8,) = sigma2, m, p, frames without data, failing pivot, kernel_ms, 0, 0).
+        ValueError if the gauge-fixed Schur complement is not positive definite.  The handle's linearisation is gone afterwards."""
+        if self._loss_fn is not None:
+            raise ValueError("covariance: named losses only (a callable loss is set)")
+        cam = np.empty((self.n, self.n))
+        fr = np.empty((self.F, 6, 6)) if frames else None
+        info = np.full(8, np.nan)
+        info[4] = -1.0
+        rc = self.lib.mcba_covariance(self.handle, int(slot), int(gauge_camera), float("nan") if sigma2 is None else float(sigma2), _p(cam), None if fr is None else _p(fr), _p(info))
+        if rc == ERR_NONFINITE and info[4] >= 0:
+            raise ValueError(self.lib.mcba_last_error().decode())
+        self._chk(rc)
+        return cam, fr, info
 
     def step_fetch(self, delta_cam, lam, src, dst, linearize):
         """step / step_linearize + get_trial in one ABI crossing; returns a view of the 8 trial scalars."""
