@@ -577,6 +577,26 @@ int mcba_detect_anchor(int height, int width, int channels, const unsigned char*
  * MCBA_ERR_ARG: a sparse-Schur handle, a tabulated loss, a numeric x_scale or frozen coordinates, gauge_camera out of range. */
 int mcba_covariance(mcba_handle* h, int slot, int gauge_camera, double sigma2_in, double* cam_cov, double* frame_cov, double* info8);
 
+/* ---- triangulation uncertainty (no reference counterpart; additive to ABI 7) ---------------------------------------------------------
+ * The covariance of every triangulated point, in the Gauss-Newton (IRLS-weighted) convention of mcba_covariance.  Stateless like
+ * mcba_triangulate_refine: points (P, 3) where to linearise (meaningful at a minimiser of that call's cost), uvs (C, P, 2) raw detections
+ * (NaN = unseen), cam12 (C, 12), dist5 (C, 5) or NULL, 2 <= C <= 64, loss 0 .. 4, f_scale > 0.  Per point, over the cameras that see it:
+ *   f = detection - five-coefficient projection, w = rho'((f / f_scale)^2) per scalar, A_c = d(u, v)/dX, B_c = d(u, v)/d(camera c's 12 of cam12);
+ *   H = sum_c A_c^T W_c A_c, inverted through the Cholesky factor of its Jacobi-scaled form;
+ *   det6 (P, 6) = sigma2 H^-1, packed 00 01 02 11 12 22;
+ *   cal6 (P, 6) = G cam_cov G^T packed likewise, G = [G_0 .. G_{C-1}], G_c = H^-1 A_c^T W_c B_c (zero for a camera that does not see the
+ *   point): how the re-triangulated point moves with the cameras.  cam_cov (12 C, 12 C) row-major, symmetric (mcba_covariance's, or any
+ *   other), or NULL: the detection term alone; cal6 is required exactly when cam_cov is given.
+ *   sigma2 = sigma2_in, or -- NaN -- sum w f^2 / (m - 3 P_u) over the P_u points of status 1 with their m present scalars, summed in a
+ *   fixed order (NaN if m <= 3 P_u).
+ * views_out (P): cameras that see the point.  status_out (P): 1 ok; -1 fewer than two views or a NaN in the point; -2 degenerate: a pivot of
+ * the scaled factor whose square is below 1e-12 (two cameras with one centre, a point on the baseline).  Both terms are NaN unless the
+ * status is 1, and such a point leaves the pooled sums.
+ * info8 = {sigma2, m, 3 P_u, points of status -1, points of status -2, kernel_ms, 0, 0}; kernel_ms may be NULL.  n_points == 0 returns at once.
+ * The environment variable MCBA_TRICOV_G (5, 10 or 16), read per call, forces the number of points a workgroup of the calibration term takes. */
+int mcba_triangulation_covariance(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, const double* cam_cov, int loss, double f_scale,
+                                  double sigma2_in, int device, double* det6, double* cal6, int* views_out, int* status_out, double* info8, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

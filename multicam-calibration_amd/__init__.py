@@ -12,7 +12,8 @@ Only what the hot path needs lives here:
   io.py      save_calibration / load_calibration (json, jarvis; gimbal needs h5py) -- SURVEY.md section 8f-3
   geometry.py  project_points / project_to_cameras / apply_rigid_transform / keypoint_reprojection_errors / refine_triangulation and the reference's matrix helpers -- SURVEY.md section 8f-8;
              triangulate_consensus (per-detection inlier masks) -- SURVEY.md section 8f-9
-  uncertainty.py  calibration_uncertainty (parameter covariance from the Schur system) -- SURVEY.md section 8f-10
+  uncertainty.py  calibration_uncertainty (parameter covariance from the Schur system) -- SURVEY.md section 8f-10;
+             triangulation_uncertainty (covariance of every triangulated point) -- SURVEY.md section 8f-11
   synth.py   deterministic synthetic board detections for tests and bench
 """
 from . import synth  # noqa: F401
@@ -27,7 +28,7 @@ from .io import save_calibration, load_calibration  # noqa: F401
 from .diagnostics import reprojection_errors, undistort_points  # noqa: F401
 from .flatibration import get_floor_points, flatibrate, center_arena, flip_z_axis  # noqa: F401
 from .detection import detect_chessboard, detect_chessboards, reorder_chessboard_corners, generate_chessboard_objpoints, extend_grid, summarize_detections  # noqa: F401
-from .uncertainty import calibration_uncertainty, CalibrationUncertainty  # noqa: F401
+from .uncertainty import calibration_uncertainty, CalibrationUncertainty, triangulation_uncertainty, TriangulationUncertainty  # noqa: F401
 from .calibration import calibrate, get_intrinsics, estimate_pose, estimate_all_extrinsics, consensus_calib_poses, get_camera_spanning_tree, estimate_pairwise_camera_transform  # noqa: F401
 
 __all__ = ["bundle_adjust", "bundle_adjustment", "serialize_params", "deserialize_params", "ops", "solver", "synth", "calibration", "calibrate", "triangulate", "get_intrinsics",
@@ -36,4 +37,4 @@ __all__ = ["bundle_adjust", "bundle_adjustment", "serialize_params", "deserializ
            "detect_chessboard", "detect_chessboards", "reorder_chessboard_corners", "generate_chessboard_objpoints", "extend_grid", "summarize_detections",
            "geometry", "project_points", "project_to_cameras", "apply_rigid_transform", "keypoint_reprojection_errors", "refine_triangulation", "triangulate_consensus", "rigid_transform_from_correspondences",
            "rodrigues", "rodrigues_inv", "get_transformation_matrix", "get_transformation_vector", "get_projection_matrix", "euclidean_to_homogenous", "homogeneous_to_euclidean",
-           "calibration_uncertainty", "CalibrationUncertainty"]
+           "calibration_uncertainty", "CalibrationUncertainty", "triangulation_uncertainty", "TriangulationUncertainty"]

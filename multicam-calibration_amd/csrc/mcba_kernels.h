@@ -208,4 +208,18 @@ void launch_cov_check(hipStream_t st, const double* rec, unsigned char* flag, in
 void launch_cov_cam(hipStream_t st, const double* S0, int n, int cw, int gauge, double sigma2, double* R, double* M, double* isd, double* Sig, int ld, int* pivot);
 int cov_frames_group(int n, int lds_limit, int force_g);   // frames per workgroup of k_cov_frames (8 or 4; 0: no shape fits)
 int launch_cov_frames(hipStream_t st, const double* rec, const double* fbuf, const unsigned char* flag, const double* Sig, int ld, double sigma2, double* out, int C, int F, int Fpad, int cw, int G);
+
+// ---- triangulation uncertainty (mcba_tricov.hip).  uvs (C, P, 2) raw detections (NaN = unseen), pts (P, 3), cams: the
+// table of mcba_tricov_math.h (TcCam) in device memory, 2 <= C <= 64.  Non-zero: arguments out of range.
+struct TcCam;
+int tricov_point_blocks(size_t npts);   // workgroups of k_tricov_point: part holds 4 doubles for each
+// hinv (P, 6) = H^-1 packed (NaN unless status is 1), views / status (P); then info[0 .. 4] = sigma2 (sigma2_in, or -- NaN -- pooled in a fixed
+// order), present scalars m and 3 P_u of the points of status 1, points of status -1, points of status -2
+int launch_tricov_point(hipStream_t st, int loss, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, double sigma2_in, double* hinv, int* views, int* status,
+                        double* part, double* info);
+void launch_tricov_scale(hipStream_t st, const double* hinv, const int* status, const double* info, size_t npts, double* det6);   // det6 = info[0] hinv
+int tricov_group(int n, int lds_limit, int force_g);   // points per workgroup of k_tricov_cal (16, 10 or 5; 0: no shape fits)
+// det6 = sigma2 H^-1 and cal6 = G Sig G^T (both (P, 6) packed), Sig the zero-padded ld x ld camera covariance (ld a multiple of 64, >= 12 C rounded up to 32)
+int launch_tricov_cal(hipStream_t st, int loss, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status, const double* Sig,
+                      int ld, const double* info, double* det6, double* cal6, int G);
 }  // namespace mcba

@@ -37,9 +37,16 @@ MCBA_HD void rigid_point(const PairConst& pc, const double X[3], double Xc[3]) {
   Xc[2] = fma(pc.Rcf[6], X[0], fma(pc.Rcf[7], X[1], fma(pc.Rcf[8], X[2], pc.tcf[2])));
 }
 
-// five-coefficient projection of the world point X; LIN: also Ju, Jv = d(u, v)/dX (rows of P R, P = d(u, v)/dX_c)
+// what the five-coefficient projection passes through on its way: the normalised point (x, y) = (Xc / Zc, Yc / Zc) and 1 / Zc, the distorted
+// point (xd, yd) and, with LIN, the rows Pu, Pv of P = d(u, v)/dX_c (project5<false> leaves Pu, Pv unwritten: undefined there) -- for callers
+// that differentiate with respect to the camera as well (mcba_tricov_math.h)
+struct Proj5Parts {
+  double x, y, xd, yd, Pu[3], Pv[3];
+};
+
+// five-coefficient projection of the world point X; LIN: also Ju, Jv = d(u, v)/dX (rows of P R, P = d(u, v)/dX_c); parts: the intermediates
 template <bool LIN>
-MCBA_HD void project5(const KpCam& kc, const double X[3], double& u, double& v, double* Ju = nullptr, double* Jv = nullptr) {
+MCBA_HD void project5(const KpCam& kc, const double X[3], double& u, double& v, double* Ju = nullptr, double* Jv = nullptr, Proj5Parts* parts = nullptr) {
   double Xc[3];
   rigid_point(kc.pc, X, Xc);
   const double iz = fast_rcp(Xc[2]);
@@ -57,7 +64,12 @@ MCBA_HD void project5(const KpCam& kc, const double X[3], double& u, double& v, 
       Ju[j] = fma(P0[0], kc.pc.Rcf[j], fma(P0[1], kc.pc.Rcf[3 + j], P0[2] * kc.pc.Rcf[6 + j]));
       Jv[j] = fma(P1[0], kc.pc.Rcf[j], fma(P1[1], kc.pc.Rcf[3 + j], P1[2] * kc.pc.Rcf[6 + j]));
     }
+    if (parts) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) { parts->Pu[j] = P0[j]; parts->Pv[j] = P1[j]; }
+    }
   }
+  if (parts) { parts->x = x; parts->y = y; parts->xd = xd; parts->yd = yd; }
 }
 
 // |detection - projection| in pixels; NaN where the camera does not see the point (a NaN coordinate in the detection) or the point has a NaN

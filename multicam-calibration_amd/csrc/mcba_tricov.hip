@@ -1,0 +1,301 @@
+// mcba_tricov.hip -- triangulation uncertainty: the covariance of every triangulated point, from the detection noise
+// (sigma2 H^-1) and from the uncertainty of the cameras (G Sigma_cc G^T).  Per-lane arithmetic: mcba_tricov_math.h (host-checked).
+//   k_tricov_point  lane = point: H^-1 (unscaled, packed), views, status; per-workgroup partials of (sum w f^2, present scalars, points of status 1,
+//                   degenerate points), summed in a fixed order by k_tricov_final, which also fixes sigma2
+//   k_tricov_scale  det6 = sigma2 H^-1 -- the whole call when no camera covariance is given
+//   k_tricov_cal    G points per workgroup: their rows of G into LDS, Z = G Sigma_cc on v_mfma_f64_16x16x4_f64, the 3 x 3 diagonal blocks of Z G^T
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "mcba_kernels.h"
+#include "mcba_tricov_math.h"
+
+namespace mcba {
+
+typedef double tricov_d4 __attribute__((ext_vector_type(4)));
+
+// ---------------------------------------------------------------- k_tricov_point
+// The camera table is staged in LDS as k_tri_refine stages it (the KpCam part of every entry).  No lane leaves before the workgroup's sums.
+template <int LOSS>
+__global__ __launch_bounds__(256) void k_tricov_point(const double2* __restrict__ uvs, const double* __restrict__ pts, size_t npts, const TcCam* __restrict__ cams, int C, double f_scale,
+                                                      double* __restrict__ hinv, int* __restrict__ views, int* __restrict__ status, double* __restrict__ part) {
+  __shared__ KpCam s_cam[kKpMaxCams];
+  __shared__ double s_r[4][256];
+  {
+    const double* src = reinterpret_cast<const double*>(cams);
+    double* dst = reinterpret_cast<double*>(s_cam);
+    for (int i = threadIdx.x; i < 21 * C; i += 256) dst[i] = src[30 * (i / 21) + i % 21];
+    __syncthreads();
+  }
+  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+  double r[4] = {0.0, 0.0, 0.0, 0.0};
+  if (p < npts) {
+    const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
+    const double2* det = uvs + p;
+    auto observation = [&](int c, double& ou, double& ov) {
+      const double2 o = det[(size_t)c * npts];
+      ou = o.x; ov = o.y;
+    };
+    double Hi[6], wss;
+    int nv;
+    const int st = tricov_point<LOSS>(s_cam, C, observation, X, f_scale, Hi, nv, wss);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) hinv[6 * p + i] = Hi[i];
+    views[p] = nv;
+    status[p] = st;
+    if (st == TC_OK) { r[0] = wss; r[1] = 2.0 * nv; r[2] = 1.0; }
+    if (st == TC_DEGENERATE) r[3] = 1.0;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) s_r[k][threadIdx.x] = r[k];
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) s_r[k][threadIdx.x] += s_r[k][threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) part[4 * (size_t)blockIdx.x + threadIdx.x] = s_r[threadIdx.x][0];
+}
+
+// the partials in order: info[0] = sigma2, [1] = m, [2] = 3 P_u, [3] = points of status -1, [4] = degenerate points
+__global__ __launch_bounds__(256) void k_tricov_final(const double* __restrict__ part, int nblocks, size_t npts, double sigma2_in, double* __restrict__ info) {
+  __shared__ double s_r[4][256];
+  double r[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = threadIdx.x; i < nblocks; i += 256) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] += part[4 * (size_t)i + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) s_r[k][threadIdx.x] = r[k];
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) s_r[k][threadIdx.x] += s_r[k][threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double wss = s_r[0][0], m = s_r[1][0], nfree = 3.0 * s_r[2][0], ndeg = s_r[3][0];
+    info[0] = sigma2_in == sigma2_in ? sigma2_in : tricov_sigma2(wss, m, nfree);
+    info[1] = m;
+    info[2] = nfree;
+    info[3] = (double)npts - s_r[2][0] - ndeg;
+    info[4] = ndeg;
+  }
+}
+
+int tricov_point_blocks(size_t npts) { return (int)((npts + 255) / 256); }
+
+int launch_tricov_point(hipStream_t st, int loss, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, double sigma2_in, double* hinv, int* views, int* status,
+                        double* part, double* info) {
+  if (C < 2 || C > kKpMaxCams || npts == 0 || npts > ((size_t)1 << 38)) return 1;
+  const int nb = tricov_point_blocks(npts);
+  const dim3 g((unsigned)nb), b(256);
+  const double2* uv = reinterpret_cast<const double2*>(uvs);
+  switch (loss) {
+    case LOSS_LINEAR: k_tricov_point<LOSS_LINEAR><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part); break;
+    case LOSS_SOFT_L1: k_tricov_point<LOSS_SOFT_L1><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part); break;
+    case LOSS_HUBER: k_tricov_point<LOSS_HUBER><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part); break;
+    case LOSS_CAUCHY: k_tricov_point<LOSS_CAUCHY><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part); break;
+    case LOSS_ARCTAN: k_tricov_point<LOSS_ARCTAN><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part); break;
+    default: return 1;
+  }
+  k_tricov_final<<<dim3(1), dim3(256), 0, st>>>(part, nb, npts, sigma2_in, info);
+  return 0;
+}
+
+// ---------------------------------------------------------------- k_tricov_scale
+__global__ __launch_bounds__(256) void k_tricov_scale(const double* __restrict__ hinv, const int* __restrict__ status, const double* __restrict__ info, size_t count, double* __restrict__ det6) {
+  const double sigma2 = info[0];
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) det6[i] = tricov_det_entry(hinv[i], sigma2, status[i / 6] == TC_OK);
+}
+
+void launch_tricov_scale(hipStream_t st, const double* hinv, const int* status, const double* info, size_t npts, double* det6) {
+  const size_t count = 6 * npts;
+  k_tricov_scale<<<dim3((unsigned)std::min<size_t>((count + 255) / 256, 8192)), dim3(256), 0, st>>>(hinv, status, info, count, det6);
+}
+
+// ---------------------------------------------------------------- k_tricov_cal
+// The plan of k_cov_frames (mcba_cov.hip) with 3 rows per item.  One workgroup = G consecutive points, 256 threads, R = 3 G rows of the stacked
+// G matrices (row 3 g + k = row k of point g), RT = ceil(R / 16) row tiles, n = 12 C, KP = ceil(n / 32) 32.
+//   1. the first 6 G threads: H^-1 of the group's points (zero unless the status is TC_OK: such a point's rows are zero)
+//   2. item (camera c, point g), points fastest: G_c of the point -> s_Y[3 g + k][12 c + j]; zero for a camera that does not see the point;
+//      columns n .. KP are zero
+//   3. per panel of 64 columns of Sigma_cc (wavefront w: columns 16 w .. 16 w + 15 of it), K in chunks of 32 rows staged through LDS (the next
+//      chunk's loads fly during the matrix-core phase): Z tile += G tile x Sigma chunk.  Z goes to LDS (over the staging buffer) and thread
+//      (g, k <= l) adds sum_j Z[3 g + k][j] G[3 g + l][j] -- each point's own diagonal block, nothing else.
+//   4. cal6 and det6 = sigma2 H^-1 through LDS in runs of consecutive doubles; points >= P write nothing.
+constexpr int kTcKC = 32, kTcPS = 80, kTcZS = 66;
+
+static size_t tricov_cal_lds(int n, int G) {
+  const int KP = (n + 31) / 32 * 32, R = 3 * G;
+  const size_t stage = std::max<size_t>((size_t)kTcKC * kTcPS, (size_t)R * kTcZS);
+  return ((size_t)R * (KP + 2) + stage + (size_t)G * 6 * 3) * sizeof(double);
+}
+
+template <int LOSS, int RT>
+__global__ __launch_bounds__(256) void k_tricov_cal(const double2* __restrict__ uvs, const double* __restrict__ pts, size_t npts, const TcCam* __restrict__ cams, int C, double f_scale,
+                                                    const double* __restrict__ hinv, const int* __restrict__ status, const double* __restrict__ Sig, int ld, const double* __restrict__ info,
+                                                    double* __restrict__ det6, double* __restrict__ cal6, int G, int KP) {
+  extern __shared__ __align__(16) double lds[];
+  const int t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int n = 12 * C, R = 3 * G, RS = KP + 2;
+  double* s_Y = lds;                                   // [R][RS]
+  double* s_P = s_Y + (size_t)R * RS;                  // [kTcKC][kTcPS], later [R][kTcZS]
+  const size_t stage = (size_t)kTcKC * kTcPS > (size_t)R * kTcZS ? (size_t)kTcKC * kTcPS : (size_t)R * kTcZS;
+  double* s_Hi = s_P + stage;                          // [G][6]
+  double* s_oc = s_Hi + G * 6;                         // [G][6] calibration term
+  double* s_od = s_oc + G * 6;                         // [G][6] detection term
+  const size_t p0 = (size_t)blockIdx.x * G;
+  const int ng = npts - p0 < (size_t)G ? (int)(npts - p0) : G;
+  const double fs2 = f_scale * f_scale, inv_fs2 = 1.0 / fs2;
+
+  const bool own = t < G * 6;
+  int og = 0, ok_ = 0, ol = 0;
+  bool good = false;   // this thread's point is inside P and TC_OK
+  if (own) {
+    og = t / 6;
+    tricov_tri3_pair(t % 6, ok_, ol);
+    good = og < ng && status[p0 + og] == TC_OK;
+    s_Hi[t] = good ? hinv[6 * p0 + t] : 0.0;
+  }
+  __syncthreads();
+  for (int it = t; it < C * G; it += 256) {
+    const int g = it % G, c = it / G;
+    double gr[36];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) gr[k] = 0.0;
+    if (g < ng && status[p0 + g] == TC_OK) {
+      const size_t p = p0 + g;
+      const double2 o = uvs[(size_t)c * npts + p];
+      if (o.x == o.x && o.y == o.y) {
+        const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
+        tricov_g_block<LOSS>(cams[c], X, o.x, o.y, s_Hi + 6 * g, fs2, inv_fs2, gr);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+      for (int j = 0; j < 12; ++j) s_Y[(size_t)(3 * g + k) * RS + 12 * c + j] = gr[12 * k + j];
+    }
+  }
+  for (int it = t; it < R * (KP - n); it += 256) s_Y[(size_t)(it / (KP - n)) * RS + n + it % (KP - n)] = 0.0;
+  // (the first barrier of the panel loop orders these stores before the first read)
+
+  double zy = 0.0;
+  const int nkc = KP / kTcKC, npan = (KP + 63) / 64;
+  int arow[RT];
+#pragma unroll
+  for (int ti = 0; ti < RT; ++ti) arow[ti] = min(16 * ti + (lane & 15), R - 1) * RS + (lane >> 4);   // (rows past R: a duplicate, its results are never stored)
+  for (int J = 0; J < npan; ++J) {
+    const bool active = 64 * J + 16 * wave < KP;   // wave-uniform: this wavefront's 16 columns hold anything
+    tricov_d4 acc[RT];
+#pragma unroll
+    for (int ti = 0; ti < RT; ++ti) acc[ti] = tricov_d4{0.0, 0.0, 0.0, 0.0};
+    double pv[8];
+    auto fetch = [&](int kc) {   // rows 32 kc .. + 31, columns 64 J .. + 63 of the zero-padded ld x ld buffer: inside it (KP <= ld, ld a multiple of 64)
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int idx = t + 256 * q;
+        pv[q] = Sig[(size_t)(kTcKC * kc + (idx >> 6)) * ld + 64 * J + (idx & 63)];
+      }
+    };
+    fetch(0);
+    for (int kc = 0; kc < nkc; ++kc) {
+      __syncthreads();   // the previous chunk's reads (or the previous panel's contraction) are done
+#pragma unroll
+      for (int q = 0; q < 8; ++q) { const int idx = t + 256 * q; s_P[(idx >> 6) * kTcPS + (idx & 63)] = pv[q]; }
+      __syncthreads();
+      if (kc + 1 < nkc) fetch(kc + 1);
+      if (active) {
+#pragma unroll
+        for (int ks = 0; ks < kTcKC / 4; ++ks) {
+          const double b = s_P[(4 * ks + (lane >> 4)) * kTcPS + 16 * wave + (lane & 15)];
+#pragma unroll
+          for (int ti = 0; ti < RT; ++ti) {
+            const double a = s_Y[arow[ti] + kTcKC * kc + 4 * ks];
+            acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[ti], 0, 0, 0);
+          }
+        }
+      }
+    }
+    __syncthreads();   // every wavefront is done with the staging buffer: Z takes its place
+    if (active) {
+#pragma unroll
+      for (int ti = 0; ti < RT; ++ti) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const int row = 16 * ti + 4 * reg + (lane >> 4);
+          if (row < R) s_P[row * kTcZS + 16 * wave + (lane & 15)] = acc[ti][reg];
+        }
+      }
+    }
+    __syncthreads();
+    if (own) {
+      const int jn = min(64, KP - 64 * J);
+      const double* zr = s_P + (3 * og + ok_) * kTcZS;
+      const double* yr = s_Y + (size_t)(3 * og + ol) * RS + 64 * J;
+      double s = 0.0;
+      for (int j = 0; j < jn; ++j) s += zr[j] * yr[j];
+      zy += s;
+    }
+  }
+  if (own) {
+    s_oc[t] = tricov_cal_entry(zy, good);
+    s_od[t] = tricov_det_entry(s_Hi[t], info[0], good);
+  }
+  __syncthreads();
+  for (int i = t; i < ng * 6; i += 256) {
+    cal6[6 * p0 + i] = s_oc[i];
+    det6[6 * p0 + i] = s_od[i];
+  }
+}
+
+// G points per workgroup: 16 (three row tiles) if its LDS fits, else 10 (two), else 5 (one: fits at 64 cameras); force_g (5, 10 or 16, tests)
+// overrides when it fits
+int tricov_group(int n, int lds_limit, int force_g) {
+  if ((force_g == 5 || force_g == 10 || force_g == 16) && tricov_cal_lds(n, force_g) <= (size_t)lds_limit) return force_g;
+  if (tricov_cal_lds(n, 16) <= (size_t)lds_limit) return 16;
+  if (tricov_cal_lds(n, 10) <= (size_t)lds_limit) return 10;
+  if (tricov_cal_lds(n, 5) <= (size_t)lds_limit) return 5;
+  return 0;
+}
+
+template <int LOSS, int RT>
+static int tricov_cal_go(hipStream_t st, size_t lds, const double2* uv, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status,
+                         const double* Sig, int ld, const double* info, double* det6, double* cal6, int G, int KP) {
+  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tricov_cal<LOSS, RT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
+  hipLaunchKernelGGL((k_tricov_cal<LOSS, RT>), dim3((unsigned)((npts + G - 1) / G)), dim3(256), lds, st, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
+  return 0;
+}
+
+template <int LOSS>
+static int tricov_cal_shape(hipStream_t st, size_t lds, const double2* uv, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status,
+                            const double* Sig, int ld, const double* info, double* det6, double* cal6, int G, int KP) {
+  if (G == 16) return tricov_cal_go<LOSS, 3>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
+  if (G == 10) return tricov_cal_go<LOSS, 2>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
+  return tricov_cal_go<LOSS, 1>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
+}
+
+int launch_tricov_cal(hipStream_t st, int loss, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status, const double* Sig,
+                      int ld, const double* info, double* det6, double* cal6, int G) {
+  const int n = 12 * C, KP = (n + 31) / 32 * 32;
+  if (C < 2 || C > kKpMaxCams || (G != 5 && G != 10 && G != 16) || KP > ld || ld % 64 != 0 || npts == 0 || (npts + G - 1) / G > 0x7fffffffu) return 1;
+  const size_t lds = tricov_cal_lds(n, G);
+  const double2* uv = reinterpret_cast<const double2*>(uvs);
+  switch (loss) {   // one kernel per loss: loss_weights takes it as a template argument
+    case LOSS_LINEAR: return tricov_cal_shape<LOSS_LINEAR>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
+    case LOSS_SOFT_L1: return tricov_cal_shape<LOSS_SOFT_L1>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
+    case LOSS_HUBER: return tricov_cal_shape<LOSS_HUBER>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
+    case LOSS_CAUCHY: return tricov_cal_shape<LOSS_CAUCHY>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
+    case LOSS_ARCTAN: return tricov_cal_shape<LOSS_ARCTAN>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
+    default: return 1;
+  }
+}
+
+}  // namespace mcba

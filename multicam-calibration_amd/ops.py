@@ -119,6 +119,8 @@ SYMBOLS = [
     ("mcba_triangulate_refine", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp]),
     ("mcba_triangulate_consensus", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                                   _dp, _dp, _dp, _dp, _dp]),   # (the inlier words, unsigned long long*, by address like the doubles)
+    ("mcba_triangulation_covariance", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                                     _dp, _dp, _dp, _dp, _dp, _dp]),   # (views and status, int*, by address like the doubles)
     ("mcba_profile_enable", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_stride", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_read", ctypes.c_int, [_h, _dp, _ip, ctypes.c_int, _ip]),
