@@ -597,6 +597,31 @@ int mcba_covariance(mcba_handle* h, int slot, int gauge_camera, double sigma2_in
 int mcba_triangulation_covariance(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, const double* cam_cov, int loss, double f_scale,
                                   double sigma2_in, int device, double* det6, double* cal6, int* views_out, int* status_out, double* info8, double* kernel_ms);
 
+/* ---- extrinsics refinement from keypoints: free-point bundle adjustment (no reference counterpart; additive to ABI 7) -----------------
+ * Minimises 0.5 f_scale^2 sum rho((f / f_scale)^2), f = raw detection - five-coefficient projection, jointly over the rotation vector and
+ * translation of every camera and every 3-D point; the intrinsics stay fixed.  Stateless: uvs (C, P, 2) raw detections (NaN = unseen), cam12
+ * (C, 12) with the start extrinsics in columns 6 .. 11, dist5 (C, 5) or NULL, points (P, 3) the start, 2 <= C <= 24, P >= 1, loss 0 .. 4,
+ * f_scale > 0, max_nfev >= 2.
+ * held (C), in and out: bit i set = scalar i (0 .. 2 rotation vector, 3 .. 5 translation) of the camera is not free.  The call holds all six
+ * of gauge_camera and of every camera that no used point sees and reports that here; the caller fixes the scale by holding one scalar of
+ * scale_camera (a different camera).
+ * Levenberg-Marquardt, Marquardt damping on cameras and points alike (from 1e-4, a tenth on an accepted trial, tenfold on a rejected one); a
+ * trial is accepted when the robust cost does not rise.  Per evaluation the Schur reduction over the 3 x 3 point blocks and the
+ * back-substitution run on the device, the reduced system (at most 143 rows) is solved on the host.  Afterwards camera centres and points are
+ * rescaled about the gauge camera's centre so that its distance to scale_camera's is what it was at the start; no projection changes.
+ * extrinsics_out (C, 6); points_out (P, 3), NaN rows unless point_status (P) is 1 (-1: fewer than two views or a NaN start; -2: a zero
+ * diagonal in the point's 3 x 3 block).
+ * result16 = {cost, cost at the start, optimality (inf-norm of the gradient over the free parameters), nfev, njev, status (scipy's: 0 max_nfev,
+ * 1 gtol, 2 ftol, 3 xtol), scale of the closing step, evaluations recorded, kernel_ms, ms in k_kpba_reduce passes, their number, ms in
+ * k_kpba_step passes, their number, points per group, 0, 0}.
+ * history (history_rows, 3) or NULL with history_rows 0: per evaluation the cost, the damping and 1 if it was accepted; evaluations beyond
+ * history_rows are counted in result16[7] and not stored.
+ * No atomics: two calls on the same input return the same bits.  The environment variable MCBA_KPBA_G (16, 32 or 64), read per call, forces
+ * the number of points in a group of k_kpba_reduce. */
+int mcba_refine_extrinsics(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points, int* held, int gauge_camera, int scale_camera, int loss,
+                           double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* extrinsics_out, double* points_out, int* point_status, double* result16,
+                           double* history, int history_rows);
+
 #ifdef __cplusplus
 }
 #endif

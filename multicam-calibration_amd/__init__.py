@@ -11,7 +11,8 @@ Only what the hot path needs lives here:
   detection.py  detect_chessboard / detect_chessboards / reorder_chessboard_corners and the reference's host helpers -- SURVEY.md section 8f-7
   io.py      save_calibration / load_calibration (json, jarvis; gimbal needs h5py) -- SURVEY.md section 8f-3
   geometry.py  project_points / project_to_cameras / apply_rigid_transform / keypoint_reprojection_errors / refine_triangulation and the reference's matrix helpers -- SURVEY.md section 8f-8;
-             triangulate_consensus (per-detection inlier masks) -- SURVEY.md section 8f-9
+             triangulate_consensus (per-detection inlier masks) -- SURVEY.md section 8f-9;
+             refine_extrinsics (free-point bundle adjustment of the extrinsics on keypoint detections) -- SURVEY.md section 8f-12
   uncertainty.py  calibration_uncertainty (parameter covariance from the Schur system) -- SURVEY.md section 8f-10;
              triangulation_uncertainty (covariance of every triangulated point) -- SURVEY.md section 8f-11
   synth.py   deterministic synthetic board detections for tests and bench
@@ -22,7 +23,7 @@ from .api import bundle_adjust, bundle_adjustment, serialize_params, deserialize
 from . import calibration  # noqa: F401
 from .triangulation import triangulate  # noqa: F401
 from . import geometry  # noqa: F401
-from .geometry import (project_points, project_to_cameras, apply_rigid_transform, keypoint_reprojection_errors, refine_triangulation, triangulate_consensus, rigid_transform_from_correspondences,  # noqa: F401
+from .geometry import (project_points, project_to_cameras, apply_rigid_transform, keypoint_reprojection_errors, refine_triangulation, triangulate_consensus, refine_extrinsics, ExtrinsicsRefinement, rigid_transform_from_correspondences,  # noqa: F401
                        rodrigues, rodrigues_inv, get_transformation_matrix, get_transformation_vector, get_projection_matrix, euclidean_to_homogenous, homogeneous_to_euclidean)
 from .io import save_calibration, load_calibration  # noqa: F401
 from .diagnostics import reprojection_errors, undistort_points  # noqa: F401
@@ -35,6 +36,6 @@ __all__ = ["bundle_adjust", "bundle_adjustment", "serialize_params", "deserializ
            "save_calibration", "load_calibration", "reprojection_errors", "undistort_points", "estimate_pose", "estimate_all_extrinsics", "consensus_calib_poses", "get_camera_spanning_tree", "estimate_pairwise_camera_transform",
            "get_floor_points", "flatibrate", "center_arena", "flip_z_axis",
            "detect_chessboard", "detect_chessboards", "reorder_chessboard_corners", "generate_chessboard_objpoints", "extend_grid", "summarize_detections",
-           "geometry", "project_points", "project_to_cameras", "apply_rigid_transform", "keypoint_reprojection_errors", "refine_triangulation", "triangulate_consensus", "rigid_transform_from_correspondences",
+           "geometry", "project_points", "project_to_cameras", "apply_rigid_transform", "keypoint_reprojection_errors", "refine_triangulation", "triangulate_consensus", "refine_extrinsics", "ExtrinsicsRefinement", "rigid_transform_from_correspondences",
            "rodrigues", "rodrigues_inv", "get_transformation_matrix", "get_transformation_vector", "get_projection_matrix", "euclidean_to_homogenous", "homogeneous_to_euclidean",
            "calibration_uncertainty", "CalibrationUncertainty", "triangulation_uncertainty", "TriangulationUncertainty"]

@@ -1,5 +1,5 @@
 // mcba_handle.h -- what the translation units of the C ABI (mcba_api.hip, mcba_lm_api.hip, mcba_prefilter_api.hip, mcba_calib_api.hip,
-// mcba_geom_api.hip, mcba_comm_api.hip, mcba_cov_api.hip, mcba_tricov_api.hip, mcba_flat.hip, mcba_detect.hip) share: the handle, the error plumbing, the buffer pool, profiling scopes and the launch helpers of the solver chain.
+// mcba_geom_api.hip, mcba_comm_api.hip, mcba_cov_api.hip, mcba_tricov_api.hip, mcba_kpba_api.hip, mcba_flat.hip, mcba_detect.hip) share: the handle, the error plumbing, the buffer pool, profiling scopes and the launch helpers of the solver chain.
 // Private to the library: not installed, not part of include/mcba.h.
 #pragma once
 #include <hip/hip_runtime.h>

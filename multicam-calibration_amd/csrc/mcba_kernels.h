@@ -222,4 +222,17 @@ int tricov_group(int n, int lds_limit, int force_g);   // points per workgroup o
 // det6 = sigma2 H^-1 and cal6 = G Sig G^T (both (P, 6) packed), Sig the zero-padded ld x ld camera covariance (ld a multiple of 64, >= 12 C rounded up to 32)
 int launch_tricov_cal(hipStream_t st, int loss, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status, const double* Sig,
                       int ld, const double* info, double* det6, double* cal6, int G);
+
+// ---- free-point bundle adjustment of the extrinsics (mcba_kpba.hip).  uvs (C, P, 2) raw detections (NaN = unseen), pts
+// (P, 3), cams: TcCam table in device memory, 2 <= C <= 24, held (C): bit i = scalar i of the camera is not free.  Non-zero: arguments out of range.
+int kpba_group(int C, int lds_limit, int force_g);   // points per group of k_kpba_reduce (64, 32 or 16; 0: no shape fits)
+int kpba_groups(size_t npts);                        // workgroups of a pass: that many partial systems
+size_t kpba_partial_size(int C);                     // doubles of one (partial) system: NP NP + 33 C + 4, NP = 6 C rounded up to 16
+int launch_kpba_status(hipStream_t st, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, int* status);
+// sys = Y Y^T (NP, NP) | per camera U_c packed lower, g_c, sum Y z (C, 33) | cost, present scalars, max |g_p|, 0; part: kpba_groups() partial systems
+int launch_kpba_reduce(hipStream_t st, int loss, const double* uvs, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale, double lam, int G,
+                       double* part, double* sys);
+// cams2: the current table and behind it the trial one; trial (P, 3) the trial points; out4 = trial cost, sum dX^2, 0, sum X^2; part4: 4 kpba_groups()
+int launch_kpba_step(hipStream_t st, int loss, const double* uvs, const double* pts, double* trial, const int* status, size_t npts, const TcCam* cams2, const double* dtheta, int C, double f_scale,
+                     double lam, double* part4, double* out4);
 }  // namespace mcba

@@ -1,0 +1,359 @@
+// mcba_kpba.hip -- free-point bundle adjustment of the camera extrinsics on keypoint detections: the Schur reduction over
+// the 3 x 3 point blocks into the 6 C x 6 C camera system, and the back-substitution with the trial cost.  Arithmetic: mcba_kpba_math.h (host-checked).
+//   k_kpba_status  lane = point, once per call: 1 used, -1 fewer than two views or a NaN start, -2 a zero diagonal in its block
+//   k_kpba_reduce  a workgroup walks chunks of 256 points.  Phase 1, lane = point: H_p, g_p, the factor L_p of the damped Jacobi-scaled block,
+//                  z_p = L^-1 D g_p -> LDS.  Then per group of G points: item (camera, point), points fastest, writes Y_cp = W_cp D L^-T into the
+//                  (NP x 3 G) panel (zero rows: unseeing or held cameras, padding) and sums U_c, g_c, Y_cp z_p over the group's points by a
+//                  butterfly of fixed order; Y Y^T on v_mfma_f64_16x16x4_f64, tiles on or below the diagonal only, each owned by one wavefront,
+//                  accumulated in registers over all the workgroup's groups.  One partial system per workgroup.
+//   k_kpba_finish  the partials in workgroup order -> the system (Y Y^T mirrored to full), sums and the maximum
+//   k_kpba_step    lane = point: the blocks again at the current iterate with q = sum_c W_cp^T dtheta_c in the same pass,
+//                  dX = -(H + lam diag H)^-1 (g + q), the trial point into the second buffer, its cost under the trial camera table
+// No atomics: every sum has one order, the same in every call.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "mcba_kernels.h"
+#include "mcba_kpba_math.h"
+
+namespace mcba {
+
+typedef double kpba_d4 __attribute__((ext_vector_type(4)));
+
+constexpr int kKbChunk = 256;      // points of one phase 1
+constexpr int kKbPt = 13;          // per point in LDS: L (6) | d (3) | z (3) | usable (1)
+constexpr int kKbMaxGroups = 512;  // workgroups of a pass at most: that many partial systems
+
+// 256-thread tree in a fixed order over s[k][256]; the result in s[k][0]
+template <int K>
+__device__ __forceinline__ void kpba_tree(double (*s)[256], const double* r, const bool* is_max) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) s[k][threadIdx.x] = r[k];
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) s[k][threadIdx.x] = is_max[k] ? fmax(s[k][threadIdx.x], s[k][threadIdx.x + h]) : s[k][threadIdx.x] + s[k][threadIdx.x + h];
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------- k_kpba_status
+__global__ __launch_bounds__(256) void k_kpba_status(const double2* __restrict__ uvs, const double* __restrict__ pts, size_t npts, const TcCam* __restrict__ cams, int C, int* __restrict__ status) {
+  __shared__ TcCam s_cam[kKbMaxCams];
+  {
+    const double* src = reinterpret_cast<const double*>(cams);
+    double* dst = reinterpret_cast<double*>(s_cam);
+    for (int i = threadIdx.x; i < 30 * C; i += 256) dst[i] = src[i];
+    __syncthreads();
+  }
+  const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= npts) return;
+  const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
+  const double2* det = uvs + p;
+  auto observation = [&](int c, double& ou, double& ov) {
+    const double2 o = det[(size_t)c * npts];
+    ou = o.x; ov = o.y;
+  };
+  KbPoint pt;
+  kpba_point<LOSS_LINEAR>(s_cam, C, observation, X, 1.0, 1.0, nullptr, pt);   // (the weights are positive for every loss: a zero diagonal is one for all)
+  status[p] = kpba_status(pt.views, X, pt.H);
+}
+
+// ---------------------------------------------------------------- k_kpba_reduce
+// Dynamic LDS: s_pt [256][13] | s_acc [C][33] | s_Y [NP][RS], RS = 3 G + 1 (odd: the 16 rows a matrix-core operand reads fall into 16 distinct
+// bank pairs).  G is 16, 32 or 64 (it divides a wavefront: the butterfly over a group's points stays inside one).
+// Partial system of a workgroup, PS = NP NP + 33 C + 4 doubles: Y Y^T (only the tiles on or below the diagonal are written) | acc | cost,
+// present scalars, max |g_p|, 0.
+constexpr size_t kKbStaticLds = 12 * 1024;   // s_cam, s_held, s_r of k_kpba_reduce, rounded up: counted against the limit with the dynamic part
+size_t kpba_reduce_lds(int C, int G) {
+  const int NP = (6 * C + 15) / 16 * 16;
+  return ((size_t)kKbChunk * kKbPt + (size_t)C * kKbAcc + (size_t)NP * (3 * G + 1)) * sizeof(double);
+}
+size_t kpba_partial_size(int C) {
+  const int NP = (6 * C + 15) / 16 * 16;
+  return (size_t)NP * NP + (size_t)C * kKbAcc + 4;
+}
+int kpba_groups(size_t npts) { return (int)std::min<size_t>((npts + kKbChunk - 1) / kKbChunk, kKbMaxGroups); }
+
+// points per group: 64 if its panel fits, else 32, else 16; force_g (16, 32 or 64: tests) overrides when it fits.  0: nothing fits
+int kpba_group(int C, int lds_limit, int force_g) {
+  if ((force_g == 16 || force_g == 32 || force_g == 64) && kpba_reduce_lds(C, force_g) + kKbStaticLds <= (size_t)lds_limit) return force_g;
+  for (int G = 64; G >= 16; G >>= 1)
+    if (kpba_reduce_lds(C, G) + kKbStaticLds <= (size_t)lds_limit) return G;
+  return 0;
+}
+
+template <int LOSS, int TQ>
+__global__ __launch_bounds__(256) void k_kpba_reduce(const double2* __restrict__ uvs, const double* __restrict__ pts, const int* __restrict__ status, size_t npts, const TcCam* __restrict__ cams,
+                                                     const int* __restrict__ held, int C, double f_scale, double lam, int G, double* __restrict__ part) {
+  extern __shared__ __align__(16) double lds[];
+  __shared__ TcCam s_cam[kKbMaxCams];
+  __shared__ int s_held[kKbMaxCams];
+  __shared__ double s_r[3][256];
+  const int t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int n6 = 6 * C, NP = (n6 + 15) / 16 * 16, NT = NP / 16, ntiles = NT * (NT + 1) / 2, RS = 3 * G + 1;
+  double* s_pt = lds;                                   // [256][13]
+  double* s_acc = s_pt + kKbChunk * kKbPt;              // [C][33]
+  double* s_Y = s_acc + C * kKbAcc;                     // [NP][RS]
+  const double fs2 = f_scale * f_scale, inv_fs2 = 1.0 / fs2;
+  {
+    const double* src = reinterpret_cast<const double*>(cams);
+    double* dst = reinterpret_cast<double*>(s_cam);
+    for (int i = t; i < 30 * C; i += 256) dst[i] = src[i];
+    for (int i = t; i < C; i += 256) s_held[i] = held[i];
+    for (int i = t; i < C * kKbAcc; i += 256) s_acc[i] = 0.0;
+    for (int i = t; i < (NP - n6) * RS; i += 256) s_Y[(size_t)n6 * RS + i] = 0.0;   // the padding rows: zero once, no item writes them
+  }
+  kpba_d4 tile[TQ];
+#pragma unroll
+  for (int q = 0; q < TQ; ++q) tile[q] = kpba_d4{0.0, 0.0, 0.0, 0.0};
+  double r[3] = {0.0, 0.0, 0.0};   // this lane's cost, present scalars, max |g_p|
+  const size_t nchunks = (npts + kKbChunk - 1) / kKbChunk;
+  for (size_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+    const size_t p0 = chunk * kKbChunk;
+    __syncthreads();   // the previous chunk's last group is done with s_pt (and, the first time, the staging above is visible)
+    {
+      const size_t p = p0 + t;
+      double* sp = s_pt + t * kKbPt;
+      KbFactor f;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) f.L[i] = 0.0;
+      f.d[0] = f.d[1] = f.d[2] = 0.0;
+      double z[3] = {0.0, 0.0, 0.0};
+      bool usable = false;
+      if (p < npts && status[p] == KB_USED) {
+        const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
+        const double2* det = uvs + p;
+        auto observation = [&](int c, double& ou, double& ov) {
+          const double2 o = det[(size_t)c * npts];
+          ou = o.x; ov = o.y;
+        };
+        KbPoint pt;
+        kpba_point<LOSS>(s_cam, C, observation, X, fs2, inv_fs2, nullptr, pt);
+        r[0] += pt.cost;
+        r[1] += 2.0 * pt.views;
+        r[2] = fmax(r[2], fmax(fabs(pt.g[0]), fmax(fabs(pt.g[1]), fabs(pt.g[2]))));
+        usable = kpba_factor(pt.H, lam, f);
+        if (usable) kpba_fwd(f, pt.g, z);
+      }
+#pragma unroll
+      for (int i = 0; i < 6; ++i) sp[i] = f.L[i];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { sp[6 + i] = f.d[i]; sp[9 + i] = z[i]; }
+      sp[12] = usable ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    const int in_chunk = npts - p0 < (size_t)kKbChunk ? (int)(npts - p0) : kKbChunk;
+    for (int sub = 0; sub * G < in_chunk; ++sub) {
+      for (int it = t; it < C * G; it += 256) {
+        const int g = it % G, c = it / G, pl = sub * G + g;
+        const double* sp = s_pt + pl * kKbPt;
+        double Y[18], a[kKbAcc];
+#pragma unroll
+        for (int k = 0; k < 18; ++k) Y[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < kKbAcc; ++k) a[k] = 0.0;
+        if (sp[12] != 0.0) {   // (a point past P is not usable)
+          const size_t p = p0 + pl;
+          const double2 o = uvs[(size_t)c * npts + p];
+          if (o.x == o.x && o.y == o.y) {
+            const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
+            KbFactor f;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) f.L[i] = sp[i];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) f.d[i] = sp[6 + i];
+            kpba_item<LOSS>(s_cam[c], X, o.x, o.y, fs2, inv_fs2, f, sp + 9, s_held[c], Y, a);
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) s_Y[(size_t)(6 * c + i) * RS + 3 * g + k] = Y[3 * i + k];
+        }
+        // the camera's sums over the group's G points: C G is a multiple of G and G divides 64, so a group's lanes are all here or all absent
+        for (int m = G >> 1; m > 0; m >>= 1) {
+#pragma unroll
+          for (int k = 0; k < kKbAcc; ++k) a[k] += __shfl_xor(a[k], m);
+        }
+        if (g == 0) {
+#pragma unroll
+          for (int k = 0; k < kKbAcc; ++k) s_acc[c * kKbAcc + k] += a[k];   // (camera c is this lane's alone until the next barrier)
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < TQ; ++q) {
+        const int id = wave + 4 * q;   // wave-uniform
+        if (id < ntiles) {
+          int ti = 0;
+          while ((ti + 1) * (ti + 2) / 2 <= id) ++ti;
+          const int tj = id - ti * (ti + 1) / 2;
+          const double* ya = s_Y + (size_t)(16 * ti + (lane & 15)) * RS + (lane >> 4);
+          const double* yb = s_Y + (size_t)(16 * tj + (lane & 15)) * RS + (lane >> 4);
+          kpba_d4 acc = tile[q];
+          for (int ks = 0; ks < 3 * G / 4; ++ks) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ya[4 * ks], yb[4 * ks], acc, 0, 0, 0);
+          tile[q] = acc;
+        }
+      }
+      __syncthreads();   // the panel is free for the next group
+    }
+  }
+  __syncthreads();
+  double* out = part + (size_t)blockIdx.x * ((size_t)NP * NP + (size_t)C * kKbAcc + 4);
+#pragma unroll
+  for (int q = 0; q < TQ; ++q) {
+    const int id = wave + 4 * q;
+    if (id < ntiles) {
+      int ti = 0;
+      while ((ti + 1) * (ti + 2) / 2 <= id) ++ti;
+      const int tj = id - ti * (ti + 1) / 2;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) out[(size_t)(16 * ti + 4 * reg + (lane >> 4)) * NP + 16 * tj + (lane & 15)] = tile[q][reg];
+    }
+  }
+  for (int i = t; i < C * kKbAcc; i += 256) out[(size_t)NP * NP + i] = s_acc[i];
+  const bool is_max[3] = {false, false, true};
+  kpba_tree<3>(s_r, r, is_max);
+  if (t < 4) out[(size_t)NP * NP + (size_t)C * kKbAcc + t] = t < 3 ? s_r[t][0] : 0.0;
+}
+
+// ---------------------------------------------------------------- k_kpba_finish
+// One thread per entry of the system: the partials in workgroup order.  With NP = C = 0 the four trailing scalars alone (k_kpba_step's).
+__global__ __launch_bounds__(256) void k_kpba_finish(const double* __restrict__ part, int nwg, int NP, int C, double* __restrict__ out) {
+  const size_t nyy = (size_t)NP * NP, PS = nyy + (size_t)C * kKbAcc + 4;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= PS) return;
+  size_t src = i;
+  if (i < nyy) {
+    const int row = (int)(i / NP), col = (int)(i % NP);
+    if (row / 16 < col / 16) src = (size_t)col * NP + row;   // above the diagonal tiles: the mirror image
+  }
+  const bool is_max = i == PS - 2;
+  double s = 0.0;
+  for (int w = 0; w < nwg; ++w) {
+    const double v = part[(size_t)w * PS + src];
+    s = is_max ? fmax(s, v) : s + v;
+  }
+  out[i] = s;
+}
+
+template <int LOSS, int TQ>
+static int kpba_reduce_go(hipStream_t st, size_t lds, int nwg, const double2* uv, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale,
+                          double lam, int G, double* part) {
+  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kpba_reduce<LOSS, TQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
+  hipLaunchKernelGGL((k_kpba_reduce<LOSS, TQ>), dim3((unsigned)nwg), dim3(256), lds, st, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part);
+  return 0;
+}
+
+template <int LOSS>
+static int kpba_reduce_shape(hipStream_t st, size_t lds, int nwg, const double2* uv, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale,
+                             double lam, int G, double* part) {
+  const int NT = (6 * C + 15) / 16, ntiles = NT * (NT + 1) / 2;   // tiles per wavefront: 3 up to 10 tiles (6 cameras), 12 up to 45
+  if (ntiles <= 12) return kpba_reduce_go<LOSS, 3>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part);
+  return kpba_reduce_go<LOSS, 12>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part);
+}
+
+int launch_kpba_status(hipStream_t st, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, int* status) {
+  if (C < 2 || C > kKbMaxCams || npts == 0 || npts > ((size_t)1 << 38)) return 1;
+  k_kpba_status<<<dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, st>>>(reinterpret_cast<const double2*>(uvs), pts, npts, cams, C, status);
+  return 0;
+}
+
+int launch_kpba_reduce(hipStream_t st, int loss, const double* uvs, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale, double lam, int G,
+                       double* part, double* sys) {
+  if (C < 2 || C > kKbMaxCams || (G != 16 && G != 32 && G != 64) || npts == 0 || npts > ((size_t)1 << 38)) return 1;
+  const size_t lds = kpba_reduce_lds(C, G);
+  const int nwg = kpba_groups(npts), NP = (6 * C + 15) / 16 * 16;
+  const double2* uv = reinterpret_cast<const double2*>(uvs);
+  int rc;
+  switch (loss) {   // one kernel per loss: loss_weights takes it as a template argument
+    case LOSS_LINEAR: rc = kpba_reduce_shape<LOSS_LINEAR>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part); break;
+    case LOSS_SOFT_L1: rc = kpba_reduce_shape<LOSS_SOFT_L1>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part); break;
+    case LOSS_HUBER: rc = kpba_reduce_shape<LOSS_HUBER>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part); break;
+    case LOSS_CAUCHY: rc = kpba_reduce_shape<LOSS_CAUCHY>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part); break;
+    case LOSS_ARCTAN: rc = kpba_reduce_shape<LOSS_ARCTAN>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part); break;
+    default: return 1;
+  }
+  if (rc) return rc;
+  const size_t PS = kpba_partial_size(C);
+  k_kpba_finish<<<dim3((unsigned)((PS + 255) / 256)), dim3(256), 0, st>>>(part, nwg, NP, C, sys);
+  return 0;
+}
+
+// ---------------------------------------------------------------- k_kpba_step
+// cams: the current table and, behind it, the trial table (2 C entries).  part4 per workgroup: trial cost, sum dX^2, 0, sum X^2.
+template <int LOSS>
+__global__ __launch_bounds__(256) void k_kpba_step(const double2* __restrict__ uvs, const double* __restrict__ pts, double* __restrict__ trial, const int* __restrict__ status, size_t npts,
+                                                   const TcCam* __restrict__ cams, const double* __restrict__ dtheta, int C, double f_scale, double lam, double* __restrict__ part4) {
+  __shared__ TcCam s_cam[2 * kKbMaxCams];
+  __shared__ double s_dth[6 * kKbMaxCams];
+  __shared__ double s_r[3][256];
+  const int t = threadIdx.x;
+  {
+    const double* src = reinterpret_cast<const double*>(cams);
+    double* dst = reinterpret_cast<double*>(s_cam);
+    for (int i = t; i < 60 * C; i += 256) dst[i] = src[i];
+    for (int i = t; i < 6 * C; i += 256) s_dth[i] = dtheta[i];
+    __syncthreads();
+  }
+  const double fs2 = f_scale * f_scale, inv_fs2 = 1.0 / fs2;
+  double r[3] = {0.0, 0.0, 0.0};   // trial cost, sum dX^2, sum X^2
+  const size_t nchunks = (npts + kKbChunk - 1) / kKbChunk;
+  for (size_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+    const size_t p = chunk * kKbChunk + t;
+    if (p >= npts) continue;
+    const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
+    double Xt[3] = {X[0], X[1], X[2]};
+    if (status[p] == KB_USED) {
+      const double2* det = uvs + p;
+      auto observation = [&](int c, double& ou, double& ov) {
+        const double2 o = det[(size_t)c * npts];
+        ou = o.x; ov = o.y;
+      };
+      KbPoint pt;
+      kpba_point<LOSS>(s_cam, C, observation, X, fs2, inv_fs2, s_dth, pt);
+      KbFactor f;
+      double dX[3] = {0.0, 0.0, 0.0};
+      if (kpba_factor(pt.H, lam, f)) kpba_point_step(f, pt.g, pt.q, dX);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        Xt[j] = X[j] + dX[j];
+        r[1] = fma(dX[j], dX[j], r[1]);
+        r[2] = fma(X[j], X[j], r[2]);
+      }
+      KbPoint tr;
+      kpba_point<LOSS>(s_cam + C, C, observation, Xt, fs2, inv_fs2, nullptr, tr);
+      r[0] += tr.cost;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) trial[3 * p + j] = Xt[j];   // (a point that takes no part keeps its value in both buffers)
+  }
+  const bool is_max[3] = {false, false, false};
+  kpba_tree<3>(s_r, r, is_max);
+  if (t < 4) part4[4 * (size_t)blockIdx.x + t] = t == 0 ? s_r[0][0] : (t == 1 ? s_r[1][0] : (t == 3 ? s_r[2][0] : 0.0));
+}
+
+int launch_kpba_step(hipStream_t st, int loss, const double* uvs, const double* pts, double* trial, const int* status, size_t npts, const TcCam* cams2, const double* dtheta, int C, double f_scale,
+                     double lam, double* part4, double* out4) {
+  if (C < 2 || C > kKbMaxCams || npts == 0 || npts > ((size_t)1 << 38)) return 1;
+  const int nwg = kpba_groups(npts);
+  const dim3 g((unsigned)nwg), b(256);
+  const double2* uv = reinterpret_cast<const double2*>(uvs);
+  switch (loss) {
+    case LOSS_LINEAR: k_kpba_step<LOSS_LINEAR><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4); break;
+    case LOSS_SOFT_L1: k_kpba_step<LOSS_SOFT_L1><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4); break;
+    case LOSS_HUBER: k_kpba_step<LOSS_HUBER><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4); break;
+    case LOSS_CAUCHY: k_kpba_step<LOSS_CAUCHY><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4); break;
+    case LOSS_ARCTAN: k_kpba_step<LOSS_ARCTAN><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4); break;
+    default: return 1;
+  }
+  k_kpba_finish<<<dim3(1), dim3(256), 0, st>>>(part4, nwg, 0, 0, out4);
+  return 0;
+}
+
+}  // namespace mcba

@@ -1,0 +1,164 @@
+// mcba_kpba_api.hip -- the stateless extrinsics-refinement call of include/mcba.h (host arrays in, host arrays out, a device ordinal, no handle),
+// in the idiom of mcba_geom_api.hip: one upload of the detections, then the whole Levenberg-Marquardt loop (kpba_lm, mcba_kpba_math.h) with the
+// kernels of mcba_kpba.hip as its back end.  Per evaluation the camera tables go up (60 C doubles) and the reduced system comes down (at most
+// 144^2 + 33 * 24 + 4 doubles); the dense solve is the host's.  The loop ends at the first HIP error and starts nothing after it.
+#include "mcba_handle.h"
+#include "mcba_kpba_math.h"
+
+using namespace mcba_internal;
+
+namespace {
+
+struct DeviceBackEnd {
+  StatelessCall& call;
+  int C, loss, G;
+  size_t P;
+  double f_scale;
+  const double* cam12;
+  const double* dist5;
+  double* d_uv = nullptr;
+  double* d_pts[2] = {nullptr, nullptr};
+  int* d_status = nullptr;
+  int* d_held = nullptr;
+  mcba::TcCam* d_cams = nullptr;   // current table | trial table
+  double *d_dth = nullptr, *d_part = nullptr, *d_sys = nullptr, *d_part4 = nullptr, *d_out4 = nullptr;
+  int cur = 0;
+  std::vector<mcba::TcCam> tab;   // 2 C
+  std::vector<double> host_sys;
+  double reduce_ms = 0.0, step_ms = 0.0;
+  int n_reduce = 0, n_step = 0;
+
+  void table(const double* ext, mcba::TcCam* t) const {
+    for (int c = 0; c < C; ++c) {
+      double q[12];
+      for (int k = 0; k < 6; ++k) { q[k] = cam12[12 * c + k]; q[6 + k] = ext[6 * c + k]; }
+      mcba::make_tc_cam(q, dist5 ? dist5 + 5 * c : nullptr, t[c]);
+    }
+  }
+  int timed(double* ms_sum) {   // after a launch between the two records
+    HIPCHK(hipEventRecord(call.e1, nullptr));
+    HIPCHK(hipEventSynchronize(call.e1));
+    if (int rc = check_launch()) return rc;
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, call.e0, call.e1));
+    *ms_sum += ms;
+    return MCBA_OK;
+  }
+  int reduce(const double* ext, double lam, mcba::KbSystem& sys) {
+    table(ext, tab.data());
+    if (int rc = call.put(d_cams, tab.data(), (size_t)C)) return rc;
+    HIPCHK(hipEventRecord(call.e0, nullptr));
+    if (mcba::launch_kpba_reduce(nullptr, loss, d_uv, d_pts[cur], d_status, P, d_cams, d_held, C, f_scale, lam, G, d_part, d_sys) != 0)
+      return fail(MCBA_ERR_HIP, "mcba_refine_extrinsics: k_kpba_reduce could not be launched");
+    if (int rc = timed(&reduce_ms)) return rc;
+    ++n_reduce;
+    const size_t PS = mcba::kpba_partial_size(C);
+    host_sys.resize(PS);
+    if (int rc = call.download(host_sys.data(), d_sys, PS)) return rc;
+    sys.shape(C);
+    const size_t nyy = (size_t)sys.NP * sys.NP;
+    std::copy(host_sys.begin(), host_sys.begin() + nyy, sys.YY.begin());
+    std::copy(host_sys.begin() + nyy, host_sys.begin() + nyy + sys.acc.size(), sys.acc.begin());
+    sys.cost = host_sys[PS - 4]; sys.count = host_sys[PS - 3]; sys.gmax = host_sys[PS - 2];
+    return MCBA_OK;
+  }
+  int step(const double* ext_trial, const double* dtheta, double lam, double out[3]) {
+    table(ext_trial, tab.data() + C);
+    if (int rc = call.put(d_cams + C, tab.data() + C, (size_t)C)) return rc;
+    if (int rc = call.put(d_dth, dtheta, (size_t)6 * C)) return rc;
+    HIPCHK(hipEventRecord(call.e0, nullptr));
+    if (mcba::launch_kpba_step(nullptr, loss, d_uv, d_pts[cur], d_pts[1 - cur], d_status, P, d_cams, d_dth, C, f_scale, lam, d_part4, d_out4) != 0)
+      return fail(MCBA_ERR_HIP, "mcba_refine_extrinsics: k_kpba_step could not be launched");
+    if (int rc = timed(&step_ms)) return rc;
+    ++n_step;
+    double o4[4];
+    if (int rc = call.download(o4, d_out4, (size_t)4)) return rc;
+    out[0] = o4[0]; out[1] = o4[1]; out[2] = o4[3];
+    return MCBA_OK;
+  }
+  void accept() { cur = 1 - cur; }
+};
+
+}  // namespace
+
+extern "C" {
+
+int mcba_refine_extrinsics(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points, int* held, int gauge_camera, int scale_camera, int loss,
+                           double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* extrinsics_out, double* points_out, int* point_status, double* result16,
+                           double* history, int history_rows) {
+  if (n_cameras < 2 || n_cameras > mcba::kKbMaxCams) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: 2 to 24 cameras (the reduced system is held to 144 rows: nine matrix-core tiles)");
+  if (!uvs || !cam12 || !points || !held || !extrinsics_out || !points_out || !point_status || !result16 || (history_rows > 0 && !history))
+    return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: non-NULL arrays required");
+  if (gauge_camera < 0 || gauge_camera >= n_cameras || scale_camera < 0 || scale_camera >= n_cameras || gauge_camera == scale_camera)
+    return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: gauge_camera and scale_camera must be two different cameras of the rig");
+  if (loss < mcba::LOSS_LINEAR || loss > mcba::LOSS_ARCTAN) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: loss must be one of linear, soft_l1, huber, cauchy, arctan (0 .. 4)");
+  if (!(f_scale > 0.0)) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: f_scale must be positive");
+  if (max_nfev < 2) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: max_nfev must be at least 2 (the start and one trial)");
+  if (!(ftol >= 0.0 && xtol >= 0.0 && gtol >= 0.0)) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: ftol, xtol, gtol must not be negative");
+  if (n_points == 0) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: no points");
+  for (int i = 0; i < 16; ++i) result16[i] = 0.0;
+  if (int rc = stateless_device(device)) return rc;
+  const int C = n_cameras;
+  const size_t P = n_points;
+
+  int force_g = 0, lds_optin = 64 * 1024;
+  if (const char* e = getenv("MCBA_KPBA_G")) force_g = atoi(e);   // test knob: the smaller groups of k_kpba_reduce at any size
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.sharedMemPerBlockOptin > 0) lds_optin = (int)std::min<size_t>(prop.sharedMemPerBlockOptin, 160 * 1024);
+  const int G = mcba::kpba_group(C, lds_optin, force_g);
+  if (!G) return fail(MCBA_ERR_HIP, "mcba_refine_extrinsics: k_kpba_reduce does not fit the LDS of this device");
+
+  StatelessCall call;
+  DeviceBackEnd be{call, C, loss, G, P, f_scale, cam12, dist5};
+  be.tab.resize((size_t)2 * C);
+  std::vector<double> ext((size_t)6 * C);
+  for (int c = 0; c < C; ++c)
+    for (int k = 0; k < 6; ++k) ext[6 * c + k] = cam12[12 * c + 6 + k];
+  be.table(ext.data(), be.tab.data());
+  be.table(ext.data(), be.tab.data() + C);
+  const int nwg = mcba::kpba_groups(P);
+  if (int rc = call.upload(&be.d_uv, uvs, (size_t)2 * C * P)) return rc;
+  if (int rc = call.upload(&be.d_pts[0], points, 3 * P)) return rc;
+  if (int rc = call.upload(&be.d_pts[1], points, 3 * P)) return rc;
+  if (int rc = call.upload(&be.d_cams, be.tab.data(), be.tab.size())) return rc;
+  if (int rc = call.scratch(&be.d_status, P)) return rc;
+  if (int rc = call.scratch(&be.d_held, (size_t)C)) return rc;
+  if (int rc = call.scratch(&be.d_dth, (size_t)6 * C)) return rc;
+  if (int rc = call.scratch(&be.d_part, (size_t)nwg * mcba::kpba_partial_size(C))) return rc;
+  if (int rc = call.scratch(&be.d_sys, mcba::kpba_partial_size(C))) return rc;
+  if (int rc = call.scratch(&be.d_part4, (size_t)4 * nwg)) return rc;
+  if (int rc = call.scratch(&be.d_out4, (size_t)4)) return rc;
+  HIPCHK(call.start());
+
+  if (mcba::launch_kpba_status(nullptr, be.d_uv, be.d_pts[0], P, be.d_cams, C, be.d_status) != 0) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: bad launch (k_kpba_status)");
+  double status_ms = 0.0;
+  if (int rc = be.timed(&status_ms)) return rc;
+  if (int rc = call.download(point_status, be.d_status, P)) return rc;
+  for (int c = 0; c < C; ++c) {   // a camera that no used point sees is held whole
+    bool seen = false;
+    const double* u = uvs + (size_t)2 * c * P;
+    for (size_t p = 0; p < P && !seen; ++p) seen = point_status[p] == mcba::KB_USED && u[2 * p] == u[2 * p] && u[2 * p + 1] == u[2 * p + 1];
+    if (!seen) held[c] = 63;
+  }
+  if (held[scale_camera] == 63) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: scale_camera sees no used point (or is held whole): nothing fixes the scale of the rig");
+  held[gauge_camera] = 63;
+  if (int rc = call.put(be.d_held, held, (size_t)C)) return rc;
+
+  const double baseline = mcba::kpba_baseline(ext.data(), gauge_camera, scale_camera);
+  const mcba::KbOptions opt{ftol, xtol, gtol, max_nfev};
+  mcba::KbResult res;
+  if (int rc = mcba::kpba_lm(be, C, held, ext.data(), opt, res, history, history_rows)) return rc;
+
+  if (int rc = call.download(points_out, be.d_pts[be.cur], 3 * P)) return rc;
+  const double nan = __builtin_nan("");
+  for (size_t p = 0; p < P; ++p)
+    if (point_status[p] != mcba::KB_USED) points_out[3 * p] = points_out[3 * p + 1] = points_out[3 * p + 2] = nan;
+  const double s = mcba::kpba_rescale(C, held, ext.data(), P, points_out, gauge_camera, scale_camera, baseline);
+  for (int k = 0; k < 6 * C; ++k) extrinsics_out[k] = ext[k];
+  result16[0] = res.cost; result16[1] = res.cost0; result16[2] = res.optimality; result16[3] = res.nfev; result16[4] = res.njev; result16[5] = res.status; result16[6] = s;
+  result16[7] = res.nhist; result16[8] = status_ms + be.reduce_ms + be.step_ms; result16[9] = be.reduce_ms; result16[10] = be.n_reduce; result16[11] = be.step_ms; result16[12] = be.n_step;
+  result16[13] = G;
+  return MCBA_OK;
+}
+
+}  // extern "C"

@@ -9,13 +9,17 @@ GPU (`csrc/mcba_keypoints.hip`; no numpy fallback -- without a device every one 
   refine_triangulation           per point, Levenberg-Marquardt on the robust reprojection cost from a start such as triangulate()'s
   triangulate_consensus          (`csrc/mcba_consensus.hip`; no counterpart in the reference) per point, every camera
                                  pair's two-view point scored against all detections, the inlier cameras named, the point refitted on them
-The last three use the five-coefficient forward model on the RAW (distorted) detections: no undistortion iteration, so none of its truncation
+  refine_extrinsics              (`csrc/mcba_kpba.hip`; no counterpart in the reference) free-point bundle adjustment:
+                                 the extrinsics and every 3-D point jointly on the robust reprojection cost of the raw detections
+The last four use the five-coefficient forward model on the RAW (distorted) detections: no undistortion iteration, so none of its truncation
 error.  With p1 = p2 = k3 = 0 (all bundle_adjust returns) the model is project_points'.
 
 Host (numpy, the reference's formulas): rigid_transform_from_correspondences (returns (t, rmsd); the one in flatibration.py returns t alone),
 get_projection_matrix, euclidean_to_homogenous, homogeneous_to_euclidean, and rodrigues / rodrigues_inv / get_transformation_matrix /
 get_transformation_vector re-exported from calibration.py.
 """
+from dataclasses import dataclass
+
 import numpy as np
 
 from . import ops
@@ -186,6 +190,128 @@ def triangulate_consensus(all_uvs, all_extrinsics, all_intrinsics, *, threshold,
     if return_errors:
         res += (err,)
     return res
+
+
+REFINE_POINT_STATUS = {1: "used", -1: "too few views", -2: "zero diagonal"}
+MAX_REFINE_CAMERAS = 24
+
+
+@dataclass
+class ExtrinsicsRefinement:
+    extrinsics: np.ndarray     # (C, 6)
+    points: np.ndarray         # (P, 3); NaN rows where point_status is not 1
+    cost: float
+    cost0: float
+    optimality: float          # inf-norm of the gradient over the free parameters
+    nfev: int
+    njev: int
+    status: int                # scipy's: 0 max_nfev, 1 gtol, 2 ftol, 3 xtol
+    message: str
+    success: bool
+    point_status: np.ndarray   # (P,): a key of REFINE_POINT_STATUS
+    held: np.ndarray           # (C, 6) bool: parameters that were not free
+    scale: float               # factor of the closing rescale about the gauge camera's centre
+    history: np.ndarray        # (evaluations, 3): cost, damping, accepted
+    info: dict                 # kernel_ms, reduce_ms, n_reduce, step_ms, n_step, group, gauge_camera, scale_camera
+
+
+def _camera_centres(ext):
+    return np.stack([-rodrigues(e[:3]).T @ e[3:] for e in ext])
+
+
+def refine_extrinsics(all_uvs, all_extrinsics, all_intrinsics, *, points=None, inliers=None, gauge_camera=0, scale_camera=None, loss="soft_l1", f_scale=1.0, ftol=1e-8, xtol=1e-8, gtol=1e-8,
+                      max_nfev=100, verbose=0, device=0):
+    """Move drifted cameras back with the detections that show the drift: free-point bundle adjustment.  Minimises
+    0.5 f_scale^2 sum rho((f / f_scale)^2) over the present scalars f = detection - projection, jointly over the extrinsics of the cameras and
+    every 3-D point; the intrinsics stay fixed.  all_uvs, all_extrinsics, all_intrinsics as `triangulate` takes them (raw detections, NaN =
+    unseen; the five-coefficient forward model of project_to_cameras(distortion="opencv5")); loss and f_scale are scipy's.
+
+        res = refine_extrinsics(uvs, ext, intr, inliers=triangulate_consensus(uvs, ext, intr, threshold=3.0)[1])
+        print(res.message, res.cost0, "->", res.cost);  ext = res.extrinsics
+
+    points: (P, 3) start; None = triangulate(all_uvs, all_extrinsics, all_intrinsics).  inliers: None, or the (C, P) mask of
+    triangulate_consensus: a camera that is False for a point is treated as not seeing it.
+    Gauge: with fixed intrinsics the cost does not change under a rigid motion or a global scale.  All six extrinsics of `gauge_camera` are held.
+    The scale is fixed by holding one scalar of `scale_camera` (default: the camera whose centre is farthest from the gauge camera's at the
+    start): the component of its translation along which d = -R_j (c_j - c_0) is largest in magnitude -- scaling the rig about c_0 moves t_j
+    along d.  A camera that no used point sees is held whole.  `held` reports all of it.  After the iteration camera centres and points are
+    rescaled about c_0 by `scale`, so that |c_j - c_0| is what it was at the start (the metric scale of the board calibration); this changes
+    no projection.
+    Levenberg-Marquardt (Marquardt damping, the bundle-adjustment tick's curvature weights); a trial is accepted when the robust cost does not
+    rise, so the result is never worse than the start.  ftol, xtol, gtol, max_nfev, status, message, success: scipy.optimize.least_squares'.
+    point_status (REFINE_POINT_STATUS): -1 fewer than two views or a NaN start, -2 a zero diagonal in the point's 3 x 3 block; such points
+    come back NaN and take no part.  history: per evaluation the cost, the damping and whether it was accepted; verbose=2 prints it.
+    ValueError: an unknown loss, f_scale <= 0, max_nfev < 2 (the start and one trial are the least a run needs), gauge_camera == scale_camera,
+    arrays of the wrong shape.  NotImplementedError: fewer than 2 or more than 24 cameras (the reduced system is held to 144 rows).  Without a
+    GPU: ops.McbaError -- there is no host path."""
+    from . import solver
+    from .triangulation import triangulate
+
+    if callable(loss) or loss not in ops.LOSSES:
+        raise ValueError(f"loss must be one of {sorted(ops.LOSSES)}")
+    if not f_scale > 0:
+        raise ValueError("`f_scale` must be positive.")
+    if int(max_nfev) < 2:
+        raise ValueError("max_nfev must be at least 2: the start and one trial are the least a run needs")
+    if min(ftol, xtol, gtol) < 0:
+        raise ValueError("ftol, xtol and gtol must not be negative")
+    uvs = _stack_uvs(all_uvs, all_extrinsics, all_intrinsics)
+    C, P = uvs.shape[:2]
+    if not 2 <= C <= MAX_REFINE_CAMERAS:
+        raise NotImplementedError(f"refine_extrinsics() supports 2 to {MAX_REFINE_CAMERAS} cameras, got {C}: the reduced camera system is held to 144 rows (nine matrix-core tiles)")
+    if P < 1:
+        raise ValueError("refine_extrinsics() needs at least one point")
+    ext0 = np.ascontiguousarray(all_extrinsics, dtype=np.float64)
+    if ext0.shape != (C, 6) or not np.isfinite(ext0).all():
+        raise ValueError("all_extrinsics must be finite (rotation vector, translation) rows, one per camera")
+    gauge_camera = int(gauge_camera)
+    if not 0 <= gauge_camera < C:
+        raise ValueError("gauge_camera is not a camera of the rig")
+    centres = _camera_centres(ext0)
+    if scale_camera is None:
+        scale_camera = int(np.argmax(np.linalg.norm(centres - centres[gauge_camera], axis=1)))
+    scale_camera = int(scale_camera)
+    if not 0 <= scale_camera < C:
+        raise ValueError("scale_camera is not a camera of the rig")
+    if scale_camera == gauge_camera:
+        raise ValueError("gauge_camera == scale_camera: the scale is fixed by the distance between two different cameras")
+    if inliers is not None:
+        mask = np.asarray(inliers)
+        if mask.shape != (C, P) or mask.dtype != np.bool_:
+            raise ValueError(f"inliers must be the ({C}, {P}) bool mask of triangulate_consensus")
+        uvs = np.where(mask[:, :, None], uvs, np.nan)   # (a copy: the one that is uploaded)
+    if points is None:
+        pts = np.ascontiguousarray(triangulate(list(uvs), all_extrinsics, all_intrinsics, device=device))
+    else:
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        if pts.shape != (P, 3):
+            raise ValueError("points must be (n_points, 3), one row per row of the cameras' uvs")
+    cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
+    d = -rodrigues(ext0[scale_camera, :3]) @ (centres[scale_camera] - centres[gauge_camera])
+    held_bits = np.zeros(C, dtype=np.int32)
+    held_bits[gauge_camera] = 63
+    held_bits[scale_camera] |= 1 << (3 + int(np.argmax(np.abs(d))))
+    ext, out, status, res = np.empty((C, 6)), np.empty((P, 3)), np.empty(P, np.int32), np.zeros(16)
+    hist = np.zeros((int(max_nfev) + 1, 3))
+    ops.call("mcba_refine_extrinsics", C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, held_bits.ctypes.data, gauge_camera, scale_camera, ops.LOSSES[loss],
+             float(f_scale), float(ftol), float(xtol), float(gtol), int(max_nfev), int(device), ext.ctypes.data, out.ctypes.data, status.ctypes.data, res.ctypes.data, hist.ctypes.data, len(hist))
+    hist = hist[:min(int(res[7]), len(hist))].copy()
+    code = int(res[5])
+    if verbose == 2:
+        print("{0:^15}{1:^15}{2:^15}{3:^15}{4:^15}".format("Iteration", "Total nfev", "Cost", "Cost reduction", "Damping"))
+        it, last = 0, None
+        for k, (c, lam, acc) in enumerate(hist):
+            if acc:
+                print("{0:^15}{1:^15}{2:^15.4e}{3:^15}{4:^15.2e}".format(it, k + 1, c, "" if last is None else "%.2e" % (last - c), lam))
+                it, last = it + 1, c
+    if verbose >= 1:
+        print(solver.TERMINATION_MESSAGES[code])
+        print("Function evaluations {0}, initial cost {1:.4e}, final cost {2:.4e}, first-order optimality {3:.2e}.".format(int(res[3]), res[1], res[0], res[2]))
+    held = ((held_bits[:, None] >> np.arange(6)) & 1).astype(bool)
+    return ExtrinsicsRefinement(extrinsics=ext, points=out, cost=float(res[0]), cost0=float(res[1]), optimality=float(res[2]), nfev=int(res[3]), njev=int(res[4]), status=code,
+                                message=solver.TERMINATION_MESSAGES[code], success=code > 0, point_status=status, held=held, scale=float(res[6]), history=hist,
+                                info={"kernel_ms": float(res[8]), "reduce_ms": float(res[9]), "n_reduce": int(res[10]), "step_ms": float(res[11]), "n_step": int(res[12]), "group": int(res[13]),
+                                      "gauge_camera": gauge_camera, "scale_camera": scale_camera})
 
 
 # ---------------------------------------------------------------- host helpers (numpy; the reference's formulas)

@@ -1,0 +1,215 @@
+// Host build of csrc/mcba_kpba_math.h -- the arithmetic of csrc/mcba_kpba.hip (k_kpba_reduce, k_kpba_step) and the Levenberg-Marquardt loop of
+// csrc/mcba_kpba_api.hip -- for g++: the kernels' sums as plain loops in the kernels' order (points ascending; per point the cameras ascending),
+// the product Y Y^T as plain loops, the loop itself the very text the C ABI runs (kpba_lm).  tests/test_hostcheck_kpba.py compiles this as a shared
+// library (plain -O2) and holds it to the GPU tier's bounds; with -DKPBA_MAIN it is a stand-alone program (two small cases) that the same test
+// builds with -fsanitize=address,undefined and runs as a child process.
+#include <cmath>
+#include <cstddef>
+#include <cstdio>
+#include <vector>
+#include "../../multicam-calibration_amd/csrc/mcba_kpba_math.h"
+
+using namespace mcba;
+
+template <int LOSS>
+struct HostBackEnd {
+  int C;
+  size_t P;
+  const double* uvs;     // (C, P, 2)
+  const double* cam12;   // (C, 12): intrinsics; the extrinsics come per call
+  const double* dist5;
+  const int* held;
+  double f_scale;
+  std::vector<double> X[2];
+  std::vector<int> status;
+  std::vector<TcCam> tab, tab_trial;
+  int cur = 0;
+
+  void table(const double* ext, std::vector<TcCam>& t) const {
+    t.resize((size_t)C);
+    for (int c = 0; c < C; ++c) {
+      double q[12];
+      for (int k = 0; k < 6; ++k) { q[k] = cam12[12 * c + k]; q[6 + k] = ext[6 * c + k]; }
+      make_tc_cam(q, dist5 ? dist5 + 5 * c : nullptr, t[c]);
+    }
+  }
+  void statuses(const double* ext) {
+    table(ext, tab);
+    status.resize(P);
+    const double fs2 = f_scale * f_scale, inv_fs2 = 1.0 / fs2;
+    for (size_t p = 0; p < P; ++p) {
+      auto obs = [&](int c, double& ou, double& ov) { ou = uvs[2 * ((size_t)c * P + p)]; ov = uvs[2 * ((size_t)c * P + p) + 1]; };
+      KbPoint pt;
+      kpba_point<LOSS_LINEAR>(tab.data(), C, obs, X[cur].data() + 3 * p, fs2, inv_fs2, nullptr, pt);
+      status[p] = kpba_status(pt.views, X[cur].data() + 3 * p, pt.H);
+    }
+  }
+  int reduce(const double* ext, double lam, KbSystem& sys) {
+    table(ext, tab);
+    sys.shape(C);
+    sys.cost = sys.count = sys.gmax = 0.0;
+    const double fs2 = f_scale * f_scale, inv_fs2 = 1.0 / fs2;
+    const int n6 = 6 * C;
+    std::vector<double> Y((size_t)n6 * 3);
+    for (size_t p = 0; p < P; ++p) {
+      if (status[p] != KB_USED) continue;
+      const double* Xp = X[cur].data() + 3 * p;
+      auto obs = [&](int c, double& ou, double& ov) { ou = uvs[2 * ((size_t)c * P + p)]; ov = uvs[2 * ((size_t)c * P + p) + 1]; };
+      KbPoint pt;
+      kpba_point<LOSS>(tab.data(), C, obs, Xp, fs2, inv_fs2, nullptr, pt);
+      sys.cost += pt.cost;
+      sys.count += 2.0 * pt.views;
+      sys.gmax = fmax(sys.gmax, fmax(fabs(pt.g[0]), fmax(fabs(pt.g[1]), fabs(pt.g[2]))));
+      KbFactor f;
+      if (!kpba_factor(pt.H, lam, f)) continue;
+      double zp[3];
+      kpba_fwd(f, pt.g, zp);
+      for (double& v : Y) v = 0.0;
+      for (int c = 0; c < C; ++c) {
+        double ou, ov;
+        obs(c, ou, ov);
+        if (!(ou == ou && ov == ov)) continue;
+        double acc[kKbAcc];
+        kpba_item<LOSS>(tab[c], Xp, ou, ov, fs2, inv_fs2, f, zp, held[c], Y.data() + 18 * c, acc);
+        for (int k = 0; k < kKbAcc; ++k) sys.acc[(size_t)c * kKbAcc + k] += acc[k];
+      }
+      for (int i = 0; i < n6; ++i)
+        for (int j = 0; j < n6; ++j) sys.YY[(size_t)i * sys.NP + j] += Y[3 * i] * Y[3 * j] + Y[3 * i + 1] * Y[3 * j + 1] + Y[3 * i + 2] * Y[3 * j + 2];
+    }
+    return 0;
+  }
+  int step(const double* ext_trial, const double* dtheta, double lam, double out[3]) {
+    table(ext_trial, tab_trial);
+    const double fs2 = f_scale * f_scale, inv_fs2 = 1.0 / fs2;
+    out[0] = out[1] = out[2] = 0.0;
+    X[1 - cur] = X[cur];
+    for (size_t p = 0; p < P; ++p) {
+      if (status[p] != KB_USED) continue;
+      const double* Xp = X[cur].data() + 3 * p;
+      auto obs = [&](int c, double& ou, double& ov) { ou = uvs[2 * ((size_t)c * P + p)]; ov = uvs[2 * ((size_t)c * P + p) + 1]; };
+      KbPoint pt, tr;
+      kpba_point<LOSS>(tab.data(), C, obs, Xp, fs2, inv_fs2, dtheta, pt);
+      KbFactor f;
+      double dX[3] = {0.0, 0.0, 0.0};
+      if (kpba_factor(pt.H, lam, f)) kpba_point_step(f, pt.g, pt.q, dX);
+      double* Xt = X[1 - cur].data() + 3 * p;
+      for (int j = 0; j < 3; ++j) { Xt[j] = Xp[j] + dX[j]; out[1] += dX[j] * dX[j]; out[2] += Xp[j] * Xp[j]; }
+      kpba_point<LOSS>(tab_trial.data(), C, obs, Xt, fs2, inv_fs2, nullptr, tr);
+      out[0] += tr.cost;
+    }
+    return 0;
+  }
+  void accept() { cur = 1 - cur; }
+};
+
+template <int LOSS>
+static int run(int C, size_t P, const double* uvs, const double* cam12, const double* dist5, const double* pts0, int* held, int gauge, int scale_cam, double f_scale, const KbOptions& opt,
+               double* ext, double* pts, int* status, double* res8, double* hist, int hist_cap) {
+  HostBackEnd<LOSS> be{C, P, uvs, cam12, dist5, held, f_scale};
+  be.X[0].assign(pts0, pts0 + 3 * P);
+  for (int c = 0; c < C; ++c)
+    for (int k = 0; k < 6; ++k) ext[6 * c + k] = cam12[12 * c + 6 + k];
+  be.statuses(ext);
+  for (int c = 0; c < C; ++c) {   // a camera that no used point sees is held whole
+    bool seen = false;
+    for (size_t p = 0; p < P && !seen; ++p) seen = be.status[p] == KB_USED && uvs[2 * ((size_t)c * P + p)] == uvs[2 * ((size_t)c * P + p)] && uvs[2 * ((size_t)c * P + p) + 1] == uvs[2 * ((size_t)c * P + p) + 1];
+    if (!seen) held[c] = 63;
+  }
+  if (held[scale_cam] == 63) return 2;   // no used point in the scale camera: nothing fixes the scale
+  const double baseline = kpba_baseline(ext, gauge, scale_cam);
+  KbResult r;
+  if (int rc = kpba_lm(be, C, held, ext, opt, r, hist, hist_cap)) return rc;
+  for (size_t p = 0; p < P; ++p) {
+    status[p] = be.status[p];
+    for (int j = 0; j < 3; ++j) pts[3 * p + j] = status[p] == KB_USED ? be.X[be.cur][3 * p + j] : std::nan("");
+  }
+  const double s = kpba_rescale(C, held, ext, P, pts, gauge, scale_cam, baseline);
+  res8[0] = r.cost; res8[1] = r.cost0; res8[2] = r.optimality; res8[3] = r.nfev; res8[4] = r.njev; res8[5] = r.status; res8[6] = s; res8[7] = r.nhist;
+  return 0;
+}
+
+template <int LOSS>
+static void system_at(int C, size_t P, const double* uvs, const double* cam12, const double* dist5, const double* pts, const int* held, double f_scale, double lam, double* YY, double* acc,
+                      double* scal3) {
+  HostBackEnd<LOSS> be{C, P, uvs, cam12, dist5, held, f_scale};
+  be.X[0].assign(pts, pts + 3 * P);
+  std::vector<double> ext((size_t)6 * C);
+  for (int c = 0; c < C; ++c)
+    for (int k = 0; k < 6; ++k) ext[6 * c + k] = cam12[12 * c + 6 + k];
+  be.statuses(ext.data());
+  KbSystem sys;
+  be.reduce(ext.data(), lam, sys);
+  for (size_t i = 0; i < sys.YY.size(); ++i) YY[i] = sys.YY[i];
+  for (size_t i = 0; i < sys.acc.size(); ++i) acc[i] = sys.acc[i];
+  scal3[0] = sys.cost; scal3[1] = sys.count; scal3[2] = sys.gmax;
+}
+
+extern "C" {
+
+// uvs (C, P, 2), cam12 (C, 12) with the start extrinsics in columns 6 .. 11, pts0 (P, 3); held (C) in/out, bit i = scalar i not free.
+// Out: ext (C, 6), pts (P, 3), status (P), res8 = cost cost0 optimality nfev njev status scale evaluations, hist (hist_cap, 3).
+int hc_kpba(int C, size_t P, const double* uvs, const double* cam12, const double* dist5, const double* pts0, int* held, int gauge, int scale_cam, int loss, double f_scale, double ftol, double xtol,
+            double gtol, int max_nfev, double* ext, double* pts, int* status, double* res8, double* hist, int hist_cap) {
+  const KbOptions opt{ftol, xtol, gtol, max_nfev};
+  switch (loss) {
+    case LOSS_LINEAR: return run<LOSS_LINEAR>(C, P, uvs, cam12, dist5, pts0, held, gauge, scale_cam, f_scale, opt, ext, pts, status, res8, hist, hist_cap);
+    case LOSS_SOFT_L1: return run<LOSS_SOFT_L1>(C, P, uvs, cam12, dist5, pts0, held, gauge, scale_cam, f_scale, opt, ext, pts, status, res8, hist, hist_cap);
+    case LOSS_HUBER: return run<LOSS_HUBER>(C, P, uvs, cam12, dist5, pts0, held, gauge, scale_cam, f_scale, opt, ext, pts, status, res8, hist, hist_cap);
+    case LOSS_CAUCHY: return run<LOSS_CAUCHY>(C, P, uvs, cam12, dist5, pts0, held, gauge, scale_cam, f_scale, opt, ext, pts, status, res8, hist, hist_cap);
+    case LOSS_ARCTAN: return run<LOSS_ARCTAN>(C, P, uvs, cam12, dist5, pts0, held, gauge, scale_cam, f_scale, opt, ext, pts, status, res8, hist, hist_cap);
+    default: return 1;
+  }
+}
+
+// the linear-loss system at (cam12, pts) and damping lam: YY (NP, NP), acc (C, 33), scal3 = cost, present scalars, max |g_p|
+void hc_kpba_system(int C, size_t P, const double* uvs, const double* cam12, const double* dist5, const double* pts, const int* held, double lam, double* YY, double* acc, double* scal3) {
+  system_at<LOSS_LINEAR>(C, P, uvs, cam12, dist5, pts, held, 1.0, lam, YY, acc, scal3);
+}
+
+// n x n solve through kpba_dense_solve: 1 = solved
+int hc_kpba_dense_solve(int n, double* A, const double* b, double* x) { return kpba_dense_solve(n, A, b, x) ? 1 : 0; }
+
+}  // extern "C"
+
+#ifdef KPBA_MAIN
+static int run_case(int C, int P, int loss, bool with_unseen) {
+  std::vector<double> cam12(12 * C), dist5(5 * C), pts(3 * P), uvs((size_t)2 * C * P);
+  for (int c = 0; c < C; ++c) {
+    const double q[12] = {900.0 + 10 * c, 905.0, 640.0, 512.0, -0.1, 0.02, 0.02 * c, 0.05 * c, -0.01 * c, -150.0 * c, 10.0 * c, 5.0 * c};
+    for (int k = 0; k < 12; ++k) cam12[12 * c + k] = q[k];
+    const double d[5] = {-0.1, 0.02, 1e-3, -5e-4, 0.01};
+    for (int k = 0; k < 5; ++k) dist5[5 * c + k] = d[k];
+  }
+  std::vector<TcCam> tab(C);
+  for (int c = 0; c < C; ++c) make_tc_cam(cam12.data() + 12 * c, dist5.data() + 5 * c, tab[c]);
+  for (int p = 0; p < P; ++p) {
+    pts[3 * p] = 37.0 * (p % 5) - 80.0 + 3.0 * p; pts[3 * p + 1] = 60.0 - 29.0 * (p % 4); pts[3 * p + 2] = 900.0 + 45.0 * (p % 3) - 11.0 * p;
+    for (int c = 0; c < C; ++c) {
+      double u, v;
+      project5<false>(tab[c].kc, pts.data() + 3 * p, u, v);
+      double* o = uvs.data() + 2 * ((size_t)c * P + p);
+      o[0] = u + 0.3 * ((p + c) % 3 - 1); o[1] = v - 0.2 * ((p + 2 * c) % 3 - 1);
+      if (with_unseen && ((p == P - 1 && c >= 1) || c == C - 1)) o[0] = o[1] = std::nan("");   // the last point: one view; the last camera sees nothing
+    }
+  }
+  for (int c = 1; c < C; ++c) { cam12[12 * c + 6] += 2e-3; cam12[12 * c + 10] += 1.0; }   // the start: off the optimum
+  std::vector<int> held(C, 0), status(P);
+  held[0] = 63; held[1] |= 1 << 3;
+  std::vector<double> ext(6 * C), out(3 * P), res(8), hist(3 * 40);
+  if (hc_kpba(C, P, uvs.data(), cam12.data(), dist5.data(), pts.data(), held.data(), 0, 1, loss, 1.5, 1e-12, 1e-12, 1e-10, 40, ext.data(), out.data(), status.data(), res.data(), hist.data(), 40) != 0)
+    return 1;
+  int bad = 0;
+  if (!(res[0] <= res[1])) { printf("the cost rose: %g -> %g\n", res[1], res[0]); ++bad; }
+  if (with_unseen && (status[P - 1] != KB_TOO_FEW_VIEWS || held[C - 1] != 63)) { printf("status %d held %d\n", status[P - 1], held[C - 1]); ++bad; }
+  for (int p = 0; p < P; ++p)
+    if (std::isfinite(out[3 * p]) != (status[p] == KB_USED)) ++bad;
+  printf("C %d P %d loss %d: cost %.6g -> %.6g, %g evaluations, status %g, scale %.12g\n", C, P, loss, res[1], res[0], res[3], res[5], res[6]);
+  return bad;
+}
+
+int main() {
+  const int bad = run_case(2, 8, LOSS_LINEAR, false) + run_case(4, 11, LOSS_SOFT_L1, true);
+  printf(bad ? "FAILED\n" : "kpba hostcheck ok\n");
+  return bad ? 1 : 0;
+}
+#endif
