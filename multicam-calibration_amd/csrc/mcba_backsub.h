@@ -29,7 +29,7 @@ constexpr int kBacksubWaves = 8;
 // cannot hang the grid.
 struct BacksubWait {
   const double* early;  // LM state after the tick's decision
-  const double* flag;   // one word the solve releases: 4 seq + 1 camera step in memory, + 2 state final, + 3 state final and no step
+  const double* flag;   // one word the solve releases: 4 seq + 1 camera step in memory, + 2 state final and the trial step wanted (DONE == 0, SKIP == 0), + 3 state final and no step to store
   const double* dc;     // the camera step the solve writes before it releases the flag
   double* mail;         // LDS, 8 + 12 C doubles: what the polling wavefront fetched, for the others
   double seq;
@@ -223,11 +223,16 @@ __device__ __forceinline__ void backsub_body(Sel sl, const double* __restrict__ 
   double a = wave_sum63(pred), b = wave_sum63(dn2), cc = wave_sum63(xn2);
   FSTAMP(4);
   if (wait) {  // the steps are ready; they count only if the solve's FINAL state still wants a trial step (a failed solve does not)
+    // The final word itself says so: the solve posts + 2 only when the state it posts has DONE == 0 and SKIP == 0, and + 3 otherwise (a
+    // failed solve, a run that terminated).  No read of the state behind the poll: that was one more dependent cache-bypassing round trip
+    // before any pose could be stored.  Nor an acquire: nothing the word guards is READ from here on (the camera step came through LDS after
+    // the first poll, the source slot and the frame data are not written by the solve) -- what follows are stores to the trial slot and the
+    // partials, which the solve never touches and which sit behind the branch on the polled value.
     const double fin_word = 4.0 * wait->seq + 2.0;
-    const bool posted = release_word_poll(wait->flag, fin_word, fin_word, -1.0, wait->max_polls) > 0;
-    release_word_acquired(wait->strict);
-    if (!posted && lane == 0) backsub_stamp_timeout(wait);
-    if (!posted || load_coherent(sl.lms + MCBA_LM_DONE) != 0.0 || load_coherent(sl.lms + MCBA_LM_SKIP) != 0.0) return;
+    const int rc = release_word_poll(wait->flag, fin_word, fin_word, fin_word + 1.0, wait->max_polls);
+    asm volatile("" ::: "memory");
+    if (rc < 0 && lane == 0) backsub_stamp_timeout(wait);
+    if (rc <= 0) return;
   }
   if (block == 0) {
     if constexpr (CW == 12) {

@@ -45,6 +45,15 @@ __device__ __forceinline__ double lane_bcast(double v, int lane) {  // `lane` wa
   return b.d;
 }
 
+// LDS hand-off between the lanes of ONE wavefront (the backward sweep): the LDS executes a wavefront's accesses in issue order, so a
+// store is seen by every later load of the same wavefront without a workgroup barrier.  The wavefront-scope fences emit no cache or
+// barrier instruction; they keep the compiler from moving LDS accesses across this point.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // 1/sqrt(a): hardware estimate + ONE third-order step  y (1 + e/2 + 3 e^2/8), e = 1 - a y^2  (estimate good to > 2^-20
 // -> full FP64); shorter dependent chain than two Newton steps -- it sits on the critical path of every pivot
 __device__ __forceinline__ double rsqrt_cubic(double a) {
@@ -96,8 +105,9 @@ __device__ __forceinline__ void post_state(const SolveArgs& a, const double* st,
     if (a.host_state) *reinterpret_cast<volatile double*>(a.host_state + MCBA_LMS - 1) = a.seq;  // (the end of the kernel releases it)
     // k_solve_backsub: the back-substitution workgroups of the same launch are polling this word; the camera step (a.dc) and
     // the state were written by other threads of this workgroup before the fence and the barrier above
-    // ONE word, three values per tick: 4 seq + 1 camera step in memory, 4 seq + 2 state final (after a step), 4 seq + 3 state
-    // final and no step this tick -- a poll is one cache-bypassing load, not two
+    // ONE word, three values per tick: 4 seq + 1 camera step in memory, 4 seq + 2 state final and the trial step is to be stored
+    // (DONE == 0, SKIP == 0), 4 seq + 3 state final and no step to store -- a poll is one cache-bypassing load, not two, and the word
+    // is all a reader needs of the state
     if (a.flag) __hip_atomic_store(a.flag, 4.0 * a.seq + (stepped ? 2.0 : 3.0), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
@@ -832,39 +842,73 @@ __device__ __forceinline__ void solve_cam_body(const SolveArgs& a) {
 
     STAMP(2);
     // ---- backward sweep  L^T d = y,  y = row n of the factor
-    for (int j = tid; j < npad; j += NTHREADS) yv[j] = j < n ? W[(size_t)n * ldw + j] : 0.0;
-    __syncthreads();
-    {
-      // d_k = L_kk^-T y_k: row i of the inverse transpose (zero left of the diagonal) times the block's right-hand side; y
-      // beyond row n is zero, so the right-hand-side row and the padding drop out.  Then y_j -= sum_t L[r0+t][j] d[r0+t].
-      for (int k = nblk - 1; k >= 0; --k) {
-        const int r0 = 16 * k;
-        double wcur[16];  // wcur[t] = L[r0 + t][j] for this thread's column j = tid: in flight during the dot products
+    // d_k = L_kk^-T y_k: row i of the inverse transpose (zero left of the diagonal) times the block's right-hand side; y
+    // beyond row n is zero, so the right-hand-side row and the padding drop out.  Then y_j -= sum_t L[r0+t][j] d[r0+t].
+    // WAVEFRONT 0 RUNS THE SWEEP ALONE: the dot products occupy 16 lanes and the update at most npad - 16 <= 96, so a workgroup has
+    // nothing to add to it but two barriers per block step.  Lane l owns the columns l and l + 64 (npad <= 112) and keeps their y in
+    // registers; yv / dv / linv stay in LDS, which serves one wavefront's accesses in the order it issued them (wave_lds_sync keeps the
+    // compiler to that order).  The arithmetic -- the s[c & 3] grouping of the dot product, the s0 / s1 split of the update -- is the
+    // workgroup form's, term for term: the camera step is bit-identical to it.  The other wavefronts wait at the barrier behind the sweep.
+    if (wave == 0) {
+      static_assert(16 * KS <= 128, "two columns per lane cover the LDS-resident systems");
+      const int j0 = lane, j1 = lane + 64, jc0 = min(j0, npad - 1);
+      double y0 = j0 < n ? W[(size_t)n * ldw + j0] : 0.0, y1 = j1 < n ? W[(size_t)n * ldw + j1] : 0.0;
+      if (j0 < npad) yv[j0] = y0;
+      if (j1 < npad) yv[j1] = y1;
+      double wn[16];  // wn[t] = L[r0 + t][j0] of the block step to come: requested a whole step ahead of its use
 #pragma unroll
-        for (int t = 0; t < 16; ++t) wcur[t] = W[(size_t)(r0 + t) * ldw + min(tid, npad - 1)];
-        if (tid < 16) {
-          const double* li = linv + (k * 16 + tid) * 17;
+      for (int t = 0; t < 16; ++t) wn[t] = W[(size_t)(16 * (nblk - 1) + t) * ldw + jc0];
+      wave_lds_sync();
+#pragma unroll
+      for (int k = KS - 1; k >= 0; --k) {  // (nblk <= KS; unrolled, so that wn / wc stay in registers)
+        if (k < nblk) {
+          const int r0 = 16 * k;
+          double wc[16];
+#pragma unroll
+          for (int t = 0; t < 16; ++t) wc[t] = wn[t];
+          // every lane runs the dot product of row (lane & 15) -- no divergent branch between the loads of this step and the requests for
+          // the next --, lanes 0 .. 15 store it
+          const double* li = linv + (k * 16 + (lane & 15)) * 17;
           double s[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
           for (int c = 0; c < 16; ++c) s[c & 3] = fma(li[c], yv[r0 + c], s[c & 3]);
-          dv[r0 + tid] = (r0 + tid < n) ? (s[0] + s[1]) + (s[2] + s[3]) : 0.0;
-        }
-        __syncthreads();
-        for (int j = tid; j < r0; j += NTHREADS) {
-          double s0 = yv[j], s1 = 0.0;
-          if (j == tid) {
+          if (k > 0) {
 #pragma unroll
-            for (int t = 0; t < 16; t += 2) { s0 = fma(-wcur[t], dv[r0 + t], s0); s1 = fma(-wcur[t + 1], dv[r0 + t + 1], s1); }
-          } else {
-            const double* wc = W + (size_t)r0 * ldw + j;
-#pragma unroll
-            for (int t = 0; t < 16; t += 2) { s0 = fma(-wc[(size_t)t * ldw], dv[r0 + t], s0); s1 = fma(-wc[(size_t)(t + 1) * ldw], dv[r0 + t + 1], s1); }
+            for (int t = 0; t < 16; ++t) wn[t] = W[(size_t)(r0 - 16 + t) * ldw + jc0];
           }
-          yv[j] = s0 + s1;
+          const double dk = (r0 + (lane & 15) < n) ? (s[0] + s[1]) + (s[2] + s[3]) : 0.0;
+          if (lane < 16) {
+            dv[r0 + lane] = dk;
+            // the step leaves as it is produced: these 16 stores drain while the remaining block steps run
+            if (r0 + lane < n) a.dc[r0 + lane] = dk;
+          }
+          wave_lds_sync();
+          if (j0 < r0) {
+            double s0 = y0, s1 = 0.0;
+#pragma unroll
+            for (int t = 0; t < 16; t += 2) { s0 = fma(-wc[t], dv[r0 + t], s0); s1 = fma(-wc[t + 1], dv[r0 + t + 1], s1); }
+            y0 = s0 + s1;
+            yv[j0] = y0;
+          }
+          if (k > 4 && j1 < r0) {  // (more than 6 cameras: the columns from 64 on, straight from LDS)
+            const double* wp = W + (size_t)r0 * ldw + j1;
+            double s0 = y1, s1 = 0.0;
+#pragma unroll
+            for (int t = 0; t < 16; t += 2) { s0 = fma(-wp[(size_t)t * ldw], dv[r0 + t], s0); s1 = fma(-wp[(size_t)(t + 1) * ldw], dv[r0 + t + 1], s1); }
+            y1 = s0 + s1;
+            yv[j1] = y1;
+          }
+          wave_lds_sync();
         }
-        __syncthreads();
       }
     }
+    // dv is complete: the step scalars below read it from LDS.  The camera step itself is in flight to memory: wavefront 0 stored all of it,
+    // the barrier orders those stores at workgroup scope, and thread 0 -- a lane of that same wavefront -- releases the word at agent scope,
+    // which makes them visible (LLVM AMDGPU memory model: a release is cumulative over what happens-before it; in the hardware's terms the
+    // releasing wavefront waits for its own stores and writes the L2 back).  The agent-scope fence every thread ran here before the barrier
+    // (a second write-back per wavefront) ordered nothing the release does not.
+    __syncthreads();
+    if (a.flag && tid == 0) __hip_atomic_store(a.flag, 4.0 * a.seq + 1.0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
 
@@ -874,17 +918,19 @@ __device__ __forceinline__ void solve_cam_body(const SolveArgs& a) {
   if (mode == 0) {
     for (int i = tid; i < n; i += NTHREADS) {
       const double d = dv[i], xv = xc[a.cw == 12 ? i : 12 * (i / 6) + 6 + i % 6];  // (camera block 6 wide: the system's row i is parameter 6 + i % 6 of camera i / 6)
-      a.dc[i] = d;
+      if constexpr (!LDSW) a.dc[i] = d;  // (LDS-resident factor: the sweep stored it block by block)
       sums[3] += (fabs(d) < 1e300) ? 0.0 : 1.0;
       sums[0] += d * (damp[i] * d - gc[i]);
       sums[1] += d * d;
       sums[2] += xv * xv;
     }
   }
-  if (a.flag && mode == 0) {  // k_solve_backsub: the camera step is in memory -- the back-substitution workgroups may start on it
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(a.flag, 4.0 * a.seq + 1.0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+  if constexpr (!LDSW) {
+    if (a.flag && mode == 0) {  // (the camera step was stored by every thread just above: fence, barrier, release)
+      __threadfence();
+      __syncthreads();
+      if (tid == 0) __hip_atomic_store(a.flag, 4.0 * a.seq + 1.0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
   block_reduce4<NTHREADS>(sums, false, s_red);
   if (tid == 0) {
@@ -904,7 +950,9 @@ __device__ __forceinline__ void solve_cam_body(const SolveArgs& a) {
     }
   }
   __syncthreads();
-  post_state(a, lst, true, a.flag != nullptr && mode == 0);
+  // the final word says "store the trial step" (+ 2) only when the state posted with it wants one: DONE == 0 and SKIP == 0.  A failed solve
+  // and a run that terminated post + 3, so the back-substitution workgroups need not read the state behind the word.
+  post_state(a, lst, true, a.flag != nullptr && mode == 0 && lms[MCBA_LM_DONE] == 0.0 && lms[MCBA_LM_SKIP] == 0.0);
 }
 
 template <int NTHREADS, bool LDSW, int KS>
