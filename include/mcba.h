@@ -622,6 +622,21 @@ int mcba_refine_extrinsics(int n_cameras, size_t n_points, const double* uvs, co
                            double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* extrinsics_out, double* points_out, int* point_status, double* result16,
                            double* history, int history_rows);
 
+/* One evaluation of mcba_refine_extrinsics laid open (additive to ABI 7): the very set-up, k_kpba_status, k_kpba_reduce + k_kpba_finish and -- with
+ * ext_trial (C, 6) and dtheta (C, 6), both or neither -- k_kpba_step of the loop, once, at the extrinsics in cam12, the given points and the
+ * damping lam (0 <= lam < 1e12), and what the kernels wrote as they wrote it.  For tests and diagnostics, as mcba_calib_normal_equations and
+ * mcba_get_reduced are for the other solvers.  uvs, cam12, dist5, points, loss, f_scale and their refusals as above.
+ * held (C) is taken as given: no gauge camera, no scale scalar and no rule for a camera without detections is applied.
+ * point_status (P) as above.  system (NP NP + 33 C + 4 doubles, NP = 6 C rounded up to a multiple of 16): Y Y^T = sum_p Y_p Y_p^T (NP, NP)
+ * row-major, rows and columns of held scalars and of the padding zero | per camera U_c packed lower (21: (i, j <= i) at i (i + 1) / 2 + j), g_c
+ * (6), sum_p Y_cp z_p (6) | robust cost, present scalars of the used points, max |g_p|, 0.  The loop solves
+ * (U + lam diag U - Y Y^T) dtheta = sum Y z - g_c over the free scalars.
+ * With a step: trial_points (P, 3) = points + dX, dX_p = -(H_p + lam diag H_p)^-1 (g_p + sum_c W_cp^T dtheta_c) (a point that is not used
+ * keeps its value, NaN included), and step4 = {robust cost at (ext_trial, trial_points), sum dX^2, 0, sum X^2 over the used points}.
+ * info4 = {points per group, workgroups of a pass (= partial systems summed), NP, kernel_ms}.  MCBA_KPBA_G as above. */
+int mcba_refine_extrinsics_system(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points, const int* held, int loss, double f_scale,
+                                  double lam, int device, const double* ext_trial, const double* dtheta, int* point_status, double* system, double* trial_points, double* step4, double* info4);
+
 #ifdef __cplusplus
 }
 #endif

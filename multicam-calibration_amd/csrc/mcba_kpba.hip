@@ -253,7 +253,7 @@ static int kpba_reduce_go(hipStream_t st, size_t lds, int nwg, const double2* uv
 template <int LOSS>
 static int kpba_reduce_shape(hipStream_t st, size_t lds, int nwg, const double2* uv, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale,
                              double lam, int G, double* part) {
-  const int NT = (6 * C + 15) / 16, ntiles = NT * (NT + 1) / 2;   // tiles per wavefront: 3 up to 10 tiles (6 cameras), 12 up to 45
+  const int NT = (6 * C + 15) / 16, ntiles = NT * (NT + 1) / 2;   // tiles per wavefront: 3 up to 10 tiles (10 cameras), 12 up to 45
   if (ntiles <= 12) return kpba_reduce_go<LOSS, 3>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part);
   return kpba_reduce_go<LOSS, 12>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part);
 }

@@ -2,6 +2,8 @@
 // in the idiom of mcba_geom_api.hip: one upload of the detections, then the whole Levenberg-Marquardt loop (kpba_lm, mcba_kpba_math.h) with the
 // kernels of mcba_kpba.hip as its back end.  Per evaluation the camera tables go up (60 C doubles) and the reduced system comes down (at most
 // 144^2 + 33 * 24 + 4 doubles); the dense solve is the host's.  The loop ends at the first HIP error and starts nothing after it.
+// mcba_refine_extrinsics_system is one evaluation of that loop laid open: the same refusals, set-up and back end (kpba_refuse, kpba_pick_group,
+// DeviceBackEnd::setup / reduce / step below), and what the kernels wrote handed back as it is.
 #include "mcba_handle.h"
 #include "mcba_kpba_math.h"
 
@@ -11,6 +13,7 @@ namespace {
 
 struct DeviceBackEnd {
   StatelessCall& call;
+  const char* who;   // the entry point, for messages
   int C, loss, G;
   size_t P;
   double f_scale;
@@ -24,8 +27,9 @@ struct DeviceBackEnd {
   double *d_dth = nullptr, *d_part = nullptr, *d_sys = nullptr, *d_part4 = nullptr, *d_out4 = nullptr;
   int cur = 0;
   std::vector<mcba::TcCam> tab;   // 2 C
-  std::vector<double> host_sys;
-  double reduce_ms = 0.0, step_ms = 0.0;
+  std::vector<double> host_sys;   // the system of the last reduce, as k_kpba_finish left it
+  double out4[4] = {0.0, 0.0, 0.0, 0.0};   // the four scalars of the last step, likewise
+  double status_ms = 0.0, reduce_ms = 0.0, step_ms = 0.0;
   int n_reduce = 0, n_step = 0;
 
   void table(const double* ext, mcba::TcCam* t) const {
@@ -34,6 +38,10 @@ struct DeviceBackEnd {
       for (int k = 0; k < 6; ++k) { q[k] = cam12[12 * c + k]; q[6 + k] = ext[6 * c + k]; }
       mcba::make_tc_cam(q, dist5 ? dist5 + 5 * c : nullptr, t[c]);
     }
+  }
+  int launch_failed(const char* what) const {
+    g_err = std::string(who) + ": " + what;
+    return MCBA_ERR_HIP;
   }
   int timed(double* ms_sum) {   // after a launch between the two records
     HIPCHK(hipEventRecord(call.e1, nullptr));
@@ -49,7 +57,7 @@ struct DeviceBackEnd {
     if (int rc = call.put(d_cams, tab.data(), (size_t)C)) return rc;
     HIPCHK(hipEventRecord(call.e0, nullptr));
     if (mcba::launch_kpba_reduce(nullptr, loss, d_uv, d_pts[cur], d_status, P, d_cams, d_held, C, f_scale, lam, G, d_part, d_sys) != 0)
-      return fail(MCBA_ERR_HIP, "mcba_refine_extrinsics: k_kpba_reduce could not be launched");
+      return launch_failed("k_kpba_reduce could not be launched");
     if (int rc = timed(&reduce_ms)) return rc;
     ++n_reduce;
     const size_t PS = mcba::kpba_partial_size(C);
@@ -68,16 +76,64 @@ struct DeviceBackEnd {
     if (int rc = call.put(d_dth, dtheta, (size_t)6 * C)) return rc;
     HIPCHK(hipEventRecord(call.e0, nullptr));
     if (mcba::launch_kpba_step(nullptr, loss, d_uv, d_pts[cur], d_pts[1 - cur], d_status, P, d_cams, d_dth, C, f_scale, lam, d_part4, d_out4) != 0)
-      return fail(MCBA_ERR_HIP, "mcba_refine_extrinsics: k_kpba_step could not be launched");
+      return launch_failed("k_kpba_step could not be launched");
     if (int rc = timed(&step_ms)) return rc;
     ++n_step;
-    double o4[4];
-    if (int rc = call.download(o4, d_out4, (size_t)4)) return rc;
-    out[0] = o4[0]; out[1] = o4[1]; out[2] = o4[3];
+    if (int rc = call.download(out4, d_out4, (size_t)4)) return rc;
+    out[0] = out4[0]; out[1] = out4[1]; out[2] = out4[3];
     return MCBA_OK;
   }
   void accept() { cur = 1 - cur; }
+  // the detections, both point buffers and the camera tables (at ext) up, the scratch of a pass, then k_kpba_status: point_status (P) on the host
+  int setup(const double* uvs, const double* points, const double* ext, int* point_status) {
+    tab.resize((size_t)2 * C);
+    table(ext, tab.data());
+    table(ext, tab.data() + C);
+    const int nwg = mcba::kpba_groups(P);
+    if (int rc = call.upload(&d_uv, uvs, (size_t)2 * C * P)) return rc;
+    if (int rc = call.upload(&d_pts[0], points, 3 * P)) return rc;
+    if (int rc = call.upload(&d_pts[1], points, 3 * P)) return rc;
+    if (int rc = call.upload(&d_cams, tab.data(), tab.size())) return rc;
+    if (int rc = call.scratch(&d_status, P)) return rc;
+    if (int rc = call.scratch(&d_held, (size_t)C)) return rc;
+    if (int rc = call.scratch(&d_dth, (size_t)6 * C)) return rc;
+    if (int rc = call.scratch(&d_part, (size_t)nwg * mcba::kpba_partial_size(C))) return rc;
+    if (int rc = call.scratch(&d_sys, mcba::kpba_partial_size(C))) return rc;
+    if (int rc = call.scratch(&d_part4, (size_t)4 * nwg)) return rc;
+    if (int rc = call.scratch(&d_out4, (size_t)4)) return rc;
+    HIPCHK(call.start());
+    if (mcba::launch_kpba_status(nullptr, d_uv, d_pts[0], P, d_cams, C, d_status) != 0) {
+      g_err = std::string(who) + ": bad launch (k_kpba_status)";
+      return MCBA_ERR_ARG;
+    }
+    if (int rc = timed(&status_ms)) return rc;
+    return call.download(point_status, d_status, P);
+  }
 };
+
+// what both entry points refuse alike
+int kpba_refuse(const char* who, int n_cameras, size_t n_points, int loss, double f_scale) {
+  const char* why = nullptr;
+  if (n_cameras < 2 || n_cameras > mcba::kKbMaxCams) why = "2 to 24 cameras (the reduced system is held to 144 rows: nine matrix-core tiles)";
+  else if (loss < mcba::LOSS_LINEAR || loss > mcba::LOSS_ARCTAN) why = "loss must be one of linear, soft_l1, huber, cauchy, arctan (0 .. 4)";
+  else if (!(f_scale > 0.0)) why = "f_scale must be positive";
+  else if (n_points == 0) why = "no points";
+  if (!why) return MCBA_OK;
+  g_err = std::string(who) + ": " + why;
+  return MCBA_ERR_ARG;
+}
+
+// points per group of k_kpba_reduce on this device; MCBA_KPBA_G (test knob) forces the smaller groups at any size
+int kpba_pick_group(const char* who, int C, int device, int* G) {
+  int force_g = 0, lds_optin = 64 * 1024;
+  if (const char* e = getenv("MCBA_KPBA_G")) force_g = atoi(e);
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.sharedMemPerBlockOptin > 0) lds_optin = (int)std::min<size_t>(prop.sharedMemPerBlockOptin, 160 * 1024);
+  *G = mcba::kpba_group(C, lds_optin, force_g);
+  if (*G) return MCBA_OK;
+  g_err = std::string(who) + ": k_kpba_reduce does not fit the LDS of this device";
+  return MCBA_ERR_HIP;
+}
 
 }  // namespace
 
@@ -86,54 +142,27 @@ extern "C" {
 int mcba_refine_extrinsics(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points, int* held, int gauge_camera, int scale_camera, int loss,
                            double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* extrinsics_out, double* points_out, int* point_status, double* result16,
                            double* history, int history_rows) {
-  if (n_cameras < 2 || n_cameras > mcba::kKbMaxCams) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: 2 to 24 cameras (the reduced system is held to 144 rows: nine matrix-core tiles)");
+  const char* who = "mcba_refine_extrinsics";
+  if (int rc = kpba_refuse(who, n_cameras, n_points, loss, f_scale)) return rc;
   if (!uvs || !cam12 || !points || !held || !extrinsics_out || !points_out || !point_status || !result16 || (history_rows > 0 && !history))
     return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: non-NULL arrays required");
   if (gauge_camera < 0 || gauge_camera >= n_cameras || scale_camera < 0 || scale_camera >= n_cameras || gauge_camera == scale_camera)
     return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: gauge_camera and scale_camera must be two different cameras of the rig");
-  if (loss < mcba::LOSS_LINEAR || loss > mcba::LOSS_ARCTAN) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: loss must be one of linear, soft_l1, huber, cauchy, arctan (0 .. 4)");
-  if (!(f_scale > 0.0)) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: f_scale must be positive");
   if (max_nfev < 2) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: max_nfev must be at least 2 (the start and one trial)");
   if (!(ftol >= 0.0 && xtol >= 0.0 && gtol >= 0.0)) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: ftol, xtol, gtol must not be negative");
-  if (n_points == 0) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: no points");
   for (int i = 0; i < 16; ++i) result16[i] = 0.0;
   if (int rc = stateless_device(device)) return rc;
   const int C = n_cameras;
   const size_t P = n_points;
-
-  int force_g = 0, lds_optin = 64 * 1024;
-  if (const char* e = getenv("MCBA_KPBA_G")) force_g = atoi(e);   // test knob: the smaller groups of k_kpba_reduce at any size
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.sharedMemPerBlockOptin > 0) lds_optin = (int)std::min<size_t>(prop.sharedMemPerBlockOptin, 160 * 1024);
-  const int G = mcba::kpba_group(C, lds_optin, force_g);
-  if (!G) return fail(MCBA_ERR_HIP, "mcba_refine_extrinsics: k_kpba_reduce does not fit the LDS of this device");
+  int G = 0;
+  if (int rc = kpba_pick_group(who, C, device, &G)) return rc;
 
   StatelessCall call;
-  DeviceBackEnd be{call, C, loss, G, P, f_scale, cam12, dist5};
-  be.tab.resize((size_t)2 * C);
+  DeviceBackEnd be{call, who, C, loss, G, P, f_scale, cam12, dist5};
   std::vector<double> ext((size_t)6 * C);
   for (int c = 0; c < C; ++c)
     for (int k = 0; k < 6; ++k) ext[6 * c + k] = cam12[12 * c + 6 + k];
-  be.table(ext.data(), be.tab.data());
-  be.table(ext.data(), be.tab.data() + C);
-  const int nwg = mcba::kpba_groups(P);
-  if (int rc = call.upload(&be.d_uv, uvs, (size_t)2 * C * P)) return rc;
-  if (int rc = call.upload(&be.d_pts[0], points, 3 * P)) return rc;
-  if (int rc = call.upload(&be.d_pts[1], points, 3 * P)) return rc;
-  if (int rc = call.upload(&be.d_cams, be.tab.data(), be.tab.size())) return rc;
-  if (int rc = call.scratch(&be.d_status, P)) return rc;
-  if (int rc = call.scratch(&be.d_held, (size_t)C)) return rc;
-  if (int rc = call.scratch(&be.d_dth, (size_t)6 * C)) return rc;
-  if (int rc = call.scratch(&be.d_part, (size_t)nwg * mcba::kpba_partial_size(C))) return rc;
-  if (int rc = call.scratch(&be.d_sys, mcba::kpba_partial_size(C))) return rc;
-  if (int rc = call.scratch(&be.d_part4, (size_t)4 * nwg)) return rc;
-  if (int rc = call.scratch(&be.d_out4, (size_t)4)) return rc;
-  HIPCHK(call.start());
-
-  if (mcba::launch_kpba_status(nullptr, be.d_uv, be.d_pts[0], P, be.d_cams, C, be.d_status) != 0) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: bad launch (k_kpba_status)");
-  double status_ms = 0.0;
-  if (int rc = be.timed(&status_ms)) return rc;
-  if (int rc = call.download(point_status, be.d_status, P)) return rc;
+  if (int rc = be.setup(uvs, points, ext.data(), point_status)) return rc;
   for (int c = 0; c < C; ++c) {   // a camera that no used point sees is held whole
     bool seen = false;
     const double* u = uvs + (size_t)2 * c * P;
@@ -156,8 +185,42 @@ int mcba_refine_extrinsics(int n_cameras, size_t n_points, const double* uvs, co
   const double s = mcba::kpba_rescale(C, held, ext.data(), P, points_out, gauge_camera, scale_camera, baseline);
   for (int k = 0; k < 6 * C; ++k) extrinsics_out[k] = ext[k];
   result16[0] = res.cost; result16[1] = res.cost0; result16[2] = res.optimality; result16[3] = res.nfev; result16[4] = res.njev; result16[5] = res.status; result16[6] = s;
-  result16[7] = res.nhist; result16[8] = status_ms + be.reduce_ms + be.step_ms; result16[9] = be.reduce_ms; result16[10] = be.n_reduce; result16[11] = be.step_ms; result16[12] = be.n_step;
+  result16[7] = res.nhist; result16[8] = be.status_ms + be.reduce_ms + be.step_ms; result16[9] = be.reduce_ms; result16[10] = be.n_reduce; result16[11] = be.step_ms; result16[12] = be.n_step;
   result16[13] = G;
+  return MCBA_OK;
+}
+
+int mcba_refine_extrinsics_system(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points, const int* held, int loss, double f_scale,
+                                  double lam, int device, const double* ext_trial, const double* dtheta, int* point_status, double* system, double* trial_points, double* step4, double* info4) {
+  const char* who = "mcba_refine_extrinsics_system";
+  if (int rc = kpba_refuse(who, n_cameras, n_points, loss, f_scale)) return rc;
+  const bool stepping = ext_trial || dtheta;
+  if (!uvs || !cam12 || !points || !held || !point_status || !system || !info4 || (stepping && (!ext_trial || !dtheta || !trial_points || !step4)))
+    return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics_system: non-NULL arrays required (ext_trial and dtheta both or neither; with them trial_points and step4)");
+  if (!(lam >= 0.0 && lam < mcba::KB_LAMBDA_MAX)) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics_system: lam must be in [0, 1e12)");
+  if (int rc = stateless_device(device)) return rc;
+  const int C = n_cameras;
+  const size_t P = n_points;
+  int G = 0;
+  if (int rc = kpba_pick_group(who, C, device, &G)) return rc;
+
+  StatelessCall call;
+  DeviceBackEnd be{call, who, C, loss, G, P, f_scale, cam12, dist5};
+  std::vector<double> ext((size_t)6 * C);
+  for (int c = 0; c < C; ++c)
+    for (int k = 0; k < 6; ++k) ext[6 * c + k] = cam12[12 * c + 6 + k];
+  if (int rc = be.setup(uvs, points, ext.data(), point_status)) return rc;
+  if (int rc = call.put(be.d_held, held, (size_t)C)) return rc;   // (as given: no gauge, no scale, no blind-camera rule here)
+  mcba::KbSystem sys;
+  if (int rc = be.reduce(ext.data(), lam, sys)) return rc;
+  std::copy(be.host_sys.begin(), be.host_sys.end(), system);
+  if (stepping) {
+    double out[3];
+    if (int rc = be.step(ext_trial, dtheta, lam, out)) return rc;
+    if (int rc = call.download(trial_points, be.d_pts[1 - be.cur], 3 * P)) return rc;
+    for (int k = 0; k < 4; ++k) step4[k] = be.out4[k];
+  }
+  info4[0] = G; info4[1] = mcba::kpba_groups(P); info4[2] = sys.NP; info4[3] = be.status_ms + be.reduce_ms + be.step_ms;
   return MCBA_OK;
 }
 

@@ -11,7 +11,8 @@ GPU (`csrc/mcba_keypoints.hip`; no numpy fallback -- without a device every one 
                                  pair's two-view point scored against all detections, the inlier cameras named, the point refitted on them
   refine_extrinsics              (`csrc/mcba_kpba.hip`; no counterpart in the reference) free-point bundle adjustment:
                                  the extrinsics and every 3-D point jointly on the robust reprojection cost of the raw detections
-The last four use the five-coefficient forward model on the RAW (distorted) detections: no undistortion iteration, so none of its truncation
+  refine_extrinsics_system       one evaluation of refine_extrinsics laid open: the reduced system and the point steps as the kernels wrote them
+The last five use the five-coefficient forward model on the RAW (distorted) detections: no undistortion iteration, so none of its truncation
 error.  With p1 = p2 = k3 = 0 (all bundle_adjust returns) the model is project_points'.
 
 Host (numpy, the reference's formulas): rigid_transform_from_correspondences (returns (t, rmsd); the one in flatibration.py returns t alone),
@@ -312,6 +313,47 @@ def refine_extrinsics(all_uvs, all_extrinsics, all_intrinsics, *, points=None, i
                                 message=solver.TERMINATION_MESSAGES[code], success=code > 0, point_status=status, held=held, scale=float(res[6]), history=hist,
                                 info={"kernel_ms": float(res[8]), "reduce_ms": float(res[9]), "n_reduce": int(res[10]), "step_ms": float(res[11]), "n_step": int(res[12]), "group": int(res[13]),
                                       "gauge_camera": gauge_camera, "scale_camera": scale_camera})
+
+
+def refine_extrinsics_system(all_uvs, all_extrinsics, all_intrinsics, *, points, held, lam, loss="soft_l1", f_scale=1.0, step=None, device=0):
+    """One evaluation of refine_extrinsics laid open (`mcba_refine_extrinsics_system`; tests and diagnostics): the loop's own set-up and kernels
+    run once at (all_extrinsics, points) and the damping lam, and what they wrote comes back as it is.  held: (C, 6) bool or (C,) bit words,
+    taken as given -- no gauge, scale or blind-camera rule.  step: None, or (ext_trial (C, 6), dtheta (C, 6)): also the back-substitution.
+    Returns a dict: point_status (P,); system (the raw NP NP + 33 C + 4 doubles) and its views YY (NP, NP), acc (C, 33) = U_c packed lower
+    (21) | g_c (6) | sum_p Y_cp z_p (6), cost, count (present scalars of the used points), gmax (max |g_p|), tail (the fourth trailing scalar);
+    group, workgroups, NP, kernel_ms; with a step trial_points (P, 3) and step4 = trial cost, sum dX^2, 0, sum X^2."""
+    if callable(loss) or loss not in ops.LOSSES:
+        raise ValueError(f"loss must be one of {sorted(ops.LOSSES)}")
+    uvs = _stack_uvs(all_uvs, all_extrinsics, all_intrinsics)
+    C, P = uvs.shape[:2]
+    if not 2 <= C <= MAX_REFINE_CAMERAS:
+        raise NotImplementedError(f"refine_extrinsics_system() supports 2 to {MAX_REFINE_CAMERAS} cameras, got {C}")
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.shape != (P, 3):
+        raise ValueError("points must be (n_points, 3), one row per row of the cameras' uvs")
+    held = np.asarray(held)
+    if held.shape == (C, 6):
+        held = (held.astype(bool).astype(np.int32) << np.arange(6, dtype=np.int32)).sum(1)
+    held_bits = np.ascontiguousarray(held, dtype=np.int32)
+    if held_bits.shape != (C,):
+        raise ValueError("held must be (n_cameras, 6) bool or (n_cameras,) bit words")
+    cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
+    NP = (6 * C + 15) // 16 * 16
+    status, system, info = np.empty(P, np.int32), np.empty(NP * NP + 33 * C + 4), np.zeros(4)
+    trial = step4 = ext_trial = dtheta = None
+    if step is not None:
+        ext_trial, dtheta = (np.ascontiguousarray(a, dtype=np.float64) for a in step)
+        if ext_trial.shape != (C, 6) or dtheta.shape != (C, 6):
+            raise ValueError("step must be (ext_trial (n_cameras, 6), dtheta (n_cameras, 6))")
+        trial, step4 = np.empty((P, 3)), np.empty(4)
+    addr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+    ops.call("mcba_refine_extrinsics_system", C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, held_bits.ctypes.data, ops.LOSSES[loss], float(f_scale), float(lam),
+             int(device), addr(ext_trial), addr(dtheta), status.ctypes.data, system.ctypes.data, addr(trial), addr(step4), info.ctypes.data)
+    out = dict(point_status=status, system=system, YY=system[:NP * NP].reshape(NP, NP), acc=system[NP * NP:NP * NP + 33 * C].reshape(C, 33), cost=float(system[-4]), count=float(system[-3]),
+               gmax=float(system[-2]), tail=float(system[-1]), group=int(info[0]), workgroups=int(info[1]), NP=int(info[2]), kernel_ms=float(info[3]))
+    if step is not None:
+        out.update(trial_points=trial, step4=step4)
+    return out
 
 
 # ---------------------------------------------------------------- host helpers (numpy; the reference's formulas)

@@ -123,6 +123,8 @@ SYMBOLS = [
                                                      _dp, _dp, _dp, _dp, _dp, _dp]),   # (views and status, int*, by address like the doubles)
     ("mcba_refine_extrinsics", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                               ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, ctypes.c_int]),   # (held and point_status, int*, by address like the doubles)
+    ("mcba_refine_extrinsics_system", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                     _dp]),   # (held and point_status, int*, by address like the doubles)
     ("mcba_profile_enable", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_stride", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_read", ctypes.c_int, [_h, _dp, _ip, ctypes.c_int, _ip]),

@@ -130,7 +130,7 @@ static int run(int C, size_t P, const double* uvs, const double* cam12, const do
 
 template <int LOSS>
 static void system_at(int C, size_t P, const double* uvs, const double* cam12, const double* dist5, const double* pts, const int* held, double f_scale, double lam, double* YY, double* acc,
-                      double* scal3) {
+                      double* scal3, int* status) {
   HostBackEnd<LOSS> be{C, P, uvs, cam12, dist5, held, f_scale};
   be.X[0].assign(pts, pts + 3 * P);
   std::vector<double> ext((size_t)6 * C);
@@ -142,6 +142,20 @@ static void system_at(int C, size_t P, const double* uvs, const double* cam12, c
   for (size_t i = 0; i < sys.YY.size(); ++i) YY[i] = sys.YY[i];
   for (size_t i = 0; i < sys.acc.size(); ++i) acc[i] = sys.acc[i];
   scal3[0] = sys.cost; scal3[1] = sys.count; scal3[2] = sys.gmax;
+  for (size_t p = 0; p < P; ++p) status[p] = be.status[p];
+}
+
+template <int LOSS>
+static void step_at(int C, size_t P, const double* uvs, const double* cam12, const double* dist5, const double* pts, double f_scale, double lam, const double* ext_trial, const double* dtheta,
+                    double* trial, double* out3) {
+  HostBackEnd<LOSS> be{C, P, uvs, cam12, dist5, nullptr, f_scale};
+  be.X[0].assign(pts, pts + 3 * P);
+  std::vector<double> ext((size_t)6 * C);
+  for (int c = 0; c < C; ++c)
+    for (int k = 0; k < 6; ++k) ext[6 * c + k] = cam12[12 * c + 6 + k];
+  be.statuses(ext.data());
+  be.step(ext_trial, dtheta, lam, out3);
+  for (size_t i = 0; i < 3 * P; ++i) trial[i] = be.X[1][i];
 }
 
 extern "C" {
@@ -161,9 +175,30 @@ int hc_kpba(int C, size_t P, const double* uvs, const double* cam12, const doubl
   }
 }
 
-// the linear-loss system at (cam12, pts) and damping lam: YY (NP, NP), acc (C, 33), scal3 = cost, present scalars, max |g_p|
-void hc_kpba_system(int C, size_t P, const double* uvs, const double* cam12, const double* dist5, const double* pts, const int* held, double lam, double* YY, double* acc, double* scal3) {
-  system_at<LOSS_LINEAR>(C, P, uvs, cam12, dist5, pts, held, 1.0, lam, YY, acc, scal3);
+// the system at (cam12, pts) and damping lam: YY (NP, NP), acc (C, 33), scal3 = cost, present scalars, max |g_p|, status (P).  1: unknown loss
+int hc_kpba_system(int C, size_t P, const double* uvs, const double* cam12, const double* dist5, const double* pts, const int* held, int loss, double f_scale, double lam, double* YY, double* acc,
+                   double* scal3, int* status) {
+  switch (loss) {
+    case LOSS_LINEAR: system_at<LOSS_LINEAR>(C, P, uvs, cam12, dist5, pts, held, f_scale, lam, YY, acc, scal3, status); return 0;
+    case LOSS_SOFT_L1: system_at<LOSS_SOFT_L1>(C, P, uvs, cam12, dist5, pts, held, f_scale, lam, YY, acc, scal3, status); return 0;
+    case LOSS_HUBER: system_at<LOSS_HUBER>(C, P, uvs, cam12, dist5, pts, held, f_scale, lam, YY, acc, scal3, status); return 0;
+    case LOSS_CAUCHY: system_at<LOSS_CAUCHY>(C, P, uvs, cam12, dist5, pts, held, f_scale, lam, YY, acc, scal3, status); return 0;
+    case LOSS_ARCTAN: system_at<LOSS_ARCTAN>(C, P, uvs, cam12, dist5, pts, held, f_scale, lam, YY, acc, scal3, status); return 0;
+    default: return 1;
+  }
+}
+
+// HostBackEnd::step once at (cam12, pts): trial (P, 3) = the points after dX (the others as they are), out3 = trial cost under ext_trial, sum dX^2, sum X^2
+int hc_kpba_step(int C, size_t P, const double* uvs, const double* cam12, const double* dist5, const double* pts, int loss, double f_scale, double lam, const double* ext_trial, const double* dtheta,
+                 double* trial, double* out3) {
+  switch (loss) {
+    case LOSS_LINEAR: step_at<LOSS_LINEAR>(C, P, uvs, cam12, dist5, pts, f_scale, lam, ext_trial, dtheta, trial, out3); return 0;
+    case LOSS_SOFT_L1: step_at<LOSS_SOFT_L1>(C, P, uvs, cam12, dist5, pts, f_scale, lam, ext_trial, dtheta, trial, out3); return 0;
+    case LOSS_HUBER: step_at<LOSS_HUBER>(C, P, uvs, cam12, dist5, pts, f_scale, lam, ext_trial, dtheta, trial, out3); return 0;
+    case LOSS_CAUCHY: step_at<LOSS_CAUCHY>(C, P, uvs, cam12, dist5, pts, f_scale, lam, ext_trial, dtheta, trial, out3); return 0;
+    case LOSS_ARCTAN: step_at<LOSS_ARCTAN>(C, P, uvs, cam12, dist5, pts, f_scale, lam, ext_trial, dtheta, trial, out3); return 0;
+    default: return 1;
+  }
 }
 
 // n x n solve through kpba_dense_solve: 1 = solved

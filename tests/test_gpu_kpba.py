@@ -36,6 +36,14 @@ def check(name, i, o, r):
     print(f"{name}: baseline {base0:.15g} -> {base:.15g}")
     assert abs(base / base0 - 1) <= 1e-12
     assert len(r.history) == r.nfev and r.history[0, 0] == r.cost0 and r.history[:, 2].sum() == r.njev
+    # the cost at the start against the oracle's at the same values, within the bound of one evaluation (kpba_oracle's docstring)
+    ref0, bound0 = ko.cost_with_bound(i["ext0"], i["pts0"], i["uvs"], i["intr"], i["loss"])
+    print(f"{name}: cost0 {r.cost0:.15g} oracle {ref0:.15g} error / bound {abs(r.cost0 - ref0) / bound0:.3g}")
+    assert abs(r.cost0 - ref0) <= bound0
+    # the stated cost is the last accepted evaluation's, and the objective at the returned values (the rescale changes no projection)
+    assert r.history[r.history[:, 2] == 1, 0].min() == r.cost and r.history[r.history[:, 2] == 1, 0][-1] == r.cost
+    X = np.where(np.isnan(r.points), i["pts0"], r.points)
+    assert abs(ko.cost_of(r.extrinsics, X, i["uvs"], i["intr"], i["loss"]) / r.cost - 1) <= 1e-10
     assert r.info["kernel_ms"] > 0 and r.info["n_step"] == r.nfev - 1
 
 

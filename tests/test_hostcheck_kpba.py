@@ -28,8 +28,8 @@ def hc(tmp_path_factory):
     subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-o", lib, SRC])
     h = ctypes.CDLL(lib)
     h.hc_kpba.argtypes = [ctypes.c_int, ctypes.c_size_t] + [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3 + [ctypes.c_double] * 4 + [ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int]
-    h.hc_kpba_system.argtypes = [ctypes.c_int, ctypes.c_size_t] + [ctypes.c_void_p] * 5 + [ctypes.c_double] + [ctypes.c_void_p] * 3
-    h.hc_kpba_system.restype = None
+    h.hc_kpba_system.argtypes = [ctypes.c_int, ctypes.c_size_t] + [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 4
+    h.hc_kpba_step.argtypes = [ctypes.c_int, ctypes.c_size_t] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 4
     h.hc_kpba_dense_solve.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 3
     return h
 
@@ -108,7 +108,7 @@ def test_schur_system_against_the_dense_jacobian(hc):
     YY, acc, scal = np.empty((NP, NP)), np.empty((C, 33)), np.empty(3)
     pts = np.ascontiguousarray(i["pts0"])
     hb = bits(o["held"])
-    hc.hc_kpba_system(C, n, P(uv), P(theta), P(d5), P(pts), P(hb), 0.0, P(YY), P(acc), P(scal))
+    assert hc.hc_kpba_system(C, n, P(uv), P(theta), P(d5), P(pts), P(hb), 0, 1.0, 0.0, P(YY), P(acc), P(scal), P(np.empty(n, np.int32))) == 0
     U = np.zeros((6 * C, 6 * C))
     tri = np.tril_indices(6)
     for c in range(C):
@@ -121,6 +121,51 @@ def test_schur_system_against_the_dense_jacobian(hc):
     free = d["free"]
     ko.check_schur("three", S[np.ix_(free, free)], rhs[free], d)
     assert abs(scal[0] / ko.cost_of(i["ext0"], i["pts0"], i["uvs"], i["intr"], "linear") - 1) <= 1e-12
+
+
+def test_block_and_dense_oracles_agree():
+    """two independent statements of the system (kpba_oracle.block_system: per-point blocks in long double; dense_system: the dense J^T J Schur
+    complement) on "three" at linear loss and lambda = 0: S to 1e-12 relative to sqrt(U_ii U_jj), the right-hand side to 1e-12 sqrt(U_ii) |f|_2"""
+    i, o = ko.case("three")
+    d = ko.dense_system(i["uvs"], i["ext0"], i["intr"], i["pts0"], o["held"])
+    b = ko.block_system(i["uvs"], i["ext0"], i["intr"], i["pts0"], o["held"], loss="linear", lam=0.0)
+    free = d["free"]
+    S, rhs = (b["U"] - b["YY"])[np.ix_(free, free)], (b["Yz"] - b["gc"])[free]
+    Ud = np.sqrt(d["Udiag"])
+    eS, er = (np.abs(S - d["S"]) / np.outer(Ud, Ud)).max(), (np.abs(rhs - d["rhs"]) / (Ud * d["fnorm"])).max()
+    print(f"block against dense: S {eS:.3g}, rhs {er:.3g} (bar 1e-12); cond {b['cond'].max():.3g} / {d['cond']:.3g}, |f| {b['fnorm']:.15g} / {d['fnorm']:.15g}")
+    assert eS <= 1e-12 and er <= 1e-12
+    assert abs(b["cond"].max() / d["cond"] - 1) <= 1e-9 and abs(b["fnorm"] / d["fnorm"] - 1) <= 1e-12 and b["maxdet"] == d["maxdet"] and b["count"] == d["n_scalars"]
+    assert abs(b["cost"] / ko.cost_of(i["ext0"], i["pts0"], i["uvs"], i["intr"], "linear") - 1) <= 1e-12
+
+
+def host_evaluation(hc, i):
+    """one evaluation of the host build at an input of kpba_oracle.system_case, in the keys of geometry.refine_extrinsics_system"""
+    theta, d5 = tco.camera_blocks(i["ext0"], i["intr"])
+    uv = np.ascontiguousarray(np.stack(i["uvs"]))
+    C, n = uv.shape[:2]
+    NP = (6 * C + 15) // 16 * 16
+    YY, acc, scal, status, trial, out3 = np.empty((NP, NP)), np.empty((C, 33)), np.empty(3), np.empty(n, np.int32), np.empty((n, 3)), np.empty(3)
+    pts, hb, loss = np.ascontiguousarray(i["pts0"]), ko.held_bits(i["held"]), LOSSES.index(i["loss"])
+    assert hc.hc_kpba_system(C, n, P(uv), P(theta), P(d5), P(pts), P(hb), loss, i["f_scale"], i["lam"], P(YY), P(acc), P(scal), P(status)) == 0
+    et, dth = (np.ascontiguousarray(a) for a in i["step"])
+    assert hc.hc_kpba_step(C, n, P(uv), P(theta), P(d5), P(pts), loss, i["f_scale"], i["lam"], P(et), P(dth), P(trial), P(out3)) == 0
+    return dict(YY=YY, acc=acc, cost=scal[0], count=scal[1], gmax=scal[2], tail=0.0, point_status=status, trial_points=trial, step4=np.r_[out3[0], out3[1], 0.0, out3[2]])
+
+
+HOST_WORST = {}
+
+
+@pytest.mark.parametrize("name", list(ko.SYSTEM_INPUTS))
+def test_one_evaluation_against_the_block_oracle(hc, name):
+    """the grid of tests/test_gpu_kpba_system.py (every input; the forced group sizes mean nothing here) on the host build: the bounds of
+    kpba_oracle hold on the reference path before any kernel is held to them"""
+    i, o = ko.system_case(name)
+    got = host_evaluation(hc, i)
+    r = ko.check_block(name, got, o)
+    r.update(ko.check_step(name, got["trial_points"], got["step4"], o, i["pts0"], i["uvs"], i["intr"], i["loss"], i["f_scale"]))
+    ko.note_worst(HOST_WORST, r)
+    print(ko.worst_line("host build so far", HOST_WORST))
 
 
 def test_dense_solve(hc):
