@@ -637,6 +637,32 @@ int mcba_refine_extrinsics(int n_cameras, size_t n_points, const double* uvs, co
 int mcba_refine_extrinsics_system(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points, const int* held, int loss, double f_scale,
                                   double lam, int device, const double* ext_trial, const double* dtheta, int* point_status, double* system, double* trial_points, double* step4, double* info4);
 
+/* ---- per-detection confidence weights (no reference counterpart; additive to ABI 7) ------------------------------------
+ * The four calls above with one more operand behind uvs: weights (C, P), w >= 0, the relative inverse variance of each detection (a pose
+ * estimator's confidence), or NULL -- then the call is the one above, launch for launch (the unweighted entry points call these with NULL).
+ * A detection of weight w enters every cost exactly as if it and fx, fy, cx, cy of its camera had been multiplied by sqrt(w): its residual
+ * pair is scaled by sqrt(w) before the loss, and so is every derivative of its projection; distortion coefficients and extrinsics are
+ * untouched.  w = 0 or NaN: the detection is unseen, exactly like a NaN detection; views, present scalars, "fewer than two views" and
+ * point_status count the detections of positive weight.  A negative or infinite weight: MCBA_ERR_ARG.  The plane goes to the device once
+ * per call, beside the detections (as sqrt(w)); the kernels are the weighted instantiations of the same templates, with the same launch
+ * shapes and summation orders: two calls on the same input return the same bits.
+ *   mcba_triangulate_refine_weighted         with points_in NULL the median of pairs is unweighted and skips the detections of weight 0 / NaN
+ *   mcba_triangulation_covariance_weighted   H, G and the pooled sigma2 = sum rho' w f^2 / (m - 3 P_u) on the weighted problem; sigma2_in is the
+ *                                            variance of a detection of weight 1
+ *   mcba_refine_extrinsics_weighted          the blind-camera rule counts the detections of positive weight
+ *   mcba_refine_extrinsics_system_weighted */
+int mcba_triangulate_refine_weighted(int n_cameras, size_t n_points, const double* uvs, const double* weights, const double* cam12, const double* dist5, const double* points_in,
+                                     int undistort_iterations, int loss, double f_scale, int max_iterations, int device, double* points_out, double* info_out, double* kernel_ms);
+int mcba_triangulation_covariance_weighted(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* weights, const double* cam12, const double* dist5,
+                                           const double* cam_cov, int loss, double f_scale, double sigma2_in, int device, double* det6, double* cal6, int* views_out, int* status_out, double* info8,
+                                           double* kernel_ms);
+int mcba_refine_extrinsics_weighted(int n_cameras, size_t n_points, const double* uvs, const double* weights, const double* cam12, const double* dist5, const double* points, int* held,
+                                    int gauge_camera, int scale_camera, int loss, double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* extrinsics_out,
+                                    double* points_out, int* point_status, double* result16, double* history, int history_rows);
+int mcba_refine_extrinsics_system_weighted(int n_cameras, size_t n_points, const double* uvs, const double* weights, const double* cam12, const double* dist5, const double* points, const int* held,
+                                           int loss, double f_scale, double lam, int device, const double* ext_trial, const double* dtheta, int* point_status, double* system, double* trial_points,
+                                           double* step4, double* info4);
+
 #ifdef __cplusplus
 }
 #endif

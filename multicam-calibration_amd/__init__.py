@@ -15,6 +15,8 @@ Only what the hot path needs lives here:
              refine_extrinsics (free-point bundle adjustment of the extrinsics on keypoint detections) -- SURVEY.md section 8f-12
   uncertainty.py  calibration_uncertainty (parameter covariance from the Schur system) -- SURVEY.md section 8f-10;
              triangulation_uncertainty (covariance of every triangulated point) -- SURVEY.md section 8f-11
+             weights= on refine_triangulation / triangulate(refine=True) / triangulation_uncertainty / refine_extrinsics (per-detection confidence
+             weights: a detection of weight w enters the cost as if it and fx, fy, cx, cy of its camera were multiplied by sqrt(w)) -- SURVEY.md section 8f-13
   synth.py   deterministic synthetic board detections for tests and bench
 """
 from . import synth  # noqa: F401

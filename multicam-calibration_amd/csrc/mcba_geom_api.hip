@@ -170,17 +170,32 @@ int mcba_keypoint_errors(int n_cameras, size_t n_points, const double* points, c
 
 int mcba_triangulate_refine(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points_in, int undistort_iterations, int loss, double f_scale,
                             int max_iterations, int device, double* points_out, double* info_out, double* kernel_ms) {
+  return mcba_triangulate_refine_weighted(n_cameras, n_points, uvs, nullptr, cam12, dist5, points_in, undistort_iterations, loss, f_scale, max_iterations, device, points_out, info_out, kernel_ms);
+}
+
+// weights NULL: the call above, launch for launch.  Otherwise the plane of sqrt(w) goes up once beside the detections; the detections of zero or
+// NaN weight go up as NaN, so that the median of pairs (which stays unweighted) does not see them either.
+int mcba_triangulate_refine_weighted(int n_cameras, size_t n_points, const double* uvs, const double* weights, const double* cam12, const double* dist5, const double* points_in,
+                                     int undistort_iterations, int loss, double f_scale, int max_iterations, int device, double* points_out, double* info_out, double* kernel_ms) {
   if (n_cameras < 2 || n_cameras > 64 || !uvs || !cam12 || !points_out || undistort_iterations < 0 || max_iterations < 0)
     return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: 2..64 cameras, non-NULL arrays, iterations >= 0 required");
   if (loss < mcba::LOSS_LINEAR || loss > mcba::LOSS_ARCTAN) return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: loss must be one of linear, soft_l1, huber, cauchy, arctan (0 .. 4)");
   if (!(f_scale > 0.0)) return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: f_scale must be positive");
+  if (int rc = check_weights("mcba_triangulate_refine_weighted", weights, (size_t)n_cameras * n_points)) return rc;
   if (n_points == 0) return MCBA_OK;
   if (int rc = stateless_device(device)) return rc;
   StatelessCall call;
-  double *d_uv = nullptr, *d_start = nullptr, *d_out = nullptr, *d_info = nullptr;
+  double *d_uv = nullptr, *d_start = nullptr, *d_out = nullptr, *d_info = nullptr, *d_sw = nullptr;
   mcba::KpCam* d_cams = nullptr;
   const size_t nuv = (size_t)2 * n_cameras * n_points;
-  if (int rc = call.upload(&d_uv, uvs, nuv)) return rc;   // the detections go up once, for the start and for the refinement
+  if (int rc = upload_sqrt_weights(call, weights, nuv / 2, &d_sw)) return rc;
+  if (weights) {
+    const double nan = __builtin_nan("");
+    std::vector<double> masked(uvs, uvs + nuv);
+    for (size_t i = 0; i < nuv / 2; ++i)
+      if (!(weights[i] > 0.0)) masked[2 * i] = masked[2 * i + 1] = nan;
+    if (int rc = call.upload(&d_uv, masked.data(), nuv)) return rc;
+  } else if (int rc = call.upload(&d_uv, uvs, nuv)) return rc;   // the detections go up once, for the start and for the refinement
   if (int rc = points_in ? call.upload(&d_start, points_in, 3 * n_points) : call.scratch(&d_start, 3 * n_points)) return rc;
   if (int rc = call.scratch(&d_out, 3 * n_points)) return rc;
   if (info_out)
@@ -194,7 +209,7 @@ int mcba_triangulate_refine(int n_cameras, size_t n_points, const double* uvs, c
     if (tri_launch(op, n_cameras, d_uv, d_start, n_points, undistort_iterations) != 0) return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: unsupported camera count");
     if (int rc = check_launch()) return rc;
   }
-  if (mcba::launch_tri_refine(nullptr, loss, d_uv, d_start, n_points, d_cams, n_cameras, f_scale, max_iterations, d_out, d_info) != 0) return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: bad launch");
+  if (mcba::launch_tri_refine(nullptr, loss, d_uv, d_start, n_points, d_cams, n_cameras, f_scale, max_iterations, d_out, d_info, d_sw) != 0) return fail(MCBA_ERR_ARG, "mcba_triangulate_refine: bad launch");
   if (int rc = check_launch()) return rc;
   HIPCHK(call.stop(kernel_ms));
   if (int rc = call.download(points_out, d_out, 3 * n_points)) return rc;

@@ -285,6 +285,26 @@ struct StatelessCall {
   }
 };
 
+// The per-detection weights of a stateless keypoint call, count = C P of them, as the kernels read them: the plane of
+// sqrt(w), 0 for a zero or NaN weight (the detection is unseen), uploaded once beside the detections.  weights NULL: *d_sw = nullptr, the
+// unweighted kernels.  check_weights (before the device is touched, with the other arguments): MCBA_ERR_ARG for a negative or infinite weight.
+inline int check_weights(const char* who, const double* weights, size_t count) {
+  if (!weights) return MCBA_OK;
+  for (size_t i = 0; i < count; ++i)
+    if (weights[i] < 0.0 || weights[i] > 1.7976931348623157e308) {
+      g_err = std::string(who) + ": weights must be finite and not negative (0 or NaN = the detection is unseen)";
+      return MCBA_ERR_ARG;
+    }
+  return MCBA_OK;
+}
+inline int upload_sqrt_weights(StatelessCall& call, const double* weights, size_t count, double** d_sw) {
+  *d_sw = nullptr;
+  if (!weights) return MCBA_OK;
+  std::vector<double> sq(count);
+  for (size_t i = 0; i < count; ++i) sq[i] = weights[i] > 0.0 ? sqrt(weights[i]) : 0.0;
+  return call.upload(d_sw, sq.data(), count);
+}
+
 inline int slot_ok(const mcba_handle* h, int slot) { return h && (slot == 0 || slot == 1); }
 
 int create_impl(mcba_handle** out, int C, int F, int N, int device, bool sparse);   // mcba_create / mcba_create_sparse (mcba_api.hip)

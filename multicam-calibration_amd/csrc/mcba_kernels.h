@@ -191,8 +191,37 @@ struct KpCam;
 int launch_project(hipStream_t st, int mode, const double* pts, size_t npts, const KpCam* cams, int C, double* out);
 // uvs (C, P, 2); err rows (C, npad) doubles, NaN where unseen and in the padding p >= npts
 int launch_keypoint_errors(hipStream_t st, const double* pts, const double* uvs, size_t npts, size_t npad, const KpCam* cams, int C, double* err);
+// How the kernels that form a residual read one point's detections: element p of the (C, P) double2 planes and -- WEIGHTED (SURVEY.md section
+// 8f-13) -- of the (C, P) plane sw of sqrt(weight), a detection counting only where sw > 0.  The observation functor of the math headers:
+// three arguments without weights, four with them (mcba_keypoint_math.h: kp_observe).
+template <bool WEIGHTED>
+struct KpDetections;
+template <>
+struct KpDetections<false> {
+  const double2* det;
+  size_t npts;
+  __device__ KpDetections(const double2* uvs, const double*, size_t npts_, size_t p) : det(uvs + p), npts(npts_) {}
+  __host__ __device__ void operator()(int c, double& ou, double& ov) const {
+    const double2 o = det[(size_t)c * npts];
+    ou = o.x; ov = o.y;
+  }
+};
+template <>
+struct KpDetections<true> {
+  const double2* det;
+  const double* sq;
+  size_t npts;
+  __device__ KpDetections(const double2* uvs, const double* sw, size_t npts_, size_t p) : det(uvs + p), sq(sw + p), npts(npts_) {}
+  __host__ __device__ void operator()(int c, double& ou, double& ov, double& s) const {
+    const double2 o = det[(size_t)c * npts];
+    ou = o.x; ov = o.y;
+    s = sq[(size_t)c * npts];
+  }
+};
+// sw, here and below: nullptr, or the (C, P) plane of sqrt(weight) in device memory (0 = the detection is unseen) -- the weighted instantiations
 // start / out (P, 3), info (P, 4) = (cost, cost at the start, iterations, status) or nullptr; loss: enum Loss, LOSS_LINEAR .. LOSS_ARCTAN
-int launch_tri_refine(hipStream_t st, int loss, const double* uvs, const double* start, size_t npts, const KpCam* cams, int C, double f_scale, int max_iterations, double* out, double* info);
+int launch_tri_refine(hipStream_t st, int loss, const double* uvs, const double* start, size_t npts, const KpCam* cams, int C, double f_scale, int max_iterations, double* out, double* info,
+                      const double* sw = nullptr);
 // consensus triangulation (mcba_consensus.hip): 2 <= C <= kKpMaxCams.  out (P, 3), mask (P) inlier words, info (P, 8) = (inliers, pair i, pair j,
 // hypothesis cost, refit cost, refit cost at the start, iterations, status) or nullptr; hyp (P, 2): scratch between the search and the refit of
 // the two-launch forms (may be nullptr for CONSENSUS_LANE).  form: CONSENSUS_AUTO picks by camera count.
@@ -216,23 +245,23 @@ int tricov_point_blocks(size_t npts);   // workgroups of k_tricov_point: part ho
 // hinv (P, 6) = H^-1 packed (NaN unless status is 1), views / status (P); then info[0 .. 4] = sigma2 (sigma2_in, or -- NaN -- pooled in a fixed
 // order), present scalars m and 3 P_u of the points of status 1, points of status -1, points of status -2
 int launch_tricov_point(hipStream_t st, int loss, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, double sigma2_in, double* hinv, int* views, int* status,
-                        double* part, double* info);
+                        double* part, double* info, const double* sw = nullptr);
 void launch_tricov_scale(hipStream_t st, const double* hinv, const int* status, const double* info, size_t npts, double* det6);   // det6 = info[0] hinv
 int tricov_group(int n, int lds_limit, int force_g);   // points per workgroup of k_tricov_cal (16, 10 or 5; 0: no shape fits)
 // det6 = sigma2 H^-1 and cal6 = G Sig G^T (both (P, 6) packed), Sig the zero-padded ld x ld camera covariance (ld a multiple of 64, >= 12 C rounded up to 32)
 int launch_tricov_cal(hipStream_t st, int loss, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status, const double* Sig,
-                      int ld, const double* info, double* det6, double* cal6, int G);
+                      int ld, const double* info, double* det6, double* cal6, int G, const double* sw = nullptr);
 
 // ---- free-point bundle adjustment of the extrinsics (mcba_kpba.hip).  uvs (C, P, 2) raw detections (NaN = unseen), pts
 // (P, 3), cams: TcCam table in device memory, 2 <= C <= 24, held (C): bit i = scalar i of the camera is not free.  Non-zero: arguments out of range.
 int kpba_group(int C, int lds_limit, int force_g);   // points per group of k_kpba_reduce (64, 32 or 16; 0: no shape fits)
 int kpba_groups(size_t npts);                        // workgroups of a pass: that many partial systems
 size_t kpba_partial_size(int C);                     // doubles of one (partial) system: NP NP + 33 C + 4, NP = 6 C rounded up to 16
-int launch_kpba_status(hipStream_t st, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, int* status);
+int launch_kpba_status(hipStream_t st, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, int* status, const double* sw = nullptr);
 // sys = Y Y^T (NP, NP) | per camera U_c packed lower, g_c, sum Y z (C, 33) | cost, present scalars, max |g_p|, 0; part: kpba_groups() partial systems
 int launch_kpba_reduce(hipStream_t st, int loss, const double* uvs, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale, double lam, int G,
-                       double* part, double* sys);
+                       double* part, double* sys, const double* sw = nullptr);
 // cams2: the current table and behind it the trial one; trial (P, 3) the trial points; out4 = trial cost, sum dX^2, 0, sum X^2; part4: 4 kpba_groups()
 int launch_kpba_step(hipStream_t st, int loss, const double* uvs, const double* pts, double* trial, const int* status, size_t npts, const TcCam* cams2, const double* dtheta, int C, double f_scale,
-                     double lam, double* part4, double* out4);
+                     double lam, double* part4, double* out4, const double* sw = nullptr);
 }  // namespace mcba

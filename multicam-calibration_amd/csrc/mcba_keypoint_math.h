@@ -80,8 +80,42 @@ MCBA_HD double keypoint_error(const KpCam& kc, const double X[3], double ou, dou
   return sqrt(fma(du, du, dv * dv));
 }
 
+// ---- per-detection confidence weights.  A detection of weight w enters every cost as if it and fx, fy, cx, cy of its
+// camera had been multiplied by sqrt(w): its residual and every derivative of its projection are scaled by sw = sqrt(w) before the loss sees
+// them.  The rows of the Jacobians are not touched for that: the factor goes into what multiplies them -- the curvature weight of a scalar
+// times w (two rows meet in every product), rho' f times sw once more (one row).  An observation functor of four arguments,
+// observation(c, ou, ov, sw), hands out sw beside the detection; one of three arguments is the unweighted problem, and what is compiled for
+// it has no trace of sw.  A detection is seen when neither coordinate is NaN and, weighted, sw > 0 (a zero or NaN weight: unseen, exactly
+// like a NaN detection).
+template <class Obs>
+MCBA_HD auto kp_observe(Obs& observation, int c, double& ou, double& ov, double& sw, int) -> decltype(observation(c, ou, ov, sw), bool()) {
+  observation(c, ou, ov, sw);
+  return ou == ou && ov == ov && sw > 0.0;
+}
+template <class Obs>
+MCBA_HD bool kp_observe(Obs& observation, int c, double& ou, double& ov, double& sw, long) {
+  observation(c, ou, ov);
+  sw = 1.0;
+  return ou == ou && ov == ov;
+}
+template <class Obs>
+struct KpWeighted {   // value: the functor takes the fourth argument.  (MCBA_HD throughout: a device-only functor is callable from these alone)
+  template <class T>
+  MCBA_HD static T& ref();
+  template <class O>
+  MCBA_HD static auto test(int) -> decltype(ref<O>()(0, ref<double>(), ref<double>(), ref<double>()), char());
+  template <class O>
+  MCBA_HD static long test(long);
+  static constexpr bool value = sizeof(test<Obs>(0)) == sizeof(char);
+};
+// WEIGHTED: the pair of a detection's two scalars (residuals, weights, gradient factors) times s
+template <bool WEIGHTED>
+MCBA_HD void kp_scale_pair(double s, double& a, double& b) {
+  if (WEIGHTED) { a *= s; b *= s; }
+}
+
 // ---- refinement of one point: minimise 0.5 sum rho(f^2) over X, f = the 2 (cameras that see it) scalars detection - projection (pixels), rho and
-// f_scale scipy's (loss_weights).  observation(c, ou, ov) hands out the point's detection in camera c.
+// f_scale scipy's (loss_weights).  observation(c, ou, ov) hands out the point's detection in camera c (with a fourth argument: and sqrt(w)).
 // One linearisation at X: packed Gauss-Newton matrix H (00 01 02 11 12 22) with the curvature weights of the bundle-adjustment tick
 // (lm_weight: Triggs' weight floored at MCBA_CURV_FLOOR_TRIGGS rho'), gradient g of the cost, the robust cost.  Returns the number of views.
 template <int LOSS, class Obs>
@@ -92,19 +126,21 @@ MCBA_HD int keypoint_linearise(const KpCam* cams, int C, Obs& observation, const
   cost = 0.0;
   int views = 0;
   for (int c = 0; c < C; ++c) {
-    double ou, ov;
-    observation(c, ou, ov);
-    if (ou == ou && ov == ov) {
+    double ou, ov, sw;
+    if (kp_observe(observation, c, ou, ov, sw, 0)) {
       ++views;
       double u, v, Ju[3], Jv[3];
       project5<true>(cams[c], X, u, v, Ju, Jv);
-      const double fu = ou - u, fv = ov - v;
+      double fu = ou - u, fv = ov - v;
+      kp_scale_pair<KpWeighted<Obs>::value>(sw, fu, fv);
       double rhu, gwu, w2u, rhv, gwv, w2v;
       loss_weights<LOSS>(fu, fs2, inv_fs2, rhu, gwu, w2u);
       loss_weights<LOSS>(fv, fs2, inv_fs2, rhv, gwv, w2v);
       cost += rhu + rhv;
-      const double wu = lm_weight(gwu, w2u, MCBA_CURV_FLOOR_TRIGGS), wv = lm_weight(gwv, w2v, MCBA_CURV_FLOOR_TRIGGS);
-      const double gu = gwu * fu, gv = gwv * fv;   // (df/dX = -J)
+      double wu = lm_weight(gwu, w2u, MCBA_CURV_FLOOR_TRIGGS), wv = lm_weight(gwv, w2v, MCBA_CURV_FLOOR_TRIGGS);
+      double gu = gwu * fu, gv = gwv * fv;   // (df/dX = -J)
+      kp_scale_pair<KpWeighted<Obs>::value>(sw * sw, wu, wv);
+      kp_scale_pair<KpWeighted<Obs>::value>(sw, gu, gv);
       int k = 0;
 #pragma unroll
       for (int i = 0; i < 3; ++i) {

@@ -13,6 +13,9 @@
 #include "mcba_kernels.h"
 #include "mcba_keypoint_math.h"
 
+// (in both compilation passes: the weighted functor is taken for weighted, the plain one for unweighted)
+static_assert(mcba::KpWeighted<mcba::KpDetections<true>>::value && !mcba::KpWeighted<mcba::KpDetections<false>>::value, "the observation functors select the weighted arithmetic");
+
 namespace mcba {
 
 __device__ __forceinline__ void stage_cams(KpCam* s_cam, const KpCam* __restrict__ cams, int C) {
@@ -64,19 +67,16 @@ __global__ __launch_bounds__(256) void k_keypoint_errors(const double* __restric
 
 // one lane = one point, any C <= kKpMaxCams: the loop over the cameras is a run-time loop over the LDS table, the detections are read again at
 // every linearisation (coalesced double2 loads) instead of being kept in per-camera register arrays.  info (P, 4) or nullptr.
-template <int LOSS>
+// WEIGHTED: sw, the (C, P) plane of sqrt(weight), is read beside each detection (one more coalesced 8-byte load); otherwise it is never touched.
+template <int LOSS, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_tri_refine(const double2* __restrict__ uvs, const double* __restrict__ start, size_t npts, const KpCam* __restrict__ cams, int C, double f_scale,
-                                                    int max_iterations, double* __restrict__ out, double* __restrict__ info) {
+                                                    int max_iterations, double* __restrict__ out, double* __restrict__ info, const double* __restrict__ sw) {
   __shared__ KpCam s_cam[kKpMaxCams];
   stage_cams(s_cam, cams, C);
   const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= npts) return;
   const double X0[3] = {start[3 * p], start[3 * p + 1], start[3 * p + 2]};
-  const double2* det = uvs + p;
-  auto observation = [&](int c, double& ou, double& ov) {
-    const double2 o = det[(size_t)c * npts];
-    ou = o.x; ov = o.y;
-  };
+  KpDetections<WEIGHTED> observation(uvs, sw, npts, p);
   double X[3], inf4[4];
   refine_point<LOSS>(s_cam, C, observation, X0, f_scale, max_iterations, X, inf4);
   out[3 * p] = X[0]; out[3 * p + 1] = X[1]; out[3 * p + 2] = X[2];
@@ -104,19 +104,27 @@ int launch_keypoint_errors(hipStream_t st, const double* pts, const double* uvs,
   return 0;
 }
 
-int launch_tri_refine(hipStream_t st, int loss, const double* uvs, const double* start, size_t npts, const KpCam* cams, int C, double f_scale, int max_iterations, double* out, double* info) {
-  if (C < 2 || C > kKpMaxCams) return 1;
+template <bool WEIGHTED>
+static int tri_refine_go(hipStream_t st, int loss, const double* uvs, const double* start, size_t npts, const KpCam* cams, int C, double f_scale, int max_iterations, double* out, double* info,
+                         const double* sw) {
   const dim3 g((unsigned)((npts + 255) / 256)), b(256);
   const double2* uv = reinterpret_cast<const double2*>(uvs);
   switch (loss) {   // one kernel per loss: loss_weights takes it as a template argument
-    case LOSS_LINEAR: k_tri_refine<LOSS_LINEAR><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info); break;
-    case LOSS_SOFT_L1: k_tri_refine<LOSS_SOFT_L1><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info); break;
-    case LOSS_HUBER: k_tri_refine<LOSS_HUBER><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info); break;
-    case LOSS_CAUCHY: k_tri_refine<LOSS_CAUCHY><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info); break;
-    case LOSS_ARCTAN: k_tri_refine<LOSS_ARCTAN><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info); break;
+    case LOSS_LINEAR: k_tri_refine<LOSS_LINEAR, WEIGHTED><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info, sw); break;
+    case LOSS_SOFT_L1: k_tri_refine<LOSS_SOFT_L1, WEIGHTED><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info, sw); break;
+    case LOSS_HUBER: k_tri_refine<LOSS_HUBER, WEIGHTED><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info, sw); break;
+    case LOSS_CAUCHY: k_tri_refine<LOSS_CAUCHY, WEIGHTED><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info, sw); break;
+    case LOSS_ARCTAN: k_tri_refine<LOSS_ARCTAN, WEIGHTED><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info, sw); break;
     default: return 1;
   }
   return 0;
+}
+
+int launch_tri_refine(hipStream_t st, int loss, const double* uvs, const double* start, size_t npts, const KpCam* cams, int C, double f_scale, int max_iterations, double* out, double* info,
+                      const double* sw) {
+  if (C < 2 || C > kKpMaxCams) return 1;
+  return sw ? tri_refine_go<true>(st, loss, uvs, start, npts, cams, C, f_scale, max_iterations, out, info, sw)
+            : tri_refine_go<false>(st, loss, uvs, start, npts, cams, C, f_scale, max_iterations, out, info, nullptr);
 }
 
 }  // namespace mcba

@@ -17,6 +17,9 @@
 #include "mcba_kernels.h"
 #include "mcba_kpba_math.h"
 
+// (in both compilation passes: the weighted functor is taken for weighted, the plain one for unweighted)
+static_assert(mcba::KpWeighted<mcba::KpDetections<true>>::value && !mcba::KpWeighted<mcba::KpDetections<false>>::value, "the observation functors select the weighted arithmetic");
+
 namespace mcba {
 
 typedef double kpba_d4 __attribute__((ext_vector_type(4)));
@@ -41,7 +44,10 @@ __device__ __forceinline__ void kpba_tree(double (*s)[256], const double* r, con
 }
 
 // ---------------------------------------------------------------- k_kpba_status
-__global__ __launch_bounds__(256) void k_kpba_status(const double2* __restrict__ uvs, const double* __restrict__ pts, size_t npts, const TcCam* __restrict__ cams, int C, int* __restrict__ status) {
+// WEIGHTED (here and in the kernels below): sw, the (C, P) plane of sqrt(weight), is read beside each detection, which counts where sw > 0.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void k_kpba_status(const double2* __restrict__ uvs, const double* __restrict__ pts, size_t npts, const TcCam* __restrict__ cams, int C, int* __restrict__ status,
+                                                     const double* __restrict__ sw) {
   __shared__ TcCam s_cam[kKbMaxCams];
   {
     const double* src = reinterpret_cast<const double*>(cams);
@@ -52,11 +58,7 @@ __global__ __launch_bounds__(256) void k_kpba_status(const double2* __restrict__
   const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= npts) return;
   const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
-  const double2* det = uvs + p;
-  auto observation = [&](int c, double& ou, double& ov) {
-    const double2 o = det[(size_t)c * npts];
-    ou = o.x; ov = o.y;
-  };
+  KpDetections<WEIGHTED> observation(uvs, sw, npts, p);
   KbPoint pt;
   kpba_point<LOSS_LINEAR>(s_cam, C, observation, X, 1.0, 1.0, nullptr, pt);   // (the weights are positive for every loss: a zero diagonal is one for all)
   status[p] = kpba_status(pt.views, X, pt.H);
@@ -86,9 +88,9 @@ int kpba_group(int C, int lds_limit, int force_g) {
   return 0;
 }
 
-template <int LOSS, int TQ>
+template <int LOSS, int TQ, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_kpba_reduce(const double2* __restrict__ uvs, const double* __restrict__ pts, const int* __restrict__ status, size_t npts, const TcCam* __restrict__ cams,
-                                                     const int* __restrict__ held, int C, double f_scale, double lam, int G, double* __restrict__ part) {
+                                                     const int* __restrict__ held, int C, double f_scale, double lam, int G, double* __restrict__ part, const double* __restrict__ sw) {
   extern __shared__ __align__(16) double lds[];
   __shared__ TcCam s_cam[kKbMaxCams];
   __shared__ int s_held[kKbMaxCams];
@@ -127,11 +129,7 @@ __global__ __launch_bounds__(256) void k_kpba_reduce(const double2* __restrict__
       bool usable = false;
       if (p < npts && status[p] == KB_USED) {
         const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
-        const double2* det = uvs + p;
-        auto observation = [&](int c, double& ou, double& ov) {
-          const double2 o = det[(size_t)c * npts];
-          ou = o.x; ov = o.y;
-        };
+        KpDetections<WEIGHTED> observation(uvs, sw, npts, p);
         KbPoint pt;
         kpba_point<LOSS>(s_cam, C, observation, X, fs2, inv_fs2, nullptr, pt);
         r[0] += pt.cost;
@@ -160,14 +158,15 @@ __global__ __launch_bounds__(256) void k_kpba_reduce(const double2* __restrict__
         if (sp[12] != 0.0) {   // (a point past P is not usable)
           const size_t p = p0 + pl;
           const double2 o = uvs[(size_t)c * npts + p];
-          if (o.x == o.x && o.y == o.y) {
+          const double sq = WEIGHTED ? sw[(size_t)c * npts + p] : 1.0;
+          if (o.x == o.x && o.y == o.y && sq > 0.0) {
             const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
             KbFactor f;
 #pragma unroll
             for (int i = 0; i < 6; ++i) f.L[i] = sp[i];
 #pragma unroll
             for (int i = 0; i < 3; ++i) f.d[i] = sp[6 + i];
-            kpba_item<LOSS>(s_cam[c], X, o.x, o.y, fs2, inv_fs2, f, sp + 9, s_held[c], Y, a);
+            kpba_item_w<LOSS, WEIGHTED>(s_cam[c], X, o.x, o.y, sq, fs2, inv_fs2, f, sp + 9, s_held[c], Y, a);
           }
         }
 #pragma unroll
@@ -242,43 +241,51 @@ __global__ __launch_bounds__(256) void k_kpba_finish(const double* __restrict__ 
   out[i] = s;
 }
 
-template <int LOSS, int TQ>
+template <int LOSS, int TQ, bool WEIGHTED>
 static int kpba_reduce_go(hipStream_t st, size_t lds, int nwg, const double2* uv, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale,
-                          double lam, int G, double* part) {
-  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kpba_reduce<LOSS, TQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
-  hipLaunchKernelGGL((k_kpba_reduce<LOSS, TQ>), dim3((unsigned)nwg), dim3(256), lds, st, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part);
+                          double lam, int G, double* part, const double* sw) {
+  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kpba_reduce<LOSS, TQ, WEIGHTED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
+  hipLaunchKernelGGL((k_kpba_reduce<LOSS, TQ, WEIGHTED>), dim3((unsigned)nwg), dim3(256), lds, st, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
   return 0;
 }
 
-template <int LOSS>
+template <int LOSS, bool WEIGHTED>
 static int kpba_reduce_shape(hipStream_t st, size_t lds, int nwg, const double2* uv, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale,
-                             double lam, int G, double* part) {
+                             double lam, int G, double* part, const double* sw) {
   const int NT = (6 * C + 15) / 16, ntiles = NT * (NT + 1) / 2;   // tiles per wavefront: 3 up to 10 tiles (10 cameras), 12 up to 45
-  if (ntiles <= 12) return kpba_reduce_go<LOSS, 3>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part);
-  return kpba_reduce_go<LOSS, 12>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part);
+  if (ntiles <= 12) return kpba_reduce_go<LOSS, 3, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
+  return kpba_reduce_go<LOSS, 12, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
 }
 
-int launch_kpba_status(hipStream_t st, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, int* status) {
+int launch_kpba_status(hipStream_t st, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, int* status, const double* sw) {
   if (C < 2 || C > kKbMaxCams || npts == 0 || npts > ((size_t)1 << 38)) return 1;
-  k_kpba_status<<<dim3((unsigned)((npts + 255) / 256)), dim3(256), 0, st>>>(reinterpret_cast<const double2*>(uvs), pts, npts, cams, C, status);
+  const dim3 g((unsigned)((npts + 255) / 256)), b(256);
+  if (sw) k_kpba_status<true><<<g, b, 0, st>>>(reinterpret_cast<const double2*>(uvs), pts, npts, cams, C, status, sw);
+  else k_kpba_status<false><<<g, b, 0, st>>>(reinterpret_cast<const double2*>(uvs), pts, npts, cams, C, status, nullptr);
   return 0;
+}
+
+template <bool WEIGHTED>
+static int kpba_reduce_loss(hipStream_t st, int loss, size_t lds, int nwg, const double2* uv, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C,
+                            double f_scale, double lam, int G, double* part, const double* sw) {
+  switch (loss) {   // one kernel per loss: loss_weights takes it as a template argument
+    case LOSS_LINEAR: return kpba_reduce_shape<LOSS_LINEAR, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
+    case LOSS_SOFT_L1: return kpba_reduce_shape<LOSS_SOFT_L1, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
+    case LOSS_HUBER: return kpba_reduce_shape<LOSS_HUBER, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
+    case LOSS_CAUCHY: return kpba_reduce_shape<LOSS_CAUCHY, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
+    case LOSS_ARCTAN: return kpba_reduce_shape<LOSS_ARCTAN, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
+    default: return 1;
+  }
 }
 
 int launch_kpba_reduce(hipStream_t st, int loss, const double* uvs, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale, double lam, int G,
-                       double* part, double* sys) {
+                       double* part, double* sys, const double* sw) {
   if (C < 2 || C > kKbMaxCams || (G != 16 && G != 32 && G != 64) || npts == 0 || npts > ((size_t)1 << 38)) return 1;
   const size_t lds = kpba_reduce_lds(C, G);
   const int nwg = kpba_groups(npts), NP = (6 * C + 15) / 16 * 16;
   const double2* uv = reinterpret_cast<const double2*>(uvs);
-  int rc;
-  switch (loss) {   // one kernel per loss: loss_weights takes it as a template argument
-    case LOSS_LINEAR: rc = kpba_reduce_shape<LOSS_LINEAR>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part); break;
-    case LOSS_SOFT_L1: rc = kpba_reduce_shape<LOSS_SOFT_L1>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part); break;
-    case LOSS_HUBER: rc = kpba_reduce_shape<LOSS_HUBER>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part); break;
-    case LOSS_CAUCHY: rc = kpba_reduce_shape<LOSS_CAUCHY>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part); break;
-    case LOSS_ARCTAN: rc = kpba_reduce_shape<LOSS_ARCTAN>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part); break;
-    default: return 1;
-  }
+  const int rc = sw ? kpba_reduce_loss<true>(st, loss, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw)
+                    : kpba_reduce_loss<false>(st, loss, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, nullptr);
   if (rc) return rc;
   const size_t PS = kpba_partial_size(C);
   k_kpba_finish<<<dim3((unsigned)((PS + 255) / 256)), dim3(256), 0, st>>>(part, nwg, NP, C, sys);
@@ -287,9 +294,10 @@ int launch_kpba_reduce(hipStream_t st, int loss, const double* uvs, const double
 
 // ---------------------------------------------------------------- k_kpba_step
 // cams: the current table and, behind it, the trial table (2 C entries).  part4 per workgroup: trial cost, sum dX^2, 0, sum X^2.
-template <int LOSS>
+template <int LOSS, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_kpba_step(const double2* __restrict__ uvs, const double* __restrict__ pts, double* __restrict__ trial, const int* __restrict__ status, size_t npts,
-                                                   const TcCam* __restrict__ cams, const double* __restrict__ dtheta, int C, double f_scale, double lam, double* __restrict__ part4) {
+                                                   const TcCam* __restrict__ cams, const double* __restrict__ dtheta, int C, double f_scale, double lam, double* __restrict__ part4,
+                                                   const double* __restrict__ sw) {
   __shared__ TcCam s_cam[2 * kKbMaxCams];
   __shared__ double s_dth[6 * kKbMaxCams];
   __shared__ double s_r[3][256];
@@ -310,11 +318,7 @@ __global__ __launch_bounds__(256) void k_kpba_step(const double2* __restrict__ u
     const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
     double Xt[3] = {X[0], X[1], X[2]};
     if (status[p] == KB_USED) {
-      const double2* det = uvs + p;
-      auto observation = [&](int c, double& ou, double& ov) {
-        const double2 o = det[(size_t)c * npts];
-        ou = o.x; ov = o.y;
-      };
+      KpDetections<WEIGHTED> observation(uvs, sw, npts, p);
       KbPoint pt;
       kpba_point<LOSS>(s_cam, C, observation, X, fs2, inv_fs2, s_dth, pt);
       KbFactor f;
@@ -338,20 +342,29 @@ __global__ __launch_bounds__(256) void k_kpba_step(const double2* __restrict__ u
   if (t < 4) part4[4 * (size_t)blockIdx.x + t] = t == 0 ? s_r[0][0] : (t == 1 ? s_r[1][0] : (t == 3 ? s_r[2][0] : 0.0));
 }
 
-int launch_kpba_step(hipStream_t st, int loss, const double* uvs, const double* pts, double* trial, const int* status, size_t npts, const TcCam* cams2, const double* dtheta, int C, double f_scale,
-                     double lam, double* part4, double* out4) {
-  if (C < 2 || C > kKbMaxCams || npts == 0 || npts > ((size_t)1 << 38)) return 1;
-  const int nwg = kpba_groups(npts);
+template <bool WEIGHTED>
+static int kpba_step_go(hipStream_t st, int nwg, int loss, const double2* uv, const double* pts, double* trial, const int* status, size_t npts, const TcCam* cams2, const double* dtheta, int C,
+                        double f_scale, double lam, double* part4, const double* sw) {
   const dim3 g((unsigned)nwg), b(256);
-  const double2* uv = reinterpret_cast<const double2*>(uvs);
   switch (loss) {
-    case LOSS_LINEAR: k_kpba_step<LOSS_LINEAR><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4); break;
-    case LOSS_SOFT_L1: k_kpba_step<LOSS_SOFT_L1><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4); break;
-    case LOSS_HUBER: k_kpba_step<LOSS_HUBER><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4); break;
-    case LOSS_CAUCHY: k_kpba_step<LOSS_CAUCHY><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4); break;
-    case LOSS_ARCTAN: k_kpba_step<LOSS_ARCTAN><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4); break;
+    case LOSS_LINEAR: k_kpba_step<LOSS_LINEAR, WEIGHTED><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw); break;
+    case LOSS_SOFT_L1: k_kpba_step<LOSS_SOFT_L1, WEIGHTED><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw); break;
+    case LOSS_HUBER: k_kpba_step<LOSS_HUBER, WEIGHTED><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw); break;
+    case LOSS_CAUCHY: k_kpba_step<LOSS_CAUCHY, WEIGHTED><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw); break;
+    case LOSS_ARCTAN: k_kpba_step<LOSS_ARCTAN, WEIGHTED><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw); break;
     default: return 1;
   }
+  return 0;
+}
+
+int launch_kpba_step(hipStream_t st, int loss, const double* uvs, const double* pts, double* trial, const int* status, size_t npts, const TcCam* cams2, const double* dtheta, int C, double f_scale,
+                     double lam, double* part4, double* out4, const double* sw) {
+  if (C < 2 || C > kKbMaxCams || npts == 0 || npts > ((size_t)1 << 38)) return 1;
+  const int nwg = kpba_groups(npts);
+  const double2* uv = reinterpret_cast<const double2*>(uvs);
+  if (sw ? kpba_step_go<true>(st, nwg, loss, uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw)
+         : kpba_step_go<false>(st, nwg, loss, uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, nullptr))
+    return 1;
   k_kpba_finish<<<dim3(1), dim3(256), 0, st>>>(part4, nwg, 0, 0, out4);
   return 0;
 }

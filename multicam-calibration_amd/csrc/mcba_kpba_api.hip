@@ -20,6 +20,7 @@ struct DeviceBackEnd {
   const double* cam12;
   const double* dist5;
   double* d_uv = nullptr;
+  double* d_sw = nullptr;   // the plane of sqrt(weight), or nullptr: the unweighted kernels
   double* d_pts[2] = {nullptr, nullptr};
   int* d_status = nullptr;
   int* d_held = nullptr;
@@ -56,7 +57,7 @@ struct DeviceBackEnd {
     table(ext, tab.data());
     if (int rc = call.put(d_cams, tab.data(), (size_t)C)) return rc;
     HIPCHK(hipEventRecord(call.e0, nullptr));
-    if (mcba::launch_kpba_reduce(nullptr, loss, d_uv, d_pts[cur], d_status, P, d_cams, d_held, C, f_scale, lam, G, d_part, d_sys) != 0)
+    if (mcba::launch_kpba_reduce(nullptr, loss, d_uv, d_pts[cur], d_status, P, d_cams, d_held, C, f_scale, lam, G, d_part, d_sys, d_sw) != 0)
       return launch_failed("k_kpba_reduce could not be launched");
     if (int rc = timed(&reduce_ms)) return rc;
     ++n_reduce;
@@ -75,7 +76,7 @@ struct DeviceBackEnd {
     if (int rc = call.put(d_cams + C, tab.data() + C, (size_t)C)) return rc;
     if (int rc = call.put(d_dth, dtheta, (size_t)6 * C)) return rc;
     HIPCHK(hipEventRecord(call.e0, nullptr));
-    if (mcba::launch_kpba_step(nullptr, loss, d_uv, d_pts[cur], d_pts[1 - cur], d_status, P, d_cams, d_dth, C, f_scale, lam, d_part4, d_out4) != 0)
+    if (mcba::launch_kpba_step(nullptr, loss, d_uv, d_pts[cur], d_pts[1 - cur], d_status, P, d_cams, d_dth, C, f_scale, lam, d_part4, d_out4, d_sw) != 0)
       return launch_failed("k_kpba_step could not be launched");
     if (int rc = timed(&step_ms)) return rc;
     ++n_step;
@@ -84,13 +85,14 @@ struct DeviceBackEnd {
     return MCBA_OK;
   }
   void accept() { cur = 1 - cur; }
-  // the detections, both point buffers and the camera tables (at ext) up, the scratch of a pass, then k_kpba_status: point_status (P) on the host
-  int setup(const double* uvs, const double* points, const double* ext, int* point_status) {
+  // the detections, their weights (or NULL), both point buffers and the camera tables (at ext) up, the scratch of a pass, then k_kpba_status: point_status (P) on the host
+  int setup(const double* uvs, const double* weights, const double* points, const double* ext, int* point_status) {
     tab.resize((size_t)2 * C);
     table(ext, tab.data());
     table(ext, tab.data() + C);
     const int nwg = mcba::kpba_groups(P);
     if (int rc = call.upload(&d_uv, uvs, (size_t)2 * C * P)) return rc;
+    if (int rc = upload_sqrt_weights(call, weights, (size_t)C * P, &d_sw)) return rc;
     if (int rc = call.upload(&d_pts[0], points, 3 * P)) return rc;
     if (int rc = call.upload(&d_pts[1], points, 3 * P)) return rc;
     if (int rc = call.upload(&d_cams, tab.data(), tab.size())) return rc;
@@ -102,7 +104,7 @@ struct DeviceBackEnd {
     if (int rc = call.scratch(&d_part4, (size_t)4 * nwg)) return rc;
     if (int rc = call.scratch(&d_out4, (size_t)4)) return rc;
     HIPCHK(call.start());
-    if (mcba::launch_kpba_status(nullptr, d_uv, d_pts[0], P, d_cams, C, d_status) != 0) {
+    if (mcba::launch_kpba_status(nullptr, d_uv, d_pts[0], P, d_cams, C, d_status, d_sw) != 0) {
       g_err = std::string(who) + ": bad launch (k_kpba_status)";
       return MCBA_ERR_ARG;
     }
@@ -142,7 +144,15 @@ extern "C" {
 int mcba_refine_extrinsics(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points, int* held, int gauge_camera, int scale_camera, int loss,
                            double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* extrinsics_out, double* points_out, int* point_status, double* result16,
                            double* history, int history_rows) {
-  const char* who = "mcba_refine_extrinsics";
+  return mcba_refine_extrinsics_weighted(n_cameras, n_points, uvs, nullptr, cam12, dist5, points, held, gauge_camera, scale_camera, loss, f_scale, ftol, xtol, gtol, max_nfev, device, extrinsics_out,
+                                         points_out, point_status, result16, history, history_rows);
+}
+
+// weights NULL: the call above, launch for launch.  Otherwise the plane of sqrt(w) goes up once beside the detections and the weighted kernels run.
+int mcba_refine_extrinsics_weighted(int n_cameras, size_t n_points, const double* uvs, const double* weights, const double* cam12, const double* dist5, const double* points, int* held,
+                                    int gauge_camera, int scale_camera, int loss, double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* extrinsics_out,
+                                    double* points_out, int* point_status, double* result16, double* history, int history_rows) {
+  const char* who = weights ? "mcba_refine_extrinsics_weighted" : "mcba_refine_extrinsics";
   if (int rc = kpba_refuse(who, n_cameras, n_points, loss, f_scale)) return rc;
   if (!uvs || !cam12 || !points || !held || !extrinsics_out || !points_out || !point_status || !result16 || (history_rows > 0 && !history))
     return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: non-NULL arrays required");
@@ -150,6 +160,7 @@ int mcba_refine_extrinsics(int n_cameras, size_t n_points, const double* uvs, co
     return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: gauge_camera and scale_camera must be two different cameras of the rig");
   if (max_nfev < 2) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: max_nfev must be at least 2 (the start and one trial)");
   if (!(ftol >= 0.0 && xtol >= 0.0 && gtol >= 0.0)) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: ftol, xtol, gtol must not be negative");
+  if (int rc = check_weights(who, weights, (size_t)n_cameras * n_points)) return rc;
   for (int i = 0; i < 16; ++i) result16[i] = 0.0;
   if (int rc = stateless_device(device)) return rc;
   const int C = n_cameras;
@@ -162,11 +173,12 @@ int mcba_refine_extrinsics(int n_cameras, size_t n_points, const double* uvs, co
   std::vector<double> ext((size_t)6 * C);
   for (int c = 0; c < C; ++c)
     for (int k = 0; k < 6; ++k) ext[6 * c + k] = cam12[12 * c + 6 + k];
-  if (int rc = be.setup(uvs, points, ext.data(), point_status)) return rc;
-  for (int c = 0; c < C; ++c) {   // a camera that no used point sees is held whole
+  if (int rc = be.setup(uvs, weights, points, ext.data(), point_status)) return rc;
+  for (int c = 0; c < C; ++c) {   // a camera that no used point sees (with a positive weight) is held whole
     bool seen = false;
     const double* u = uvs + (size_t)2 * c * P;
-    for (size_t p = 0; p < P && !seen; ++p) seen = point_status[p] == mcba::KB_USED && u[2 * p] == u[2 * p] && u[2 * p + 1] == u[2 * p + 1];
+    const double* w = weights ? weights + (size_t)c * P : nullptr;
+    for (size_t p = 0; p < P && !seen; ++p) seen = point_status[p] == mcba::KB_USED && u[2 * p] == u[2 * p] && u[2 * p + 1] == u[2 * p + 1] && (!w || w[p] > 0.0);
     if (!seen) held[c] = 63;
   }
   if (held[scale_camera] == 63) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: scale_camera sees no used point (or is held whole): nothing fixes the scale of the rig");
@@ -192,12 +204,20 @@ int mcba_refine_extrinsics(int n_cameras, size_t n_points, const double* uvs, co
 
 int mcba_refine_extrinsics_system(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points, const int* held, int loss, double f_scale,
                                   double lam, int device, const double* ext_trial, const double* dtheta, int* point_status, double* system, double* trial_points, double* step4, double* info4) {
-  const char* who = "mcba_refine_extrinsics_system";
+  return mcba_refine_extrinsics_system_weighted(n_cameras, n_points, uvs, nullptr, cam12, dist5, points, held, loss, f_scale, lam, device, ext_trial, dtheta, point_status, system, trial_points, step4,
+                                                info4);
+}
+
+int mcba_refine_extrinsics_system_weighted(int n_cameras, size_t n_points, const double* uvs, const double* weights, const double* cam12, const double* dist5, const double* points, const int* held,
+                                           int loss, double f_scale, double lam, int device, const double* ext_trial, const double* dtheta, int* point_status, double* system, double* trial_points,
+                                           double* step4, double* info4) {
+  const char* who = weights ? "mcba_refine_extrinsics_system_weighted" : "mcba_refine_extrinsics_system";
   if (int rc = kpba_refuse(who, n_cameras, n_points, loss, f_scale)) return rc;
   const bool stepping = ext_trial || dtheta;
   if (!uvs || !cam12 || !points || !held || !point_status || !system || !info4 || (stepping && (!ext_trial || !dtheta || !trial_points || !step4)))
     return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics_system: non-NULL arrays required (ext_trial and dtheta both or neither; with them trial_points and step4)");
   if (!(lam >= 0.0 && lam < mcba::KB_LAMBDA_MAX)) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics_system: lam must be in [0, 1e12)");
+  if (int rc = check_weights(who, weights, (size_t)n_cameras * n_points)) return rc;
   if (int rc = stateless_device(device)) return rc;
   const int C = n_cameras;
   const size_t P = n_points;
@@ -209,7 +229,7 @@ int mcba_refine_extrinsics_system(int n_cameras, size_t n_points, const double* 
   std::vector<double> ext((size_t)6 * C);
   for (int c = 0; c < C; ++c)
     for (int k = 0; k < 6; ++k) ext[6 * c + k] = cam12[12 * c + 6 + k];
-  if (int rc = be.setup(uvs, points, ext.data(), point_status)) return rc;
+  if (int rc = be.setup(uvs, weights, points, ext.data(), point_status)) return rc;
   if (int rc = call.put(be.d_held, held, (size_t)C)) return rc;   // (as given: no gauge, no scale, no blind-camera rule here)
   mcba::KbSystem sys;
   if (int rc = be.reduce(ext.data(), lam, sys)) return rc;

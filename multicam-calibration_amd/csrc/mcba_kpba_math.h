@@ -22,7 +22,8 @@ constexpr int kKbMaxCams = 24;                                             // 6 
 constexpr int kKbAcc = 33;                                                 // per camera: U_c packed lower (21) | g_c (6) | sum_p Y_cp z_p (6)
 constexpr double KB_LAMBDA0 = 1e-4, KB_LAMBDA_MIN = 1e-12, KB_LAMBDA_MAX = 1e12;
 
-// ---- one point at X: packed H (00 01 02 11 12 22), gradient g, robust cost, views; with dtheta (6 per camera, or NULL) also q = sum_c W_cp^T dtheta_c
+// ---- one point at X: packed H (00 01 02 11 12 22), gradient g, robust cost, views; with dtheta (6 per camera, or NULL) also q = sum_c W_cp^T dtheta_c.
+// An observation functor of four arguments also hands out sqrt(w) of the detection (mcba_keypoint_math.h): f, A and B as if times it, unseen unless it is > 0.
 struct KbPoint {
   double H[6], g[3], q[3], cost;
   int views;
@@ -37,20 +38,22 @@ MCBA_HD void kpba_point(const TcCam* cams, int C, Obs& observation, const double
   pt.cost = 0.0;
   pt.views = 0;
   for (int c = 0; c < C; ++c) {
-    double ou, ov;
-    observation(c, ou, ov);
-    if (!(ou == ou && ov == ov)) continue;
+    double ou, ov, sw;
+    if (!kp_observe(observation, c, ou, ov, sw, 0)) continue;
     ++pt.views;
     double u, v, Ju[3], Jv[3], Bu[12], Bv[12];
     if (dtheta) tricov_cam_rows(cams[c], X, u, v, Ju, Jv, Bu, Bv);
     else project5<true>(cams[c].kc, X, u, v, Ju, Jv);
-    const double fu = ou - u, fv = ov - v;
+    double fu = ou - u, fv = ov - v;
+    kp_scale_pair<KpWeighted<Obs>::value>(sw, fu, fv);
     double rhu, gwu, w2u, rhv, gwv, w2v;
     loss_weights<LOSS>(fu, fs2, inv_fs2, rhu, gwu, w2u);
     loss_weights<LOSS>(fv, fs2, inv_fs2, rhv, gwv, w2v);
     pt.cost += rhu + rhv;
-    const double wu = lm_weight(gwu, w2u, MCBA_CURV_FLOOR_TRIGGS), wv = lm_weight(gwv, w2v, MCBA_CURV_FLOOR_TRIGGS);
-    const double gu = gwu * fu, gv = gwv * fv;   // (df/dX = -A)
+    double wu = lm_weight(gwu, w2u, MCBA_CURV_FLOOR_TRIGGS), wv = lm_weight(gwv, w2v, MCBA_CURV_FLOOR_TRIGGS);
+    double gu = gwu * fu, gv = gwv * fv;   // (df/dX = -A)
+    kp_scale_pair<KpWeighted<Obs>::value>(sw * sw, wu, wv);
+    kp_scale_pair<KpWeighted<Obs>::value>(sw, gu, gv);
     double bu = 0.0, bv = 0.0;                    // B_c dtheta_c, per scalar
     if (dtheta) {
 #pragma unroll
@@ -112,16 +115,20 @@ MCBA_HD void kpba_point_step(const KbFactor& f, const double* g, const double* q
 
 // ---- one (camera, point) item, the camera seeing the point: the rows Y_cp (6 x 3, row-major; a row whose bit in `held` is set is zero) and the
 // camera's sums acc[kKbAcc] = U_c packed lower (i, j <= i) | g_c | Y_cp z_p
-template <int LOSS>
-MCBA_HD void kpba_item(const TcCam& tc, const double X[3], double ou, double ov, double fs2, double inv_fs2, const KbFactor& f, const double* zp, int held, double* Y, double* acc) {
+// WEIGHTED: the detection has the weight sw^2 > 0 (the residual times sw; the curvature weights times sw^2, rho' f once more times sw)
+template <int LOSS, bool WEIGHTED>
+MCBA_HD void kpba_item_w(const TcCam& tc, const double X[3], double ou, double ov, double sw, double fs2, double inv_fs2, const KbFactor& f, const double* zp, int held, double* Y, double* acc) {
   double u, v, Ju[3], Jv[3], Bu[12], Bv[12];
   tricov_cam_rows(tc, X, u, v, Ju, Jv, Bu, Bv);
-  const double fu = ou - u, fv = ov - v;
+  double fu = ou - u, fv = ov - v;
+  kp_scale_pair<WEIGHTED>(sw, fu, fv);
   double rh, gwu, w2u, gwv, w2v;
   loss_weights<LOSS>(fu, fs2, inv_fs2, rh, gwu, w2u);
   loss_weights<LOSS>(fv, fs2, inv_fs2, rh, gwv, w2v);
-  const double wu = lm_weight(gwu, w2u, MCBA_CURV_FLOOR_TRIGGS), wv = lm_weight(gwv, w2v, MCBA_CURV_FLOOR_TRIGGS);
-  const double gu = gwu * fu, gv = gwv * fv;
+  double wu = lm_weight(gwu, w2u, MCBA_CURV_FLOOR_TRIGGS), wv = lm_weight(gwv, w2v, MCBA_CURV_FLOOR_TRIGGS);
+  double gu = gwu * fu, gv = gwv * fv;
+  kp_scale_pair<WEIGHTED>(sw * sw, wu, wv);
+  kp_scale_pair<WEIGHTED>(sw, gu, gv);
   int k = 0;
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
@@ -137,6 +144,14 @@ MCBA_HD void kpba_item(const TcCam& tc, const double X[3], double ou, double ov,
     for (int j = 0; j < 3; ++j) Y[3 * i + j] = off ? 0.0 : y[j];
     acc[27 + i] = off ? 0.0 : fma(y[0], zp[0], fma(y[1], zp[1], y[2] * zp[2]));
   }
+}
+template <int LOSS>
+MCBA_HD void kpba_item(const TcCam& tc, const double X[3], double ou, double ov, double fs2, double inv_fs2, const KbFactor& f, const double* zp, int held, double* Y, double* acc) {
+  kpba_item_w<LOSS, false>(tc, X, ou, ov, 1.0, fs2, inv_fs2, f, zp, held, Y, acc);
+}
+template <int LOSS>
+MCBA_HD void kpba_item(const TcCam& tc, const double X[3], double ou, double ov, double sw, double fs2, double inv_fs2, const KbFactor& f, const double* zp, int held, double* Y, double* acc) {
+  kpba_item_w<LOSS, true>(tc, X, ou, ov, sw, fs2, inv_fs2, f, zp, held, Y, acc);
 }
 
 // ================================================================ host side

@@ -11,15 +11,20 @@
 #include "mcba_kernels.h"
 #include "mcba_tricov_math.h"
 
+// (in both compilation passes: the weighted functor is taken for weighted, the plain one for unweighted)
+static_assert(mcba::KpWeighted<mcba::KpDetections<true>>::value && !mcba::KpWeighted<mcba::KpDetections<false>>::value, "the observation functors select the weighted arithmetic");
+
 namespace mcba {
 
 typedef double tricov_d4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------- k_tricov_point
 // The camera table is staged in LDS as k_tri_refine stages it (the KpCam part of every entry).  No lane leaves before the workgroup's sums.
-template <int LOSS>
+// WEIGHTED: sw, the (C, P) plane of sqrt(weight), is read beside each detection; views and the present scalars count the detections with sw > 0.
+template <int LOSS, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_tricov_point(const double2* __restrict__ uvs, const double* __restrict__ pts, size_t npts, const TcCam* __restrict__ cams, int C, double f_scale,
-                                                      double* __restrict__ hinv, int* __restrict__ views, int* __restrict__ status, double* __restrict__ part) {
+                                                      double* __restrict__ hinv, int* __restrict__ views, int* __restrict__ status, double* __restrict__ part,
+                                                      const double* __restrict__ sw) {
   __shared__ KpCam s_cam[kKpMaxCams];
   __shared__ double s_r[4][256];
   {
@@ -32,11 +37,7 @@ __global__ __launch_bounds__(256) void k_tricov_point(const double2* __restrict_
   double r[4] = {0.0, 0.0, 0.0, 0.0};
   if (p < npts) {
     const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
-    const double2* det = uvs + p;
-    auto observation = [&](int c, double& ou, double& ov) {
-      const double2 o = det[(size_t)c * npts];
-      ou = o.x; ov = o.y;
-    };
+    KpDetections<WEIGHTED> observation(uvs, sw, npts, p);
     double Hi[6], wss;
     int nv;
     const int st = tricov_point<LOSS>(s_cam, C, observation, X, f_scale, Hi, nv, wss);
@@ -90,20 +91,29 @@ __global__ __launch_bounds__(256) void k_tricov_final(const double* __restrict__
 
 int tricov_point_blocks(size_t npts) { return (int)((npts + 255) / 256); }
 
-int launch_tricov_point(hipStream_t st, int loss, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, double sigma2_in, double* hinv, int* views, int* status,
-                        double* part, double* info) {
-  if (C < 2 || C > kKpMaxCams || npts == 0 || npts > ((size_t)1 << 38)) return 1;
-  const int nb = tricov_point_blocks(npts);
+template <bool WEIGHTED>
+static int tricov_point_go(hipStream_t st, int nb, int loss, const double2* uv, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, double* hinv, int* views, int* status,
+                           double* part, const double* sw) {
   const dim3 g((unsigned)nb), b(256);
-  const double2* uv = reinterpret_cast<const double2*>(uvs);
   switch (loss) {
-    case LOSS_LINEAR: k_tricov_point<LOSS_LINEAR><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part); break;
-    case LOSS_SOFT_L1: k_tricov_point<LOSS_SOFT_L1><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part); break;
-    case LOSS_HUBER: k_tricov_point<LOSS_HUBER><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part); break;
-    case LOSS_CAUCHY: k_tricov_point<LOSS_CAUCHY><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part); break;
-    case LOSS_ARCTAN: k_tricov_point<LOSS_ARCTAN><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part); break;
+    case LOSS_LINEAR: k_tricov_point<LOSS_LINEAR, WEIGHTED><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part, sw); break;
+    case LOSS_SOFT_L1: k_tricov_point<LOSS_SOFT_L1, WEIGHTED><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part, sw); break;
+    case LOSS_HUBER: k_tricov_point<LOSS_HUBER, WEIGHTED><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part, sw); break;
+    case LOSS_CAUCHY: k_tricov_point<LOSS_CAUCHY, WEIGHTED><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part, sw); break;
+    case LOSS_ARCTAN: k_tricov_point<LOSS_ARCTAN, WEIGHTED><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part, sw); break;
     default: return 1;
   }
+  return 0;
+}
+
+int launch_tricov_point(hipStream_t st, int loss, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, double sigma2_in, double* hinv, int* views, int* status,
+                        double* part, double* info, const double* sw) {
+  if (C < 2 || C > kKpMaxCams || npts == 0 || npts > ((size_t)1 << 38)) return 1;
+  const int nb = tricov_point_blocks(npts);
+  const double2* uv = reinterpret_cast<const double2*>(uvs);
+  if (sw ? tricov_point_go<true>(st, nb, loss, uv, pts, npts, cams, C, f_scale, hinv, views, status, part, sw)
+         : tricov_point_go<false>(st, nb, loss, uv, pts, npts, cams, C, f_scale, hinv, views, status, part, nullptr))
+    return 1;
   k_tricov_final<<<dim3(1), dim3(256), 0, st>>>(part, nb, npts, sigma2_in, info);
   return 0;
 }
@@ -137,10 +147,13 @@ static size_t tricov_cal_lds(int n, int G) {
   return ((size_t)R * (KP + 2) + stage + (size_t)G * 6 * 3) * sizeof(double);
 }
 
-template <int LOSS, int RT>
-__global__ __launch_bounds__(256) void k_tricov_cal(const double2* __restrict__ uvs, const double* __restrict__ pts, size_t npts, const TcCam* __restrict__ cams, int C, double f_scale,
+// WEIGHTED: item (camera, point) also reads element (c, p) of sw, the plane of sqrt(weight), and is zero unless it is > 0.  The operand costs
+// four registers; the linear loss with three row tiles sits at 128 without it, the last count with four wavefronts per SIMD, so that one
+// instantiation asks for them (the second launch bound) and gets 108 without scratch; every other one stays in the class of its unweighted twin.
+template <int LOSS, int RT, bool WEIGHTED>
+__global__ __launch_bounds__(256, (WEIGHTED && LOSS == LOSS_LINEAR && RT == 3) ? 4 : 1) void k_tricov_cal(const double2* __restrict__ uvs, const double* __restrict__ pts, size_t npts, const TcCam* __restrict__ cams, int C, double f_scale,
                                                     const double* __restrict__ hinv, const int* __restrict__ status, const double* __restrict__ Sig, int ld, const double* __restrict__ info,
-                                                    double* __restrict__ det6, double* __restrict__ cal6, int G, int KP) {
+                                                    double* __restrict__ det6, double* __restrict__ cal6, int G, int KP, const double* __restrict__ sw) {
   extern __shared__ __align__(16) double lds[];
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -173,9 +186,10 @@ __global__ __launch_bounds__(256) void k_tricov_cal(const double2* __restrict__ 
     if (g < ng && status[p0 + g] == TC_OK) {
       const size_t p = p0 + g;
       const double2 o = uvs[(size_t)c * npts + p];
-      if (o.x == o.x && o.y == o.y) {
+      const double s = WEIGHTED ? sw[(size_t)c * npts + p] : 1.0;
+      if (o.x == o.x && o.y == o.y && s > 0.0) {
         const double X[3] = {pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]};
-        tricov_g_block<LOSS>(cams[c], X, o.x, o.y, s_Hi + 6 * g, fs2, inv_fs2, gr);
+        tricov_g_block_w<LOSS, WEIGHTED>(cams[c], X, o.x, o.y, s, s_Hi + 6 * g, fs2, inv_fs2, gr);
       }
     }
 #pragma unroll
@@ -266,36 +280,43 @@ int tricov_group(int n, int lds_limit, int force_g) {
   return 0;
 }
 
-template <int LOSS, int RT>
+template <int LOSS, int RT, bool WEIGHTED>
 static int tricov_cal_go(hipStream_t st, size_t lds, const double2* uv, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status,
-                         const double* Sig, int ld, const double* info, double* det6, double* cal6, int G, int KP) {
-  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tricov_cal<LOSS, RT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
-  hipLaunchKernelGGL((k_tricov_cal<LOSS, RT>), dim3((unsigned)((npts + G - 1) / G)), dim3(256), lds, st, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
+                         const double* Sig, int ld, const double* info, double* det6, double* cal6, int G, int KP, const double* sw) {
+  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tricov_cal<LOSS, RT, WEIGHTED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
+  hipLaunchKernelGGL((k_tricov_cal<LOSS, RT, WEIGHTED>), dim3((unsigned)((npts + G - 1) / G)), dim3(256), lds, st, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
   return 0;
 }
 
-template <int LOSS>
+template <int LOSS, bool WEIGHTED>
 static int tricov_cal_shape(hipStream_t st, size_t lds, const double2* uv, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status,
-                            const double* Sig, int ld, const double* info, double* det6, double* cal6, int G, int KP) {
-  if (G == 16) return tricov_cal_go<LOSS, 3>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
-  if (G == 10) return tricov_cal_go<LOSS, 2>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
-  return tricov_cal_go<LOSS, 1>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
+                            const double* Sig, int ld, const double* info, double* det6, double* cal6, int G, int KP, const double* sw) {
+  if (G == 16) return tricov_cal_go<LOSS, 3, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
+  if (G == 10) return tricov_cal_go<LOSS, 2, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
+  return tricov_cal_go<LOSS, 1, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
+}
+
+template <bool WEIGHTED>
+static int tricov_cal_loss(hipStream_t st, int loss, size_t lds, const double2* uv, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status,
+                           const double* Sig, int ld, const double* info, double* det6, double* cal6, int G, int KP, const double* sw) {
+  switch (loss) {   // one kernel per loss: loss_weights takes it as a template argument
+    case LOSS_LINEAR: return tricov_cal_shape<LOSS_LINEAR, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
+    case LOSS_SOFT_L1: return tricov_cal_shape<LOSS_SOFT_L1, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
+    case LOSS_HUBER: return tricov_cal_shape<LOSS_HUBER, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
+    case LOSS_CAUCHY: return tricov_cal_shape<LOSS_CAUCHY, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
+    case LOSS_ARCTAN: return tricov_cal_shape<LOSS_ARCTAN, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
+    default: return 1;
+  }
 }
 
 int launch_tricov_cal(hipStream_t st, int loss, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status, const double* Sig,
-                      int ld, const double* info, double* det6, double* cal6, int G) {
+                      int ld, const double* info, double* det6, double* cal6, int G, const double* sw) {
   const int n = 12 * C, KP = (n + 31) / 32 * 32;
   if (C < 2 || C > kKpMaxCams || (G != 5 && G != 10 && G != 16) || KP > ld || ld % 64 != 0 || npts == 0 || (npts + G - 1) / G > 0x7fffffffu) return 1;
   const size_t lds = tricov_cal_lds(n, G);
   const double2* uv = reinterpret_cast<const double2*>(uvs);
-  switch (loss) {   // one kernel per loss: loss_weights takes it as a template argument
-    case LOSS_LINEAR: return tricov_cal_shape<LOSS_LINEAR>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
-    case LOSS_SOFT_L1: return tricov_cal_shape<LOSS_SOFT_L1>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
-    case LOSS_HUBER: return tricov_cal_shape<LOSS_HUBER>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
-    case LOSS_CAUCHY: return tricov_cal_shape<LOSS_CAUCHY>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
-    case LOSS_ARCTAN: return tricov_cal_shape<LOSS_ARCTAN>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP);
-    default: return 1;
-  }
+  return sw ? tricov_cal_loss<true>(st, loss, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw)
+            : tricov_cal_loss<false>(st, loss, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, nullptr);
 }
 
 }  // namespace mcba

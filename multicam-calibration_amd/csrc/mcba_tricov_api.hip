@@ -9,12 +9,20 @@ extern "C" {
 
 int mcba_triangulation_covariance(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, const double* cam_cov, int loss, double f_scale,
                                   double sigma2_in, int device, double* det6, double* cal6, int* views_out, int* status_out, double* info8, double* kernel_ms) {
+  return mcba_triangulation_covariance_weighted(n_cameras, n_points, points, uvs, nullptr, cam12, dist5, cam_cov, loss, f_scale, sigma2_in, device, det6, cal6, views_out, status_out, info8, kernel_ms);
+}
+
+// weights NULL: the call above, launch for launch.  Otherwise the plane of sqrt(w) goes up once beside the detections and the weighted kernels run.
+int mcba_triangulation_covariance_weighted(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* weights, const double* cam12, const double* dist5,
+                                           const double* cam_cov, int loss, double f_scale, double sigma2_in, int device, double* det6, double* cal6, int* views_out, int* status_out, double* info8,
+                                           double* kernel_ms) {
   if (n_cameras < 2 || n_cameras > 64 || !points || !uvs || !cam12 || !det6 || !views_out || !status_out || !info8)
     return fail(MCBA_ERR_ARG, "mcba_triangulation_covariance: 2..64 cameras, non-NULL arrays required");
   if ((cam_cov != nullptr) != (cal6 != nullptr)) return fail(MCBA_ERR_ARG, "mcba_triangulation_covariance: cal6 is required exactly when cam_cov is given");
   if (loss < mcba::LOSS_LINEAR || loss > mcba::LOSS_ARCTAN) return fail(MCBA_ERR_ARG, "mcba_triangulation_covariance: loss must be one of linear, soft_l1, huber, cauchy, arctan (0 .. 4)");
   if (!(f_scale > 0.0)) return fail(MCBA_ERR_ARG, "mcba_triangulation_covariance: f_scale must be positive");
   if (!(sigma2_in != sigma2_in) && !(sigma2_in >= 0.0)) return fail(MCBA_ERR_ARG, "mcba_triangulation_covariance: sigma2 >= 0, or NaN to estimate it");
+  if (int rc = check_weights("mcba_triangulation_covariance_weighted", weights, (size_t)n_cameras * n_points)) return rc;
   for (int i = 0; i < 8; ++i) info8[i] = 0.0;
   info8[0] = sigma2_in;
   if (kernel_ms) *kernel_ms = 0.0;
@@ -33,12 +41,13 @@ int mcba_triangulation_covariance(int n_cameras, size_t n_points, const double* 
   }
 
   StatelessCall call;
-  double *d_uv = nullptr, *d_pts = nullptr, *d_hinv = nullptr, *d_det = nullptr, *d_cal = nullptr, *d_part = nullptr, *d_info = nullptr, *d_sig = nullptr;
+  double *d_uv = nullptr, *d_pts = nullptr, *d_hinv = nullptr, *d_det = nullptr, *d_cal = nullptr, *d_part = nullptr, *d_info = nullptr, *d_sig = nullptr, *d_sw = nullptr;
   int *d_views = nullptr, *d_status = nullptr;
   mcba::TcCam* d_cams = nullptr;
   std::vector<mcba::TcCam> tab((size_t)n_cameras);
   for (int c = 0; c < n_cameras; ++c) mcba::make_tc_cam(cam12 + 12 * c, dist5 ? dist5 + 5 * c : nullptr, tab[c]);
   if (int rc = call.upload(&d_uv, uvs, (size_t)2 * n_cameras * n_points)) return rc;
+  if (int rc = upload_sqrt_weights(call, weights, (size_t)n_cameras * n_points, &d_sw)) return rc;
   if (int rc = call.upload(&d_pts, points, 3 * n_points)) return rc;
   if (int rc = call.upload(&d_cams, tab.data(), tab.size())) return rc;
   if (int rc = call.scratch(&d_hinv, 6 * n_points)) return rc;
@@ -54,11 +63,11 @@ int mcba_triangulation_covariance(int n_cameras, size_t n_points, const double* 
     if (int rc = call.scratch(&d_cal, 6 * n_points)) return rc;
   }
   HIPCHK(call.start());
-  if (mcba::launch_tricov_point(nullptr, loss, d_uv, d_pts, n_points, d_cams, n_cameras, f_scale, sigma2_in, d_hinv, d_views, d_status, d_part, d_info) != 0)
+  if (mcba::launch_tricov_point(nullptr, loss, d_uv, d_pts, n_points, d_cams, n_cameras, f_scale, sigma2_in, d_hinv, d_views, d_status, d_part, d_info, d_sw) != 0)
     return fail(MCBA_ERR_ARG, "mcba_triangulation_covariance: bad launch");
   if (int rc = check_launch()) return rc;
   if (cam_cov) {
-    if (mcba::launch_tricov_cal(nullptr, loss, d_uv, d_pts, n_points, d_cams, n_cameras, f_scale, d_hinv, d_status, d_sig, ld, d_info, d_det, d_cal, G) != 0)
+    if (mcba::launch_tricov_cal(nullptr, loss, d_uv, d_pts, n_points, d_cams, n_cameras, f_scale, d_hinv, d_status, d_sig, ld, d_info, d_det, d_cal, G, d_sw) != 0)
       return fail(MCBA_ERR_ARG, "mcba_triangulation_covariance: bad launch (k_tricov_cal)");
   } else {
     mcba::launch_tricov_scale(nullptr, d_hinv, d_status, d_info, n_points, d_det);

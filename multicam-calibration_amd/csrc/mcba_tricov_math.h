@@ -30,7 +30,8 @@ MCBA_HD void make_tc_cam(const double* cam12, const double* dist5, TcCam& tc) {
 }
 
 // ---- the rho'-weighted linearisation at X: packed H (00 01 02 11 12 22) and wss = sum w f^2 over the cameras that see the point.  Returns the
-// number of views (the point's present scalars are twice that).  observation(c, ou, ov) hands out the point's detection in camera c.
+// number of views (the point's present scalars are twice that).  observation(c, ou, ov) hands out the point's detection in camera c; with a
+// fourth argument also sw = sqrt(w) of the detection (mcba_keypoint_math.h: the residual times sw, rho' times w, unseen unless sw > 0).
 template <int LOSS, class Obs>
 MCBA_HD int tricov_linearise(const KpCam* cams, int C, Obs& observation, const double X[3], double fs2, double inv_fs2, double* H, double& wss) {
 #pragma unroll
@@ -38,17 +39,18 @@ MCBA_HD int tricov_linearise(const KpCam* cams, int C, Obs& observation, const d
   wss = 0.0;
   int views = 0;
   for (int c = 0; c < C; ++c) {
-    double ou, ov;
-    observation(c, ou, ov);
-    if (ou == ou && ov == ov) {
+    double ou, ov, sw;
+    if (kp_observe(observation, c, ou, ov, sw, 0)) {
       ++views;
       double u, v, Ju[3], Jv[3];
       project5<true>(cams[c], X, u, v, Ju, Jv);
-      const double fu = ou - u, fv = ov - v;
+      double fu = ou - u, fv = ov - v;
+      kp_scale_pair<KpWeighted<Obs>::value>(sw, fu, fv);
       double rh, wu, wv, w2;
       loss_weights<LOSS>(fu, fs2, inv_fs2, rh, wu, w2);
       loss_weights<LOSS>(fv, fs2, inv_fs2, rh, wv, w2);
       wss += fma(wu, fu * fu, wv * (fv * fv));
+      kp_scale_pair<KpWeighted<Obs>::value>(sw * sw, wu, wv);
       int k = 0;
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
@@ -139,15 +141,27 @@ MCBA_HD void tricov_g_rows(const double* Hi, const double* Ju, const double* Jv,
   }
 }
 
-// G_c of the point X for the detection (ou, ov) of camera tc, present
-template <int LOSS>
-MCBA_HD void tricov_g_block(const TcCam& tc, const double X[3], double ou, double ov, const double* Hi, double fs2, double inv_fs2, double* g) {
+// G_c of the point X for the detection (ou, ov) of camera tc, present; WEIGHTED: of weight sw^2 > 0 (the residual times sw, rho' times sw^2
+// for A_c and B_c)
+template <int LOSS, bool WEIGHTED>
+MCBA_HD void tricov_g_block_w(const TcCam& tc, const double X[3], double ou, double ov, double sw, const double* Hi, double fs2, double inv_fs2, double* g) {
   double u, v, Ju[3], Jv[3], Bu[12], Bv[12];
   tricov_cam_rows(tc, X, u, v, Ju, Jv, Bu, Bv);
+  double fu = ou - u, fv = ov - v;
+  kp_scale_pair<WEIGHTED>(sw, fu, fv);
   double rh, wu, wv, w2;
-  loss_weights<LOSS>(ou - u, fs2, inv_fs2, rh, wu, w2);
-  loss_weights<LOSS>(ov - v, fs2, inv_fs2, rh, wv, w2);
+  loss_weights<LOSS>(fu, fs2, inv_fs2, rh, wu, w2);
+  loss_weights<LOSS>(fv, fs2, inv_fs2, rh, wv, w2);
+  kp_scale_pair<WEIGHTED>(sw * sw, wu, wv);
   tricov_g_rows(Hi, Ju, Jv, wu, wv, Bu, Bv, g);
+}
+template <int LOSS>
+MCBA_HD void tricov_g_block(const TcCam& tc, const double X[3], double ou, double ov, const double* Hi, double fs2, double inv_fs2, double* g) {
+  tricov_g_block_w<LOSS, false>(tc, X, ou, ov, 1.0, Hi, fs2, inv_fs2, g);
+}
+template <int LOSS>
+MCBA_HD void tricov_g_block(const TcCam& tc, const double X[3], double ou, double ov, double sw, const double* Hi, double fs2, double inv_fs2, double* g) {
+  tricov_g_block_w<LOSS, true>(tc, X, ou, ov, sw, Hi, fs2, inv_fs2, g);
 }
 
 // ---- the packed output blocks (00 01 02 11 12 22).  entry e -> (k, l), k <= l

@@ -25,7 +25,7 @@ import numpy as np
 
 from . import ops
 from .calibration import rodrigues, rodrigues_inv, get_transformation_matrix, get_transformation_vector  # noqa: F401
-from .triangulation import _cam_blocks, _stack_uvs, DEFAULT_MAX_ITERATIONS
+from .triangulation import _cam_blocks, _stack_uvs, _weight_plane, DEFAULT_MAX_ITERATIONS
 
 STATUS = {1: "converged", 0: "iteration limit", -1: "too few views"}
 
@@ -107,7 +107,7 @@ def keypoint_reprojection_errors(points, all_uvs, all_extrinsics, all_intrinsics
     return err, med
 
 
-def refine_triangulation(points, all_uvs, all_extrinsics, all_intrinsics, *, loss="soft_l1", f_scale=1.0, max_iterations=DEFAULT_MAX_ITERATIONS, device=0, return_info=False):
+def refine_triangulation(points, all_uvs, all_extrinsics, all_intrinsics, *, loss="soft_l1", f_scale=1.0, max_iterations=DEFAULT_MAX_ITERATIONS, device=0, return_info=False, weights=None):
     """Per point, minimise 0.5 sum rho(f^2) over X from the start `points` (P, 3): f = the 2 (cameras that see the point) residuals
     detection - projection in pixels, rho and f_scale exactly scipy.optimize.least_squares' (loss one of linear, soft_l1, huber, cauchy,
     arctan).  Points seen by fewer than two cameras, or whose start has a NaN, come back NaN.  A point is never made worse: a step is taken
@@ -116,6 +116,12 @@ def refine_triangulation(points, all_uvs, all_extrinsics, all_intrinsics, *, los
     Levenberg-Marquardt per point (Marquardt damping from 1e-4, a tenth on an accepted step, tenfold on a rejected one); it stops when the
     step is below 1e-12 (1 + |X|), when an accepted step gains less than 1e-15 of the cost, when the gradient is below 1e-12, or after
     max_iterations (default 100) linearisations -- a point that is done costs nothing further, the others go on.
+
+    weights: None, or (C, P) per-detection weights w >= 0, the relative inverse variance of each detection (a pose estimator's
+    confidence).  A detection of weight w enters the cost exactly as if it and fx, fy, cx, cy of its camera had been multiplied by sqrt(w):
+    its residual pair is scaled by sqrt(w) before the loss.  w = 0 or NaN: the detection is unseen, like a NaN detection (the views count
+    detections of positive weight).  ValueError: another shape, a negative or infinite weight.  The same keyword, with the same meaning,
+    on `triangulate(refine=True)`, `triangulation_uncertainty`, `refine_extrinsics` and `refine_extrinsics_system`.
 
     return_info=True: (points, info) with per-point arrays info["cost"] (robust cost at the result), info["cost0"] (at the start),
     info["n_iterations"], info["status"] (1 converged, 0 iteration limit, -1 too few views: `geometry.STATUS`)."""
@@ -129,9 +135,13 @@ def refine_triangulation(points, all_uvs, all_extrinsics, all_intrinsics, *, los
     C, P = uvs.shape[:2]
     if not 2 <= C <= 64:
         raise NotImplementedError("refine_triangulation() supports 2 to 64 cameras")
+    w = _weight_plane(weights, C, P)
     out = np.empty((P, 3))
     info = np.empty((P, 4))
-    if P:
+    if P and w is not None:
+        ops.call("mcba_triangulate_refine_weighted", C, P, uvs.ctypes.data, w.ctypes.data, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, 0, ops.LOSSES[loss], float(f_scale),
+                 int(max_iterations), int(device), out.ctypes.data, info.ctypes.data, None)
+    elif P:
         ops.call("mcba_triangulate_refine", C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, 0, ops.LOSSES[loss], float(f_scale), int(max_iterations), int(device),
                  out.ctypes.data, info.ctypes.data, None)
     if not return_info:
@@ -221,7 +231,7 @@ def _camera_centres(ext):
 
 
 def refine_extrinsics(all_uvs, all_extrinsics, all_intrinsics, *, points=None, inliers=None, gauge_camera=0, scale_camera=None, loss="soft_l1", f_scale=1.0, ftol=1e-8, xtol=1e-8, gtol=1e-8,
-                      max_nfev=100, verbose=0, device=0):
+                      max_nfev=100, verbose=0, device=0, weights=None):
     """Move drifted cameras back with the detections that show the drift: free-point bundle adjustment.  Minimises
     0.5 f_scale^2 sum rho((f / f_scale)^2) over the present scalars f = detection - projection, jointly over the extrinsics of the cameras and
     every 3-D point; the intrinsics stay fixed.  all_uvs, all_extrinsics, all_intrinsics as `triangulate` takes them (raw detections, NaN =
@@ -231,7 +241,10 @@ def refine_extrinsics(all_uvs, all_extrinsics, all_intrinsics, *, points=None, i
         print(res.message, res.cost0, "->", res.cost);  ext = res.extrinsics
 
     points: (P, 3) start; None = triangulate(all_uvs, all_extrinsics, all_intrinsics).  inliers: None, or the (C, P) mask of
-    triangulate_consensus: a camera that is False for a point is treated as not seeing it.
+    triangulate_consensus: a camera that is False for a point is treated as not seeing it.  weights: None, or (C, P) per-detection weights
+    as `refine_triangulation` takes them: the reduction, the cost, the trial cost and the point steps are those of the weighted problem; a
+    detection of weight 0 or NaN is unseen (for points=None, point_status and the camera no used point sees alike); with inliers the mask
+    zeroes weights.
     Gauge: with fixed intrinsics the cost does not change under a rigid motion or a global scale.  All six extrinsics of `gauge_camera` are held.
     The scale is fixed by holding one scalar of `scale_camera` (default: the camera whose centre is farthest from the gauge camera's at the
     start): the component of its translation along which d = -R_j (c_j - c_0) is largest in magnitude -- scaling the rig about c_0 moves t_j
@@ -281,8 +294,10 @@ def refine_extrinsics(all_uvs, all_extrinsics, all_intrinsics, *, points=None, i
         if mask.shape != (C, P) or mask.dtype != np.bool_:
             raise ValueError(f"inliers must be the ({C}, {P}) bool mask of triangulate_consensus")
         uvs = np.where(mask[:, :, None], uvs, np.nan)   # (a copy: the one that is uploaded)
+    w = _weight_plane(weights, C, P)
     if points is None:
-        pts = np.ascontiguousarray(triangulate(list(uvs), all_extrinsics, all_intrinsics, device=device))
+        start_uvs = uvs if w is None else np.where((w > 0)[:, :, None], uvs, np.nan)
+        pts = np.ascontiguousarray(triangulate(list(start_uvs), all_extrinsics, all_intrinsics, device=device))
     else:
         pts = np.ascontiguousarray(points, dtype=np.float64)
         if pts.shape != (P, 3):
@@ -294,8 +309,12 @@ def refine_extrinsics(all_uvs, all_extrinsics, all_intrinsics, *, points=None, i
     held_bits[scale_camera] |= 1 << (3 + int(np.argmax(np.abs(d))))
     ext, out, status, res = np.empty((C, 6)), np.empty((P, 3)), np.empty(P, np.int32), np.zeros(16)
     hist = np.zeros((int(max_nfev) + 1, 3))
-    ops.call("mcba_refine_extrinsics", C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, held_bits.ctypes.data, gauge_camera, scale_camera, ops.LOSSES[loss],
-             float(f_scale), float(ftol), float(xtol), float(gtol), int(max_nfev), int(device), ext.ctypes.data, out.ctypes.data, status.ctypes.data, res.ctypes.data, hist.ctypes.data, len(hist))
+    tail = (held_bits.ctypes.data, gauge_camera, scale_camera, ops.LOSSES[loss], float(f_scale), float(ftol), float(xtol), float(gtol), int(max_nfev), int(device), ext.ctypes.data, out.ctypes.data,
+            status.ctypes.data, res.ctypes.data, hist.ctypes.data, len(hist))
+    if w is None:
+        ops.call("mcba_refine_extrinsics", C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, *tail)
+    else:
+        ops.call("mcba_refine_extrinsics_weighted", C, P, uvs.ctypes.data, w.ctypes.data, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, *tail)
     hist = hist[:min(int(res[7]), len(hist))].copy()
     code = int(res[5])
     if verbose == 2:
@@ -315,10 +334,10 @@ def refine_extrinsics(all_uvs, all_extrinsics, all_intrinsics, *, points=None, i
                                       "gauge_camera": gauge_camera, "scale_camera": scale_camera})
 
 
-def refine_extrinsics_system(all_uvs, all_extrinsics, all_intrinsics, *, points, held, lam, loss="soft_l1", f_scale=1.0, step=None, device=0):
+def refine_extrinsics_system(all_uvs, all_extrinsics, all_intrinsics, *, points, held, lam, loss="soft_l1", f_scale=1.0, step=None, device=0, weights=None):
     """One evaluation of refine_extrinsics laid open (`mcba_refine_extrinsics_system`; tests and diagnostics): the loop's own set-up and kernels
     run once at (all_extrinsics, points) and the damping lam, and what they wrote comes back as it is.  held: (C, 6) bool or (C,) bit words,
-    taken as given -- no gauge, scale or blind-camera rule.  step: None, or (ext_trial (C, 6), dtheta (C, 6)): also the back-substitution.
+    taken as given -- no gauge, scale or blind-camera rule.  weights: None or (C, P), as refine_extrinsics takes them.  step: None, or (ext_trial (C, 6), dtheta (C, 6)): also the back-substitution.
     Returns a dict: point_status (P,); system (the raw NP NP + 33 C + 4 doubles) and its views YY (NP, NP), acc (C, 33) = U_c packed lower
     (21) | g_c (6) | sum_p Y_cp z_p (6), cost, count (present scalars of the used points), gmax (max |g_p|), tail (the fourth trailing scalar);
     group, workgroups, NP, kernel_ms; with a step trial_points (P, 3) and step4 = trial cost, sum dX^2, 0, sum X^2."""
@@ -347,8 +366,13 @@ def refine_extrinsics_system(all_uvs, all_extrinsics, all_intrinsics, *, points,
             raise ValueError("step must be (ext_trial (n_cameras, 6), dtheta (n_cameras, 6))")
         trial, step4 = np.empty((P, 3)), np.empty(4)
     addr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
-    ops.call("mcba_refine_extrinsics_system", C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, held_bits.ctypes.data, ops.LOSSES[loss], float(f_scale), float(lam),
-             int(device), addr(ext_trial), addr(dtheta), status.ctypes.data, system.ctypes.data, addr(trial), addr(step4), info.ctypes.data)
+    w = _weight_plane(weights, C, P)
+    tail = (cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, held_bits.ctypes.data, ops.LOSSES[loss], float(f_scale), float(lam), int(device), addr(ext_trial), addr(dtheta), status.ctypes.data,
+            system.ctypes.data, addr(trial), addr(step4), info.ctypes.data)
+    if w is None:
+        ops.call("mcba_refine_extrinsics_system", C, P, uvs.ctypes.data, *tail)
+    else:
+        ops.call("mcba_refine_extrinsics_system_weighted", C, P, uvs.ctypes.data, w.ctypes.data, *tail)
     out = dict(point_status=status, system=system, YY=system[:NP * NP].reshape(NP, NP), acc=system[NP * NP:NP * NP + 33 * C].reshape(C, 33), cost=float(system[-4]), count=float(system[-3]),
                gmax=float(system[-2]), tail=float(system[-1]), group=int(info[0]), workgroups=int(info[1]), NP=int(info[2]), kernel_ms=float(info[3]))
     if step is not None:

@@ -40,16 +40,33 @@ def _stack_uvs(all_uvs, all_extrinsics, all_intrinsics):
     return uvs
 
 
+def _weight_plane(weights, C, P):
+    """weights=None, or the (C, P) float64 plane of per-detection weights w >= 0 (relative inverse variances; 0 or NaN = the detection is
+    unseen), checked.  ValueError: another shape, a negative or an infinite weight."""
+    if weights is None:
+        return None
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (C, P):
+        raise ValueError(f"weights must be ({C}, {P}): one per camera and point, got {w.shape}")
+    if (w < 0).any() or np.isinf(w).any():
+        raise ValueError("weights must be finite and not negative (0 or NaN: the detection is unseen)")
+    return w
+
+
 DEFAULT_MAX_ITERATIONS = 100   # linearisations per point of the refinement (geometry.refine_triangulation)
 
 
-def triangulate(all_uvs, all_extrinsics, all_intrinsics, device=0, undistort_iterations=5, return_kernel_ms=False, *, refine=False, loss="soft_l1", f_scale=1.0):
+def triangulate(all_uvs, all_extrinsics, all_intrinsics, device=0, undistort_iterations=5, return_kernel_ms=False, *, refine=False, loss="soft_l1", f_scale=1.0, weights=None):
     """all_uvs: per camera (n_points, 2), NaN = not seen.  Returns (n_points, 3); NaN rows where fewer than two cameras see
     the point (geometry.py:361-433).
 
     refine=True: the reference's estimate (the median over the camera pairs) is only the start; every point is then moved to the minimiser
     of its robust reprojection cost (`geometry.refine_triangulation` with `loss`, `f_scale` and its default iteration limit).  The
-    detections go to the device once; the two kernels run back to back there."""
+    detections go to the device once; the two kernels run back to back there.
+
+    weights (with refine=True only; ValueError otherwise, so that weights are never silently ignored): (C, P) per-detection weights as
+    `geometry.refine_triangulation` takes them.  The refinement is weighted; the median over the pairs is not, but skips the detections of
+    weight 0 or NaN."""
     uvs = _stack_uvs(all_uvs, all_extrinsics, all_intrinsics)
     C, P = uvs.shape[:2]
     if not 2 <= C <= 64:
@@ -58,10 +75,16 @@ def triangulate(all_uvs, all_extrinsics, all_intrinsics, device=0, undistort_ite
         raise ValueError(f"loss must be one of {sorted(ops.LOSSES)}")
     if refine and not f_scale > 0:
         raise ValueError("`f_scale` must be positive.")
+    if weights is not None and not refine:
+        raise ValueError("weights= needs refine=True: the median over the camera pairs is unweighted")
+    w = _weight_plane(weights, C, P)
     cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
     out = np.empty((P, 3))
     ms = ctypes.c_double(0.0)
-    if refine:
+    if w is not None:
+        ops.call("mcba_triangulate_refine_weighted", C, P, uvs.ctypes.data, w.ctypes.data, cam.ctypes.data, dist.ctypes.data, None, int(undistort_iterations), ops.LOSSES[loss], float(f_scale),
+                 DEFAULT_MAX_ITERATIONS, int(device), out.ctypes.data, None, ctypes.addressof(ms))
+    elif refine:
         ops.call("mcba_triangulate_refine", C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, None, int(undistort_iterations), ops.LOSSES[loss], float(f_scale), DEFAULT_MAX_ITERATIONS,
                  int(device), out.ctypes.data, None, ctypes.addressof(ms))
     else:

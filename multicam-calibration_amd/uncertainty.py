@@ -15,7 +15,7 @@ import numpy as np
 
 from . import ops
 from .api import serialize_params
-from .geometry import _keypoint_inputs
+from .geometry import _keypoint_inputs, _weight_plane
 
 MAX_CAMERAS = 40   # the dense handle's limit (ops.Problem); the sparse-Schur handle of wider rigs is not covered yet
 
@@ -135,7 +135,7 @@ def _unpack3(packed):
     return np.ascontiguousarray(packed[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3))
 
 
-def triangulation_uncertainty(points, all_uvs, all_extrinsics, all_intrinsics, *, camera_covariance=None, sigma=None, inliers=None, loss="linear", f_scale=1.0, device=0):
+def triangulation_uncertainty(points, all_uvs, all_extrinsics, all_intrinsics, *, camera_covariance=None, sigma=None, inliers=None, loss="linear", f_scale=1.0, device=0, weights=None):
     """Covariance of triangulated points.  `points` (P, 3) is where the cost is linearised: the result means what it says only at a minimiser
     of the robust reprojection cost, which is what `refine_triangulation` and `triangulate_consensus` return (with the same loss and f_scale);
     all_uvs, all_extrinsics, all_intrinsics are exactly what those take (raw detections, NaN = unseen; the five-coefficient forward model).
@@ -156,6 +156,10 @@ def triangulation_uncertainty(points, all_uvs, all_extrinsics, all_intrinsics, *
     sigma: the detection noise in pixels if known; None pools sigma2 = sum w f^2 / (m - 3 P_u) over the P_u points of status 1 with their m
     present scalars (NaN, with a RuntimeWarning, if m <= 3 P_u).
     inliers: None, or the (C, P) mask `triangulate_consensus` returns: a camera that is False for a point is treated as not seeing it.
+    weights: None, or (C, P) per-detection weights w >= 0 as `refine_triangulation` takes them (relative inverse variances; 0 or NaN =
+    unseen): f, A_c and B_c of a detection are scaled by sqrt(w), so H, G, both terms and the pooled sigma2 = sum rho' w f^2 / (m - 3 P_u) are
+    those of the weighted problem, m and n_views counting the detections of positive weight.  With true inverse variances as weights sigma2
+    is about 1; `sigma` stays the standard deviation of a detection of weight 1.  With inliers the mask zeroes weights.
     status (POINT_STATUS): -1 fewer than two views or a NaN in the point; -2 degenerate (H, Jacobi-scaled by its diagonal, has a Cholesky
     pivot whose square is below 1e-12: two cameras with one centre, a point on the baseline).  Both terms are NaN for such points and they
     leave the pooled sums.
@@ -179,12 +183,16 @@ def triangulation_uncertainty(points, all_uvs, all_extrinsics, all_intrinsics, *
         if mask.shape != (C, P) or mask.dtype != np.bool_:
             raise ValueError(f"inliers must be the ({C}, {P}) bool mask of triangulate_consensus")
         uvs = np.where(mask[:, :, None], uvs, np.nan)   # (a copy: the one that is uploaded)
+    w = _weight_plane(weights, C, P)
     det, cal = np.empty((P, 6)), None if cov is None else np.empty((P, 6))
     views, status, info = np.empty(P, np.int32), np.empty(P, np.int32), np.zeros(8)
     ms = ctypes.c_double(0.0)
-    ops.call("mcba_triangulation_covariance", C, P, pts.ctypes.data, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, None if cov is None else cov.ctypes.data, ops.LOSSES[loss],
-             float(f_scale), float("nan") if sigma is None else float(sigma) ** 2, int(device), det.ctypes.data, None if cal is None else cal.ctypes.data, views.ctypes.data,
-             status.ctypes.data, info.ctypes.data, ctypes.addressof(ms))
+    tail = (cam.ctypes.data, dist.ctypes.data, None if cov is None else cov.ctypes.data, ops.LOSSES[loss], float(f_scale), float("nan") if sigma is None else float(sigma) ** 2, int(device),
+            det.ctypes.data, None if cal is None else cal.ctypes.data, views.ctypes.data, status.ctypes.data, info.ctypes.data, ctypes.addressof(ms))
+    if w is None:
+        ops.call("mcba_triangulation_covariance", C, P, pts.ctypes.data, uvs.ctypes.data, *tail)
+    else:
+        ops.call("mcba_triangulation_covariance_weighted", C, P, pts.ctypes.data, uvs.ctypes.data, w.ctypes.data, *tail)
     sigma2, m, nfree = float(info[0]), int(info[1]), int(info[2])
     if sigma is None and not m > nfree:
         warnings.warn(f"triangulation_uncertainty: {m} residuals for {nfree} point coordinates -- the noise scale cannot be estimated (pass sigma)", RuntimeWarning, stacklevel=2)

@@ -5,7 +5,9 @@ points (the algorithmic traffic); its share of the 8 TB/s HBM roof is reported, 
 
   python scripts/extrinsics_refinement_timing.py [--out DIR] [--shapes 2000000x6,200000x24] [--reps R] [--nfev N]
   python scripts/extrinsics_refinement_timing.py --child PxC --reps R --nfev N      one measurement (JSON on stdout)
-  python scripts/extrinsics_refinement_timing.py --design JSON                      rewrite the marked block of DESIGN.md section 8f-12 from a result file"""
+  python scripts/extrinsics_refinement_timing.py --design JSON                      rewrite the marked block of DESIGN.md section 8f-12 from a result file
+  --weights: the same shapes again with a random weight plane (uniform in [0.1, 3]): the weighted milliseconds per pass beside
+  the unweighted ones in the JSON and in the kpba block of DESIGN.md section 8f-13"""
 import json
 import os
 import subprocess
@@ -17,7 +19,7 @@ HBM_BYTES_PER_S = 8.0e12
 BEGIN, END = "<!-- extrinsics_refinement_timing:begin -->", "<!-- extrinsics_refinement_timing:end -->"
 
 
-def child(shape, reps, nfev):
+def child(shape, reps, nfev, weights=False):
     import numpy as np
 
     sys.path.insert(0, ROOT)
@@ -37,7 +39,8 @@ def child(shape, reps, nfev):
     ext[1:, :3] += rng.normal(0, 2e-3, (C - 1, 3))   # drifted cameras
     ext[1:, 3:] += rng.normal(0, 1.0, (C - 1, 3))
     X0 = X + rng.normal(0, 0.5, X.shape)
-    wall, red, stp, kern = [], [], [], []
+    wall, red, stp, kern, wred, wstp = [], [], [], [], [], []
+    W = rng.uniform(0.1, 3.0, (C, P)) if weights else None
     for _ in range(reps + 1):   # the first round warms up
         t0 = time.perf_counter()
         r = refine_extrinsics(uvs, ext, intr, points=X0, loss="soft_l1", max_nfev=nfev)
@@ -45,12 +48,18 @@ def child(shape, reps, nfev):
         red.append(r.info["reduce_ms"] / max(r.info["n_reduce"], 1))
         stp.append(r.info["step_ms"] / max(r.info["n_step"], 1))
         kern.append(r.info["kernel_ms"])
+        if weights:
+            rw = refine_extrinsics(uvs, ext, intr, points=X0, loss="soft_l1", max_nfev=nfev, weights=W)
+            wred.append(rw.info["reduce_ms"] / max(rw.info["n_reduce"], 1))
+            wstp.append(rw.info["step_ms"] / max(rw.info["n_step"], 1))
     med = lambda v: float(np.median(v[1:]))   # noqa: E731
     nbytes = 16.0 * C * P + 24.0 * P
     out = {"shape": shape, "points": P, "cameras": C, "used_points": int((r.point_status == 1).sum()), "group": r.info["group"], "max_nfev": nfev, "nfev": r.nfev, "njev": r.njev,
            "n_reduce": r.info["n_reduce"], "n_step": r.info["n_step"], "status": r.status, "cost0": r.cost0, "cost": r.cost,
            "call_ms": med(wall), "kernel_ms": med(kern), "reduce_ms_per_pass": med(red), "step_ms_per_pass": med(stp), "all_reduce_ms_per_pass": red[1:], "all_step_ms_per_pass": stp[1:],
            "pass_bytes": nbytes, "reduce_hbm_fraction": nbytes / (med(red) * 1e-3) / HBM_BYTES_PER_S, "step_hbm_fraction": (nbytes + 24.0 * P) / (med(stp) * 1e-3) / HBM_BYTES_PER_S}
+    if weights:
+        out["weighted"] = {"reduce_ms_per_pass": med(wred), "step_ms_per_pass": med(wstp), "reduce_ratio": med(wred) / med(red), "step_ratio": med(wstp) / med(stp), "nfev": rw.nfev}
     print(json.dumps(out))
 
 
@@ -64,6 +73,28 @@ def design_block(results):
     return "\n".join(lines)
 
 
+W_BEGIN, W_END = "<!-- weights_timing:%s:begin -->", "<!-- weights_timing:%s:end -->"
+
+
+def write_weights_block(key, header, rows):
+    """rewrite this script's marked block of DESIGN.md section 8f-13 (weighted against unweighted kernel times from the same build)"""
+    design = os.path.join(ROOT, "DESIGN.md")
+    text = open(design).read()
+    begin, end = W_BEGIN % key, W_END % key
+    if begin not in text or end not in text:
+        raise SystemExit("DESIGN.md has no weights_timing:%s block" % key)
+    a, b = text.index(begin), text.index(end) + len(end)
+    open(design, "w").write(text[:a] + "\n".join([begin, header, "|" + "---|" * (header.count("|") - 1)] + rows + [end]) + text[b:])
+
+
+def weights_rows(results):
+    return [f"| {r['points']} x {r['cameras']} | {r['reduce_ms_per_pass']:.2f} | {r['weighted']['reduce_ms_per_pass']:.2f} | {r['weighted']['reduce_ratio']:.2f} | {r['step_ms_per_pass']:.2f} | "
+            f"{r['weighted']['step_ms_per_pass']:.2f} | {r['weighted']['step_ratio']:.2f} |" for r in results if "weighted" in r]
+
+
+W_HEADER = "| points x cameras | `k_kpba_reduce` pass (ms) | weighted (ms) | ratio | `k_kpba_step` pass (ms) | weighted (ms) | ratio |"
+
+
 def write_design(path):
     results = json.load(open(path))
     design = os.path.join(ROOT, "DESIGN.md")
@@ -72,6 +103,8 @@ def write_design(path):
         raise SystemExit("DESIGN.md has no extrinsics_refinement_timing block")
     a, b = text.index(BEGIN), text.index(END) + len(END)
     open(design, "w").write(text[:a] + design_block(results) + text[b:])
+    if any("weighted" in r for r in results):
+        write_weights_block("kpba", W_HEADER, weights_rows(results))
 
 
 def arg(name, default):
@@ -85,7 +118,7 @@ def main():
     os.makedirs(out_dir, exist_ok=True)
     results = []
     for shape in shapes:
-        r = subprocess.run(["timeout", "-k", "10", "420", sys.executable, __file__, "--child", shape, "--reps", reps, "--nfev", nfev], cwd=ROOT, capture_output=True, text=True)
+        r = subprocess.run(["timeout", "-k", "10", "420", sys.executable, __file__, "--child", shape, "--reps", reps, "--nfev", nfev] + (["--weights"] if "--weights" in sys.argv else []), cwd=ROOT, capture_output=True, text=True)
         if r.returncode != 0:
             sys.stderr.write(r.stdout[-3000:] + r.stderr[-3000:])
             raise SystemExit("step failed (exit %d): %s" % (r.returncode, shape))
@@ -94,11 +127,13 @@ def main():
         with open(os.path.join(out_dir, "extrinsics_refinement_timing.json"), "w") as fh:
             json.dump(results, fh, indent=1)
     print(design_block(results))
+    if "--weights" in sys.argv:
+        write_weights_block("kpba", W_HEADER, weights_rows(results))
 
 
 if __name__ == "__main__":
     if "--child" in sys.argv:
-        child(arg("--child", "2000000x6"), int(arg("--reps", "5")), int(arg("--nfev", "6")))
+        child(arg("--child", "2000000x6"), int(arg("--reps", "5")), int(arg("--nfev", "6")), "--weights" in sys.argv)
     elif "--design" in sys.argv:
         write_design(arg("--design", ""))
     else:

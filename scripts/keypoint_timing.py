@@ -4,7 +4,9 @@ refinement's iteration counts, and rocprofv3 --kernel-trace --stats per kernel i
 section 8f-4 times triangulate() at) and x 24 cameras (the rig of BASELINE configs[4]); 0.3 px noise, 10 % of the detections missing.
 
   python scripts/keypoint_timing.py [--out DIR] [--cameras 6,24] [--points N]   driver: every step a child process under its own `timeout -k`
-  python scripts/keypoint_timing.py --child C --points N                        one measurement (JSON on stdout)"""
+  python scripts/keypoint_timing.py --child C --points N                        one measurement (JSON on stdout)
+  --weights: also k_tri_refine's weighted instantiation on the same shapes with a random weight plane (uniform in [0.1, 3]; SURVEY.md section
+  8f-13), its kernel time beside the unweighted one in the JSON, and -- with --out profiles -- the keypoint block of DESIGN.md section 8f-13"""
 import ctypes
 import glob
 import json
@@ -34,7 +36,7 @@ def make_scene(C, P, seed=1):
     return list(uvs), cam[:, 6:], intr
 
 
-def child(C, P, reps):
+def child(C, P, reps, weights=False):
     import numpy as np
 
     sys.path.insert(0, ROOT)
@@ -88,7 +90,29 @@ def child(C, P, reps):
     out["algorithmic_bytes"] = {"k_project": b_proj, "k_keypoint_errors": b_err, "k_tri_refine": b_ref}
     out["share_of_copy_rate"] = {"k_project_radial2": b_proj / (k_proj * 1e-3) / COPY_RATE, "k_project_opencv5": b_proj / (k_proj5 * 1e-3) / COPY_RATE}
     out["refine_bytes_per_s"] = b_ref / (k_ref * 1e-3)
+    if weights:   # the same launch with the (C, P) plane beside the detections: 8 C more bytes per linearisation
+        W = np.ascontiguousarray(np.random.default_rng(11).uniform(0.1, 3.0, (C, P)))
+        winfo = np.empty((P, 4))
+        lib.mcba_triangulate_refine_weighted(C, P, U.ctypes.data, W.ctypes.data, cam.ctypes.data, dist.ctypes.data, start.ctypes.data, 5, ops.LOSSES["soft_l1"], 1.0, 100, 0, o3.ctypes.data,
+                                             winfo.ctypes.data, a)
+        out["kernel_ms"]["k_tri_refine_soft_l1_weighted"] = ms.value
+        wok = winfo[:, 3] >= 0
+        out["weighted"] = {"k_tri_refine_ratio": ms.value / k_ref, "iterations_mean": float(winfo[wok, 2].mean()), "iterations_mean_unweighted": float(info[ok, 2].mean())}
     print(json.dumps(out))
+
+
+W_BEGIN, W_END = "<!-- weights_timing:%s:begin -->", "<!-- weights_timing:%s:end -->"
+
+
+def write_weights_block(key, header, rows):
+    """rewrite this script's marked block of DESIGN.md section 8f-13 (weighted against unweighted kernel times from the same build)"""
+    design = os.path.join(ROOT, "DESIGN.md")
+    text = open(design).read()
+    begin, end = W_BEGIN % key, W_END % key
+    if begin not in text or end not in text:
+        raise SystemExit("DESIGN.md has no weights_timing:%s block" % key)
+    a, b = text.index(begin), text.index(end) + len(end)
+    open(design, "w").write(text[:a] + "\n".join([begin, header, "|" + "---|" * (header.count("|") - 1)] + rows + [end]) + text[b:])
 
 
 def run(cmd, seconds):
@@ -107,14 +131,21 @@ def main():
     out_dir = arg("--out", os.path.join(ROOT, "build", "keypoint_timing"))
     cams = [int(c) for c in arg("--cameras", "6,24").split(",")]
     P = arg("--points", "2000000")
+    weighted = "--weights" in sys.argv
     os.makedirs(out_dir, exist_ok=True)
     results = []
     for C in cams:
-        res = json.loads(run([sys.executable, __file__, "--child", str(C), "--points", P], 900).strip().splitlines()[-1])
+        res = json.loads(run([sys.executable, __file__, "--child", str(C), "--points", P] + (["--weights"] if weighted else []), 900).strip().splitlines()[-1])
         results.append(res)
         print(json.dumps(res, indent=1), flush=True)
         with open(os.path.join(out_dir, "keypoint_timing.json"), "w") as fh:
             json.dump(results, fh, indent=1)
+    if weighted:
+        write_weights_block("keypoint", "| points x cameras | `k_tri_refine<soft_l1>` (ms) | weighted (ms) | ratio | iterations per point, mean (unweighted, weighted) |",
+                            [f"| {r['points']} x {r['cameras']} | {r['kernel_ms']['k_tri_refine_soft_l1']:.2f} | {r['kernel_ms']['k_tri_refine_soft_l1_weighted']:.2f} | "
+                             f"{r['weighted']['k_tri_refine_ratio']:.2f} | {r['weighted']['iterations_mean_unweighted']:.2f}, {r['weighted']['iterations_mean']:.2f} |" for r in results])
+    if "--no-profile" in sys.argv:
+        return
     for C in cams:   # kernel statistics, profiler in a run of its own (no counters)
         d = os.path.join(out_dir, "rocprof_%d" % C)
         run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "kp", "--", sys.executable, __file__, "--child", str(C), "--points", P, "--reps", "1"], 900)
@@ -127,6 +158,6 @@ def main():
 
 if __name__ == "__main__":
     if "--child" in sys.argv:
-        child(int(arg("--child", "6")), int(arg("--points", "2000000")), int(arg("--reps", "7")))
+        child(int(arg("--child", "6")), int(arg("--points", "2000000")), int(arg("--reps", "7")), "--weights" in sys.argv)
     else:
         main()

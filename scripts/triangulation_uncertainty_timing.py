@@ -5,7 +5,9 @@ product Z = G Sigma_cc costs 2 * 3 * n^2 FP64 flops per point on the matrix core
 
   python scripts/triangulation_uncertainty_timing.py [--out DIR] [--shapes 2000000x6,200000x24] [--reps R]
   python scripts/triangulation_uncertainty_timing.py --child PxC --reps R        one measurement (JSON on stdout)
-  python scripts/triangulation_uncertainty_timing.py --design JSON               rewrite the marked block of DESIGN.md section 8f-11 from a result file"""
+  python scripts/triangulation_uncertainty_timing.py --design JSON               rewrite the marked block of DESIGN.md section 8f-11 from a result file
+  --weights: the same shapes again with a random weight plane (uniform in [0.1, 3]): the weighted kernel times beside the
+  unweighted ones in the JSON and in the tricov block of DESIGN.md section 8f-13"""
 import json
 import os
 import subprocess
@@ -17,7 +19,7 @@ FP64_MFMA_FLOPS = 78.6e12
 BEGIN, END = "<!-- triangulation_uncertainty_timing:begin -->", "<!-- triangulation_uncertainty_timing:end -->"
 
 
-def child(shape, reps):
+def child(shape, reps, weights=False):
     import numpy as np
 
     sys.path.insert(0, ROOT)
@@ -41,12 +43,16 @@ def child(shape, reps):
     S = 0.5 * (S + S.T)
     wall = {True: [], False: []}
     kern = {True: [], False: []}
+    wkern = {True: [], False: []}
+    W = rng.uniform(0.1, 3.0, (C, P)) if weights else None
     for _ in range(reps + 1):   # the first round warms up
         for with_cov in (True, False):
             t0 = time.perf_counter()
             u = triangulation_uncertainty(X, uvs, ext, intr, camera_covariance=S if with_cov else None, sigma=0.3)
             wall[with_cov].append((time.perf_counter() - t0) * 1e3)
             kern[with_cov].append(u.info["kernel_ms"])
+            if weights:
+                wkern[with_cov].append(triangulation_uncertainty(X, uvs, ext, intr, camera_covariance=S if with_cov else None, sigma=0.3, weights=W).info["kernel_ms"])
     med = lambda v: float(np.median(v[1:]))   # noqa: E731
     cal_ms = med(kern[True]) - med(kern[False])   # (k_tricov_cal against k_tricov_scale, which streams 96 bytes per point)
     flops = 2.0 * 3 * n * n * P
@@ -55,6 +61,9 @@ def child(shape, reps):
            "call_ms_detection_only": med(wall[False]), "kernel_ms_detection_only": med(kern[False]),
            "all_kernel_ms_with_covariance": kern[True][1:], "all_kernel_ms_detection_only": kern[False][1:],
            "gemm_flops": flops, "mfma_fraction": flops / (max(cal_ms, 1e-9) * 1e-3) / FP64_MFMA_FLOPS}
+    if weights:
+        out["weighted"] = {"kernel_ms_with_covariance": med(wkern[True]), "kernel_ms_detection_only": med(wkern[False]), "ratio_with_covariance": med(wkern[True]) / med(kern[True]),
+                           "ratio_detection_only": med(wkern[False]) / med(kern[False])}
     print(json.dumps(out))
 
 
@@ -68,6 +77,28 @@ def design_block(results):
     return "\n".join(lines)
 
 
+W_BEGIN, W_END = "<!-- weights_timing:%s:begin -->", "<!-- weights_timing:%s:end -->"
+
+
+def write_weights_block(key, header, rows):
+    """rewrite this script's marked block of DESIGN.md section 8f-13 (weighted against unweighted kernel times from the same build)"""
+    design = os.path.join(ROOT, "DESIGN.md")
+    text = open(design).read()
+    begin, end = W_BEGIN % key, W_END % key
+    if begin not in text or end not in text:
+        raise SystemExit("DESIGN.md has no weights_timing:%s block" % key)
+    a, b = text.index(begin), text.index(end) + len(end)
+    open(design, "w").write(text[:a] + "\n".join([begin, header, "|" + "---|" * (header.count("|") - 1)] + rows + [end]) + text[b:])
+
+
+def weights_rows(results):
+    return [f"| {r['points']} x {r['cameras']} | {r['kernel_ms_detection_only']:.2f} | {r['weighted']['kernel_ms_detection_only']:.2f} | {r['weighted']['ratio_detection_only']:.2f} | "
+            f"{r['kernel_ms_with_covariance']:.2f} | {r['weighted']['kernel_ms_with_covariance']:.2f} | {r['weighted']['ratio_with_covariance']:.2f} |" for r in results if "weighted" in r]
+
+
+W_HEADER = "| points x cameras | `k_tricov_point` + `k_tricov_scale` (ms) | weighted (ms) | ratio | `k_tricov_point` + `k_tricov_cal` (ms) | weighted (ms) | ratio |"
+
+
 def write_design(path):
     results = json.load(open(path))
     design = os.path.join(ROOT, "DESIGN.md")
@@ -76,6 +107,8 @@ def write_design(path):
         raise SystemExit("DESIGN.md has no triangulation_uncertainty_timing block")
     a, b = text.index(BEGIN), text.index(END) + len(END)
     open(design, "w").write(text[:a] + design_block(results) + text[b:])
+    if any("weighted" in r for r in results):
+        write_weights_block("tricov", W_HEADER, weights_rows(results))
 
 
 def arg(name, default):
@@ -89,7 +122,7 @@ def main():
     os.makedirs(out_dir, exist_ok=True)
     results = []
     for shape in shapes:
-        r = subprocess.run(["timeout", "-k", "10", "420", sys.executable, __file__, "--child", shape, "--reps", reps], cwd=ROOT, capture_output=True, text=True)
+        r = subprocess.run(["timeout", "-k", "10", "420", sys.executable, __file__, "--child", shape, "--reps", reps] + (["--weights"] if "--weights" in sys.argv else []), cwd=ROOT, capture_output=True, text=True)
         if r.returncode != 0:
             sys.stderr.write(r.stdout[-3000:] + r.stderr[-3000:])
             raise SystemExit("step failed (exit %d): %s" % (r.returncode, shape))
@@ -98,11 +131,13 @@ def main():
         with open(os.path.join(out_dir, "triangulation_uncertainty_timing.json"), "w") as fh:
             json.dump(results, fh, indent=1)
     print(design_block(results))
+    if "--weights" in sys.argv:
+        write_weights_block("tricov", W_HEADER, weights_rows(results))
 
 
 if __name__ == "__main__":
     if "--child" in sys.argv:
-        child(arg("--child", "2000000x6"), int(arg("--reps", "5")))
+        child(arg("--child", "2000000x6"), int(arg("--reps", "5")), "--weights" in sys.argv)
     elif "--design" in sys.argv:
         write_design(arg("--design", ""))
     else:
