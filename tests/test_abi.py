@@ -77,3 +77,19 @@ def test_more_than_40_cameras_is_refused_with_the_reason():
 
     with pytest.raises(ops.McbaError, match="at most 40"):
         ops.Problem(np.zeros((41, 3, 4, 2)), np.zeros((4, 3)))
+
+
+def test_flat_order_stats_refuses_bad_ranks():
+    """mcba_flat_order_stats takes at most 8 ranks, each in 0 .. n - 1: nine ranks, a negative rank and rank == n are MCBA_ERR_ARG (checked before any device
+    is touched), and nothing is written."""
+    import numpy as np
+    from multicam_calibration_amd import ops
+
+    n = 5
+    P, rt12 = np.zeros((n, 3)), np.r_[np.eye(3).ravel(), np.zeros(3)]
+    for ranks in (np.zeros(9, dtype=np.int64), np.array([0, -1], dtype=np.int64), np.array([n - 1, n], dtype=np.int64)):
+        values, sums, nans = np.full((2, 9), 7.0), np.full(2, 7.0), np.full(2, 7, dtype=np.uint64)
+        with pytest.raises(ops.McbaError) as e:
+            ops.call("mcba_flat_order_stats", n, P.ctypes.data, rt12.ctypes.data, len(ranks), ranks.ctypes.data, 0, values.ctypes.data, sums.ctypes.data, nans.ctypes.data, None)
+        assert e.value.code == ops.ERR_ARG
+        assert (values == 7.0).all() and (sums == 7.0).all() and (nans == 7).all()
