@@ -174,14 +174,10 @@ int launch_consensus(hipStream_t st, int form, int loss, const double* uvs, size
   const dim3 g((unsigned)((npts + 255) / 256)), b(256);
   const double2* uv = reinterpret_cast<const double2*>(uvs);
   if (form == CONSENSUS_LANE) {
-    switch (loss) {   // one kernel per loss: loss_weights takes it as a template argument
-      case LOSS_LINEAR: k_consensus_lane<LOSS_LINEAR><<<g, b, 0, st>>>(uv, npts, cams, C, threshold, min_views, und_iters, f_scale, max_iterations, out, mask, info); break;
-      case LOSS_SOFT_L1: k_consensus_lane<LOSS_SOFT_L1><<<g, b, 0, st>>>(uv, npts, cams, C, threshold, min_views, und_iters, f_scale, max_iterations, out, mask, info); break;
-      case LOSS_HUBER: k_consensus_lane<LOSS_HUBER><<<g, b, 0, st>>>(uv, npts, cams, C, threshold, min_views, und_iters, f_scale, max_iterations, out, mask, info); break;
-      case LOSS_CAUCHY: k_consensus_lane<LOSS_CAUCHY><<<g, b, 0, st>>>(uv, npts, cams, C, threshold, min_views, und_iters, f_scale, max_iterations, out, mask, info); break;
-      default: k_consensus_lane<LOSS_ARCTAN><<<g, b, 0, st>>>(uv, npts, cams, C, threshold, min_views, und_iters, f_scale, max_iterations, out, mask, info); break;
-    }
-    return 0;
+    return with_loss(loss, [&](auto L) {
+      k_consensus_lane<decltype(L)::value><<<g, b, 0, st>>>(uv, npts, cams, C, threshold, min_views, und_iters, f_scale, max_iterations, out, mask, info);
+      return 0;
+    });
   }
   if (!hyp) return 1;
   if (form == CONSENSUS_WAVE) {
@@ -192,14 +188,10 @@ int launch_consensus(hipStream_t st, int form, int loss, const double* uvs, size
   } else {
     return 1;
   }
-  switch (loss) {
-    case LOSS_LINEAR: k_consensus_refit<LOSS_LINEAR><<<g, b, 0, st>>>(uv, npts, cams, C, min_views, f_scale, max_iterations, out, mask, hyp, info); break;
-    case LOSS_SOFT_L1: k_consensus_refit<LOSS_SOFT_L1><<<g, b, 0, st>>>(uv, npts, cams, C, min_views, f_scale, max_iterations, out, mask, hyp, info); break;
-    case LOSS_HUBER: k_consensus_refit<LOSS_HUBER><<<g, b, 0, st>>>(uv, npts, cams, C, min_views, f_scale, max_iterations, out, mask, hyp, info); break;
-    case LOSS_CAUCHY: k_consensus_refit<LOSS_CAUCHY><<<g, b, 0, st>>>(uv, npts, cams, C, min_views, f_scale, max_iterations, out, mask, hyp, info); break;
-    default: k_consensus_refit<LOSS_ARCTAN><<<g, b, 0, st>>>(uv, npts, cams, C, min_views, f_scale, max_iterations, out, mask, hyp, info); break;
-  }
-  return 0;
+  return with_loss(loss, [&](auto L) {
+    k_consensus_refit<decltype(L)::value><<<g, b, 0, st>>>(uv, npts, cams, C, min_views, f_scale, max_iterations, out, mask, hyp, info);
+    return 0;
+  });
 }
 
 }  // namespace mcba

@@ -11,64 +11,51 @@
 #include <algorithm>
 
 #include "mcba_cov_math.h"
+#include "mcba_device.h"
 #include "mcba_kernels.h"
+#include "mcba_quadform.h"
 
 namespace mcba {
-
-typedef double cov_d4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------- k_cov_wss
 constexpr int kCovWssBlocks = 1024;
 
 template <int LOSS>
 __global__ __launch_bounds__(256) void k_cov_wss(const double* __restrict__ res, size_t count, double fs2, double ifs2, double* __restrict__ part) {
-  __shared__ double s_a[256], s_b[256];
-  double a = 0.0, b = 0.0;
+  __shared__ double s_r[2][256];
+  double r[2] = {0.0, 0.0};
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) {
-    const double r = res[i];
-    if (r == r) {
+    const double v = res[i];
+    if (v == v) {
       double rh, gw, w2;
-      loss_weights<LOSS>(r, fs2, ifs2, rh, gw, w2);
-      a += gw * (r * r);
-      b += 1.0;
+      loss_weights<LOSS>(v, fs2, ifs2, rh, gw, w2);
+      r[0] += gw * (v * v);
+      r[1] += 1.0;
     }
   }
-  s_a[threadIdx.x] = a;
-  s_b[threadIdx.x] = b;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) { s_a[threadIdx.x] += s_a[threadIdx.x + s]; s_b[threadIdx.x] += s_b[threadIdx.x + s]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { part[2 * blockIdx.x] = s_a[0]; part[2 * blockIdx.x + 1] = s_b[0]; }
+  const bool is_max[2] = {false, false};   // sums alone
+  block_tree<2>(s_r, r, is_max);
+  if (threadIdx.x == 0) { part[2 * blockIdx.x] = s_r[0][0]; part[2 * blockIdx.x + 1] = s_r[1][0]; }
 }
 
 // the partials in order: out[0] = sum w f^2, out[1] = present scalars
 __global__ __launch_bounds__(256) void k_cov_wss_final(const double* __restrict__ part, int nblocks, double* __restrict__ out) {
-  __shared__ double s_a[256], s_b[256];
-  double a = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < nblocks; i += 256) { a += part[2 * i]; b += part[2 * i + 1]; }
-  s_a[threadIdx.x] = a;
-  s_b[threadIdx.x] = b;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) { s_a[threadIdx.x] += s_a[threadIdx.x + s]; s_b[threadIdx.x] += s_b[threadIdx.x + s]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { out[0] = s_a[0]; out[1] = s_b[0]; }
+  __shared__ double s_r[2][256];
+  double r[2] = {0.0, 0.0};
+  for (int i = threadIdx.x; i < nblocks; i += 256) { r[0] += part[2 * i]; r[1] += part[2 * i + 1]; }
+  const bool is_max[2] = {false, false};   // sums alone
+  block_tree<2>(s_r, r, is_max);
+  if (threadIdx.x == 0) { out[0] = s_r[0][0]; out[1] = s_r[1][0]; }
 }
 
 int launch_cov_wss(hipStream_t st, int loss, double f_scale, const double* res, size_t count, double* part, double* out) {
   const int nb = (int)std::max<size_t>(1, std::min<size_t>(kCovWssBlocks, (count + 2047) / 2048));
   const double fs2 = f_scale * f_scale, ifs2 = 1.0 / fs2;
-  switch (loss) {
-    case LOSS_LINEAR: hipLaunchKernelGGL(k_cov_wss<LOSS_LINEAR>, dim3(nb), dim3(256), 0, st, res, count, fs2, ifs2, part); break;
-    case LOSS_SOFT_L1: hipLaunchKernelGGL(k_cov_wss<LOSS_SOFT_L1>, dim3(nb), dim3(256), 0, st, res, count, fs2, ifs2, part); break;
-    case LOSS_HUBER: hipLaunchKernelGGL(k_cov_wss<LOSS_HUBER>, dim3(nb), dim3(256), 0, st, res, count, fs2, ifs2, part); break;
-    case LOSS_CAUCHY: hipLaunchKernelGGL(k_cov_wss<LOSS_CAUCHY>, dim3(nb), dim3(256), 0, st, res, count, fs2, ifs2, part); break;
-    case LOSS_ARCTAN: hipLaunchKernelGGL(k_cov_wss<LOSS_ARCTAN>, dim3(nb), dim3(256), 0, st, res, count, fs2, ifs2, part); break;
-    default: return 1;
-  }
+  if (with_loss(loss, [&](auto L) {
+        hipLaunchKernelGGL(k_cov_wss<decltype(L)::value>, dim3(nb), dim3(256), 0, st, res, count, fs2, ifs2, part);
+        return 0;
+      }))
+    return 1;
   hipLaunchKernelGGL(k_cov_wss_final, dim3(1), dim3(256), 0, st, part, nb, out);
   return 0;
 }
@@ -176,31 +163,22 @@ void launch_cov_cam(hipStream_t st, const double* S0, int n, int cw, int gauge, 
 // 256 threads.  R = 6 G rows of the stacked Y (row 6 g + k = row k of Y of frame g), RT = ceil(R / 16) row tiles, KP = ceil(n / 32) 32.
 //   1. the first G threads: V_f^-1 from fbuf's L_f (zero for a frame that is flagged or past the end: its Y is zero)
 //   2. item (camera-system row r, frame g), frames fastest: the record's W row -> y = V^-1 w -> s_Y[6 g + k][r]; columns n .. KP are zero
-//   3. per panel of 64 columns of Sigma_cc (wavefront w: columns 16 w .. 16 w + 15 of it), K in chunks of 32 rows staged through LDS (the
-//      next chunk's loads fly during the matrix-core phase): Z tile += Y tile x Sigma chunk.  Z goes to LDS (over the staging buffer) and is
-//      contracted with Y: thread (g, k <= l) adds sum_j Z[6 g + k][j] Y[6 g + l][j] -- each frame's own diagonal block, nothing else.
+//   3. the diagonal blocks of Y Sigma_cc Y^T: diag_blocks (mcba_quadform.h), thread (g, k <= l) gets entry (k, l) of frame g
 //   4. Sigma_ff = sigma2 V^-1 + that, mirrored, through LDS to out[f][36] in runs of consecutive doubles; frames >= F write nothing.
-constexpr int kCovKC = 32, kCovPS = 80, kCovZS = 66;
-
-struct CovFramesShape { int G, RT, KP; size_t lds; };
-
 static size_t cov_frames_lds(int n, int G) {
   const int KP = (n + 31) / 32 * 32, R = 6 * G;
-  const size_t stage = std::max<size_t>((size_t)kCovKC * kCovPS, (size_t)R * kCovZS);
-  return ((size_t)R * (KP + 2) + stage + (size_t)G * 21 + (size_t)G * 36) * sizeof(double);
+  return ((size_t)R * (KP + 2) + stage_doubles(R) + (size_t)G * 21 + (size_t)G * 36) * sizeof(double);
 }
 
 template <int CW, int RT>
 __global__ __launch_bounds__(256) void k_cov_frames(const double* __restrict__ rec, const double* __restrict__ fbuf, const unsigned char* __restrict__ flag, const double* __restrict__ Sig, int ld,
                                                    double sigma2, double* __restrict__ out, int C, int F, int Fpad, int G, int KP) {
   extern __shared__ __align__(16) double lds[];
-  const int t = threadIdx.x, lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int t = threadIdx.x;
   const int n = CW * C, nfb = Fpad >> 6, R = 6 * G, RS = KP + 2;
   double* s_Y = lds;                                   // [R][RS]
-  double* s_P = s_Y + (size_t)R * RS;                  // [kCovKC][kCovPS], later [R][kCovZS]
-  const size_t stage = (size_t)kCovKC * kCovPS > (size_t)R * kCovZS ? (size_t)kCovKC * kCovPS : (size_t)R * kCovZS;
-  double* s_Vi = s_P + stage;                          // [G][21]
+  double* s_P = s_Y + (size_t)R * RS;                  // the staging buffer of diag_blocks
+  double* s_Vi = s_P + stage_doubles(R);               // [G][21]
   double* s_o = s_Vi + G * 21;                         // [G][36]
   const int f0 = blockIdx.x * G, ng = min(G, F - f0);
 
@@ -234,74 +212,15 @@ __global__ __launch_bounds__(256) void k_cov_frames(const double* __restrict__ r
     for (int k = 0; k < 6; ++k) s_Y[(size_t)(6 * g + k) * RS + r] = y[k];
   }
   for (int it = t; it < R * (KP - n); it += 256) s_Y[(size_t)(it / (KP - n)) * RS + n + it % (KP - n)] = 0.0;
-  // (the first barrier of the panel loop orders these stores before the first read)
+  // (the first barrier of diag_blocks orders these stores before the first read)
 
-  constexpr int NQ = 1;   // G <= 8: at most 168 (frame, k <= l) outputs, one per thread
-  double zy[NQ] = {0.0};
   int og = 0, ok_ = 0, ol = 0;
-  const bool own = t < G * 21;
+  const bool own = t < G * 21;   // G <= 8: at most 168 (frame, k <= l) outputs, one per thread
   if (own) { og = t / 21; cov_tri6_pair(t % 21, ok_, ol); }
-
-  const int nkc = KP / kCovKC, npan = (KP + 63) / 64;
-  int arow[RT];
-#pragma unroll
-  for (int ti = 0; ti < RT; ++ti) arow[ti] = min(16 * ti + (lane & 15), R - 1) * RS + (lane >> 4);   // (rows past R: a duplicate, its results are never stored)
-  for (int J = 0; J < npan; ++J) {
-    const bool active = 64 * J + 16 * wave < KP;   // wave-uniform: this wavefront's 16 columns hold anything
-    cov_d4 acc[RT];
-#pragma unroll
-    for (int ti = 0; ti < RT; ++ti) acc[ti] = cov_d4{0.0, 0.0, 0.0, 0.0};
-    double pv[8];
-    auto fetch = [&](int kc) {   // rows 32 kc .. + 31, columns 64 J .. + 63 of the zero-padded ld x ld buffer: inside it (KP <= ld, ld a multiple of 64)
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int idx = t + 256 * q;
-        pv[q] = Sig[(size_t)(kCovKC * kc + (idx >> 6)) * ld + 64 * J + (idx & 63)];
-      }
-    };
-    fetch(0);
-    for (int kc = 0; kc < nkc; ++kc) {
-      __syncthreads();   // the previous chunk's reads (or the previous panel's contraction) are done
-#pragma unroll
-      for (int q = 0; q < 8; ++q) { const int idx = t + 256 * q; s_P[(idx >> 6) * kCovPS + (idx & 63)] = pv[q]; }
-      __syncthreads();
-      if (kc + 1 < nkc) fetch(kc + 1);
-      if (active) {
-#pragma unroll
-        for (int ks = 0; ks < kCovKC / 4; ++ks) {
-          const double b = s_P[(4 * ks + (lane >> 4)) * kCovPS + 16 * wave + (lane & 15)];
-#pragma unroll
-          for (int ti = 0; ti < RT; ++ti) {
-            const double a = s_Y[arow[ti] + kCovKC * kc + 4 * ks];
-            acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[ti], 0, 0, 0);
-          }
-        }
-      }
-    }
-    __syncthreads();   // every wavefront is done with the staging buffer: Z takes its place
-    if (active) {
-#pragma unroll
-      for (int ti = 0; ti < RT; ++ti) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const int row = 16 * ti + 4 * reg + (lane >> 4);
-          if (row < R) s_P[row * kCovZS + 16 * wave + (lane & 15)] = acc[ti][reg];
-        }
-      }
-    }
-    __syncthreads();
-    if (own) {
-      const int jn = min(64, KP - 64 * J);
-      const double* zr = s_P + (6 * og + ok_) * kCovZS;
-      const double* yr = s_Y + (size_t)(6 * og + ol) * RS + 64 * J;
-      double s = 0.0;
-      for (int j = 0; j < jn; ++j) s += zr[j] * yr[j];
-      zy[0] += s;
-    }
-  }
+  const double zy = diag_blocks<RT, 6>(s_Y, s_P, Sig, ld, R, KP, own, og, ok_, ol);
   if (own) {
     const bool deg = og < ng && flag[f0 + og] != 0;
-    const double v = cov_frame_entry(s_Vi[og * 21 + tri6(ok_, ol)], zy[0], sigma2, deg);
+    const double v = cov_frame_entry(s_Vi[og * 21 + tri6(ok_, ol)], zy, sigma2, deg);
     s_o[og * 36 + 6 * ok_ + ol] = v;
     s_o[og * 36 + 6 * ol + ok_] = v;
   }
@@ -317,19 +236,15 @@ int cov_frames_group(int n, int lds_limit, int force_g) {
   return 0;
 }
 
-template <int CW, int RT>
-static int cov_frames_go(hipStream_t st, size_t lds, const double* rec, const double* fbuf, const unsigned char* flag, const double* Sig, int ld, double sigma2, double* out, int C, int F, int Fpad, int G, int KP) {
-  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cov_frames<CW, RT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
-  hipLaunchKernelGGL((k_cov_frames<CW, RT>), dim3((F + G - 1) / G), dim3(256), lds, st, rec, fbuf, flag, Sig, ld, sigma2, out, C, F, Fpad, G, KP);
-  return 0;
-}
-
 int launch_cov_frames(hipStream_t st, const double* rec, const double* fbuf, const unsigned char* flag, const double* Sig, int ld, double sigma2, double* out, int C, int F, int Fpad, int cw, int G) {
   const int n = cw * C, KP = (n + 31) / 32 * 32;
   if ((G != 4 && G != 8) || KP > ld || ld % 64 != 0) return 1;
   const size_t lds = cov_frames_lds(n, G);
-  if (cw == 12) return G == 8 ? cov_frames_go<12, 3>(st, lds, rec, fbuf, flag, Sig, ld, sigma2, out, C, F, Fpad, G, KP) : cov_frames_go<12, 2>(st, lds, rec, fbuf, flag, Sig, ld, sigma2, out, C, F, Fpad, G, KP);
-  return G == 8 ? cov_frames_go<6, 3>(st, lds, rec, fbuf, flag, Sig, ld, sigma2, out, C, F, Fpad, G, KP) : cov_frames_go<6, 2>(st, lds, rec, fbuf, flag, Sig, ld, sigma2, out, C, F, Fpad, G, KP);
+  return with_int<6, 12>(cw == 12 ? 12 : 6, [&](auto CW) {
+    return with_int<2, 3>(G == 8 ? 3 : 2, [&](auto RT) {
+      return launch_with_lds(k_cov_frames<decltype(CW)::value, decltype(RT)::value>, dim3((F + G - 1) / G), lds, st, rec, fbuf, flag, Sig, ld, sigma2, out, C, F, Fpad, G, KP);
+    });
+  });
 }
 
 }  // namespace mcba

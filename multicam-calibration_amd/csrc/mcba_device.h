@@ -1,5 +1,5 @@
-// mcba_device.h -- small device helpers shared by the kernel translation units (wave reductions on DPP moves, the
-// selection of double-buffered operands from the device-resident LM state).
+// mcba_device.h -- small device helpers shared by the kernel translation units (wave reductions on DPP moves, the 256-thread
+// block tree, the selection of double-buffered operands from the device-resident LM state).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "mcba_kernels.h"
@@ -18,6 +18,21 @@ __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
   return v;
+}
+// 256-thread tree in a fixed order (128, 64, ... 1: s[t] += s[t + h]) over s[k][256]; the result in s[k][0].  is_max[k]: the maximum
+// instead of the sum.  Every thread of the workgroup calls this.
+template <int K>
+__device__ __forceinline__ void block_tree(double (*s)[256], const double* r, const bool* is_max) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) s[k][threadIdx.x] = r[k];
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) s[k][threadIdx.x] = is_max[k] ? fmax(s[k][threadIdx.x], s[k][threadIdx.x + h]) : s[k][threadIdx.x] + s[k][threadIdx.x + h];
+    }
+    __syncthreads();
+  }
 }
 // Sum over the 64 lanes, result valid in lane 63 only.  DPP moves (pure VALU, no LDS round trip):
 // xor 1, xor 2 (quad_perm), row_half_mirror, row_mirror -> every lane holds its 16-lane row total;

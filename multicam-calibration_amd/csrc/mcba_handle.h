@@ -226,6 +226,13 @@ inline int stateless_device(int device, const char* who = nullptr) {
   return MCBA_OK;
 }
 
+// the LDS a workgroup of this device may ask for (dynamic, after opting in): at most 160 KiB; 64 KiB where the device does not say
+inline int lds_optin_of(int device) {
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.sharedMemPerBlockOptin > 0) return (int)std::min<size_t>(prop.sharedMemPerBlockOptin, 160 * 1024);
+  return 64 * 1024;
+}
+
 // the device buffers and events of one stateless call (null stream), released on every path out.  upload / scratch / put / download return
 // an MCBA_* code with g_err set; counts are elements of T, the type of both the host and the device side; start / stop time the call's kernels
 struct StatelessCall {

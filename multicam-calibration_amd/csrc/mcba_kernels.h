@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include <type_traits>
+
 #define MCBA_REC 100  // per (frame, camera) record: W 72 | V 21 | g_f 6 | pad
 #define MCBA_GP 92    // k_gram per-wavefront sums, stored [camera][k][frame block]: k = U 78 | g_c 12 | cost | pairs with data
 #define MCBA_FB 40    // per frame: L 21 (diagonal slots hold 1 / L_ii) | z 6 | g_f 6 | D_f 6 | pad
@@ -11,6 +13,29 @@
 #include "mcba_math.h"
 
 namespace mcba {
+// ---- run-time values to template arguments (host side).  A launcher computes its grid and LDS size, then makes one nested call whose
+// innermost generic lambda names the kernel: with_loss(loss, [&](auto L) { ... k_x<decltype(L)::value> ... return 0; }).
+// with_int: f(std::integral_constant<int, V>{}) for the V of the list equal to v; 1, without calling f, when there is none
+template <int... Vs, class F>
+int with_int(int v, F&& f) {
+  int rc = 1;
+  (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+  return rc;
+}
+// one kernel per loss: loss_weights takes it as a template argument.  1 for anything but the five losses
+template <class F>
+int with_loss(int loss, F&& f) { return with_int<LOSS_LINEAR, LOSS_SOFT_L1, LOSS_HUBER, LOSS_CAUCHY, LOSS_ARCTAN>(loss, f); }
+// sw != nullptr: the weighted instantiation
+template <class F>
+int with_weights(const double* sw, F&& f) { return sw ? f(std::true_type{}) : f(std::false_type{}); }
+// opt in to more than 64 KiB of dynamic LDS where the launch asks for it, then launch (256 threads)
+template <class... P, class... A>
+int launch_with_lds(void (*kernel)(P...), dim3 grid, size_t lds, hipStream_t st, A... args) {
+  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, args...);
+  return 0;
+}
+
 // Double-buffered operands (parameter slots, linearisation records) and the damping are chosen either from host
 // values (lms == nullptr: idx / lam as given) or from the device-resident LM state (idx is XORed with state[3],
 // lam = state[1]) -- so a whole LM iteration can be enqueued without knowing whether its trial step is accepted.
@@ -187,6 +212,7 @@ int launch_triangulate_wave(hipStream_t st, int C, const double* uvs, const void
 // keypoint projection, reprojection errors and per-point refinement (mcba_keypoints.hip).  cams: C <= kKpMaxCams (64) entries of the camera
 // table (KpCam, mcba_keypoint_math.h) in device memory -- callers with more cameras launch per group.  Non-zero: arguments out of range.
 struct KpCam;
+struct TcCam;   // (mcba_tricov_math.h: a KpCam and the nine doubles behind it)
 // mode 0: k1, k2 model, 1: five coefficients -- out (C, P, 2); mode 2: the rigid transform of cams[0] -- out (P, 3)
 int launch_project(hipStream_t st, int mode, const double* pts, size_t npts, const KpCam* cams, int C, double* out);
 // uvs (C, P, 2); err rows (C, npad) doubles, NaN where unseen and in the padding p >= npts
@@ -218,6 +244,16 @@ struct KpDetections<true> {
     s = sq[(size_t)c * npts];
   }
 };
+// The camera table into LDS, once per workgroup: the 21 doubles of every KpCam, from a KpCam table or from the KpCam part of a TcCam table
+// (mcba_tricov_math.h: 30 doubles per entry).  Every thread of the workgroup calls this (one barrier).
+template <int SRC_STRIDE>
+__device__ __forceinline__ void stage_cam_doubles(KpCam* s_cam, const double* __restrict__ src, int C) {
+  double* dst = reinterpret_cast<double*>(s_cam);
+  for (int i = threadIdx.x; i < 21 * C; i += blockDim.x) dst[i] = SRC_STRIDE == 21 ? src[i] : src[SRC_STRIDE * (i / 21) + i % 21];
+  __syncthreads();
+}
+__device__ __forceinline__ void stage_cams(KpCam* s_cam, const KpCam* __restrict__ cams, int C) { stage_cam_doubles<21>(s_cam, reinterpret_cast<const double*>(cams), C); }
+__device__ __forceinline__ void stage_cams(KpCam* s_cam, const TcCam* __restrict__ cams, int C) { stage_cam_doubles<30>(s_cam, reinterpret_cast<const double*>(cams), C); }
 // sw, here and below: nullptr, or the (C, P) plane of sqrt(weight) in device memory (0 = the detection is unseen) -- the weighted instantiations
 // start / out (P, 3), info (P, 4) = (cost, cost at the start, iterations, status) or nullptr; loss: enum Loss, LOSS_LINEAR .. LOSS_ARCTAN
 int launch_tri_refine(hipStream_t st, int loss, const double* uvs, const double* start, size_t npts, const KpCam* cams, int C, double f_scale, int max_iterations, double* out, double* info,
@@ -240,7 +276,6 @@ int launch_cov_frames(hipStream_t st, const double* rec, const double* fbuf, con
 
 // ---- triangulation uncertainty (mcba_tricov.hip).  uvs (C, P, 2) raw detections (NaN = unseen), pts (P, 3), cams: the
 // table of mcba_tricov_math.h (TcCam) in device memory, 2 <= C <= 64.  Non-zero: arguments out of range.
-struct TcCam;
 int tricov_point_blocks(size_t npts);   // workgroups of k_tricov_point: part holds 4 doubles for each
 // hinv (P, 6) = H^-1 packed (NaN unless status is 1), views / status (P); then info[0 .. 4] = sigma2 (sigma2_in, or -- NaN -- pooled in a fixed
 // order), present scalars m and 3 P_u of the points of status 1, points of status -1, points of status -2

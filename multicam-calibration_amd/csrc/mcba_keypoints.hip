@@ -18,13 +18,6 @@ static_assert(mcba::KpWeighted<mcba::KpDetections<true>>::value && !mcba::KpWeig
 
 namespace mcba {
 
-__device__ __forceinline__ void stage_cams(KpCam* s_cam, const KpCam* __restrict__ cams, int C) {
-  const double* src = reinterpret_cast<const double*>(cams);
-  double* dst = reinterpret_cast<double*>(s_cam);
-  for (int i = threadIdx.x; i < 21 * C; i += blockDim.x) dst[i] = src[i];
-  __syncthreads();
-}
-
 // MODE 0: k1, k2 (project_only, the reference's project_points); 1: five coefficients; 2: the rigid transform of camera 0 alone, out (P, 3).
 // MODE 0 / 1: out (C, P) double2 planes -- consecutive lanes store consecutive 16-byte elements.  24 + 16 C bytes per point.
 template <int MODE>
@@ -104,27 +97,17 @@ int launch_keypoint_errors(hipStream_t st, const double* pts, const double* uvs,
   return 0;
 }
 
-template <bool WEIGHTED>
-static int tri_refine_go(hipStream_t st, int loss, const double* uvs, const double* start, size_t npts, const KpCam* cams, int C, double f_scale, int max_iterations, double* out, double* info,
-                         const double* sw) {
-  const dim3 g((unsigned)((npts + 255) / 256)), b(256);
-  const double2* uv = reinterpret_cast<const double2*>(uvs);
-  switch (loss) {   // one kernel per loss: loss_weights takes it as a template argument
-    case LOSS_LINEAR: k_tri_refine<LOSS_LINEAR, WEIGHTED><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info, sw); break;
-    case LOSS_SOFT_L1: k_tri_refine<LOSS_SOFT_L1, WEIGHTED><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info, sw); break;
-    case LOSS_HUBER: k_tri_refine<LOSS_HUBER, WEIGHTED><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info, sw); break;
-    case LOSS_CAUCHY: k_tri_refine<LOSS_CAUCHY, WEIGHTED><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info, sw); break;
-    case LOSS_ARCTAN: k_tri_refine<LOSS_ARCTAN, WEIGHTED><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info, sw); break;
-    default: return 1;
-  }
-  return 0;
-}
-
 int launch_tri_refine(hipStream_t st, int loss, const double* uvs, const double* start, size_t npts, const KpCam* cams, int C, double f_scale, int max_iterations, double* out, double* info,
                       const double* sw) {
   if (C < 2 || C > kKpMaxCams) return 1;
-  return sw ? tri_refine_go<true>(st, loss, uvs, start, npts, cams, C, f_scale, max_iterations, out, info, sw)
-            : tri_refine_go<false>(st, loss, uvs, start, npts, cams, C, f_scale, max_iterations, out, info, nullptr);
+  const dim3 g((unsigned)((npts + 255) / 256)), b(256);
+  const double2* uv = reinterpret_cast<const double2*>(uvs);
+  return with_weights(sw, [&](auto W) {
+    return with_loss(loss, [&](auto L) {
+      k_tri_refine<decltype(L)::value, decltype(W)::value><<<g, b, 0, st>>>(uv, start, npts, cams, C, f_scale, max_iterations, out, info, sw);
+      return 0;
+    });
+  });
 }
 
 }  // namespace mcba

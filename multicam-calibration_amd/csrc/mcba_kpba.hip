@@ -14,6 +14,7 @@
 
 #include <algorithm>
 
+#include "mcba_device.h"
 #include "mcba_kernels.h"
 #include "mcba_kpba_math.h"
 
@@ -27,21 +28,6 @@ typedef double kpba_d4 __attribute__((ext_vector_type(4)));
 constexpr int kKbChunk = 256;      // points of one phase 1
 constexpr int kKbPt = 13;          // per point in LDS: L (6) | d (3) | z (3) | usable (1)
 constexpr int kKbMaxGroups = 512;  // workgroups of a pass at most: that many partial systems
-
-// 256-thread tree in a fixed order over s[k][256]; the result in s[k][0]
-template <int K>
-__device__ __forceinline__ void kpba_tree(double (*s)[256], const double* r, const bool* is_max) {
-#pragma unroll
-  for (int k = 0; k < K; ++k) s[k][threadIdx.x] = r[k];
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) s[k][threadIdx.x] = is_max[k] ? fmax(s[k][threadIdx.x], s[k][threadIdx.x + h]) : s[k][threadIdx.x] + s[k][threadIdx.x + h];
-    }
-    __syncthreads();
-  }
-}
 
 // ---------------------------------------------------------------- k_kpba_status
 // WEIGHTED (here and in the kernels below): sw, the (C, P) plane of sqrt(weight), is read beside each detection, which counts where sw > 0.
@@ -217,7 +203,7 @@ __global__ __launch_bounds__(256) void k_kpba_reduce(const double2* __restrict__
   }
   for (int i = t; i < C * kKbAcc; i += 256) out[(size_t)NP * NP + i] = s_acc[i];
   const bool is_max[3] = {false, false, true};
-  kpba_tree<3>(s_r, r, is_max);
+  block_tree<3>(s_r, r, is_max);
   if (t < 4) out[(size_t)NP * NP + (size_t)C * kKbAcc + t] = t < 3 ? s_r[t][0] : 0.0;
 }
 
@@ -241,41 +227,13 @@ __global__ __launch_bounds__(256) void k_kpba_finish(const double* __restrict__ 
   out[i] = s;
 }
 
-template <int LOSS, int TQ, bool WEIGHTED>
-static int kpba_reduce_go(hipStream_t st, size_t lds, int nwg, const double2* uv, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale,
-                          double lam, int G, double* part, const double* sw) {
-  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kpba_reduce<LOSS, TQ, WEIGHTED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
-  hipLaunchKernelGGL((k_kpba_reduce<LOSS, TQ, WEIGHTED>), dim3((unsigned)nwg), dim3(256), lds, st, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
-  return 0;
-}
-
-template <int LOSS, bool WEIGHTED>
-static int kpba_reduce_shape(hipStream_t st, size_t lds, int nwg, const double2* uv, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale,
-                             double lam, int G, double* part, const double* sw) {
-  const int NT = (6 * C + 15) / 16, ntiles = NT * (NT + 1) / 2;   // tiles per wavefront: 3 up to 10 tiles (10 cameras), 12 up to 45
-  if (ntiles <= 12) return kpba_reduce_go<LOSS, 3, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
-  return kpba_reduce_go<LOSS, 12, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
-}
-
 int launch_kpba_status(hipStream_t st, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, int* status, const double* sw) {
   if (C < 2 || C > kKbMaxCams || npts == 0 || npts > ((size_t)1 << 38)) return 1;
   const dim3 g((unsigned)((npts + 255) / 256)), b(256);
-  if (sw) k_kpba_status<true><<<g, b, 0, st>>>(reinterpret_cast<const double2*>(uvs), pts, npts, cams, C, status, sw);
-  else k_kpba_status<false><<<g, b, 0, st>>>(reinterpret_cast<const double2*>(uvs), pts, npts, cams, C, status, nullptr);
-  return 0;
-}
-
-template <bool WEIGHTED>
-static int kpba_reduce_loss(hipStream_t st, int loss, size_t lds, int nwg, const double2* uv, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C,
-                            double f_scale, double lam, int G, double* part, const double* sw) {
-  switch (loss) {   // one kernel per loss: loss_weights takes it as a template argument
-    case LOSS_LINEAR: return kpba_reduce_shape<LOSS_LINEAR, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
-    case LOSS_SOFT_L1: return kpba_reduce_shape<LOSS_SOFT_L1, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
-    case LOSS_HUBER: return kpba_reduce_shape<LOSS_HUBER, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
-    case LOSS_CAUCHY: return kpba_reduce_shape<LOSS_CAUCHY, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
-    case LOSS_ARCTAN: return kpba_reduce_shape<LOSS_ARCTAN, WEIGHTED>(st, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
-    default: return 1;
-  }
+  return with_weights(sw, [&](auto W) {
+    k_kpba_status<decltype(W)::value><<<g, b, 0, st>>>(reinterpret_cast<const double2*>(uvs), pts, npts, cams, C, status, sw);
+    return 0;
+  });
 }
 
 int launch_kpba_reduce(hipStream_t st, int loss, const double* uvs, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale, double lam, int G,
@@ -284,8 +242,14 @@ int launch_kpba_reduce(hipStream_t st, int loss, const double* uvs, const double
   const size_t lds = kpba_reduce_lds(C, G);
   const int nwg = kpba_groups(npts), NP = (6 * C + 15) / 16 * 16;
   const double2* uv = reinterpret_cast<const double2*>(uvs);
-  const int rc = sw ? kpba_reduce_loss<true>(st, loss, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw)
-                    : kpba_reduce_loss<false>(st, loss, lds, nwg, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, nullptr);
+  const int NT = NP / 16, ntiles = NT * (NT + 1) / 2;   // tiles per wavefront: 3 up to 10 tiles (10 cameras), 12 up to 45
+  const int rc = with_weights(sw, [&](auto W) {
+    return with_loss(loss, [&](auto L) {
+      return with_int<3, 12>(ntiles <= 12 ? 3 : 12, [&](auto TQ) {
+        return launch_with_lds(k_kpba_reduce<decltype(L)::value, decltype(TQ)::value, decltype(W)::value>, dim3((unsigned)nwg), lds, st, uv, pts, status, npts, cams, held, C, f_scale, lam, G, part, sw);
+      });
+    });
+  });
   if (rc) return rc;
   const size_t PS = kpba_partial_size(C);
   k_kpba_finish<<<dim3((unsigned)((PS + 255) / 256)), dim3(256), 0, st>>>(part, nwg, NP, C, sys);
@@ -337,24 +301,9 @@ __global__ __launch_bounds__(256) void k_kpba_step(const double2* __restrict__ u
 #pragma unroll
     for (int j = 0; j < 3; ++j) trial[3 * p + j] = Xt[j];   // (a point that takes no part keeps its value in both buffers)
   }
-  const bool is_max[3] = {false, false, false};
-  kpba_tree<3>(s_r, r, is_max);
+  const bool is_max[3] = {false, false, false};   // sums alone
+  block_tree<3>(s_r, r, is_max);
   if (t < 4) part4[4 * (size_t)blockIdx.x + t] = t == 0 ? s_r[0][0] : (t == 1 ? s_r[1][0] : (t == 3 ? s_r[2][0] : 0.0));
-}
-
-template <bool WEIGHTED>
-static int kpba_step_go(hipStream_t st, int nwg, int loss, const double2* uv, const double* pts, double* trial, const int* status, size_t npts, const TcCam* cams2, const double* dtheta, int C,
-                        double f_scale, double lam, double* part4, const double* sw) {
-  const dim3 g((unsigned)nwg), b(256);
-  switch (loss) {
-    case LOSS_LINEAR: k_kpba_step<LOSS_LINEAR, WEIGHTED><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw); break;
-    case LOSS_SOFT_L1: k_kpba_step<LOSS_SOFT_L1, WEIGHTED><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw); break;
-    case LOSS_HUBER: k_kpba_step<LOSS_HUBER, WEIGHTED><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw); break;
-    case LOSS_CAUCHY: k_kpba_step<LOSS_CAUCHY, WEIGHTED><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw); break;
-    case LOSS_ARCTAN: k_kpba_step<LOSS_ARCTAN, WEIGHTED><<<g, b, 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw); break;
-    default: return 1;
-  }
-  return 0;
 }
 
 int launch_kpba_step(hipStream_t st, int loss, const double* uvs, const double* pts, double* trial, const int* status, size_t npts, const TcCam* cams2, const double* dtheta, int C, double f_scale,
@@ -362,8 +311,12 @@ int launch_kpba_step(hipStream_t st, int loss, const double* uvs, const double* 
   if (C < 2 || C > kKbMaxCams || npts == 0 || npts > ((size_t)1 << 38)) return 1;
   const int nwg = kpba_groups(npts);
   const double2* uv = reinterpret_cast<const double2*>(uvs);
-  if (sw ? kpba_step_go<true>(st, nwg, loss, uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw)
-         : kpba_step_go<false>(st, nwg, loss, uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, nullptr))
+  if (with_weights(sw, [&](auto W) {
+        return with_loss(loss, [&](auto L) {
+          k_kpba_step<decltype(L)::value, decltype(W)::value><<<dim3((unsigned)nwg), dim3(256), 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw);
+          return 0;
+        });
+      }))
     return 1;
   k_kpba_finish<<<dim3(1), dim3(256), 0, st>>>(part4, nwg, 0, 0, out4);
   return 0;

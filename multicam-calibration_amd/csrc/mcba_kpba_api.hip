@@ -127,11 +127,9 @@ int kpba_refuse(const char* who, int n_cameras, size_t n_points, int loss, doubl
 
 // points per group of k_kpba_reduce on this device; MCBA_KPBA_G (test knob) forces the smaller groups at any size
 int kpba_pick_group(const char* who, int C, int device, int* G) {
-  int force_g = 0, lds_optin = 64 * 1024;
+  int force_g = 0;
   if (const char* e = getenv("MCBA_KPBA_G")) force_g = atoi(e);
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.sharedMemPerBlockOptin > 0) lds_optin = (int)std::min<size_t>(prop.sharedMemPerBlockOptin, 160 * 1024);
-  *G = mcba::kpba_group(C, lds_optin, force_g);
+  *G = mcba::kpba_group(C, lds_optin_of(device), force_g);
   if (*G) return MCBA_OK;
   g_err = std::string(who) + ": k_kpba_reduce does not fit the LDS of this device";
   return MCBA_ERR_HIP;

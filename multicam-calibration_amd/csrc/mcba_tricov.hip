@@ -8,15 +8,15 @@
 
 #include <algorithm>
 
+#include "mcba_device.h"
 #include "mcba_kernels.h"
+#include "mcba_quadform.h"
 #include "mcba_tricov_math.h"
 
 // (in both compilation passes: the weighted functor is taken for weighted, the plain one for unweighted)
 static_assert(mcba::KpWeighted<mcba::KpDetections<true>>::value && !mcba::KpWeighted<mcba::KpDetections<false>>::value, "the observation functors select the weighted arithmetic");
 
 namespace mcba {
-
-typedef double tricov_d4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------- k_tricov_point
 // The camera table is staged in LDS as k_tri_refine stages it (the KpCam part of every entry).  No lane leaves before the workgroup's sums.
@@ -27,12 +27,7 @@ __global__ __launch_bounds__(256) void k_tricov_point(const double2* __restrict_
                                                       const double* __restrict__ sw) {
   __shared__ KpCam s_cam[kKpMaxCams];
   __shared__ double s_r[4][256];
-  {
-    const double* src = reinterpret_cast<const double*>(cams);
-    double* dst = reinterpret_cast<double*>(s_cam);
-    for (int i = threadIdx.x; i < 21 * C; i += 256) dst[i] = src[30 * (i / 21) + i % 21];
-    __syncthreads();
-  }
+  stage_cams(s_cam, cams, C);
   const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
   double r[4] = {0.0, 0.0, 0.0, 0.0};
   if (p < npts) {
@@ -48,16 +43,8 @@ __global__ __launch_bounds__(256) void k_tricov_point(const double2* __restrict_
     if (st == TC_OK) { r[0] = wss; r[1] = 2.0 * nv; r[2] = 1.0; }
     if (st == TC_DEGENERATE) r[3] = 1.0;
   }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) s_r[k][threadIdx.x] = r[k];
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s_r[k][threadIdx.x] += s_r[k][threadIdx.x + s];
-    }
-    __syncthreads();
-  }
+  const bool is_max[4] = {false, false, false, false};   // sums alone
+  block_tree<4>(s_r, r, is_max);
   if (threadIdx.x < 4) part[4 * (size_t)blockIdx.x + threadIdx.x] = s_r[threadIdx.x][0];
 }
 
@@ -69,16 +56,8 @@ __global__ __launch_bounds__(256) void k_tricov_final(const double* __restrict__
 #pragma unroll
     for (int k = 0; k < 4; ++k) r[k] += part[4 * (size_t)i + k];
   }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) s_r[k][threadIdx.x] = r[k];
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s_r[k][threadIdx.x] += s_r[k][threadIdx.x + s];
-    }
-    __syncthreads();
-  }
+  const bool is_max[4] = {false, false, false, false};   // sums alone
+  block_tree<4>(s_r, r, is_max);
   if (threadIdx.x == 0) {
     const double wss = s_r[0][0], m = s_r[1][0], nfree = 3.0 * s_r[2][0], ndeg = s_r[3][0];
     info[0] = sigma2_in == sigma2_in ? sigma2_in : tricov_sigma2(wss, m, nfree);
@@ -91,28 +70,17 @@ __global__ __launch_bounds__(256) void k_tricov_final(const double* __restrict__
 
 int tricov_point_blocks(size_t npts) { return (int)((npts + 255) / 256); }
 
-template <bool WEIGHTED>
-static int tricov_point_go(hipStream_t st, int nb, int loss, const double2* uv, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, double* hinv, int* views, int* status,
-                           double* part, const double* sw) {
-  const dim3 g((unsigned)nb), b(256);
-  switch (loss) {
-    case LOSS_LINEAR: k_tricov_point<LOSS_LINEAR, WEIGHTED><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part, sw); break;
-    case LOSS_SOFT_L1: k_tricov_point<LOSS_SOFT_L1, WEIGHTED><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part, sw); break;
-    case LOSS_HUBER: k_tricov_point<LOSS_HUBER, WEIGHTED><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part, sw); break;
-    case LOSS_CAUCHY: k_tricov_point<LOSS_CAUCHY, WEIGHTED><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part, sw); break;
-    case LOSS_ARCTAN: k_tricov_point<LOSS_ARCTAN, WEIGHTED><<<g, b, 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part, sw); break;
-    default: return 1;
-  }
-  return 0;
-}
-
 int launch_tricov_point(hipStream_t st, int loss, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, double sigma2_in, double* hinv, int* views, int* status,
                         double* part, double* info, const double* sw) {
   if (C < 2 || C > kKpMaxCams || npts == 0 || npts > ((size_t)1 << 38)) return 1;
   const int nb = tricov_point_blocks(npts);
   const double2* uv = reinterpret_cast<const double2*>(uvs);
-  if (sw ? tricov_point_go<true>(st, nb, loss, uv, pts, npts, cams, C, f_scale, hinv, views, status, part, sw)
-         : tricov_point_go<false>(st, nb, loss, uv, pts, npts, cams, C, f_scale, hinv, views, status, part, nullptr))
+  if (with_weights(sw, [&](auto W) {
+        return with_loss(loss, [&](auto L) {
+          k_tricov_point<decltype(L)::value, decltype(W)::value><<<dim3((unsigned)nb), dim3(256), 0, st>>>(uv, pts, npts, cams, C, f_scale, hinv, views, status, part, sw);
+          return 0;
+        });
+      }))
     return 1;
   k_tricov_final<<<dim3(1), dim3(256), 0, st>>>(part, nb, npts, sigma2_in, info);
   return 0;
@@ -135,16 +103,11 @@ void launch_tricov_scale(hipStream_t st, const double* hinv, const int* status, 
 //   1. the first 6 G threads: H^-1 of the group's points (zero unless the status is TC_OK: such a point's rows are zero)
 //   2. item (camera c, point g), points fastest: G_c of the point -> s_Y[3 g + k][12 c + j]; zero for a camera that does not see the point;
 //      columns n .. KP are zero
-//   3. per panel of 64 columns of Sigma_cc (wavefront w: columns 16 w .. 16 w + 15 of it), K in chunks of 32 rows staged through LDS (the next
-//      chunk's loads fly during the matrix-core phase): Z tile += G tile x Sigma chunk.  Z goes to LDS (over the staging buffer) and thread
-//      (g, k <= l) adds sum_j Z[3 g + k][j] G[3 g + l][j] -- each point's own diagonal block, nothing else.
+//   3. the diagonal blocks of G Sigma_cc G^T: diag_blocks (mcba_quadform.h), thread (g, k <= l) gets entry (k, l) of point g
 //   4. cal6 and det6 = sigma2 H^-1 through LDS in runs of consecutive doubles; points >= P write nothing.
-constexpr int kTcKC = 32, kTcPS = 80, kTcZS = 66;
-
 static size_t tricov_cal_lds(int n, int G) {
   const int KP = (n + 31) / 32 * 32, R = 3 * G;
-  const size_t stage = std::max<size_t>((size_t)kTcKC * kTcPS, (size_t)R * kTcZS);
-  return ((size_t)R * (KP + 2) + stage + (size_t)G * 6 * 3) * sizeof(double);
+  return ((size_t)R * (KP + 2) + stage_doubles(R) + (size_t)G * 6 * 3) * sizeof(double);
 }
 
 // WEIGHTED: item (camera, point) also reads element (c, p) of sw, the plane of sqrt(weight), and is zero unless it is > 0.  The operand costs
@@ -155,13 +118,11 @@ __global__ __launch_bounds__(256, (WEIGHTED && LOSS == LOSS_LINEAR && RT == 3) ?
                                                     const double* __restrict__ hinv, const int* __restrict__ status, const double* __restrict__ Sig, int ld, const double* __restrict__ info,
                                                     double* __restrict__ det6, double* __restrict__ cal6, int G, int KP, const double* __restrict__ sw) {
   extern __shared__ __align__(16) double lds[];
-  const int t = threadIdx.x, lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int t = threadIdx.x;
   const int n = 12 * C, R = 3 * G, RS = KP + 2;
   double* s_Y = lds;                                   // [R][RS]
-  double* s_P = s_Y + (size_t)R * RS;                  // [kTcKC][kTcPS], later [R][kTcZS]
-  const size_t stage = (size_t)kTcKC * kTcPS > (size_t)R * kTcZS ? (size_t)kTcKC * kTcPS : (size_t)R * kTcZS;
-  double* s_Hi = s_P + stage;                          // [G][6]
+  double* s_P = s_Y + (size_t)R * RS;                  // the staging buffer of diag_blocks
+  double* s_Hi = s_P + stage_doubles(R);               // [G][6]
   double* s_oc = s_Hi + G * 6;                         // [G][6] calibration term
   double* s_od = s_oc + G * 6;                         // [G][6] detection term
   const size_t p0 = (size_t)blockIdx.x * G;
@@ -199,66 +160,9 @@ __global__ __launch_bounds__(256, (WEIGHTED && LOSS == LOSS_LINEAR && RT == 3) ?
     }
   }
   for (int it = t; it < R * (KP - n); it += 256) s_Y[(size_t)(it / (KP - n)) * RS + n + it % (KP - n)] = 0.0;
-  // (the first barrier of the panel loop orders these stores before the first read)
+  // (the first barrier of diag_blocks orders these stores before the first read)
 
-  double zy = 0.0;
-  const int nkc = KP / kTcKC, npan = (KP + 63) / 64;
-  int arow[RT];
-#pragma unroll
-  for (int ti = 0; ti < RT; ++ti) arow[ti] = min(16 * ti + (lane & 15), R - 1) * RS + (lane >> 4);   // (rows past R: a duplicate, its results are never stored)
-  for (int J = 0; J < npan; ++J) {
-    const bool active = 64 * J + 16 * wave < KP;   // wave-uniform: this wavefront's 16 columns hold anything
-    tricov_d4 acc[RT];
-#pragma unroll
-    for (int ti = 0; ti < RT; ++ti) acc[ti] = tricov_d4{0.0, 0.0, 0.0, 0.0};
-    double pv[8];
-    auto fetch = [&](int kc) {   // rows 32 kc .. + 31, columns 64 J .. + 63 of the zero-padded ld x ld buffer: inside it (KP <= ld, ld a multiple of 64)
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int idx = t + 256 * q;
-        pv[q] = Sig[(size_t)(kTcKC * kc + (idx >> 6)) * ld + 64 * J + (idx & 63)];
-      }
-    };
-    fetch(0);
-    for (int kc = 0; kc < nkc; ++kc) {
-      __syncthreads();   // the previous chunk's reads (or the previous panel's contraction) are done
-#pragma unroll
-      for (int q = 0; q < 8; ++q) { const int idx = t + 256 * q; s_P[(idx >> 6) * kTcPS + (idx & 63)] = pv[q]; }
-      __syncthreads();
-      if (kc + 1 < nkc) fetch(kc + 1);
-      if (active) {
-#pragma unroll
-        for (int ks = 0; ks < kTcKC / 4; ++ks) {
-          const double b = s_P[(4 * ks + (lane >> 4)) * kTcPS + 16 * wave + (lane & 15)];
-#pragma unroll
-          for (int ti = 0; ti < RT; ++ti) {
-            const double a = s_Y[arow[ti] + kTcKC * kc + 4 * ks];
-            acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[ti], 0, 0, 0);
-          }
-        }
-      }
-    }
-    __syncthreads();   // every wavefront is done with the staging buffer: Z takes its place
-    if (active) {
-#pragma unroll
-      for (int ti = 0; ti < RT; ++ti) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const int row = 16 * ti + 4 * reg + (lane >> 4);
-          if (row < R) s_P[row * kTcZS + 16 * wave + (lane & 15)] = acc[ti][reg];
-        }
-      }
-    }
-    __syncthreads();
-    if (own) {
-      const int jn = min(64, KP - 64 * J);
-      const double* zr = s_P + (3 * og + ok_) * kTcZS;
-      const double* yr = s_Y + (size_t)(3 * og + ol) * RS + 64 * J;
-      double s = 0.0;
-      for (int j = 0; j < jn; ++j) s += zr[j] * yr[j];
-      zy += s;
-    }
-  }
+  const double zy = diag_blocks<RT, 3>(s_Y, s_P, Sig, ld, R, KP, own, og, ok_, ol);
   if (own) {
     s_oc[t] = tricov_cal_entry(zy, good);
     s_od[t] = tricov_det_entry(s_Hi[t], info[0], good);
@@ -280,43 +184,21 @@ int tricov_group(int n, int lds_limit, int force_g) {
   return 0;
 }
 
-template <int LOSS, int RT, bool WEIGHTED>
-static int tricov_cal_go(hipStream_t st, size_t lds, const double2* uv, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status,
-                         const double* Sig, int ld, const double* info, double* det6, double* cal6, int G, int KP, const double* sw) {
-  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tricov_cal<LOSS, RT, WEIGHTED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
-  hipLaunchKernelGGL((k_tricov_cal<LOSS, RT, WEIGHTED>), dim3((unsigned)((npts + G - 1) / G)), dim3(256), lds, st, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
-  return 0;
-}
-
-template <int LOSS, bool WEIGHTED>
-static int tricov_cal_shape(hipStream_t st, size_t lds, const double2* uv, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status,
-                            const double* Sig, int ld, const double* info, double* det6, double* cal6, int G, int KP, const double* sw) {
-  if (G == 16) return tricov_cal_go<LOSS, 3, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
-  if (G == 10) return tricov_cal_go<LOSS, 2, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
-  return tricov_cal_go<LOSS, 1, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
-}
-
-template <bool WEIGHTED>
-static int tricov_cal_loss(hipStream_t st, int loss, size_t lds, const double2* uv, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status,
-                           const double* Sig, int ld, const double* info, double* det6, double* cal6, int G, int KP, const double* sw) {
-  switch (loss) {   // one kernel per loss: loss_weights takes it as a template argument
-    case LOSS_LINEAR: return tricov_cal_shape<LOSS_LINEAR, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
-    case LOSS_SOFT_L1: return tricov_cal_shape<LOSS_SOFT_L1, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
-    case LOSS_HUBER: return tricov_cal_shape<LOSS_HUBER, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
-    case LOSS_CAUCHY: return tricov_cal_shape<LOSS_CAUCHY, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
-    case LOSS_ARCTAN: return tricov_cal_shape<LOSS_ARCTAN, WEIGHTED>(st, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw);
-    default: return 1;
-  }
-}
-
 int launch_tricov_cal(hipStream_t st, int loss, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status, const double* Sig,
                       int ld, const double* info, double* det6, double* cal6, int G, const double* sw) {
   const int n = 12 * C, KP = (n + 31) / 32 * 32;
   if (C < 2 || C > kKpMaxCams || (G != 5 && G != 10 && G != 16) || KP > ld || ld % 64 != 0 || npts == 0 || (npts + G - 1) / G > 0x7fffffffu) return 1;
   const size_t lds = tricov_cal_lds(n, G);
   const double2* uv = reinterpret_cast<const double2*>(uvs);
-  return sw ? tricov_cal_loss<true>(st, loss, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, sw)
-            : tricov_cal_loss<false>(st, loss, lds, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6, G, KP, nullptr);
+  const dim3 grid((unsigned)((npts + G - 1) / G));
+  return with_weights(sw, [&](auto W) {
+    return with_loss(loss, [&](auto L) {
+      return with_int<1, 2, 3>(G == 16 ? 3 : (G == 10 ? 2 : 1), [&](auto RT) {
+        return launch_with_lds(k_tricov_cal<decltype(L)::value, decltype(RT)::value, decltype(W)::value>, grid, lds, st, uv, pts, npts, cams, C, f_scale, hinv, status, Sig, ld, info, det6, cal6,
+                               G, KP, sw);
+      });
+    });
+  });
 }
 
 }  // namespace mcba

@@ -32,11 +32,9 @@ int mcba_triangulation_covariance_weighted(int n_cameras, size_t n_points, const
   const int n = 12 * n_cameras, ld = (n + 63) / 64 * 64;
   int G = 0;
   if (cam_cov) {
-    int force_g = 0, lds_optin = 64 * 1024;
+    int force_g = 0;
     if (const char* e = getenv("MCBA_TRICOV_G")) force_g = atoi(e);   // test knob: the smaller shapes of k_tricov_cal at any size
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.sharedMemPerBlockOptin > 0) lds_optin = (int)std::min<size_t>(prop.sharedMemPerBlockOptin, 160 * 1024);
-    G = mcba::tricov_group(n, lds_optin, force_g);
+    G = mcba::tricov_group(n, lds_optin_of(device), force_g);
     if (!G) return fail(MCBA_ERR_HIP, "mcba_triangulation_covariance: k_tricov_cal does not fit the LDS of this device");
   }
 
