@@ -663,6 +663,26 @@ int mcba_refine_extrinsics_system_weighted(int n_cameras, size_t n_points, const
                                            int loss, double f_scale, double lam, int device, const double* ext_trial, const double* dtheta, int* point_status, double* system, double* trial_points,
                                            double* step4, double* info4);
 
+/* ---- the tiled Schur reduction: extrinsics refinement for rigs of up to 64 cameras (additive to ABI 7) -------------------
+ * The two weighted calls above with one more operand, reduction, behind weights (which may be NULL): MCBA_KPBA_RESIDENT (0) is the call above,
+ * launch for launch (the entry points above call these with 0), with its 2 <= C <= 24.  MCBA_KPBA_TILED (1) takes 2 <= C <= 64 and delivers the
+ * same system in the same layout by k_kpba_factors + k_kpba_reduce_tiled + k_kpba_finish (csrc/mcba_kpba_tiled.hip): the cameras in bands of 16,
+ * the lower triangle of Y Y^T in band pairs, each a workgroup's own, groups of 16 points; the sums are in another order than the resident
+ * reduction's, so the two agree within the rounding bound of either, not bit for bit.  The loop, the gauge rules, the closing step, the host's
+ * solve (at most 377 free rows) and every refusal are the same.  Any other value of reduction: MCBA_ERR_ARG.  MCBA_KPBA_G is not read by the
+ * tiled reduction.
+ *   mcba_refine_extrinsics_reduction          result16[13 .. 15] = {points per group, cameras per band (0: resident), band pairs (0: resident)}
+ *   mcba_refine_extrinsics_system_reduction   info8 = {points per group, partial systems summed, NP, kernel_ms, cameras per band (0: resident),
+ *                                             band pairs (0: resident), reduction, 0} */
+#define MCBA_KPBA_RESIDENT 0
+#define MCBA_KPBA_TILED 1
+int mcba_refine_extrinsics_reduction(int n_cameras, size_t n_points, const double* uvs, const double* weights, int reduction, const double* cam12, const double* dist5, const double* points, int* held,
+                                     int gauge_camera, int scale_camera, int loss, double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* extrinsics_out,
+                                     double* points_out, int* point_status, double* result16, double* history, int history_rows);
+int mcba_refine_extrinsics_system_reduction(int n_cameras, size_t n_points, const double* uvs, const double* weights, int reduction, const double* cam12, const double* dist5, const double* points,
+                                            const int* held, int loss, double f_scale, double lam, int device, const double* ext_trial, const double* dtheta, int* point_status, double* system,
+                                            double* trial_points, double* step4, double* info8);
+
 #ifdef __cplusplus
 }
 #endif

@@ -292,11 +292,21 @@ int launch_tricov_cal(hipStream_t st, int loss, const double* uvs, const double*
 int kpba_group(int C, int lds_limit, int force_g);   // points per group of k_kpba_reduce (64, 32 or 16; 0: no shape fits)
 int kpba_groups(size_t npts);                        // workgroups of a pass: that many partial systems
 size_t kpba_partial_size(int C);                     // doubles of one (partial) system: NP NP + 33 C + 4, NP = 6 C rounded up to 16
-int launch_kpba_status(hipStream_t st, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, int* status, const double* sw = nullptr);
+// wide (here and in launch_kpba_step): the instantiation whose camera tables hold kKtMaxCams, for the tiled reduction
+int launch_kpba_status(hipStream_t st, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, int* status, const double* sw = nullptr, bool wide = false);
 // sys = Y Y^T (NP, NP) | per camera U_c packed lower, g_c, sum Y z (C, 33) | cost, present scalars, max |g_p|, 0; part: kpba_groups() partial systems
 int launch_kpba_reduce(hipStream_t st, int loss, const double* uvs, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale, double lam, int G,
                        double* part, double* sys, const double* sw = nullptr);
 // cams2: the current table and behind it the trial one; trial (P, 3) the trial points; out4 = trial cost, sum dX^2, 0, sum X^2; part4: 4 kpba_groups()
 int launch_kpba_step(hipStream_t st, int loss, const double* uvs, const double* pts, double* trial, const int* status, size_t npts, const TcCam* cams2, const double* dtheta, int C, double f_scale,
-                     double lam, double* part4, double* out4, const double* sw = nullptr);
+                     double lam, double* part4, double* out4, const double* sw = nullptr, bool wide = false);
+void launch_kpba_finish(hipStream_t st, const double* part, int nwg, int C, double* sys);   // k_kpba_finish: nwg partial systems in order -> sys
+// ---- the tiled reduction (mcba_kpba_tiled.hip): the same system for 2 <= C <= 64, camera bands of kKtBand, groups of kKtGroup points.
+constexpr int kKtMaxCams = 64, kKtBand = 16, kKtGroup = 16;
+int kpba_tiled_groups(int C, size_t npts);   // workgroups along the points = partial systems: all of them within the resident path's largest allocation
+int kpba_tiled_pairs(int C);                 // band pairs (I >= J)
+size_t kpba_tiled_lds();                     // dynamic LDS of k_kpba_reduce_tiled, the same for every C
+// fac: (P, 13) point factors, written by k_kpba_factors and read by k_kpba_reduce_tiled; part: kpba_tiled_groups() partial systems
+int launch_kpba_reduce_tiled(hipStream_t st, int loss, const double* uvs, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale, double lam,
+                             double* fac, double* part, double* sys, const double* sw = nullptr);
 }  // namespace mcba

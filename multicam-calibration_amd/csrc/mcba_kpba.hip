@@ -31,10 +31,11 @@ constexpr int kKbMaxGroups = 512;  // workgroups of a pass at most: that many pa
 
 // ---------------------------------------------------------------- k_kpba_status
 // WEIGHTED (here and in the kernels below): sw, the (C, P) plane of sqrt(weight), is read beside each detection, which counts where sw > 0.
-template <bool WEIGHTED>
+// CAP (here and in k_kpba_step): the cameras the static tables hold -- kKbMaxCams for the resident reduction, kKtMaxCams for the tiled one.
+template <bool WEIGHTED, int CAP>
 __global__ __launch_bounds__(256) void k_kpba_status(const double2* __restrict__ uvs, const double* __restrict__ pts, size_t npts, const TcCam* __restrict__ cams, int C, int* __restrict__ status,
                                                      const double* __restrict__ sw) {
-  __shared__ TcCam s_cam[kKbMaxCams];
+  __shared__ TcCam s_cam[CAP];
   {
     const double* src = reinterpret_cast<const double*>(cams);
     double* dst = reinterpret_cast<double*>(s_cam);
@@ -227,12 +228,19 @@ __global__ __launch_bounds__(256) void k_kpba_finish(const double* __restrict__ 
   out[i] = s;
 }
 
-int launch_kpba_status(hipStream_t st, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, int* status, const double* sw) {
-  if (C < 2 || C > kKbMaxCams || npts == 0 || npts > ((size_t)1 << 38)) return 1;
+void launch_kpba_finish(hipStream_t st, const double* part, int nwg, int C, double* sys) {
+  const size_t PS = kpba_partial_size(C);
+  k_kpba_finish<<<dim3((unsigned)((PS + 255) / 256)), dim3(256), 0, st>>>(part, nwg, (6 * C + 15) / 16 * 16, C, sys);
+}
+
+int launch_kpba_status(hipStream_t st, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, int* status, const double* sw, bool wide) {
+  if (C < 2 || C > (wide ? kKtMaxCams : kKbMaxCams) || npts == 0 || npts > ((size_t)1 << 38)) return 1;
   const dim3 g((unsigned)((npts + 255) / 256)), b(256);
   return with_weights(sw, [&](auto W) {
-    k_kpba_status<decltype(W)::value><<<g, b, 0, st>>>(reinterpret_cast<const double2*>(uvs), pts, npts, cams, C, status, sw);
-    return 0;
+    return with_int<kKbMaxCams, kKtMaxCams>(wide ? kKtMaxCams : kKbMaxCams, [&](auto CAP) {
+      k_kpba_status<decltype(W)::value, decltype(CAP)::value><<<g, b, 0, st>>>(reinterpret_cast<const double2*>(uvs), pts, npts, cams, C, status, sw);
+      return 0;
+    });
   });
 }
 
@@ -251,19 +259,18 @@ int launch_kpba_reduce(hipStream_t st, int loss, const double* uvs, const double
     });
   });
   if (rc) return rc;
-  const size_t PS = kpba_partial_size(C);
-  k_kpba_finish<<<dim3((unsigned)((PS + 255) / 256)), dim3(256), 0, st>>>(part, nwg, NP, C, sys);
+  launch_kpba_finish(st, part, nwg, C, sys);
   return 0;
 }
 
 // ---------------------------------------------------------------- k_kpba_step
 // cams: the current table and, behind it, the trial table (2 C entries).  part4 per workgroup: trial cost, sum dX^2, 0, sum X^2.
-template <int LOSS, bool WEIGHTED>
+template <int LOSS, bool WEIGHTED, int CAP>
 __global__ __launch_bounds__(256) void k_kpba_step(const double2* __restrict__ uvs, const double* __restrict__ pts, double* __restrict__ trial, const int* __restrict__ status, size_t npts,
                                                    const TcCam* __restrict__ cams, const double* __restrict__ dtheta, int C, double f_scale, double lam, double* __restrict__ part4,
                                                    const double* __restrict__ sw) {
-  __shared__ TcCam s_cam[2 * kKbMaxCams];
-  __shared__ double s_dth[6 * kKbMaxCams];
+  __shared__ TcCam s_cam[2 * CAP];
+  __shared__ double s_dth[6 * CAP];
   __shared__ double s_r[3][256];
   const int t = threadIdx.x;
   {
@@ -307,14 +314,16 @@ __global__ __launch_bounds__(256) void k_kpba_step(const double2* __restrict__ u
 }
 
 int launch_kpba_step(hipStream_t st, int loss, const double* uvs, const double* pts, double* trial, const int* status, size_t npts, const TcCam* cams2, const double* dtheta, int C, double f_scale,
-                     double lam, double* part4, double* out4, const double* sw) {
-  if (C < 2 || C > kKbMaxCams || npts == 0 || npts > ((size_t)1 << 38)) return 1;
+                     double lam, double* part4, double* out4, const double* sw, bool wide) {
+  if (C < 2 || C > (wide ? kKtMaxCams : kKbMaxCams) || npts == 0 || npts > ((size_t)1 << 38)) return 1;
   const int nwg = kpba_groups(npts);
   const double2* uv = reinterpret_cast<const double2*>(uvs);
   if (with_weights(sw, [&](auto W) {
         return with_loss(loss, [&](auto L) {
-          k_kpba_step<decltype(L)::value, decltype(W)::value><<<dim3((unsigned)nwg), dim3(256), 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw);
-          return 0;
+          return with_int<kKbMaxCams, kKtMaxCams>(wide ? kKtMaxCams : kKbMaxCams, [&](auto CAP) {
+            k_kpba_step<decltype(L)::value, decltype(W)::value, decltype(CAP)::value><<<dim3((unsigned)nwg), dim3(256), 0, st>>>(uv, pts, trial, status, npts, cams2, dtheta, C, f_scale, lam, part4, sw);
+            return 0;
+          });
         });
       }))
     return 1;

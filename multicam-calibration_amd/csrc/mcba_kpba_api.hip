@@ -1,7 +1,7 @@
 // mcba_kpba_api.hip -- the stateless extrinsics-refinement call of include/mcba.h (host arrays in, host arrays out, a device ordinal, no handle),
 // in the idiom of mcba_geom_api.hip: one upload of the detections, then the whole Levenberg-Marquardt loop (kpba_lm, mcba_kpba_math.h) with the
-// kernels of mcba_kpba.hip as its back end.  Per evaluation the camera tables go up (60 C doubles) and the reduced system comes down (at most
-// 144^2 + 33 * 24 + 4 doubles); the dense solve is the host's.  The loop ends at the first HIP error and starts nothing after it.
+// kernels of mcba_kpba.hip -- or, with reduction = MCBA_KPBA_TILED, the reduce of mcba_kpba_tiled.hip (2 to 64 cameras) -- as its back end.  Per
+// evaluation the camera tables go up (60 C doubles) and the reduced system comes down (NP^2 + 33 C + 4 doubles); the dense solve is the host's.  The loop ends at the first HIP error and starts nothing after it.
 // mcba_refine_extrinsics_system is one evaluation of that loop laid open: the same refusals, set-up and back end (kpba_refuse, kpba_pick_group,
 // DeviceBackEnd::setup / reduce / step below), and what the kernels wrote handed back as it is.
 #include "mcba_handle.h"
@@ -15,6 +15,7 @@ struct DeviceBackEnd {
   StatelessCall& call;
   const char* who;   // the entry point, for messages
   int C, loss, G;
+  bool tiled;   // the reduce of mcba_kpba_tiled.hip and the 64-camera tables of k_kpba_status and k_kpba_step
   size_t P;
   double f_scale;
   const double* cam12;
@@ -25,7 +26,7 @@ struct DeviceBackEnd {
   int* d_status = nullptr;
   int* d_held = nullptr;
   mcba::TcCam* d_cams = nullptr;   // current table | trial table
-  double *d_dth = nullptr, *d_part = nullptr, *d_sys = nullptr, *d_part4 = nullptr, *d_out4 = nullptr;
+  double *d_dth = nullptr, *d_part = nullptr, *d_sys = nullptr, *d_part4 = nullptr, *d_out4 = nullptr, *d_fac = nullptr;
   int cur = 0;
   std::vector<mcba::TcCam> tab;   // 2 C
   std::vector<double> host_sys;   // the system of the last reduce, as k_kpba_finish left it
@@ -57,8 +58,9 @@ struct DeviceBackEnd {
     table(ext, tab.data());
     if (int rc = call.put(d_cams, tab.data(), (size_t)C)) return rc;
     HIPCHK(hipEventRecord(call.e0, nullptr));
-    if (mcba::launch_kpba_reduce(nullptr, loss, d_uv, d_pts[cur], d_status, P, d_cams, d_held, C, f_scale, lam, G, d_part, d_sys, d_sw) != 0)
-      return launch_failed("k_kpba_reduce could not be launched");
+    if ((tiled ? mcba::launch_kpba_reduce_tiled(nullptr, loss, d_uv, d_pts[cur], d_status, P, d_cams, d_held, C, f_scale, lam, d_fac, d_part, d_sys, d_sw)
+               : mcba::launch_kpba_reduce(nullptr, loss, d_uv, d_pts[cur], d_status, P, d_cams, d_held, C, f_scale, lam, G, d_part, d_sys, d_sw)) != 0)
+      return launch_failed(tiled ? "k_kpba_reduce_tiled could not be launched" : "k_kpba_reduce could not be launched");
     if (int rc = timed(&reduce_ms)) return rc;
     ++n_reduce;
     const size_t PS = mcba::kpba_partial_size(C);
@@ -76,7 +78,7 @@ struct DeviceBackEnd {
     if (int rc = call.put(d_cams + C, tab.data() + C, (size_t)C)) return rc;
     if (int rc = call.put(d_dth, dtheta, (size_t)6 * C)) return rc;
     HIPCHK(hipEventRecord(call.e0, nullptr));
-    if (mcba::launch_kpba_step(nullptr, loss, d_uv, d_pts[cur], d_pts[1 - cur], d_status, P, d_cams, d_dth, C, f_scale, lam, d_part4, d_out4, d_sw) != 0)
+    if (mcba::launch_kpba_step(nullptr, loss, d_uv, d_pts[cur], d_pts[1 - cur], d_status, P, d_cams, d_dth, C, f_scale, lam, d_part4, d_out4, d_sw, tiled) != 0)
       return launch_failed("k_kpba_step could not be launched");
     if (int rc = timed(&step_ms)) return rc;
     ++n_step;
@@ -85,6 +87,7 @@ struct DeviceBackEnd {
     return MCBA_OK;
   }
   void accept() { cur = 1 - cur; }
+  int partials() const { return tiled ? mcba::kpba_tiled_groups(C, P) : mcba::kpba_groups(P); }   // partial systems of a reduce
   // the detections, their weights (or NULL), both point buffers and the camera tables (at ext) up, the scratch of a pass, then k_kpba_status: point_status (P) on the host
   int setup(const double* uvs, const double* weights, const double* points, const double* ext, int* point_status) {
     tab.resize((size_t)2 * C);
@@ -99,12 +102,14 @@ struct DeviceBackEnd {
     if (int rc = call.scratch(&d_status, P)) return rc;
     if (int rc = call.scratch(&d_held, (size_t)C)) return rc;
     if (int rc = call.scratch(&d_dth, (size_t)6 * C)) return rc;
-    if (int rc = call.scratch(&d_part, (size_t)nwg * mcba::kpba_partial_size(C))) return rc;
+    if (int rc = call.scratch(&d_part, (size_t)partials() * mcba::kpba_partial_size(C))) return rc;
+    if (tiled)
+      if (int rc = call.scratch(&d_fac, (size_t)13 * P)) return rc;
     if (int rc = call.scratch(&d_sys, mcba::kpba_partial_size(C))) return rc;
     if (int rc = call.scratch(&d_part4, (size_t)4 * nwg)) return rc;
     if (int rc = call.scratch(&d_out4, (size_t)4)) return rc;
     HIPCHK(call.start());
-    if (mcba::launch_kpba_status(nullptr, d_uv, d_pts[0], P, d_cams, C, d_status, d_sw) != 0) {
+    if (mcba::launch_kpba_status(nullptr, d_uv, d_pts[0], P, d_cams, C, d_status, d_sw, tiled) != 0) {
       g_err = std::string(who) + ": bad launch (k_kpba_status)";
       return MCBA_ERR_ARG;
     }
@@ -114,9 +119,12 @@ struct DeviceBackEnd {
 };
 
 // what both entry points refuse alike
-int kpba_refuse(const char* who, int n_cameras, size_t n_points, int loss, double f_scale) {
+int kpba_refuse(const char* who, int n_cameras, size_t n_points, int loss, double f_scale, int reduction) {
   const char* why = nullptr;
-  if (n_cameras < 2 || n_cameras > mcba::kKbMaxCams) why = "2 to 24 cameras (the reduced system is held to 144 rows: nine matrix-core tiles)";
+  if (reduction != MCBA_KPBA_RESIDENT && reduction != MCBA_KPBA_TILED) why = "reduction must be MCBA_KPBA_RESIDENT (0) or MCBA_KPBA_TILED (1)";
+  else if (reduction == MCBA_KPBA_TILED && (n_cameras < 2 || n_cameras > mcba::kKtMaxCams)) why = "2 to 64 cameras (the tiled reduction: four bands of 16 cameras)";
+  else if (reduction == MCBA_KPBA_RESIDENT && (n_cameras < 2 || n_cameras > mcba::kKbMaxCams))
+    why = "2 to 24 cameras (the resident reduction holds the reduced system to 144 rows: nine matrix-core tiles; reduction = MCBA_KPBA_TILED takes up to 64)";
   else if (loss < mcba::LOSS_LINEAR || loss > mcba::LOSS_ARCTAN) why = "loss must be one of linear, soft_l1, huber, cauchy, arctan (0 .. 4)";
   else if (!(f_scale > 0.0)) why = "f_scale must be positive";
   else if (n_points == 0) why = "no points";
@@ -126,7 +134,13 @@ int kpba_refuse(const char* who, int n_cameras, size_t n_points, int loss, doubl
 }
 
 // points per group of k_kpba_reduce on this device; MCBA_KPBA_G (test knob) forces the smaller groups at any size
-int kpba_pick_group(const char* who, int C, int device, int* G) {
+int kpba_pick_group(const char* who, int C, int device, int reduction, int* G) {
+  if (reduction == MCBA_KPBA_TILED) {   // one shape for every C
+    *G = mcba::kKtGroup;
+    if (mcba::kpba_tiled_lds() + 8 * 1024 <= (size_t)lds_optin_of(device)) return MCBA_OK;
+    g_err = std::string(who) + ": k_kpba_reduce_tiled does not fit the LDS of this device";
+    return MCBA_ERR_HIP;
+  }
   int force_g = 0;
   if (const char* e = getenv("MCBA_KPBA_G")) force_g = atoi(e);
   *G = mcba::kpba_group(C, lds_optin_of(device), force_g);
@@ -142,16 +156,24 @@ extern "C" {
 int mcba_refine_extrinsics(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, const double* points, int* held, int gauge_camera, int scale_camera, int loss,
                            double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* extrinsics_out, double* points_out, int* point_status, double* result16,
                            double* history, int history_rows) {
-  return mcba_refine_extrinsics_weighted(n_cameras, n_points, uvs, nullptr, cam12, dist5, points, held, gauge_camera, scale_camera, loss, f_scale, ftol, xtol, gtol, max_nfev, device, extrinsics_out,
-                                         points_out, point_status, result16, history, history_rows);
+  return mcba_refine_extrinsics_reduction(n_cameras, n_points, uvs, nullptr, MCBA_KPBA_RESIDENT, cam12, dist5, points, held, gauge_camera, scale_camera, loss, f_scale, ftol, xtol, gtol, max_nfev, device,
+                                          extrinsics_out, points_out, point_status, result16, history, history_rows);
 }
 
 // weights NULL: the call above, launch for launch.  Otherwise the plane of sqrt(w) goes up once beside the detections and the weighted kernels run.
 int mcba_refine_extrinsics_weighted(int n_cameras, size_t n_points, const double* uvs, const double* weights, const double* cam12, const double* dist5, const double* points, int* held,
                                     int gauge_camera, int scale_camera, int loss, double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* extrinsics_out,
                                     double* points_out, int* point_status, double* result16, double* history, int history_rows) {
+  return mcba_refine_extrinsics_reduction(n_cameras, n_points, uvs, weights, MCBA_KPBA_RESIDENT, cam12, dist5, points, held, gauge_camera, scale_camera, loss, f_scale, ftol, xtol, gtol, max_nfev, device,
+                                          extrinsics_out, points_out, point_status, result16, history, history_rows);
+}
+
+// reduction MCBA_KPBA_TILED: the reduce of mcba_kpba_tiled.hip and the wide tables; everything else is the same text
+int mcba_refine_extrinsics_reduction(int n_cameras, size_t n_points, const double* uvs, const double* weights, int reduction, const double* cam12, const double* dist5, const double* points, int* held,
+                                     int gauge_camera, int scale_camera, int loss, double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* extrinsics_out,
+                                     double* points_out, int* point_status, double* result16, double* history, int history_rows) {
   const char* who = weights ? "mcba_refine_extrinsics_weighted" : "mcba_refine_extrinsics";
-  if (int rc = kpba_refuse(who, n_cameras, n_points, loss, f_scale)) return rc;
+  if (int rc = kpba_refuse(who, n_cameras, n_points, loss, f_scale, reduction)) return rc;
   if (!uvs || !cam12 || !points || !held || !extrinsics_out || !points_out || !point_status || !result16 || (history_rows > 0 && !history))
     return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics: non-NULL arrays required");
   if (gauge_camera < 0 || gauge_camera >= n_cameras || scale_camera < 0 || scale_camera >= n_cameras || gauge_camera == scale_camera)
@@ -164,10 +186,10 @@ int mcba_refine_extrinsics_weighted(int n_cameras, size_t n_points, const double
   const int C = n_cameras;
   const size_t P = n_points;
   int G = 0;
-  if (int rc = kpba_pick_group(who, C, device, &G)) return rc;
+  if (int rc = kpba_pick_group(who, C, device, reduction, &G)) return rc;
 
   StatelessCall call;
-  DeviceBackEnd be{call, who, C, loss, G, P, f_scale, cam12, dist5};
+  DeviceBackEnd be{call, who, C, loss, G, reduction == MCBA_KPBA_TILED, P, f_scale, cam12, dist5};
   std::vector<double> ext((size_t)6 * C);
   for (int c = 0; c < C; ++c)
     for (int k = 0; k < 6; ++k) ext[6 * c + k] = cam12[12 * c + 6 + k];
@@ -197,6 +219,7 @@ int mcba_refine_extrinsics_weighted(int n_cameras, size_t n_points, const double
   result16[0] = res.cost; result16[1] = res.cost0; result16[2] = res.optimality; result16[3] = res.nfev; result16[4] = res.njev; result16[5] = res.status; result16[6] = s;
   result16[7] = res.nhist; result16[8] = be.status_ms + be.reduce_ms + be.step_ms; result16[9] = be.reduce_ms; result16[10] = be.n_reduce; result16[11] = be.step_ms; result16[12] = be.n_step;
   result16[13] = G;
+  if (be.tiled) { result16[14] = mcba::kKtBand; result16[15] = mcba::kpba_tiled_pairs(C); }
   return MCBA_OK;
 }
 
@@ -209,10 +232,22 @@ int mcba_refine_extrinsics_system(int n_cameras, size_t n_points, const double* 
 int mcba_refine_extrinsics_system_weighted(int n_cameras, size_t n_points, const double* uvs, const double* weights, const double* cam12, const double* dist5, const double* points, const int* held,
                                            int loss, double f_scale, double lam, int device, const double* ext_trial, const double* dtheta, int* point_status, double* system, double* trial_points,
                                            double* step4, double* info4) {
+  if (!info4) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics_system: non-NULL arrays required (ext_trial and dtheta both or neither; with them trial_points and step4)");
+  double info8[8];
+  const int rc = mcba_refine_extrinsics_system_reduction(n_cameras, n_points, uvs, weights, MCBA_KPBA_RESIDENT, cam12, dist5, points, held, loss, f_scale, lam, device, ext_trial, dtheta, point_status,
+                                                         system, trial_points, step4, info8);
+  if (rc == MCBA_OK)
+    for (int k = 0; k < 4; ++k) info4[k] = info8[k];
+  return rc;
+}
+
+int mcba_refine_extrinsics_system_reduction(int n_cameras, size_t n_points, const double* uvs, const double* weights, int reduction, const double* cam12, const double* dist5, const double* points,
+                                            const int* held, int loss, double f_scale, double lam, int device, const double* ext_trial, const double* dtheta, int* point_status, double* system,
+                                            double* trial_points, double* step4, double* info8) {
   const char* who = weights ? "mcba_refine_extrinsics_system_weighted" : "mcba_refine_extrinsics_system";
-  if (int rc = kpba_refuse(who, n_cameras, n_points, loss, f_scale)) return rc;
+  if (int rc = kpba_refuse(who, n_cameras, n_points, loss, f_scale, reduction)) return rc;
   const bool stepping = ext_trial || dtheta;
-  if (!uvs || !cam12 || !points || !held || !point_status || !system || !info4 || (stepping && (!ext_trial || !dtheta || !trial_points || !step4)))
+  if (!uvs || !cam12 || !points || !held || !point_status || !system || !info8 || (stepping && (!ext_trial || !dtheta || !trial_points || !step4)))
     return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics_system: non-NULL arrays required (ext_trial and dtheta both or neither; with them trial_points and step4)");
   if (!(lam >= 0.0 && lam < mcba::KB_LAMBDA_MAX)) return fail(MCBA_ERR_ARG, "mcba_refine_extrinsics_system: lam must be in [0, 1e12)");
   if (int rc = check_weights(who, weights, (size_t)n_cameras * n_points)) return rc;
@@ -220,10 +255,10 @@ int mcba_refine_extrinsics_system_weighted(int n_cameras, size_t n_points, const
   const int C = n_cameras;
   const size_t P = n_points;
   int G = 0;
-  if (int rc = kpba_pick_group(who, C, device, &G)) return rc;
+  if (int rc = kpba_pick_group(who, C, device, reduction, &G)) return rc;
 
   StatelessCall call;
-  DeviceBackEnd be{call, who, C, loss, G, P, f_scale, cam12, dist5};
+  DeviceBackEnd be{call, who, C, loss, G, reduction == MCBA_KPBA_TILED, P, f_scale, cam12, dist5};
   std::vector<double> ext((size_t)6 * C);
   for (int c = 0; c < C; ++c)
     for (int k = 0; k < 6; ++k) ext[6 * c + k] = cam12[12 * c + 6 + k];
@@ -238,7 +273,8 @@ int mcba_refine_extrinsics_system_weighted(int n_cameras, size_t n_points, const
     if (int rc = call.download(trial_points, be.d_pts[1 - be.cur], 3 * P)) return rc;
     for (int k = 0; k < 4; ++k) step4[k] = be.out4[k];
   }
-  info4[0] = G; info4[1] = mcba::kpba_groups(P); info4[2] = sys.NP; info4[3] = be.status_ms + be.reduce_ms + be.step_ms;
+  info8[0] = G; info8[1] = be.partials(); info8[2] = sys.NP; info8[3] = be.status_ms + be.reduce_ms + be.step_ms;
+  info8[4] = be.tiled ? mcba::kKtBand : 0; info8[5] = be.tiled ? mcba::kpba_tiled_pairs(C) : 0; info8[6] = reduction; info8[7] = 0.0;
   return MCBA_OK;
 }
 

@@ -11,6 +11,7 @@ GPU (`csrc/mcba_keypoints.hip`; no numpy fallback -- without a device every one 
                                  pair's two-view point scored against all detections, the inlier cameras named, the point refitted on them
   refine_extrinsics              (`csrc/mcba_kpba.hip`; no counterpart in the reference) free-point bundle adjustment:
                                  the extrinsics and every 3-D point jointly on the robust reprojection cost of the raw detections
+                                 (2 to 24 cameras; reduction="tiled", `csrc/mcba_kpba_tiled.hip`: up to 64)
   refine_extrinsics_system       one evaluation of refine_extrinsics laid open: the reduced system and the point steps as the kernels wrote them
 The last five use the five-coefficient forward model on the RAW (distorted) detections: no undistortion iteration, so none of its truncation
 error.  With p1 = p2 = k3 = 0 (all bundle_adjust returns) the model is project_points'.
@@ -205,6 +206,21 @@ def triangulate_consensus(all_uvs, all_extrinsics, all_intrinsics, *, threshold,
 
 REFINE_POINT_STATUS = {1: "used", -1: "too few views", -2: "zero diagonal"}
 MAX_REFINE_CAMERAS = 24
+MAX_REFINE_CAMERAS_TILED = 64
+REDUCTIONS = {"resident": 0, "tiled": 1}   # MCBA_KPBA_RESIDENT, MCBA_KPBA_TILED of include/mcba.h
+
+
+def _reduction_limit(who, reduction, C):
+    """the code of `reduction`; ValueError for an unknown one, NotImplementedError for a camera count its reduction does not take"""
+    if not isinstance(reduction, str) or reduction not in REDUCTIONS:
+        raise ValueError(f"reduction must be one of {sorted(REDUCTIONS)}")
+    if reduction == "tiled":
+        if not 2 <= C <= MAX_REFINE_CAMERAS_TILED:
+            raise NotImplementedError(f"{who}(reduction=\"tiled\") supports 2 to {MAX_REFINE_CAMERAS_TILED} cameras, got {C}: four bands of 16 cameras")
+    elif not 2 <= C <= MAX_REFINE_CAMERAS:
+        raise NotImplementedError(f"{who}() supports 2 to {MAX_REFINE_CAMERAS} cameras, got {C}: the resident reduction holds the reduced camera system to 144 rows (nine matrix-core tiles); "
+                                  f"reduction=\"tiled\" takes up to {MAX_REFINE_CAMERAS_TILED}")
+    return REDUCTIONS[reduction]
 
 
 @dataclass
@@ -223,7 +239,7 @@ class ExtrinsicsRefinement:
     held: np.ndarray           # (C, 6) bool: parameters that were not free
     scale: float               # factor of the closing rescale about the gauge camera's centre
     history: np.ndarray        # (evaluations, 3): cost, damping, accepted
-    info: dict                 # kernel_ms, reduce_ms, n_reduce, step_ms, n_step, group, gauge_camera, scale_camera
+    info: dict                 # kernel_ms, reduce_ms, n_reduce, step_ms, n_step, group, reduction, band, band_pairs, gauge_camera, scale_camera
 
 
 def _camera_centres(ext):
@@ -231,7 +247,7 @@ def _camera_centres(ext):
 
 
 def refine_extrinsics(all_uvs, all_extrinsics, all_intrinsics, *, points=None, inliers=None, gauge_camera=0, scale_camera=None, loss="soft_l1", f_scale=1.0, ftol=1e-8, xtol=1e-8, gtol=1e-8,
-                      max_nfev=100, verbose=0, device=0, weights=None):
+                      max_nfev=100, verbose=0, device=0, weights=None, reduction="resident"):
     """Move drifted cameras back with the detections that show the drift: free-point bundle adjustment.  Minimises
     0.5 f_scale^2 sum rho((f / f_scale)^2) over the present scalars f = detection - projection, jointly over the extrinsics of the cameras and
     every 3-D point; the intrinsics stay fixed.  all_uvs, all_extrinsics, all_intrinsics as `triangulate` takes them (raw detections, NaN =
@@ -256,8 +272,11 @@ def refine_extrinsics(all_uvs, all_extrinsics, all_intrinsics, *, points=None, i
     point_status (REFINE_POINT_STATUS): -1 fewer than two views or a NaN start, -2 a zero diagonal in the point's 3 x 3 block; such points
     come back NaN and take no part.  history: per evaluation the cost, the damping and whether it was accepted; verbose=2 prints it.
     ValueError: an unknown loss, f_scale <= 0, max_nfev < 2 (the start and one trial are the least a run needs), gauge_camera == scale_camera,
-    arrays of the wrong shape.  NotImplementedError: fewer than 2 or more than 24 cameras (the reduced system is held to 144 rows).  Without a
-    GPU: ops.McbaError -- there is no host path."""
+    arrays of the wrong shape, an unknown reduction.  NotImplementedError: fewer than 2 or more than 24 cameras (the reduced system is held to
+    144 rows), with reduction="tiled" more than 64.  Without a GPU: ops.McbaError -- there is no host path.
+    reduction: "resident" (a workgroup keeps the whole reduced system in registers: 2 to 24 cameras) or "tiled" (`csrc/mcba_kpba_tiled.hip`:
+    cameras in bands of 16, the system in band pairs: 2 to 64 cameras).  The same system, loop, gauge and closing step; the sums are in another
+    order, so results agree to rounding, not bit for bit.  info gains band and band_pairs (0 for "resident")."""
     from . import solver
     from .triangulation import triangulate
 
@@ -271,8 +290,7 @@ def refine_extrinsics(all_uvs, all_extrinsics, all_intrinsics, *, points=None, i
         raise ValueError("ftol, xtol and gtol must not be negative")
     uvs = _stack_uvs(all_uvs, all_extrinsics, all_intrinsics)
     C, P = uvs.shape[:2]
-    if not 2 <= C <= MAX_REFINE_CAMERAS:
-        raise NotImplementedError(f"refine_extrinsics() supports 2 to {MAX_REFINE_CAMERAS} cameras, got {C}: the reduced camera system is held to 144 rows (nine matrix-core tiles)")
+    red = _reduction_limit("refine_extrinsics", reduction, C)
     if P < 1:
         raise ValueError("refine_extrinsics() needs at least one point")
     ext0 = np.ascontiguousarray(all_extrinsics, dtype=np.float64)
@@ -311,7 +329,9 @@ def refine_extrinsics(all_uvs, all_extrinsics, all_intrinsics, *, points=None, i
     hist = np.zeros((int(max_nfev) + 1, 3))
     tail = (held_bits.ctypes.data, gauge_camera, scale_camera, ops.LOSSES[loss], float(f_scale), float(ftol), float(xtol), float(gtol), int(max_nfev), int(device), ext.ctypes.data, out.ctypes.data,
             status.ctypes.data, res.ctypes.data, hist.ctypes.data, len(hist))
-    if w is None:
+    if red:
+        ops.call("mcba_refine_extrinsics_reduction", C, P, uvs.ctypes.data, None if w is None else w.ctypes.data, red, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, *tail)
+    elif w is None:
         ops.call("mcba_refine_extrinsics", C, P, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, *tail)
     else:
         ops.call("mcba_refine_extrinsics_weighted", C, P, uvs.ctypes.data, w.ctypes.data, cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, *tail)
@@ -331,22 +351,22 @@ def refine_extrinsics(all_uvs, all_extrinsics, all_intrinsics, *, points=None, i
     return ExtrinsicsRefinement(extrinsics=ext, points=out, cost=float(res[0]), cost0=float(res[1]), optimality=float(res[2]), nfev=int(res[3]), njev=int(res[4]), status=code,
                                 message=solver.TERMINATION_MESSAGES[code], success=code > 0, point_status=status, held=held, scale=float(res[6]), history=hist,
                                 info={"kernel_ms": float(res[8]), "reduce_ms": float(res[9]), "n_reduce": int(res[10]), "step_ms": float(res[11]), "n_step": int(res[12]), "group": int(res[13]),
-                                      "gauge_camera": gauge_camera, "scale_camera": scale_camera})
+                                      "reduction": reduction, "band": int(res[14]), "band_pairs": int(res[15]), "gauge_camera": gauge_camera, "scale_camera": scale_camera})
 
 
-def refine_extrinsics_system(all_uvs, all_extrinsics, all_intrinsics, *, points, held, lam, loss="soft_l1", f_scale=1.0, step=None, device=0, weights=None):
+def refine_extrinsics_system(all_uvs, all_extrinsics, all_intrinsics, *, points, held, lam, loss="soft_l1", f_scale=1.0, step=None, device=0, weights=None, reduction="resident"):
     """One evaluation of refine_extrinsics laid open (`mcba_refine_extrinsics_system`; tests and diagnostics): the loop's own set-up and kernels
     run once at (all_extrinsics, points) and the damping lam, and what they wrote comes back as it is.  held: (C, 6) bool or (C,) bit words,
     taken as given -- no gauge, scale or blind-camera rule.  weights: None or (C, P), as refine_extrinsics takes them.  step: None, or (ext_trial (C, 6), dtheta (C, 6)): also the back-substitution.
     Returns a dict: point_status (P,); system (the raw NP NP + 33 C + 4 doubles) and its views YY (NP, NP), acc (C, 33) = U_c packed lower
     (21) | g_c (6) | sum_p Y_cp z_p (6), cost, count (present scalars of the used points), gmax (max |g_p|), tail (the fourth trailing scalar);
-    group, workgroups, NP, kernel_ms; with a step trial_points (P, 3) and step4 = trial cost, sum dX^2, 0, sum X^2."""
+    group, workgroups (the partial systems summed), NP, kernel_ms, reduction, band (cameras per band) and band_pairs (both 0 for "resident"); with a
+    step trial_points (P, 3) and step4 = trial cost, sum dX^2, 0, sum X^2.  reduction: as refine_extrinsics takes it."""
     if callable(loss) or loss not in ops.LOSSES:
         raise ValueError(f"loss must be one of {sorted(ops.LOSSES)}")
     uvs = _stack_uvs(all_uvs, all_extrinsics, all_intrinsics)
     C, P = uvs.shape[:2]
-    if not 2 <= C <= MAX_REFINE_CAMERAS:
-        raise NotImplementedError(f"refine_extrinsics_system() supports 2 to {MAX_REFINE_CAMERAS} cameras, got {C}")
+    red = _reduction_limit("refine_extrinsics_system", reduction, C)
     pts = np.ascontiguousarray(points, dtype=np.float64)
     if pts.shape != (P, 3):
         raise ValueError("points must be (n_points, 3), one row per row of the cameras' uvs")
@@ -358,7 +378,7 @@ def refine_extrinsics_system(all_uvs, all_extrinsics, all_intrinsics, *, points,
         raise ValueError("held must be (n_cameras, 6) bool or (n_cameras,) bit words")
     cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
     NP = (6 * C + 15) // 16 * 16
-    status, system, info = np.empty(P, np.int32), np.empty(NP * NP + 33 * C + 4), np.zeros(4)
+    status, system, info = np.empty(P, np.int32), np.empty(NP * NP + 33 * C + 4), np.zeros(8)
     trial = step4 = ext_trial = dtheta = None
     if step is not None:
         ext_trial, dtheta = (np.ascontiguousarray(a, dtype=np.float64) for a in step)
@@ -369,12 +389,15 @@ def refine_extrinsics_system(all_uvs, all_extrinsics, all_intrinsics, *, points,
     w = _weight_plane(weights, C, P)
     tail = (cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, held_bits.ctypes.data, ops.LOSSES[loss], float(f_scale), float(lam), int(device), addr(ext_trial), addr(dtheta), status.ctypes.data,
             system.ctypes.data, addr(trial), addr(step4), info.ctypes.data)
-    if w is None:
+    if red:
+        ops.call("mcba_refine_extrinsics_system_reduction", C, P, uvs.ctypes.data, addr(w), red, *tail)
+    elif w is None:
         ops.call("mcba_refine_extrinsics_system", C, P, uvs.ctypes.data, *tail)
     else:
         ops.call("mcba_refine_extrinsics_system_weighted", C, P, uvs.ctypes.data, w.ctypes.data, *tail)
     out = dict(point_status=status, system=system, YY=system[:NP * NP].reshape(NP, NP), acc=system[NP * NP:NP * NP + 33 * C].reshape(C, 33), cost=float(system[-4]), count=float(system[-3]),
-               gmax=float(system[-2]), tail=float(system[-1]), group=int(info[0]), workgroups=int(info[1]), NP=int(info[2]), kernel_ms=float(info[3]))
+               gmax=float(system[-2]), tail=float(system[-1]), group=int(info[0]), workgroups=int(info[1]), NP=int(info[2]), kernel_ms=float(info[3]),
+               reduction=reduction, band=int(info[4]), band_pairs=int(info[5]))
     if step is not None:
         out.update(trial_points=trial, step4=step4)
     return out

@@ -133,6 +133,11 @@ SYMBOLS = [
                                                        ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, ctypes.c_int]),
     ("mcba_refine_extrinsics_system_weighted", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _dp, _dp, _dp,
                                                               _dp, _dp, _dp, _dp]),
+    # the tiled Schur reduction: the two calls above with the reduction (0 resident, 1 tiled: up to 64 cameras) behind weights
+    ("mcba_refine_extrinsics_reduction", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, ctypes.c_int]),
+    ("mcba_refine_extrinsics_system_reduction", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                                               _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("mcba_profile_enable", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_stride", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_read", ctypes.c_int, [_h, _dp, _ip, ctypes.c_int, _ip]),

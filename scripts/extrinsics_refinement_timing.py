@@ -1,10 +1,12 @@
 """Extrinsics refinement on the MI355X: wall time of refine_extrinsics (the upload of the detections, the Levenberg-Marquardt loop with its kernels
 and host solves, the copies out) and the milliseconds per k_kpba_reduce pass and per k_kpba_step pass (HIP events around each launch, its finishing
-kernel included), at 2 M points x 6 cameras and at 200 k points x 24 cameras.  Warm, median of five.  A pass reads 16 C P + 24 P bytes of detections and
+kernel included), at 2 M points x 6 cameras and at 200 k points x 24 cameras with the resident reduction, and at 200 k x 24, 48 and 64 cameras with the tiled
+one (k_kpba_factors + k_kpba_reduce_tiled; 200 k x 24 with both: the pair to compare).  Warm, median of five.  A pass reads 16 C P + 24 P bytes of detections and
 points (the algorithmic traffic); its share of the 8 TB/s HBM roof is reported, not gated.
 
-  python scripts/extrinsics_refinement_timing.py [--out DIR] [--shapes 2000000x6,200000x24] [--reps R] [--nfev N]
-  python scripts/extrinsics_refinement_timing.py --child PxC --reps R --nfev N      one measurement (JSON on stdout)
+  python scripts/extrinsics_refinement_timing.py [--out DIR] [--shapes 2000000x6,200000x24,200000x24:tiled,...] [--reduction resident|tiled] [--reps R] [--nfev N]
+  python scripts/extrinsics_refinement_timing.py --child PxC[:reduction] --reps R --nfev N      one measurement (JSON on stdout)
+  A shape is PxC or PxC:reduction; --reduction names the reduction of the shapes that do not say.
   python scripts/extrinsics_refinement_timing.py --design JSON                      rewrite the marked block of DESIGN.md section 8f-12 from a result file
   --weights: the same shapes again with a random weight plane (uniform in [0.1, 3]): the weighted milliseconds per pass beside
   the unweighted ones in the JSON and in the kpba block of DESIGN.md section 8f-13"""
@@ -19,12 +21,17 @@ HBM_BYTES_PER_S = 8.0e12
 BEGIN, END = "<!-- extrinsics_refinement_timing:begin -->", "<!-- extrinsics_refinement_timing:end -->"
 
 
-def child(shape, reps, nfev, weights=False):
+DEFAULT_SHAPES = "2000000x6,200000x24,200000x24:tiled,200000x48:tiled,200000x64:tiled"
+
+
+def child(shape, reps, nfev, weights=False, reduction="resident"):
     import numpy as np
 
     sys.path.insert(0, ROOT)
     from multicam_calibration_amd import synth, refine_extrinsics
 
+    if ":" in shape:
+        shape, reduction = shape.split(":")
     P, C = (int(v) for v in shape.split("x"))
     p = synth.make_problem(C, 2, noise=0.0)
     cam = p["true_cam"]
@@ -43,18 +50,18 @@ def child(shape, reps, nfev, weights=False):
     W = rng.uniform(0.1, 3.0, (C, P)) if weights else None
     for _ in range(reps + 1):   # the first round warms up
         t0 = time.perf_counter()
-        r = refine_extrinsics(uvs, ext, intr, points=X0, loss="soft_l1", max_nfev=nfev)
+        r = refine_extrinsics(uvs, ext, intr, points=X0, loss="soft_l1", max_nfev=nfev, reduction=reduction)
         wall.append((time.perf_counter() - t0) * 1e3)
         red.append(r.info["reduce_ms"] / max(r.info["n_reduce"], 1))
         stp.append(r.info["step_ms"] / max(r.info["n_step"], 1))
         kern.append(r.info["kernel_ms"])
         if weights:
-            rw = refine_extrinsics(uvs, ext, intr, points=X0, loss="soft_l1", max_nfev=nfev, weights=W)
+            rw = refine_extrinsics(uvs, ext, intr, points=X0, loss="soft_l1", max_nfev=nfev, weights=W, reduction=reduction)
             wred.append(rw.info["reduce_ms"] / max(rw.info["n_reduce"], 1))
             wstp.append(rw.info["step_ms"] / max(rw.info["n_step"], 1))
     med = lambda v: float(np.median(v[1:]))   # noqa: E731
     nbytes = 16.0 * C * P + 24.0 * P
-    out = {"shape": shape, "points": P, "cameras": C, "used_points": int((r.point_status == 1).sum()), "group": r.info["group"], "max_nfev": nfev, "nfev": r.nfev, "njev": r.njev,
+    out = {"shape": shape, "points": P, "cameras": C, "reduction": reduction, "band_pairs": r.info["band_pairs"], "used_points": int((r.point_status == 1).sum()), "group": r.info["group"], "max_nfev": nfev, "nfev": r.nfev, "njev": r.njev,
            "n_reduce": r.info["n_reduce"], "n_step": r.info["n_step"], "status": r.status, "cost0": r.cost0, "cost": r.cost,
            "call_ms": med(wall), "kernel_ms": med(kern), "reduce_ms_per_pass": med(red), "step_ms_per_pass": med(stp), "all_reduce_ms_per_pass": red[1:], "all_step_ms_per_pass": stp[1:],
            "pass_bytes": nbytes, "reduce_hbm_fraction": nbytes / (med(red) * 1e-3) / HBM_BYTES_PER_S, "step_hbm_fraction": (nbytes + 24.0 * P) / (med(stp) * 1e-3) / HBM_BYTES_PER_S}
@@ -64,10 +71,10 @@ def child(shape, reps, nfev, weights=False):
 
 
 def design_block(results):
-    lines = [BEGIN, "| points x cameras | points per group | `k_kpba_reduce` pass (ms) | of the HBM roof | `k_kpba_step` pass (ms) | of the HBM roof | whole call (ms), evaluations |",
-             "|---|---|---|---|---|---|---|"]
+    lines = [BEGIN, "| points x cameras | reduction | points per group | reduce pass (ms) | of the HBM roof | `k_kpba_step` pass (ms) | of the HBM roof | whole call (ms), evaluations |",
+             "|---|---|---|---|---|---|---|---|"]
     for r in results:
-        lines.append(f"| {r['points']} x {r['cameras']} | {r['group']} | {r['reduce_ms_per_pass']:.2f} | {100 * r['reduce_hbm_fraction']:.1f} % | {r['step_ms_per_pass']:.2f} | "
+        lines.append(f"| {r['points']} x {r['cameras']} | {r.get('reduction', 'resident')} | {r['group']} | {r['reduce_ms_per_pass']:.2f} | {100 * r['reduce_hbm_fraction']:.1f} % | {r['step_ms_per_pass']:.2f} | "
                      f"{100 * r['step_hbm_fraction']:.1f} % | {r['call_ms']:.0f}, {r['nfev']} |")
     lines.append(END)
     return "\n".join(lines)
@@ -113,7 +120,7 @@ def arg(name, default):
 
 def main():
     out_dir = arg("--out", os.path.join(ROOT, "profiles"))
-    shapes = arg("--shapes", "2000000x6,200000x24").split(",")
+    shapes = [sh if ":" in sh else sh + ":" + arg("--reduction", "resident") for sh in arg("--shapes", DEFAULT_SHAPES).split(",")]
     reps, nfev = arg("--reps", "5"), arg("--nfev", "6")
     os.makedirs(out_dir, exist_ok=True)
     results = []
@@ -133,7 +140,7 @@ def main():
 
 if __name__ == "__main__":
     if "--child" in sys.argv:
-        child(arg("--child", "2000000x6"), int(arg("--reps", "5")), int(arg("--nfev", "6")), "--weights" in sys.argv)
+        child(arg("--child", "2000000x6"), int(arg("--reps", "5")), int(arg("--nfev", "6")), "--weights" in sys.argv, arg("--reduction", "resident"))
     elif "--design" in sys.argv:
         write_design(arg("--design", ""))
     else:
