@@ -138,9 +138,7 @@ static int tile_tables(int device, int NT, int** ti, int** tj) {
 // mcba_create and again by mcba_set_camera_block.
 static int derive_geometry(mcba_handle* h) {
   const int C = h->C, F = h->F, N = h->N, device = h->device;
-  (void)N;
-  const int ncu = h->ncu, slots = 4 * h->ncu;  // wavefront slots at one wavefront per SIMD
-  h->slots = slots;
+  const int ncu = h->ncu, slots = 4 * h->ncu;  // wavefront slots at one wavefront per SIMD: where k_gram's launch variants cut this shard into rounds
   h->n = h->cw * C;
   h->nsys = (size_t)h->n * h->n + 3 * h->n + 16;
   if (h->sparse) {
@@ -183,57 +181,23 @@ static int derive_geometry(mcba_handle* h) {
   }
   }
   h->nbblocks = h->Fpad / 64;
-  // fused k_gram needs >= ~1 wavefront per SIMD (1024) to fill the chip; with fewer (camera, frame-block) pairs the
-  // split-role variant doubles the number of wavefronts.  MCBA_GRAM_SPLIT=0/1 overrides (tuning knob).
-  // Beyond one round (1024 wavefront slots) a small second round costs the fused variant a full pass; the split roles
-  // share SIMDs and fill the tail better (measured 6 x 12500 x 54: 102 us split vs 132 us fused; equal at 1.84 and 2.3 rounds).
+  // k_gram: which launches linearise this shard is a pure function of its shape (mcba_gram_plan.h); what the device and the
+  // environment have to say about it is gathered here
   {
-    const int items = C * h->nfb;
-    h->gram_split = items < 3 * slots / 4 || (items > slots && items <= 3 * slots / 2);
-    // more than one round with a short last round: fused for the whole rounds + split roles for the tail (mode 2)
-    // (measured 24 x 6250 x 200, 2.3 rounds: 536 us vs 561 us fused, 612 us split; at 1.15 rounds plain split roles win)
-    if (items > 2 * slots && (items % slots) > 0 && (items % slots) <= slots / 2) h->gram_split = 2;
-    // Round 3: more than one round with a short last round -> whole rounds fused + the tail's POINTS in chunks over the idle SIMDs
-    // (mode 3; measured 24 x 6250 x 200: k_gram 381 -> 360 us -- profiles/round3/NOTES_round3.md section 6)
-    if (items > slots) {
-      const int fba = ((items / slots) * slots / C) & ~3, tail = C * (h->nfb - fba);
-      // (worth it for large boards only: the chunk launch + the combine launch cost ~25 us whatever the board, the split-role
-      //  tail 0.73 of a fused pass -- break-even near 90 points; 6 x 12500 x 54: 88 us against 79 us with plain split roles)
-      if (fba > 0 && tail > 0 && tail <= slots / 2 && N >= 128) {
-        const int nch = std::min(std::min(8, slots / tail), N / 8);
-        if (nch >= 2) { h->gram_split = 3; h->gram_nchunk = nch; }
-      }
-    }
-  }
-  // Round 4: point split INSIDE the workgroup (k_gram_psplit: the 4 or 2 wavefronts of a (camera, frame block) take a part of the board's
-  // points each and meet in LDS) -- for shards with at most half a round of items, and for a short last round behind whole fused rounds.
-  {
-    static bool ps_ready[64] = {};  // the dynamic-LDS limit of its instances is raised once per device
+    static bool ps_ready[64] = {};  // the dynamic-LDS limit of the point split's instances is raised once per device
     static std::mutex ps_mu;        // (handles may be created from several threads: solver.InProcessShards)
-    bool ps_ok = (size_t)h->lds_optin >= mcba::gram_psplit_lds_bytes(4) + 2048;
+    bool ps_ok = (size_t)h->lds_optin >= mcba::kGramPsplitLdsMax + 2048;
     {
       std::lock_guard<std::mutex> lk(ps_mu);
       if (ps_ok && !ps_ready[device & 63]) { ps_ok = mcba::gram_psplit_set_lds_limit() == 0; ps_ready[device & 63] = ps_ok; (void)hipGetLastError(); }
     }
-    const int items = C * h->nfb;
-    if (ps_ok) {
-      if (items <= slots / 4) { h->gram_split = 4; h->gram_npw = 4; }
-      else if (items <= slots / 2) { h->gram_split = 4; h->gram_npw = 2; }
-      else if (items <= slots) h->gram_split = 0;  // (measured in round 4 at 6 x 7 000 x 54, 660 items: fused 47.4 us, split roles 53.2 us)
-      else if (items > slots) {
-        const int fba = mcba::gram_round_blocks(C, h->nfb, slots), tail = C * (h->nfb - fba);
-        if (fba > 0 && tail > 0 && tail <= slots / 4) { h->gram_split = 5; h->gram_npw = 4; }
-        else if (fba > 0 && tail > 0 && tail <= slots / 2 && h->gram_split != 3) { h->gram_split = 5; h->gram_npw = 2; }
-      }
-    }
-    if (const char* e = getenv("MCBA_GRAM_SPLIT")) {  // 0 fused, 1 split roles, 2 fused + split-role tail, 3 fused + point-chunk tail, 4 point split, 5 fused + point-split tail
-      h->gram_split = std::max(0, std::min(5, atoi(e)));
-      if (h->gram_split == 3 && h->gram_nchunk < 2) h->gram_nchunk = std::max(2, std::min(4, N / 8));
-      if (h->gram_split >= 4 && !ps_ok) { return fail(MCBA_ERR_ARG, "MCBA_GRAM_SPLIT=4/5: this device cannot give k_gram_psplit its LDS"); }
-    }
-    if (const char* e = getenv("MCBA_GRAM_NPW")) h->gram_npw = atoi(e) == 2 ? 2 : 4;
+    mcba::GramShape shape{C, h->nfb, N, slots, h->cw, ps_ok, -1, -1};
+    // tuning knobs: 0 fused, 1 split roles, 2 fused + split-role tail, 3 fused + point-chunk tail, 4 point split, 5 fused + point-split tail
+    if (const char* e = getenv("MCBA_GRAM_SPLIT")) shape.force_split = std::max(0, std::min(5, atoi(e)));
+    if (const char* e = getenv("MCBA_GRAM_NPW")) shape.force_npw = atoi(e) == 2 ? 2 : 4;
+    h->gram = mcba::gram_plan(shape);
+    if (h->gram.refused) { return fail(MCBA_ERR_ARG, "MCBA_GRAM_SPLIT=4/5: this device cannot give k_gram_psplit its LDS"); }
   }
-  if (h->cw == 6 && h->gram_split != 4) h->gram_split = 1;  // intrinsics held fixed: role A alone -- the point split (4), else the role-A half of the split roles
   // k_cost: split the board points so that ~4 waves per SIMD (1024 SIMDs) are in flight
   h->nch = std::max(1, std::min(std::min(8, N / 8), (4 * slots + C * h->nfb - 1) / (C * h->nfb)));
   h->nfblocks = h->G;  // (kept: k_syrk's workgroups factorise their own frames: one (max |g_f|, #failures) pair each)
@@ -296,7 +260,7 @@ int ensure_solver(mcba_handle* h) {
                       {&h->sp_damp, h->sparse ? (size_t)h->npad : 0}, {&h->sp_y, h->sparse ? (size_t)h->npad : 0}, {reinterpret_cast<double**>(&h->sp_ctl), h->sparse ? (size_t)1 : 0}};
     Piece plain[] = {{&h->rec2[0], (size_t)h->Fpad * C * MCBA_REC}, {&h->rec2[1], (size_t)h->Fpad * C * MCBA_REC},
                      {&h->spart, (size_t)h->G * h->NP * 256 + 64},
-                     {&h->gchunk, h->gram_split == 3 ? mcba::gram_chunk_doubles(C, h->nfb, h->gram_nchunk, h->slots) : 0}};
+                     {&h->gchunk, h->gram.chunk_doubles()}};
     auto padded = [](size_t count) { return (std::max<size_t>(count, 1) * sizeof(double) + 255) / 256 * 256; };
     size_t zero_bytes = 0, total = 0;
     for (auto& pc : zeroed) if (pc.count) zero_bytes += padded(pc.count);   // (the sparse-Schur pieces have count 0 on a dense handle: no bytes)
@@ -370,7 +334,7 @@ int upload_impl(mcba_handle* h, const double* uvs, const double* objpoints, bool
 // ---- the solver chain's launches, shared by the host-driven entry points here and the device-resident loops (mcba_lm_api.hip)
 int gram_launch(mcba_handle* h, mcba::Sel sel, const double* xa, const double* xb, int la, int lb) {
   sel.cfl = h->curv_floor;   // (a linearisation's selector carries the curvature floor this handle linearises with: mcba_set_curvature_floor)
-  { Scope sc(h, K_GRAM); mcba::launch_gram(h->stream, h->loss, h->f_scale, h->obs_t, h->obj, sel, xa, xb, h->rec2[la], h->rec2[lb], h->gpart2[la], h->gpart2[lb], h->C, h->N, h->Fpad, h->gram_split, h->planar, h->gchunk, h->gram_nchunk, h->gram_npw, h->cw, h->slots, h->loss_tab); }
+  { Scope sc(h, K_GRAM); mcba::launch_gram(h->stream, h->loss, h->f_scale, h->obs_t, h->obj, sel, xa, xb, h->rec2[la], h->rec2[lb], h->gpart2[la], h->gpart2[lb], h->C, h->N, h->Fpad, h->gram, h->planar, h->gchunk, h->loss_tab); }
   return check_launch();
 }
 

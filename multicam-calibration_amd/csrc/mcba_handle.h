@@ -70,11 +70,8 @@ struct mcba_handle {
   int planar = 0;              // every board point has z = 0 exactly (the fused k_gram then runs its planar instance)
   int *tile_i = nullptr, *tile_j = nullptr;
   int NT = 0, NP = 0, G = 0, sq = 0, sr = 0, FS = 0, ppw = 4, nfblocks = 0, nbblocks = 0, nch = 1;  // k_syrk: G workgroups, sq stages of FS frames each, the first sr one more
-  int gram_nchunk = 0;  // gram_split == 3: point chunks per (camera, frame block) of the tail
-  double* gchunk = nullptr;  // ... and their raw sums
-  int gram_split = 0;  // 0: both accumulator sets in one lane (1 wave/SIMD); 1: two roles, two waves/SIMD (few frames); 2 / 3: fused rounds + split-role / point-chunk tail;
-                       // 4: point split inside the workgroup (gram_npw wavefronts per (camera, frame block)); 5: fused rounds + point-split tail
-  int gram_npw = 4;
+  mcba::GramPlan gram;       // which launches linearise this shard (mcba_gram_plan.h; derive_geometry)
+  double* gchunk = nullptr;  // gram.chunk_doubles() of raw sums: the point-chunk tail's scratch
   double curv_floor = 1.0;  // curvature weight of the NEXT linearisations: max(Triggs, curv_floor rho') -- 1 = IRLS (mcba_set_curvature_floor; csrc/mcba_math.h)
   int cw = 12;         // camera block width: 12, or 6 = the intrinsics of every camera are held fixed (mcba_set_camera_block; BASELINE configs[1]): n = cw C
   size_t nx = 0, nsys = 0;
@@ -103,7 +100,6 @@ struct mcba_handle {
   unsigned long long last_solve_seq = 0;  // sequence number of the last mcba_lm_auto_solve / tick (what a timed-out back-substitution of that launch stamps)
   unsigned long long waited_seq = 0;      // the last tick whose posted state the host has read (mcba_lm_auto_wait): equal to last_solve_seq = nothing posts into the ring any more
   unsigned long long solve_launches = 0;  // k_solve_cam launches so far (SolveArgs.stage_tag)
-  int slots = 1024;  // wavefront slots of the device (4 x CUs): where k_gram's launch variants cut this shard into rounds
   int ncu = 256, lds_optin = 160 * 1024;  // compute units and the LDS a workgroup may ask for (hipGetDeviceProperties at create; MI355X: 256 / 160 KiB)
   bool spec_copy_ready = false;  // the last k_reduce_system was a speculative one: the pre-decision state copy is in place
   double ftol = 1e-8, xtol = 1e-8, gtol = 1e-8, lam_min = 1e-12, lam_max = 1e12;

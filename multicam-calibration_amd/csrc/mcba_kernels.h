@@ -9,6 +9,7 @@
 #define MCBA_GP 92    // k_gram per-wavefront sums, stored [camera][k][frame block]: k = U 78 | g_c 12 | cost | pairs with data
 #define MCBA_FB 40    // per frame: L 21 (diagonal slots hold 1 / L_ii) | z 6 | g_f 6 | D_f 6 | pad
 
+#include "mcba_gram_plan.h"
 #include "mcba_lm_state.h"
 #include "mcba_math.h"
 
@@ -22,18 +23,36 @@ int with_int(int v, F&& f) {
   (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
   return rc;
 }
+// for_each_int: f(std::integral_constant<int, V>{}) for every V of the list, in order -- with_int's twin for the launchers whose kernels
+// need an opt-in to their LDS: the launcher and the opt-in name ONE list (an IntList), so no instance the launcher can reach is left out
+template <int... Vs>
+struct IntList {};
+template <int... Vs, class F>
+int with_int(IntList<Vs...>, int v, F&& f) { return with_int<Vs...>(v, f); }
+template <int... Vs, class F>
+void for_each_int(IntList<Vs...>, F&& f) { (f(std::integral_constant<int, Vs>{}), ...); }
 // one kernel per loss: loss_weights takes it as a template argument.  1 for anything but the five losses
+using LossList = IntList<LOSS_LINEAR, LOSS_SOFT_L1, LOSS_HUBER, LOSS_CAUCHY, LOSS_ARCTAN>;
 template <class F>
-int with_loss(int loss, F&& f) { return with_int<LOSS_LINEAR, LOSS_SOFT_L1, LOSS_HUBER, LOSS_CAUCHY, LOSS_ARCTAN>(loss, f); }
+int with_loss(int loss, F&& f) { return with_int(LossList{}, loss, f); }
+template <class F>
+int with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F>
+void for_each_bool(F&& f) { f(std::false_type{}); f(std::true_type{}); }
 // sw != nullptr: the weighted instantiation
 template <class F>
-int with_weights(const double* sw, F&& f) { return sw ? f(std::true_type{}) : f(std::false_type{}); }
+int with_weights(const double* sw, F&& f) { return with_bool(sw != nullptr, f); }
+// the launch as an expression (0), for the innermost lambda of such a call
+template <class... P, class... A>
+int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+  return 0;
+}
 // opt in to more than 64 KiB of dynamic LDS where the launch asks for it, then launch (256 threads)
 template <class... P, class... A>
 int launch_with_lds(void (*kernel)(P...), dim3 grid, size_t lds, hipStream_t st, A... args) {
   if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
-  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, args...);
-  return 0;
+  return launch(kernel, grid, dim3(256), lds, st, args...);
 }
 
 // Double-buffered operands (parameter slots, linearisation records) and the damping are chosen either from host
@@ -96,19 +115,14 @@ struct SolveArgs {
   double stage_tag;          // > 9 cameras: this launch's number in the handle's life (never repeats: the stager workgroups release it, workgroup 0 waits for it)
 };
 void launch_transpose_obs(hipStream_t st, const double* raw, double* obs_t, int C, int F, int N, int Fpad);
-void launch_gram(hipStream_t st, int loss, double f_scale, const double* obs_t, const double* obj, Sel s, const double* x0, const double* x1, double* rec0, double* rec1, double* gp0, double* gp1, int C, int N, int Fpad, int split,
-                 int planar = 0,   // planar: every board point has z = 0 exactly (with f_scale = 1 the fused kernel's FAST instance runs)
-                 double* chunk = nullptr, int nchunk = 0,   // split == 3: scratch for the point-chunk tail (gram_chunk_doubles) and the number of chunks
-                 int npw = 4,                               // split == 4 / 5 (point split inside the workgroup): wavefronts per (camera, frame block), 4 or 2
-                 int cw = 12,                               // camera block width: 12, or 6 = intrinsics held fixed (role A alone: split 4 = point split, anything else = the role-A half of the split roles)
-                 int slots = 1024,                          // wavefront slots of the device (4 x CUs): where the launch variants cut a shard into rounds
-                 const double* ltab = nullptr);             // loss == LOSS_TABLE: three planes [C][N][Fpad] of (u, v) pairs -- 0.5 f_scale^2 rho, rho', J_scale^2 (mcba_set_loss_table)
+// executes a plan (mcba_gram_plan.h) over C cameras x Fpad / 64 frame blocks.  planar: every board point has z = 0 exactly (with f_scale = 1 the FAST
+// instances run); chunk: plan.chunk_doubles() of scratch; ltab (loss == LOSS_TABLE): three planes [C][N][Fpad] of (u, v) pairs -- 0.5 f_scale^2 rho,
+// rho', J_scale^2 (mcba_set_loss_table)
+void launch_gram(hipStream_t st, int loss, double f_scale, const double* obs_t, const double* obj, Sel s, const double* x0, const double* x1, double* rec0, double* rec1, double* gp0, double* gp1, int C, int N, int Fpad,
+                 const GramPlan& plan, int planar = 0, double* chunk = nullptr, const double* ltab = nullptr);
 void gram_time_next_launch(hipEvent_t start, hipEvent_t stop);  // measurement: the next fused k_gram launch of this thread carries the events on its dispatch (the kernel's own begin / end)
 bool gram_time_pending();                                       // ... still pending after the launch: another variant ran, bracket it the usual way
-int gram_round_blocks(int C, int nfb, int slots);   // frame blocks (a multiple of 4) that whole rounds of the wavefront slots cover; split 2 / 3 / 5 handle the rest as a tail
-size_t gram_psplit_lds_bytes(int npw, int cw = 12);  // dynamic LDS of k_gram_psplit
-int gram_psplit_set_lds_limit();             // raises the dynamic-LDS limit of its instances (0 = ok)
-size_t gram_chunk_doubles(int C, int nfb, int nchunk, int slots);   // doubles of that scratch for C cameras x nfb frame blocks
+int gram_psplit_set_lds_limit();             // raises the dynamic-LDS limit of the point split's instances to kGramPsplitLdsMax (0 = ok)
 void launch_cost(hipStream_t st, int loss, double f_scale, const double* obs_t, const double* obj, const double* x, double* cpart, double* res, int C, int F, int N, int Fpad, int nch,
                  double fill = 0.0);   // what the residual vector holds where a scalar is missing: 0, or NaN (then the vector carries its own row mask)
 size_t syrk_lds_bytes(int C, int FS, int cw = 12);

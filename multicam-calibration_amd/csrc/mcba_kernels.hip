@@ -161,12 +161,7 @@ __global__ __launch_bounds__(256) void k_transpose_obs(const double2* __restrict
 // group's wavefront 0, the role-B sums (ii, ie, hi: 59) to its wavefront 1, each adds them IN PART ORDER and runs its role's half of
 // the expansion (the two halves are independent, see mcba_math.h) -- no second launch and no trip of the raw sums through HBM.  For
 // every shape that is not a whole number of rounds of the 1 024 wavefront slots: few (camera, frame block) items, or a short last round.
-constexpr int kGramRaw = 88;  // ee 21 | he 6 | cost | ii 17 | ie 36 | hi 6 | any
-constexpr int kGramRawA = 29, kGramRawB = 59;  // what role A / role B of the expansion needs of them
-// doubles of the LDS exchange area of a point-split workgroup (gram_body MODE 3): npw wavefronts per group, with / without role B
-__host__ __device__ constexpr int gram_xch_doubles(int npw, bool with_b) {
-  return npw == 4 ? (with_b ? (4 * kGramRawA + 3 * 32 + 3 * 27) * 64 : 4 * kGramRawA * 64) : (4 / npw) * (npw - 1) * (with_b ? kGramRaw : kGramRawA) * 64;
-}
+// (kGramRaw, kGramRawA / B -- the raw per-lane sums and what each role needs of them -- and gram_xch_doubles, the LDS exchange area: mcba_gram_plan.h)
 template <int LOSS, int ROLE, bool FAST = false, int MODE = 0, int NPW = 1>
 __device__ __forceinline__ void gram_body(const CamConst& s_cam, const double2* __restrict__ obs_t, const double* __restrict__ obj, const double* __restrict__ x,
                                           double* __restrict__ rec, double* __restrict__ gpart, int c, int fb, int lane, int C, int N, int Fpad, int nfb, double fs2, double ifs2, double cfl,
@@ -1599,25 +1594,8 @@ __global__ __launch_bounds__(64) void k_jacobian(const double2* __restrict__ obs
 }
 
 // ---------------------------------------------------------------- launch wrappers (host)
-#define DISPATCH_LOSS(loss, CALL)                                  \
-  switch (loss) {                                                  \
-    case LOSS_LINEAR: { constexpr int L = LOSS_LINEAR; CALL; } break;   \
-    case LOSS_SOFT_L1: { constexpr int L = LOSS_SOFT_L1; CALL; } break; \
-    case LOSS_HUBER: { constexpr int L = LOSS_HUBER; CALL; } break;     \
-    case LOSS_CAUCHY: { constexpr int L = LOSS_CAUCHY; CALL; } break;   \
-    default: { constexpr int L = LOSS_ARCTAN; CALL; } break;            \
-  }
-
 void launch_transpose_obs(hipStream_t st, const double* raw, double* obs_t, int C, int F, int N, int Fpad) {
   k_transpose_obs<<<dim3(Fpad / 64, C, (N + 15) / 16), dim3(256), 0, st>>>(reinterpret_cast<const double2*>(raw), reinterpret_cast<double2*>(obs_t), C, F, N, Fpad);
-}
-
-// slots: wavefront slots of the handle's device at one wavefront per SIMD (4 x compute units; derive_geometry keeps it in the handle --
-// not a process-wide value: handles on devices of different sizes may be driven from different threads)
-int gram_round_blocks(int C, int nfb, int slots) { return std::min(nfb, (((C * nfb) / slots) * slots / C) & ~3); }
-size_t gram_psplit_lds_bytes(int npw, int cw) {
-  size_t b = (size_t)gram_xch_doubles(npw == 4 ? 4 : 2, cw != 6) * sizeof(double);
-  return b;
 }
 
 // Measurement aid: the next fused k_gram launch of this thread carries these two events ON ITS DISPATCH (hipExtLaunchKernelGGL): the
@@ -1626,126 +1604,74 @@ static thread_local hipEvent_t t_ext_start = nullptr, t_ext_stop = nullptr;
 void gram_time_next_launch(hipEvent_t start, hipEvent_t stop) { t_ext_start = start; t_ext_stop = stop; }
 bool gram_time_pending() { return t_ext_start != nullptr; }
 
-void launch_gram(hipStream_t st, int loss, double f_scale, const double* obs_t, const double* obj, Sel s, const double* x0, const double* x1, double* rec0, double* rec1, double* gp0, double* gp1, int C, int N, int Fpad, int split,
-                 int planar, double* chunk, int nchunk, int npw, int cw, int slots, const double* ltab) {
+using GramNpwList = IntList<4, 2>;   // the point split's wavefronts per (camera, frame block)
+
+// Executes a plan (mcba_gram_plan.h): which kernels run over which frame blocks, their grids and their LDS are the plan's.
+void launch_gram(hipStream_t st, int loss, double f_scale, const double* obs_t, const double* obj, Sel s, const double* x0, const double* x1, double* rec0, double* rec1, double* gp0, double* gp1, int C, int N, int Fpad,
+                 const GramPlan& p, int planar, double* chunk, const double* ltab) {
   const int nfb = Fpad / 64;
-  dim3 block(256);
-  if (loss == LOSS_TABLE) {   // (the caller's tabulated loss: one launch variant, whatever the shape; the intrinsics held fixed = role A alone)
-    k_gram_table<<<dim3((nfb + 3) / 4, C, cw == 6 ? 1 : 2), block, 0, st>>>(reinterpret_cast<const double2*>(obs_t), obj, s, x0, x1, rec0, rec1, gp0, gp1, C, N, Fpad, nfb, 0, nfb, reinterpret_cast<const double2*>(ltab));
+  const dim3 block(256);
+  const double2* o2 = reinterpret_cast<const double2*>(obs_t);
+  if (loss == LOSS_TABLE) {   // (the caller's tabulated loss: one launch variant, whatever the plan; the intrinsics held fixed = role A alone)
+    k_gram_table<<<dim3(GramPlan::quads(nfb), C, p.with_b ? 2 : 1), block, 0, st>>>(o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, C, N, Fpad, nfb, 0, nfb, reinterpret_cast<const double2*>(ltab));
     return;
   }
   const double fs2 = f_scale * f_scale, ifs2 = 1.0 / fs2;
-  const double2* o2 = reinterpret_cast<const double2*>(obs_t);
-  auto fused = [&](int fb0, int fb1) {
-    dim3 grid((fb1 - fb0 + 3) / 4, C, 1);
-    if (t_ext_start && t_ext_stop) {
-      // measurement (gram_time_next_launch): the events ride on the dispatch itself -- they get the kernel's own begin / end
-      // timestamps, what rocprofv3 reports, not the arrival times of barrier packets around it
-      hipEvent_t ea = t_ext_start, eb = t_ext_stop;
-      t_ext_start = t_ext_stop = nullptr;
-      if (planar && f_scale == 1.0) {
-        DISPATCH_LOSS(loss, (hipExtLaunchKernelGGL((k_gram<L, true>), grid, block, 0, st, ea, eb, 0, o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, C, N, Fpad, nfb, fb0, fb1, fs2, ifs2)));
-      } else {
-        DISPATCH_LOSS(loss, (hipExtLaunchKernelGGL((k_gram<L, false>), grid, block, 0, st, ea, eb, 0, o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, C, N, Fpad, nfb, fb0, fb1, fs2, ifs2)));
-      }
+  const bool fast = planar && f_scale == 1.0;
+  const int head = p.fused_blocks();
+  // the kernels with k_gram's argument list, over the frame blocks [fb0, fb1)
+  auto go = [&](auto kernel, dim3 grid, size_t lds, int fb0, int fb1) { return launch(kernel, grid, block, lds, st, o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, C, N, Fpad, nfb, fb0, fb1, fs2, ifs2); };
+  auto fused = [&](int fb1) {
+    const dim3 grid(GramPlan::quads(fb1), C, 1);
+    // measurement (gram_time_next_launch): the events ride on the dispatch itself -- they get the kernel's own begin / end
+    // timestamps, what rocprofv3 reports, not the arrival times of barrier packets around it
+    hipEvent_t ea = t_ext_start, eb = t_ext_stop;
+    const bool timed = ea && eb;
+    if (timed) t_ext_start = t_ext_stop = nullptr;
+    return with_loss(loss, [&](auto L) { return with_bool(fast, [&](auto FAST) {
+      const auto kernel = k_gram<decltype(L)::value, decltype(FAST)::value>;
+      if (!timed) return go(kernel, grid, 0, 0, fb1);
+      hipExtLaunchKernelGGL(kernel, grid, block, 0, st, ea, eb, 0, o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, C, N, Fpad, nfb, 0, fb1, fs2, ifs2);
+      return 0;
+    }); });
+  };
+  auto roles = [&](int fb0, int nroles) {   // nroles = 1: the role-A half alone (two wavefronts per SIMD)
+    return with_loss(loss, [&](auto L) { return go(k_gram_split<decltype(L)::value>, dim3(GramPlan::quads(nfb - fb0), C, nroles), 0, fb0, nfb); });
+  };
+  // the point split's instances: loss x FAST x wavefronts per (camera, frame block); gram_psplit_set_lds_limit walks the same lists
+  auto point_split = [&](auto&& launch) {
+    return with_loss(loss, [&](auto L) { return with_bool(fast, [&](auto FAST) { return with_int(GramNpwList{}, p.npw, [&](auto NPW) { return launch(L, FAST, NPW); }); }); });
+  };
+  switch (p.whole) {
+    case GRAM_PSPLIT:
+      (void)point_split([&](auto L, auto FAST, auto NPW) { return with_bool(p.with_b, [&](auto B) {
+        return go(k_gram_psplit<decltype(L)::value, decltype(FAST)::value, decltype(NPW)::value, decltype(B)::value ? 2 : 0>, dim3(p.psplit_groups(nfb), C, 1), p.psplit_lds_bytes(), 0, nfb);
+      }); });
       return;
-    }
-    if (planar && f_scale == 1.0) {
-      DISPATCH_LOSS(loss, (k_gram<L, true><<<grid, block, 0, st>>>(o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, C, N, Fpad, nfb, fb0, fb1, fs2, ifs2)));
-    } else {
-      DISPATCH_LOSS(loss, (k_gram<L, false><<<grid, block, 0, st>>>(o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, C, N, Fpad, nfb, fb0, fb1, fs2, ifs2)));
-    }
-  };
-  auto roles = [&](int fb0, int fb1) {
-    dim3 grid((fb1 - fb0 + 3) / 4, C, 2);
-    DISPATCH_LOSS(loss, (k_gram_split<L><<<grid, block, 0, st>>>(o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, C, N, Fpad, nfb, fb0, fb1, fs2, ifs2)));
-  };
-  // point split inside the workgroup: npw = 4 / 2 wavefronts per (camera, frame block), 1 / 2 of them per workgroup
-  auto psplit = [&](int fb0, int fb1) {
-    const int per = npw == 4 ? 1 : 2;
-    dim3 grid((fb1 - fb0 + per - 1) / per, C, 1);
-    const size_t lds = gram_psplit_lds_bytes(npw == 4 ? 4 : 2, cw);
-    const bool fast = planar && f_scale == 1.0;
-#define PS_GO(FASTV, NPWV, ROLEV) DISPATCH_LOSS(loss, (k_gram_psplit<L, FASTV, NPWV, ROLEV><<<grid, block, lds, st>>>(o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, C, N, Fpad, nfb, fb0, fb1, fs2, ifs2)))
-    if (cw == 6) {
-      if (npw == 4) {
-        if (fast) { PS_GO(true, 4, 0); } else { PS_GO(false, 4, 0); }
-      } else {
-        if (fast) { PS_GO(true, 2, 0); } else { PS_GO(false, 2, 0); }
-      }
-    } else if (npw == 4) {
-      if (fast) { PS_GO(true, 4, 2); } else { PS_GO(false, 4, 2); }
-    } else {
-      if (fast) { PS_GO(true, 2, 2); } else { PS_GO(false, 2, 2); }
-    }
-#undef PS_GO
-  };
-  if (cw == 6) {
-    // intrinsics held fixed (camera block 6 wide): role A alone -- the point split for shards of at most half a round of the wavefront
-    // slots, otherwise the role-A half of the split-role kernel (grid.z = 1: two wavefronts per SIMD)
-    if (split == 4) { psplit(0, nfb); return; }
-    dim3 grid((nfb + 3) / 4, C, 1);
-    DISPATCH_LOSS(loss, (k_gram_split<L><<<grid, block, 0, st>>>(o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, C, N, Fpad, nfb, 0, nfb, fs2, ifs2)));
-    return;
+    case GRAM_ROLES: (void)roles(0, 2); return;
+    case GRAM_ROLE_A: (void)roles(0, 1); return;
+    case GRAM_FUSED: break;
   }
-  if (split == 4) { psplit(0, nfb); return; }
-  if (split == 5) {  // whole rounds of the wavefront slots fused, the short last round point-split
-    const int fba5 = gram_round_blocks(C, nfb, slots);
-    if (fba5 > 0 && fba5 < nfb) {
-      const int per = npw == 4 ? 1 : 2, nf = (fba5 + 3) / 4, nt = (nfb - fba5 + per - 1) / per;
-      const size_t lds = gram_psplit_lds_bytes(npw == 4 ? 4 : 2, 12);
-      const bool fast = planar && f_scale == 1.0;
-      dim3 grid((nf + nt) * C);
-#define MX_GO(FASTV, NPWV) DISPATCH_LOSS(loss, (k_gram_mixed<L, FASTV, NPWV><<<grid, block, lds, st>>>(o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, C, N, Fpad, nfb, fba5, nf, nt, fs2, ifs2)))
-      if (npw == 4) {
-        if (fast) { MX_GO(true, 4); } else { MX_GO(false, 4); }
-      } else {
-        if (fast) { MX_GO(true, 2); } else { MX_GO(false, 2); }
-      }
-#undef MX_GO
-    } else fused(0, nfb);
-    return;
-  }
-  if (split == 1) { roles(0, nfb); return; }
-  if (split == 3) {
-    // whole rounds of the 1 024 wavefront slots fused; the last, short round as POINT CHUNKS: nchunk wavefronts per (camera, frame
-    // block), each over 1 / nchunk of the board's points (ppc a multiple of the loop's four), + one combine launch
-    const int items3 = C * nfb;
-    const int fba3 = ((items3 / slots) * slots / C) & ~3;
-    if (fba3 > 0 && fba3 < nfb && chunk && nchunk >= 2) {
-      fused(0, fba3);
-      const int ppc = ((N + nchunk - 1) / nchunk + 3) & ~3;
-      const int nch = (N + ppc - 1) / ppc;
-      dim3 gridc(nfb - fba3, C, nch), gridm((nfb - fba3 + 3) / 4, C, 1);
+  switch (p.tail) {
+    case GRAM_TAIL_NONE: (void)fused(nfb); return;
+    case GRAM_TAIL_ROLES: (void)fused(head); (void)roles(head, 2); return;   // (the split roles' wavefronts are lighter: a tail of r items costs ~0.55 of a fused pass instead of a whole one)
+    case GRAM_TAIL_CHUNKS: {   // p.nrun wavefronts per (camera, frame block) of the tail, each over p.ppc of the board's points, + one combine launch
+      (void)fused(head);
       double2* ck = reinterpret_cast<double2*>(chunk);
-      const bool fast = planar && f_scale == 1.0;
-      if (fast) {
-        DISPATCH_LOSS(loss, (k_gram_chunk<L, true><<<gridc, dim3(64), 0, st>>>(o2, obj, s, x0, x1, ck, C, N, Fpad, nfb, fba3, nfb, fs2, ifs2, ppc, nch)));
-        DISPATCH_LOSS(loss, (k_gram_combine<L, true><<<gridm, block, 0, st>>>(o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, ck, C, N, Fpad, nfb, fba3, nfb, fs2, ifs2, nch)));
-      } else {
-        DISPATCH_LOSS(loss, (k_gram_chunk<L, false><<<gridc, dim3(64), 0, st>>>(o2, obj, s, x0, x1, ck, C, N, Fpad, nfb, fba3, nfb, fs2, ifs2, ppc, nch)));
-        DISPATCH_LOSS(loss, (k_gram_combine<L, false><<<gridm, block, 0, st>>>(o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, ck, C, N, Fpad, nfb, fba3, nfb, fs2, ifs2, nch)));
-      }
+      (void)with_loss(loss, [&](auto L) { return with_bool(fast, [&](auto FAST) {
+        launch(k_gram_chunk<decltype(L)::value, decltype(FAST)::value>, dim3(p.tail_blocks(), C, p.nrun), dim3(64), 0, st, o2, obj, s, x0, x1, ck, C, N, Fpad, nfb, head, nfb, fs2, ifs2, p.ppc, p.nrun);
+        return launch(k_gram_combine<decltype(L)::value, decltype(FAST)::value>, dim3(GramPlan::quads(p.tail_blocks()), C, 1), block, 0, st, o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, ck, C, N, Fpad, nfb, head, nfb, fs2, ifs2, p.nrun);
+      }); });
       return;
     }
-    fused(0, nfb);
-    return;
+    case GRAM_TAIL_PSPLIT: {   // one launch: nf fused workgroups per camera, then nt point-split ones
+      const int nf = GramPlan::quads(head), nt = p.psplit_groups(p.tail_blocks());
+      (void)point_split([&](auto L, auto FAST, auto NPW) {
+        return launch(k_gram_mixed<decltype(L)::value, decltype(FAST)::value, decltype(NPW)::value>, dim3((nf + nt) * C), block, p.psplit_lds_bytes(), st, o2, obj, s, x0, x1, rec0, rec1, gp0, gp1, C, N, Fpad, nfb, head, nf, nt, fs2, ifs2);
+      });
+      return;
+    }
   }
-  // split == 2: whole rounds of the 1024 wavefront slots with the fused variant, the (short) last round with the split
-  // roles -- their wavefronts are lighter, so a tail of r items costs ~0.55 of a fused pass instead of a whole one
-  const int items = C * nfb;
-  const int fba = split == 2 ? (((items / slots) * slots / C) & ~3) : nfb;
-  if (split == 2 && fba > 0 && fba < nfb) {
-    fused(0, fba);
-    roles(fba, nfb);
-  } else {
-    fused(0, nfb);
-  }
-}
-
-size_t gram_chunk_doubles(int C, int nfb, int nchunk, int slots) {
-  const int items = C * nfb, fba = ((items / slots) * slots / C) & ~3;
-  return (size_t)C * (nfb - fba) * nchunk * kGramRaw * 64;
 }
 
 void launch_cost(hipStream_t st, int loss, double f_scale, const double* obs_t, const double* obj, const double* x, double* cpart, double* res, int C, int F, int N, int Fpad, int nch, double fill) {
@@ -1753,11 +1679,9 @@ void launch_cost(hipStream_t st, int loss, double f_scale, const double* obs_t, 
   dim3 grid((nfb + 3) / 4, C, nch), block(256);
   double fs2 = f_scale * f_scale, ifs2 = 1.0 / fs2;
   if (loss == LOSS_TABLE) loss = LOSS_LINEAR;   // (residuals are what this launch is for then: the cost of a tabulated loss is the caller's to evaluate)
-  if (res) {
-    DISPATCH_LOSS(loss, (k_cost<L, true><<<grid, block, 0, st>>>(reinterpret_cast<const double2*>(obs_t), obj, x, cpart, res, C, F, N, Fpad, nfb, nch, fs2, ifs2, fill)));
-  } else {
-    DISPATCH_LOSS(loss, (k_cost<L, false><<<grid, block, 0, st>>>(reinterpret_cast<const double2*>(obs_t), obj, x, cpart, res, C, F, N, Fpad, nfb, nch, fs2, ifs2, fill)));
-  }
+  (void)with_loss(loss, [&](auto L) { return with_bool(res != nullptr, [&](auto WRITE_RES) {
+    return launch(k_cost<decltype(L)::value, decltype(WRITE_RES)::value>, grid, block, 0, st, reinterpret_cast<const double2*>(obs_t), obj, x, cpart, res, C, F, N, Fpad, nfb, nch, fs2, ifs2, fill);
+  }); });
 }
 
 size_t syrk_lds_bytes(int C, int FS, int cw) {
@@ -1765,38 +1689,33 @@ size_t syrk_lds_bytes(int C, int FS, int cw) {
   return ((size_t)NT * 16 * (6 * FS + 2) + (size_t)kSyrkSuper * (34 + 28)) * sizeof(double);
 }
 
-#define SYRK_IPT 5  // (12C+1)*FS <= 256*SYRK_IPT is guaranteed by the choice of FS in mcba_create
-#define SYRK_IPT_SMALL 3
+// The instances of k_syrk: a shape (tile pairs per wavefront, items per thread, camera block width) x DECIDE x XS.  launch_syrk picks the
+// shape and syrk_set_lds_limit walks all of them, both over SyrkShapeList.  Items per thread: (cw C + 1) rows x FS frames over 256 threads --
+// (12 C + 1) FS <= 256 x 5 is guaranteed by the choice of FS in mcba_create; 3 is enough up to 7 cameras at 8 frames per stage (fewer
+// prefetch registers: the kernel stays within 256 registers, two workgroups per CU, without scratch)
+constexpr int kSyrkIpt = 5, kSyrkIptSmall = 3;
+struct SyrkShape { int ppw, ipt, cw; };
+constexpr SyrkShape kSyrkShapes[] = {{4, kSyrkIpt, 12}, {4, kSyrkIptSmall, 12}, {16, kSyrkIpt, 12}, {4, kSyrkIpt, 6}, {4, kSyrkIptSmall, 6}};
+using SyrkShapeList = IntList<0, 1, 2, 3, 4>;
+template <int SHAPE, bool DECIDE, bool XS>
+constexpr auto syrk_kernel = k_syrk<kSyrkShapes[SHAPE].ppw, kSyrkShapes[SHAPE].ipt, DECIDE, XS, kSyrkShapes[SHAPE].cw>;
 
 void launch_syrk(hipStream_t st, Sel s, const SyrkFuse& fz, const double* rec0, const double* rec1, double* fbuf, double* fpart, const int* tile_i, const int* tile_j, double* spart, int C, int F, int Fpad, int NT, int NP, int G, int sq, int sr, int FS, int ppw,
                  const double* dscale, int cw) {
-  size_t lds = syrk_lds_bytes(C, FS, cw);
-#define SYRK_GO(PPW, IPT, GY, CWV)                                                                                                                              \
-  do {                                                                                                                                                          \
-    const bool remap = (GY) > 1;                                                                                                                                \
-    dim3 grid(remap ? 8 * ((G / 8) * (GY) + ((G % 8) * (GY) + 7) / 8) : G, remap ? 1 : (GY));                                                                   \
-    const int xg = remap ? G : 0, yg = remap ? (GY) : 0;                                                                                                        \
-    if (fz.decide && dscale) k_syrk<PPW, IPT, true, true, CWV><<<grid, dim3(256), lds, st>>>(s, fz, rec0, rec1, fbuf, fpart, tile_i, tile_j, spart, C, F, Fpad, NT, NP, sq, sr, FS, dscale, xg, yg);    \
-    else if (fz.decide) k_syrk<PPW, IPT, true, false, CWV><<<grid, dim3(256), lds, st>>>(s, fz, rec0, rec1, fbuf, fpart, tile_i, tile_j, spart, C, F, Fpad, NT, NP, sq, sr, FS, dscale, xg, yg);      \
-    else if (dscale) k_syrk<PPW, IPT, false, true, CWV><<<grid, dim3(256), lds, st>>>(s, fz, rec0, rec1, fbuf, fpart, tile_i, tile_j, spart, C, F, Fpad, NT, NP, sq, sr, FS, dscale, xg, yg);         \
-    else k_syrk<PPW, IPT, false, false, CWV><<<grid, dim3(256), lds, st>>>(s, fz, rec0, rec1, fbuf, fpart, tile_i, tile_j, spart, C, F, Fpad, NT, NP, sq, sr, FS, dscale, xg, yg);                    \
-  } while (0)
-  // items per thread: (12C + 1) rows x FS frames over 256 threads -- 3 is enough up to 7 cameras at 8 frames per stage
-  // (fewer prefetch registers: the kernel stays within 256 registers, two workgroups per CU, without scratch)
-  const bool small = (cw * C + 1) * FS <= 256 * SYRK_IPT_SMALL;
-  if (cw == 6) {  // intrinsics held fixed: rows of (rho, t) alone; mcba_set_camera_block admits it only where the 4-tile variant serves (<= 64 tile pairs)
-    if (small) SYRK_GO(4, SYRK_IPT_SMALL, (NP + 15) / 16, 6);
-    else SYRK_GO(4, SYRK_IPT, (NP + 15) / 16, 6);
-  } else if (ppw <= 4) {
-    if (small) SYRK_GO(4, SYRK_IPT_SMALL, (NP + 15) / 16, 12);
-    else SYRK_GO(4, SYRK_IPT, (NP + 15) / 16, 12);
-  } else {
-    SYRK_GO(16, SYRK_IPT, (NP + 63) / 64, 12);
-  }
-#undef SYRK_GO
+  const size_t lds = syrk_lds_bytes(C, FS, cw);
+  const bool small = (cw * C + 1) * FS <= 256 * kSyrkIptSmall;
+  // intrinsics held fixed: rows of (rho, t) alone; mcba_set_camera_block admits it only where the 4-tile variant serves (<= 64 tile pairs)
+  const int shape = cw == 6 ? (small ? 4 : 3) : ppw <= 4 ? (small ? 1 : 0) : 2;
+  const int gy = (NP + 4 * kSyrkShapes[shape].ppw - 1) / (4 * kSyrkShapes[shape].ppw);
+  const bool remap = gy > 1;
+  const dim3 grid(remap ? 8 * ((G / 8) * gy + ((G % 8) * gy + 7) / 8) : G, remap ? 1 : gy);
+  const int xg = remap ? G : 0, yg = remap ? gy : 0;
+  (void)with_int(SyrkShapeList{}, shape, [&](auto SHAPE) { return with_bool(fz.decide != 0, [&](auto DECIDE) { return with_bool(dscale != nullptr, [&](auto XS) {
+    return launch(syrk_kernel<decltype(SHAPE)::value, decltype(DECIDE)::value, decltype(XS)::value>, grid, dim3(256), lds, st, s, fz, rec0, rec1, fbuf, fpart, tile_i, tile_j, spart, C, F, Fpad, NT, NP, sq, sr, FS, dscale, xg, yg);
+  }); }); });
 }
 
-int syrk_items_per_thread() { return SYRK_IPT; }
+int syrk_items_per_thread() { return kSyrkIpt; }
 
 void launch_reduce_system(hipStream_t st, Sel s, const double* gp0, const double* gp1, const double* spart, const double* fpart, const int* tile_i, const int* tile_j, double* red, int C, int nfb, int G, int NT, int NP, int nfblocks, int rank_slot,
                           const double* bpart, int nbp, double* state_copy, int cw, const double* timeout_word, double seq_prev) {
@@ -1807,13 +1726,17 @@ void launch_reduce_system(hipStream_t st, Sel s, const double* gp0, const double
   else k_reduce_system<1><<<dim3(16 * NP + tail_blocks), dim3(1024), 0, st>>>(s, gp0, gp1, spart, fpart, tile_i, tile_j, red, C, nfb, G, NT, NP, nfblocks, rank_slot, bpart, nbp, state_copy, cw, timeout_word, seq_prev);
 }
 
+template <class DcSrc>
+static void backsub_go(hipStream_t st, Sel s, const double* rec0, const double* rec1, const double* fbuf, const DcSrc& dc, double* x0, double* x1, double* bpart, int C, int F, int Fpad, int cw) {
+  (void)with_int<6, 12>(cw == 6 ? 6 : 12, [&](auto CW) {
+    return launch(k_backsub<DcSrc, decltype(CW)::value>, dim3(Fpad / 64), dim3(64 * std::min(C, kBacksubWaves)), 0, st, s, rec0, rec1, fbuf, dc, x0, x1, bpart, C, F, Fpad);
+  });
+}
 void launch_backsub(hipStream_t st, Sel s, const double* rec0, const double* rec1, const double* fbuf, const CamStep& dc, double* x0, double* x1, double* bpart, int C, int F, int Fpad, int cw) {
-  if (cw == 6) k_backsub<CamStep, 6><<<dim3(Fpad / 64), dim3(64 * std::min(C, kBacksubWaves)), 0, st>>>(s, rec0, rec1, fbuf, dc, x0, x1, bpart, C, F, Fpad);
-  else k_backsub<CamStep, 12><<<dim3(Fpad / 64), dim3(64 * std::min(C, kBacksubWaves)), 0, st>>>(s, rec0, rec1, fbuf, dc, x0, x1, bpart, C, F, Fpad);
+  backsub_go(st, s, rec0, rec1, fbuf, dc, x0, x1, bpart, C, F, Fpad, cw);
 }
 void launch_backsub_dev(hipStream_t st, Sel s, const double* rec0, const double* rec1, const double* fbuf, const double* dc_dev, double* x0, double* x1, double* bpart, int C, int F, int Fpad, int cw) {
-  if (cw == 6) k_backsub<DevStep, 6><<<dim3(Fpad / 64), dim3(64 * std::min(C, kBacksubWaves)), 0, st>>>(s, rec0, rec1, fbuf, DevStep{dc_dev}, x0, x1, bpart, C, F, Fpad);
-  else k_backsub<DevStep, 12><<<dim3(Fpad / 64), dim3(64 * std::min(C, kBacksubWaves)), 0, st>>>(s, rec0, rec1, fbuf, DevStep{dc_dev}, x0, x1, bpart, C, F, Fpad);
+  backsub_go(st, s, rec0, rec1, fbuf, DevStep{dc_dev}, x0, x1, bpart, C, F, Fpad, cw);
 }
 
 void launch_sum_trial(hipStream_t st, Sel s, const double* cp0, const double* cp1, int cstride, int cinner, size_t couter, int ncp, const double* bpart, int nbp, double* out, DecideArgs da) {
@@ -1870,36 +1793,33 @@ void launch_decide(hipStream_t st, const double* trial8, DecideArgs da) {
 void launch_jacobian(hipStream_t st, int loss, double f_scale, const double* obs_raw, const double* obj, const double* x, double* jac, double* res, int C, int F, int N, int Fpad, int robust) {
   if (loss == LOSS_TABLE) { loss = LOSS_LINEAR; robust = 0; }   // (tabulated loss: the unscaled rows; the caller scales them with its own rho)
   double fs2 = f_scale * f_scale, ifs2 = 1.0 / fs2;
-  DISPATCH_LOSS(loss, (k_jacobian<L><<<dim3(F, C), dim3(64), 0, st>>>(reinterpret_cast<const double2*>(obs_raw), obj, x, jac, res, C, F, N, Fpad, robust, fs2, ifs2)));
+  (void)with_loss(loss, [&](auto L) { return launch(k_jacobian<decltype(L)::value>, dim3(F, C), dim3(64), 0, st, reinterpret_cast<const double2*>(obs_raw), obj, x, jac, res, C, F, N, Fpad, robust, fs2, ifs2); });
 }
+
+// The LDS opt-ins, once per device (derive_geometry, ensure_solver): every instance its launcher can reach with more than 64 KiB
+static int raise_lds_limit(const void* kernel, size_t bytes) { return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); }
 
 int gram_psplit_set_lds_limit() {
   int rc = 0;
-#define PS_K(L) reinterpret_cast<const void*>(k_gram_psplit<L, true, 4, 2>), reinterpret_cast<const void*>(k_gram_psplit<L, false, 4, 2>), \
-                reinterpret_cast<const void*>(k_gram_psplit<L, true, 2, 2>), reinterpret_cast<const void*>(k_gram_psplit<L, false, 2, 2>)
-#define MX_K(L) reinterpret_cast<const void*>(k_gram_mixed<L, true, 4>), reinterpret_cast<const void*>(k_gram_mixed<L, false, 4>), \
-                reinterpret_cast<const void*>(k_gram_mixed<L, true, 2>), reinterpret_cast<const void*>(k_gram_mixed<L, false, 2>)
-  const void* ks[] = {PS_K(LOSS_LINEAR), PS_K(LOSS_SOFT_L1), PS_K(LOSS_HUBER), PS_K(LOSS_CAUCHY), PS_K(LOSS_ARCTAN),
-                      MX_K(LOSS_LINEAR), MX_K(LOSS_SOFT_L1), MX_K(LOSS_HUBER), MX_K(LOSS_CAUCHY), MX_K(LOSS_ARCTAN)};
-#undef MX_K
-#undef PS_K
-  for (const void* k : ks) {
-    int r = (int)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_psplit_lds_bytes(4, 12));
-    rc = rc ? rc : r;
-  }
+  for_each_int(LossList{}, [&](auto L) { for_each_bool([&](auto FAST) { for_each_int(GramNpwList{}, [&](auto NPW) {
+    constexpr int l = decltype(L)::value, npw = decltype(NPW)::value;
+    constexpr bool fast = decltype(FAST)::value;
+    // role A alone (ROLE 0) is launched without the opt-in: its exchange area fits
+    static_assert(gram_xch_doubles(npw, false) * sizeof(double) <= 64 * 1024, "k_gram_psplit<..., ROLE 0> needs the LDS opt-in too");
+    for (const void* k : {reinterpret_cast<const void*>(k_gram_psplit<l, fast, npw, 2>), reinterpret_cast<const void*>(k_gram_mixed<l, fast, npw>)}) {
+      const int r = raise_lds_limit(k, kGramPsplitLdsMax);
+      rc = rc ? rc : r;
+    }
+  }); }); });
   return rc;
 }
 
 int syrk_set_lds_limit(size_t bytes) {
   int rc = 0;
-#define SYRK_K(P, I, W) reinterpret_cast<const void*>(k_syrk<P, I, false, false, W>), reinterpret_cast<const void*>(k_syrk<P, I, true, false, W>), \
-                        reinterpret_cast<const void*>(k_syrk<P, I, false, true, W>), reinterpret_cast<const void*>(k_syrk<P, I, true, true, W>)
-  const void* ks[] = {SYRK_K(4, SYRK_IPT, 12), SYRK_K(4, SYRK_IPT_SMALL, 12), SYRK_K(16, SYRK_IPT, 12), SYRK_K(4, SYRK_IPT, 6), SYRK_K(4, SYRK_IPT_SMALL, 6)};
-#undef SYRK_K
-  for (const void* k : ks) {
-    int r = (int)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  for_each_int(SyrkShapeList{}, [&](auto SHAPE) { for_each_bool([&](auto DECIDE) { for_each_bool([&](auto XS) {
+    const int r = raise_lds_limit(reinterpret_cast<const void*>(syrk_kernel<decltype(SHAPE)::value, decltype(DECIDE)::value, decltype(XS)::value>), bytes);
     rc = rc ? rc : r;
-  }
+  }); }); });
   return rc;
 }
 

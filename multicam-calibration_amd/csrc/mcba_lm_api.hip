@@ -61,15 +61,8 @@ static int lm_reduce_chain(mcba_handle* h, int rank_slot, bool spec = false, boo
     fz.decide = 1;
     fz.cp0 = h->gpart2[0] + (size_t)90 * h->nfb;
     fz.cp1 = h->gpart2[1] + (size_t)90 * h->nfb;
-    fz.cstride = 4;  // k_gram: per-workgroup sums in every fourth frame block's slot ...
-    fz.cinner = (h->nfb + 3) / 4;
-    fz.cdense = 1 << 30;
-    // ... except where its point-split variant ran (one frame block per wavefront group: every slot holds its own cost)
-    if (h->gram_split == 4) { fz.cdense = 0; fz.cinner = h->nfb; }
-    else if (h->gram_split == 5) {
-      const int fba = mcba::gram_round_blocks(h->C, h->nfb, h->slots);
-      if (fba > 0 && fba < h->nfb) { fz.cdense = fba / 4; fz.cinner = fba / 4 + (h->nfb - fba); }
-    }
+    const mcba::GramCostSlots cs = h->gram.cost_slots();   // where the linearisation's launches left the trial cost
+    fz.cstride = cs.cstride; fz.cinner = cs.cinner; fz.cdense = cs.cdense;
     fz.couter = (size_t)MCBA_GP * h->nfb;
     fz.ncp = h->C * fz.cinner;
     fz.bpart = h->bpart;
