@@ -155,6 +155,7 @@ static int auto_solve_impl(mcba_handle* h, unsigned long long seq, int decide, b
   // pre-decision state behind): the back-substitution of the next trial step rides along as well
   if (decide && h && h->fuse_backsub && h->spec_copy_ready) fuse_next = true;
   if (!h || !h->auto_ready || seq == 0) return fail(MCBA_ERR_ARG, "mcba_lm_auto_solve: call mcba_lm_auto_config first; seq >= 1");
+  if (h->have_bounds) return fail(MCBA_ERR_ARG, "box constraints are set (mcba_set_bounds): the device-resident loop does not project its trial points -- use the host-driven loop");
   if (!h->have_red) return fail(MCBA_ERR_ARG, "mcba_lm_auto_solve: no reduced system");
   HIPCHK(hipSetDevice(h->device));
   mcba::SolveArgs a;
