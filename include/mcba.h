@@ -683,6 +683,28 @@ int mcba_refine_extrinsics_system_reduction(int n_cameras, size_t n_points, cons
                                             const int* held, int loss, double f_scale, double lam, int device, const double* ext_trial, const double* dtheta, int* point_status, double* system,
                                             double* trial_points, double* step4, double* info8);
 
+/* ---- two-view RANSAC: relative pose from keypoints alone (no reference counterpart; additive to ABI 7) --------------------
+ * Stateless.  uv_a, uv_b (M, 2): the detections of the M >= 8 points both cameras see, compacted by the caller (no NaN); cam12, dist5: two rows
+ * each, camera a then camera b (of cam12 only fx fy cx cy are read); samples (H, 8) ints: the 8 correspondences of each hypothesis, drawn
+ * by the caller.  Per hypothesis the 8-point essential matrix (Hartley-normalised, projected onto singular values 1, 1, 0, |E|_F = sqrt 2, the
+ * entry of largest magnitude positive; x_b^T E x_a = 0 on normalised coordinates, row-major), status 1, or -1 (void: not finite, cost +inf);
+ * every hypothesis is scored over all M points with the truncated squared Sampson distance of the undistorted pixels (undistort_iterations
+ * rounds), sum min(e^2, threshold^2), inlier <=> e^2 <= threshold^2; the lowest (cost, index) wins.  Its four (R, t) are voted on by the
+ * inliers in front of both cameras; the highest (count, -index) wins.  essential_in (H, 9) or NULL: the generator is skipped and these
+ * matrices are scored (tests and diagnostics; samples may then be NULL).
+ * Out: rt12 = R row-major, then t (|t| = 1), x_b = R x_a + t; best4 = {winning hypothesis, its cost, its inliers, inliers in front};
+ * inliers (M bytes, 0 / 1); points (M, 3): the two-view point of every inlier in camera a's frame at unit baseline, NaN for the others;
+ * optional tables essential_out (H, 9), cost_out (H), count_out (H), status_out (H); kernel_ms (6 doubles or NULL): the call's kernels, then
+ * the stages prepare, hypotheses, score, finish, pose.  No sum uses atomics: two calls on the same input return the same bits.
+ * MCBA_ERR_ARG, checked before any device is touched and with nothing written: M < 8, H < 1 or H > MCBA_TWOVIEW_MAX_HYPOTHESES, a sample
+ * index outside 0 .. M - 1 or repeated within a sample, threshold <= 0. */
+#define MCBA_TWOVIEW_MAX_HYPOTHESES 4096
+#define MCBA_TWOVIEW_CHUNK 64               /* hypotheses per workgroup of the scoring kernel (its second grid dimension counts chunks) */
+#define MCBA_TWOVIEW_POINTS_PER_BLOCK 1024  /* points per workgroup of the scoring kernel */
+int mcba_two_view_ransac(size_t n_points, const double* uv_a, const double* uv_b, const double* cam12, const double* dist5, int n_hypotheses, const int* samples, const double* essential_in,
+                         double threshold, int undistort_iterations, int device, double* rt12, double* best4, unsigned char* inliers, double* points, double* essential_out, double* cost_out,
+                         unsigned* count_out, int* status_out, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

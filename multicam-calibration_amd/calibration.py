@@ -87,7 +87,16 @@ def _co_detection_counts(detected):
     buf = np.zeros((bits.shape[0], (bits.shape[1] + 7) // 8 * 8), dtype=np.uint8)
     buf[:, : bits.shape[1]] = bits
     words = buf.view(np.uint64)
-    return np.bitwise_count(words[:, None, :] & words[None, :, :]).sum(2, dtype=np.int64)
+    C = len(words)
+    counts = np.empty((C, C), dtype=np.int64)
+    if hasattr(np, "bitwise_count"):   # NumPy >= 2.  One row at a time: the temporary is C x F / 64 words, not C x C x F / 64
+        for i in range(C):             # (extrinsics_from_keypoints hands in points by the million, not frames by the thousand)
+            counts[i] = np.bitwise_count(words[i] & words).sum(1, dtype=np.int64)
+        return counts
+    flags = np.asarray(detected, dtype=bool)
+    for i in range(C):                 # older NumPy: the integer product, row by row (exact; no BLAS, which is why it is not the first choice)
+        counts[i] = (flags & flags[i]).sum(1, dtype=np.int64)
+    return counts
 
 
 def _spanning_tree(detected, root=0):

@@ -278,6 +278,25 @@ int launch_tri_refine(hipStream_t st, int loss, const double* uvs, const double*
 enum ConsensusForm { CONSENSUS_AUTO = -1, CONSENSUS_LANE = 0, CONSENSUS_WAVE = 1, CONSENSUS_LANE_SEARCH = 2 };
 int launch_consensus(hipStream_t st, int form, int loss, const double* uvs, size_t npts, const KpCam* cams, int C, double threshold, int min_views, int und_iters, double f_scale,
                      int max_iterations, double* out, unsigned long long* mask, double* hyp, double* info);
+// two-view RANSAC (mcba_twoview.hip): the device side of mcba_two_view_ransac, one launcher per stage, every buffer the
+// caller's.  M >= 8 common points, 1 <= H <= MCBA_TWOVIEW_MAX_HYPOTHESES.  Nothing is accumulated with atomics: the results depend on (M, H) alone.
+constexpr int kTvThreads = 256, kTvPPT = 4, kTvPoints = kTvThreads * kTvPPT;   // k_tv_score: points per lane and per workgroup
+constexpr int kTvChunk = 64;                                                    // hypotheses whose F one workgroup of k_tv_score holds in LDS
+struct TvCams { double ka[4], da[5], kb[4], db[5]; };                           // (fx fy cx cy), (k1 k2 p1 p2 k3) of camera a and of camera b
+inline size_t tv_score_blocks(size_t M) { return (M + kTvPoints - 1) / kTvPoints; }
+inline size_t tv_pose_blocks(size_t M) { return (M + kTvThreads - 1) / kTvThreads; }
+// prep: 8 planes of M doubles (undistorted pixels a.x a.y b.x b.y, normalised a.x a.y b.x b.y)
+void launch_tv_prepare(hipStream_t st, const double* uv_a, const double* uv_b, size_t M, const TvCams& cams, int und_iters, double* prep);
+// E, F (H, 9), status (H).  e_in (H, 9) or nullptr: the generator is skipped, E = e_in (void where not finite)
+void launch_tv_hypotheses(hipStream_t st, const double* prep, size_t M, const int* samples, int H, const double* e_in, const TvCams& cams, double* E, double* F, int* status);
+// part_c, part_n: tv_score_blocks(M) x H per-workgroup partial costs and inlier counts
+void launch_tv_score(hipStream_t st, const double* prep, size_t M, const double* F, int H, double threshold, double* part_c, unsigned* part_n);
+// cost (H; +inf for a void hypothesis), count (H); then the winner: win_idx[0], best4[0 .. 2] = (index, cost, inliers), cand (4 x 12) = its four (R, t)
+void launch_tv_finish(hipStream_t st, const double* part_c, const unsigned* part_n, size_t nblk, int H, const double* E, const int* status, double* cost, unsigned* count, int* win_idx, double* best4,
+                      double* cand);
+// inliers (M bytes), part_f: tv_pose_blocks(M) x 4 in-front counts; then win_idx[1] = the candidate, best4[3] = its count, rt12; points (M, 3), NaN for non-inliers
+void launch_tv_pose(hipStream_t st, const double* prep, size_t M, const double* F, const int* status, double threshold, const double* cand, unsigned* part_f, int* win_idx, double* best4, double* rt12,
+                    unsigned char* inliers, double* points);
 // calibration uncertainty (mcba_cov.hip).  Non-zero: arguments out of range.
 // part: 2 x 1024 doubles of scratch; out[0] = sum rho' f^2, out[1] = present scalars of the residual vector res (NaN = missing)
 int launch_cov_wss(hipStream_t st, int loss, double f_scale, const double* res, size_t count, double* part, double* out);

@@ -13,6 +13,9 @@ GPU (`csrc/mcba_keypoints.hip`; no numpy fallback -- without a device every one 
                                  the extrinsics and every 3-D point jointly on the robust reprojection cost of the raw detections
                                  (2 to 24 cameras; reduction="tiled", `csrc/mcba_kpba_tiled.hip`: up to 64)
   refine_extrinsics_system       one evaluation of refine_extrinsics laid open: the reduced system and the point steps as the kernels wrote them
+  estimate_relative_pose         (`csrc/mcba_twoview.hip`; no counterpart in the reference) two-view RANSAC: the pose of one
+                                 camera relative to another from the keypoints both detect, known intrinsics, nothing else
+  extrinsics_from_keypoints      the rig's extrinsics from keypoints alone: a spanning tree of such pairs, a scale chain, refine_extrinsics
 The last five use the five-coefficient forward model on the RAW (distorted) detections: no undistortion iteration, so none of its truncation
 error.  With p1 = p2 = k3 = 0 (all bundle_adjust returns) the model is project_points'.
 
@@ -401,6 +404,206 @@ def refine_extrinsics_system(all_uvs, all_extrinsics, all_intrinsics, *, points,
     if step is not None:
         out.update(trial_points=trial, step4=step4)
     return out
+
+
+# ---------------------------------------------------------------- extrinsics from keypoints alone
+RELATIVE_POSE_STATUS = {1: "ok", -1: "fewer than 8 common points", -2: "too few inliers", -3: "too few points for the scale"}
+MAX_HYPOTHESES = ops.TWOVIEW_MAX_HYPOTHESES
+
+
+def draw_samples(n_common, n_hypotheses, seed):
+    """(n_hypotheses, 8) int32: per hypothesis eight different indices in 0 .. n_common - 1, one
+    `np.random.default_rng(seed).choice(n_common, 8, replace=False)` each from a generator of its own -- the global numpy generator is never
+    touched.  seed: anything default_rng takes (an int, a sequence of ints)."""
+    if int(n_common) < 8:
+        raise ValueError("a sample needs 8 different correspondences")
+    rng = np.random.default_rng(seed)
+    return np.ascontiguousarray(np.stack([rng.choice(int(n_common), 8, replace=False) for _ in range(int(n_hypotheses))]), dtype=np.int32)
+
+
+def _rotation_vector(R):
+    """rodrigues_inv with the cosine clipped to [-1, 1]: a product of rotations may have a trace a rounding above 3"""
+    v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    n = np.linalg.norm(v)
+    return v * np.arccos(np.clip((np.trace(R) - 1) / 2, -1.0, 1.0)) / (n + (n == 0))
+
+
+def _min_inliers(n_common):
+    return max(16, n_common // 10)
+
+
+def _intrinsics_rows(intrinsics_a, intrinsics_b):
+    return _cam_blocks([np.zeros(6), np.zeros(6)], [intrinsics_a, intrinsics_b])
+
+
+def estimate_relative_pose(uvs_a, uvs_b, intrinsics_a, intrinsics_b, *, threshold, n_hypotheses=512, seed=0, undistort_iterations=5, refine=False, loss="soft_l1", f_scale=1.0, device=0,
+                           return_info=False):
+    """The pose of camera b relative to camera a from the keypoints both detect, with known intrinsics and nothing else:
+    (transform (6,), inliers (P,) bool), transform = the rotation vector and the UNIT translation of x_b = R x_a + t (a two-view geometry
+    has no scale).  uvs_a, uvs_b: (P, 2) raw detections, NaN = unseen; intrinsics: (camera_matrix, dist_coefs) each.
+
+    Two-view RANSAC on the GPU (`mcba_two_view_ransac`, `csrc/mcba_twoview.hip`): `n_hypotheses` (at most 4096) 8-point essential matrices from
+    samples drawn on the host (`draw_samples(n_common, n_hypotheses, seed)`), each scored over all common points by the truncated squared
+    Sampson distance of the undistorted pixels, sum min(e^2, threshold^2); the lowest (cost, index) wins, its inliers are e^2 <= threshold^2;
+    of the four (R, t) of the winner the one with most inliers in front of both cameras is returned.  `threshold` (pixels) has no default: it
+    is the detector's noise.  Seeded, without atomics: two calls return the same bits.  A planar scene or a purely rotating pair is
+    degenerate for the 8-point estimate: it shows as few inliers (status -2), not as an exception.
+
+    refine=True: `refine_extrinsics` on the two cameras with the inlier mask (`loss`, `f_scale`), |t| renormalised to 1.
+    return_info=True: also a dict -- n_common, n_inliers, cost, hypothesis, n_in_front, points (P, 3: the two-view point of every inlier in
+    camera a's frame at unit baseline, NaN elsewhere), status (`RELATIVE_POSE_STATUS`: 1 ok, -1 fewer than 8 common points: transform NaN,
+    -2 fewer than max(16, a tenth of the common points) inliers: the estimate is returned but not to be trusted), samples, kernel_ms (the
+    call's kernels, then prepare, hypotheses, score, finish, pose)."""
+    if not threshold > 0:
+        raise ValueError("`threshold` (pixels) must be positive.")
+    H = int(n_hypotheses)
+    if not 1 <= H <= MAX_HYPOTHESES:
+        raise ValueError(f"n_hypotheses must be 1 .. {MAX_HYPOTHESES}")
+    if int(undistort_iterations) < 0:
+        raise ValueError("undistort_iterations must not be negative")
+    ua, ub = np.asarray(uvs_a, dtype=np.float64), np.asarray(uvs_b, dtype=np.float64)
+    if ua.ndim != 2 or ua.shape[1] != 2 or ua.shape != ub.shape:
+        raise ValueError("uvs_a and uvs_b must both be (n_points, 2)")
+    P = len(ua)
+    idx = np.flatnonzero(np.isfinite(ua).all(1) & np.isfinite(ub).all(1))
+    M = len(idx)
+    transform, inliers, points = np.full(6, np.nan), np.zeros(P, dtype=bool), np.full((P, 3), np.nan)
+    info = dict(n_common=M, n_inliers=0, cost=np.nan, hypothesis=-1, n_in_front=0, points=points, status=-1, samples=None, kernel_ms=np.zeros(6))
+    if M >= 8:
+        cam, dist = _intrinsics_rows(intrinsics_a, intrinsics_b)
+        ca, cb = np.ascontiguousarray(ua[idx]), np.ascontiguousarray(ub[idx])
+        samples = draw_samples(M, H, seed)
+        rt, best, mask, pts, ms = np.empty(12), np.empty(4), np.empty(M, dtype=np.uint8), np.empty((M, 3)), np.zeros(6)
+        ops.call("mcba_two_view_ransac", M, ca.ctypes.data, cb.ctypes.data, cam.ctypes.data, dist.ctypes.data, H, samples.ctypes.data, None, float(threshold), int(undistort_iterations), int(device),
+                 rt.ctypes.data, best.ctypes.data, mask.ctypes.data, pts.ctypes.data, None, None, None, None, ms.ctypes.data)
+        inliers[idx] = mask.astype(bool)
+        points[idx] = pts
+        n_in = int(best[2])
+        if np.isfinite(rt).all():
+            transform = np.r_[_rotation_vector(rt[:9].reshape(3, 3)), rt[9:]]
+        info.update(n_inliers=n_in, cost=float(best[1]), hypothesis=int(best[0]), n_in_front=int(best[3]), status=1 if n_in >= _min_inliers(M) else -2, samples=samples, kernel_ms=ms)
+        if refine and np.isfinite(transform).all():
+            res = refine_extrinsics([ua, ub], np.stack([np.zeros(6), transform]), [intrinsics_a, intrinsics_b], inliers=np.stack([inliers, inliers]), gauge_camera=0, scale_camera=1, loss=loss,
+                                    f_scale=f_scale, device=device)
+            transform = res.extrinsics[1].copy()
+            transform[3:] /= np.linalg.norm(transform[3:])
+            info["refinement"] = res
+    return (transform, inliers, info) if return_info else (transform, inliers)
+
+
+@dataclass
+class KeypointExtrinsics:
+    extrinsics: np.ndarray     # (C, 6); the root's row is the exact zero vector
+    points: np.ndarray         # (P, 3) in the root camera's frame
+    tree: list                 # [(i, j), ...]: camera j placed from camera i, in the order of placement
+    edges: list                # per tree edge a dict: cameras, n_common, n_inliers, cost, scale, status
+    edge_inliers: np.ndarray   # (C, P) bool: row j = the inliers of the edge that placed camera j (the root's row is empty)
+    refinement: object         # the ExtrinsicsRefinement, or None
+    scale_camera: int
+    info: dict                 # root, baseline, kernel_ms (the two-view calls), rescale (factor of the closing rescale), reduction
+
+
+def _rescale_about(ext, points, root, scale_camera, baseline):
+    centres = _camera_centres(ext)
+    c0 = centres[root]
+    s = float(baseline) / np.linalg.norm(centres[scale_camera] - c0)
+    out = np.array(ext, dtype=np.float64)
+    for k in range(len(out)):
+        if k != root:
+            out[k, 3:] = -rodrigues(out[k, :3]) @ (c0 + s * (centres[k] - c0))
+    return out, c0 + s * (np.asarray(points) - c0), s
+
+
+def extrinsics_from_keypoints(all_uvs, all_intrinsics, *, threshold, root=0, n_hypotheses=512, seed=0, baseline=1.0, scale_camera=None, refine=True, loss="soft_l1", f_scale=1.0, min_common=16,
+                              reduction=None, device=0, **refine_kwargs):
+    """The extrinsics of a rig from the pose estimator's keypoints alone -- known intrinsics, no board, no starting calibration -- as a
+    `KeypointExtrinsics`: the initialiser in front of `refine_extrinsics` and `triangulate`.  all_uvs: per camera (P, 2) raw detections, NaN =
+    unseen; all_intrinsics: per camera (camera_matrix, dist_coefs).  The frame is camera `root`'s (its extrinsics are the exact zero vector).
+
+    The reconstruction is metric ONLY through `baseline`: keypoints fix the rig up to one global scale, and the result is scaled so that the
+    distance between the centres of `root` and `scale_camera` (None: the other camera of the first tree edge) is exactly `baseline`.  Pass
+    the one distance you have measured, in the unit you want the translations and points in.
+
+    1. the maximum spanning tree of the co-visibility counts (`calibration.get_camera_spanning_tree`'s rule on the (C, P) plane of seen
+       points), edges in order of distance from `root`; a tree edge with fewer than `min_common` common points: ValueError naming the cameras;
+    2. `estimate_relative_pose` per tree edge (i, j), seed [seed, i, j], `threshold`, `n_hypotheses`; an edge of status -2 (too few inliers:
+       a planar scene, a pure rotation, a wrong threshold): ValueError;
+    3. the scale chain, in tree order: the first edge has scale 1; for a later edge (i -> j), X = `triangulate` over the cameras placed so
+       far, Y = the edge's two-view points in camera i's frame, s = median(|R_i X + t_i| / |Y|) over the edge's inliers with finite X,
+       T_j = [R | s t] o T_i; fewer than 8 such points: status -3, ValueError;
+    4. refine=True: `refine_extrinsics(all_uvs, start, all_intrinsics, points=None, gauge_camera=root, scale_camera=..., loss=loss,
+       f_scale=f_scale, reduction=..., **refine_kwargs)`; reduction None = "resident" up to 24 cameras, "tiled" beyond; more than 64 cameras:
+       NotImplementedError.  refine=False returns the chained start and its `triangulate` points;
+    5. the closing rescale about the root to `baseline`.
+    Out of scope: loop closure over pairs outside the tree, unknown intrinsics, per-detection weights."""
+    from .calibration import _spanning_tree
+    from .triangulation import triangulate
+
+    uvs = np.ascontiguousarray(np.stack([np.asarray(u, dtype=np.float64) for u in all_uvs]))
+    if uvs.ndim != 3 or uvs.shape[2] != 2 or len(all_intrinsics) != len(uvs):
+        raise ValueError("all_uvs must be one (n_points, 2) array per camera, matching all_intrinsics")
+    C, P = uvs.shape[:2]
+    if C < 2:
+        raise ValueError("extrinsics_from_keypoints() needs at least two cameras")
+    if C > MAX_REFINE_CAMERAS_TILED:
+        raise NotImplementedError(f"extrinsics_from_keypoints() supports 2 to {MAX_REFINE_CAMERAS_TILED} cameras, got {C}")
+    root = int(root)
+    if not 0 <= root < C:
+        raise ValueError("root is not a camera of the rig")
+    if not baseline > 0:
+        raise ValueError("`baseline` must be positive.")
+    if reduction is None:
+        reduction = "resident" if C <= MAX_REFINE_CAMERAS else "tiled"
+    _reduction_limit("extrinsics_from_keypoints", reduction, C)
+    seen = np.isfinite(uvs).all(-1)
+    tree = [(int(i), int(j)) for i, j in _spanning_tree(seen, root)]
+    for i, j in tree:
+        n = int((seen[i] & seen[j]).sum())
+        if n < int(min_common):
+            raise ValueError(f"cameras {i} and {j} share {n} points, fewer than min_common = {int(min_common)}: the rig is not connected by keypoints")
+    if scale_camera is None:
+        scale_camera = tree[0][1] if tree[0][0] == root else tree[0][0]
+    scale_camera = int(scale_camera)
+    if not 0 <= scale_camera < C or scale_camera == root:
+        raise ValueError("scale_camera must be a camera of the rig other than root")
+    intr = list(all_intrinsics)
+    T = {root: (np.eye(3), np.zeros(3))}
+    edges, edge_inliers, kernel_ms = [], np.zeros((C, P), dtype=bool), 0.0
+    for n, (i, j) in enumerate(tree):
+        tr, inl, info = estimate_relative_pose(uvs[i], uvs[j], intr[i], intr[j], threshold=threshold, n_hypotheses=n_hypotheses, seed=[int(seed), i, j], device=device, return_info=True)
+        kernel_ms += float(info["kernel_ms"][0])
+        edge = dict(cameras=(i, j), n_common=info["n_common"], n_inliers=info["n_inliers"], cost=info["cost"], scale=np.nan, status=info["status"])
+        edges.append(edge)
+        if info["status"] != 1:
+            raise ValueError(f"cameras {i} and {j}: {RELATIVE_POSE_STATUS[info['status']]} ({info['n_inliers']} of {info['n_common']} common points within {threshold} px)")
+        R, t = rodrigues(tr[:3]), tr[3:]
+        Ri, ti = T[i]
+        s = 1.0
+        if n > 0:
+            placed = sorted(T)
+            X = triangulate([uvs[c] for c in placed], np.stack([np.r_[_rotation_vector(T[c][0]), T[c][1]] for c in placed]), [intr[c] for c in placed], device=device)
+            Y = info["points"]
+            ok = inl & np.isfinite(X).all(1) & np.isfinite(Y).all(1)
+            if int(ok.sum()) < 8:
+                edge["status"] = -3
+                raise ValueError(f"cameras {i} and {j}: {RELATIVE_POSE_STATUS[-3]} ({int(ok.sum())} inliers are also seen by two placed cameras)")
+            s = float(np.median(np.linalg.norm(X[ok] @ Ri.T + ti, axis=1) / np.linalg.norm(Y[ok], axis=1)))
+        edge["scale"] = s
+        T[j] = (R @ Ri, R @ ti + s * t)
+        edge_inliers[j] = inl
+    ext0 = np.zeros((C, 6))
+    for c in range(C):
+        if c != root:
+            ext0[c] = np.r_[_rotation_vector(T[c][0]), T[c][1]]
+    res = None
+    if refine:
+        res = refine_extrinsics(list(uvs), ext0, intr, points=None, gauge_camera=root, scale_camera=scale_camera, loss=loss, f_scale=f_scale, reduction=reduction, device=device, **refine_kwargs)
+        ext, pts = res.extrinsics, res.points
+    else:
+        ext, pts = ext0, triangulate(list(uvs), ext0, intr, device=device)
+    ext, pts, factor = _rescale_about(ext, pts, root, scale_camera, baseline)
+    return KeypointExtrinsics(extrinsics=ext, points=pts, tree=tree, edges=edges, edge_inliers=edge_inliers, refinement=res, scale_camera=scale_camera,
+                              info=dict(root=root, baseline=float(baseline), kernel_ms=kernel_ms, rescale=factor, reduction=reduction))
 
 
 # ---------------------------------------------------------------- host helpers (numpy; the reference's formulas)
