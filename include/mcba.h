@@ -683,6 +683,29 @@ int mcba_refine_extrinsics_system_reduction(int n_cameras, size_t n_points, cons
                                             const int* held, int loss, double f_scale, double lam, int device, const double* ext_trial, const double* dtheta, int* point_status, double* system,
                                             double* trial_points, double* step4, double* info8);
 
+/* ---- camera refinement from keypoints, intrinsics free (no reference counterpart; additive to ABI 7) ---------------------
+ * mcba_refine_extrinsics_weighted with 12 unknowns per camera, theta_c = (fx fy cx cy k1 k2 | rotation vector | translation), the layout of
+ * cam12; p1, p2, k3 (dist5) stay constants.  2 <= C <= 12 (the reduced system is held to 144 rows); weights may be NULL.
+ * held (C) in/out: 12 bits per camera in theta_c order, bit set = not free; bits 6 .. 11 mean what the bits 0 .. 5 of mcba_refine_extrinsics
+ * mean.  The call sets the bits 6 .. 11 of gauge_camera and all 12 of a camera that no used point sees.
+ * prior_weight (C, 6) or NULL: 1 / std^2 of a Gaussian prior on each intrinsic scalar about its input value, 0 = none.  The prior is the
+ * host's alone: 0.5 sum prior_weight (theta - theta_0)^2 over the free intrinsic scalars is added to the cost (never through the loss),
+ * prior_weight to the diagonal of the camera block before the damping, prior_weight (theta - theta_0) to the gradient.
+ * Out: cameras_out (C, 12); points_out, point_status, history as mcba_refine_extrinsics; result16 = {cost (prior included), cost0,
+ * optimality, nfev, njev, status, scale, evaluations, kernel_ms, reduce_ms, reductions, step_ms, steps, points per group, prior cost, 0}.
+ * Kernels (csrc/mcba_kpcam.hip): k_kpba_status, k_kpcam_reduce, k_kpba_finish, k_kpcam_step; no atomics, two calls return the same bits.
+ * MCBA_KPCAM_G (16, 32, 64; tests) forces the points per group where it fits.
+ *   mcba_refine_cameras_system   one evaluation laid open, as mcba_refine_extrinsics_system: held as given, no prior; cameras_trial and
+ *                                dtheta (C, 12 each) both or neither; system = Y Y^T (NP, NP; NP = 12 C rounded up to 16) | per camera U_c
+ *                                packed lower (78), g_c (12), sum Y z (12) | cost, present scalars, max |g_p|, 0;
+ *                                info4 = {points per group, partial systems summed, NP, kernel_ms} */
+int mcba_refine_cameras(int n_cameras, size_t n_points, const double* uvs, const double* weights, const double* cam12, const double* dist5, const double* points, int* held, const double* prior_weight,
+                        int gauge_camera, int scale_camera, int loss, double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* cameras_out, double* points_out,
+                        int* point_status, double* result16, double* history, int history_rows);
+int mcba_refine_cameras_system(int n_cameras, size_t n_points, const double* uvs, const double* weights, const double* cam12, const double* dist5, const double* points, const int* held, int loss,
+                               double f_scale, double lam, int device, const double* cameras_trial, const double* dtheta, int* point_status, double* system, double* trial_points, double* step4,
+                               double* info4);
+
 /* ---- two-view RANSAC: relative pose from keypoints alone (no reference counterpart; additive to ABI 7) --------------------
  * Stateless.  uv_a, uv_b (M, 2): the detections of the M >= 8 points both cameras see, compacted by the caller (no NaN); cam12, dist5: two rows
  * each, camera a then camera b (of cam12 only fx fy cx cy are read); samples (H, 8) ints: the 8 correspondences of each hypothesis, drawn

@@ -13,7 +13,8 @@ Only what the hot path needs lives here:
   geometry.py  project_points / project_to_cameras / apply_rigid_transform / keypoint_reprojection_errors / refine_triangulation and the reference's matrix helpers -- SURVEY.md section 8f-8;
              triangulate_consensus (per-detection inlier masks) -- SURVEY.md section 8f-9;
              refine_extrinsics (free-point bundle adjustment of the extrinsics on keypoint detections) -- SURVEY.md section 8f-12;
-             estimate_relative_pose / extrinsics_from_keypoints (two-view RANSAC and a scale chain: extrinsics from keypoints alone) -- SURVEY.md section 8f-14
+             estimate_relative_pose / extrinsics_from_keypoints (two-view RANSAC and a scale chain: extrinsics from keypoints alone) -- SURVEY.md section 8f-14;
+             refine_cameras (refine_extrinsics with free intrinsics and a Gaussian prior on them: 12 unknowns per camera, 2 to 12 cameras) -- SURVEY.md section 8f-15
   uncertainty.py  calibration_uncertainty (parameter covariance from the Schur system) -- SURVEY.md section 8f-10;
              triangulation_uncertainty (covariance of every triangulated point) -- SURVEY.md section 8f-11
              weights= on refine_triangulation / triangulate(refine=True) / triangulation_uncertainty / refine_extrinsics (per-detection confidence
@@ -27,7 +28,7 @@ from . import calibration  # noqa: F401
 from .triangulation import triangulate  # noqa: F401
 from . import geometry  # noqa: F401
 from .geometry import (project_points, project_to_cameras, apply_rigid_transform, keypoint_reprojection_errors, refine_triangulation, triangulate_consensus, refine_extrinsics, ExtrinsicsRefinement, rigid_transform_from_correspondences,  # noqa: F401
-                       estimate_relative_pose, extrinsics_from_keypoints, KeypointExtrinsics, draw_samples,
+                       estimate_relative_pose, extrinsics_from_keypoints, KeypointExtrinsics, draw_samples, refine_cameras, CameraRefinement,
                        rodrigues, rodrigues_inv, get_transformation_matrix, get_transformation_vector, get_projection_matrix, euclidean_to_homogenous, homogeneous_to_euclidean)
 from .io import save_calibration, load_calibration  # noqa: F401
 from .diagnostics import reprojection_errors, undistort_points  # noqa: F401
@@ -41,6 +42,6 @@ __all__ = ["bundle_adjust", "bundle_adjustment", "serialize_params", "deserializ
            "get_floor_points", "flatibrate", "center_arena", "flip_z_axis",
            "detect_chessboard", "detect_chessboards", "reorder_chessboard_corners", "generate_chessboard_objpoints", "extend_grid", "summarize_detections",
            "geometry", "project_points", "project_to_cameras", "apply_rigid_transform", "keypoint_reprojection_errors", "refine_triangulation", "triangulate_consensus", "refine_extrinsics", "ExtrinsicsRefinement", "rigid_transform_from_correspondences",
-           "estimate_relative_pose", "extrinsics_from_keypoints", "KeypointExtrinsics", "draw_samples",
+           "estimate_relative_pose", "extrinsics_from_keypoints", "KeypointExtrinsics", "draw_samples", "refine_cameras", "CameraRefinement",
            "rodrigues", "rodrigues_inv", "get_transformation_matrix", "get_transformation_vector", "get_projection_matrix", "euclidean_to_homogenous", "homogeneous_to_euclidean",
            "calibration_uncertainty", "CalibrationUncertainty", "triangulation_uncertainty", "TriangulationUncertainty"]

@@ -334,6 +334,18 @@ int launch_kpba_reduce(hipStream_t st, int loss, const double* uvs, const double
 int launch_kpba_step(hipStream_t st, int loss, const double* uvs, const double* pts, double* trial, const int* status, size_t npts, const TcCam* cams2, const double* dtheta, int C, double f_scale,
                      double lam, double* part4, double* out4, const double* sw = nullptr, bool wide = false);
 void launch_kpba_finish(hipStream_t st, const double* part, int nwg, int C, double* sys);   // k_kpba_finish: nwg partial systems in order -> sys
+void launch_kpba_finish_sized(hipStream_t st, const double* part, int nwg, int NP, int nacc, double* sys);   // the same kernel for a system of NP NP + nacc + 4 doubles
+// ---- free-point bundle adjustment of the cameras, intrinsics free (mcba_kpcam.hip): the calls above with 12 scalars
+// per camera, 2 <= C <= 12, held (C): 12 bits in theta_c order.  k_kpba_status and k_kpba_finish are the ones above.
+int kpcam_group(int C, int lds_limit, int force_g);   // points per group of k_kpcam_reduce (64, 32 or 16; 0: no shape fits)
+size_t kpcam_partial_size(int C);                     // doubles of one (partial) system: NP NP + 102 C + 4, NP = 12 C rounded up to 16
+size_t kpcam_reduce_lds(int C, int G);                // dynamic LDS of k_kpcam_reduce
+// sys = Y Y^T (NP, NP) | per camera U_c packed lower (78), g_c (12), sum Y z (12) | cost, present scalars, max |g_p|, 0; part: kpba_groups() partial systems
+int launch_kpcam_reduce(hipStream_t st, int loss, const double* uvs, const double* pts, const int* status, size_t npts, const TcCam* cams, const int* held, int C, double f_scale, double lam, int G,
+                        double* part, double* sys, const double* sw = nullptr);
+// cams2: the current table and behind it the trial one; dtheta (C, 12); out4 = trial cost, sum dX^2, 0, sum X^2; part4: 4 kpba_groups()
+int launch_kpcam_step(hipStream_t st, int loss, const double* uvs, const double* pts, double* trial, const int* status, size_t npts, const TcCam* cams2, const double* dtheta, int C, double f_scale,
+                      double lam, double* part4, double* out4, const double* sw = nullptr);
 // ---- the tiled reduction (mcba_kpba_tiled.hip): the same system for 2 <= C <= 64, camera bands of kKtBand, groups of kKtGroup points.
 constexpr int kKtMaxCams = 64, kKtBand = 16, kKtGroup = 16;
 int kpba_tiled_groups(int C, size_t npts);   // workgroups along the points = partial systems: all of them within the resident path's largest allocation

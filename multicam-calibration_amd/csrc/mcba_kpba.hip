@@ -209,9 +209,10 @@ __global__ __launch_bounds__(256) void k_kpba_reduce(const double2* __restrict__
 }
 
 // ---------------------------------------------------------------- k_kpba_finish
-// One thread per entry of the system: the partials in workgroup order.  With NP = C = 0 the four trailing scalars alone (k_kpba_step's).
-__global__ __launch_bounds__(256) void k_kpba_finish(const double* __restrict__ part, int nwg, int NP, int C, double* __restrict__ out) {
-  const size_t nyy = (size_t)NP * NP, PS = nyy + (size_t)C * kKbAcc + 4;
+// One thread per entry of the system: the partials in workgroup order.  nacc: the doubles of the cameras' sums between Y Y^T and the four trailing
+// scalars (33 C here, 102 C for mcba_kpcam.hip).  With NP = nacc = 0 the four trailing scalars alone (k_kpba_step's).
+__global__ __launch_bounds__(256) void k_kpba_finish(const double* __restrict__ part, int nwg, int NP, int nacc, double* __restrict__ out) {
+  const size_t nyy = (size_t)NP * NP, PS = nyy + (size_t)nacc + 4;
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= PS) return;
   size_t src = i;
@@ -228,10 +229,11 @@ __global__ __launch_bounds__(256) void k_kpba_finish(const double* __restrict__ 
   out[i] = s;
 }
 
-void launch_kpba_finish(hipStream_t st, const double* part, int nwg, int C, double* sys) {
-  const size_t PS = kpba_partial_size(C);
-  k_kpba_finish<<<dim3((unsigned)((PS + 255) / 256)), dim3(256), 0, st>>>(part, nwg, (6 * C + 15) / 16 * 16, C, sys);
+void launch_kpba_finish_sized(hipStream_t st, const double* part, int nwg, int NP, int nacc, double* sys) {
+  const size_t PS = (size_t)NP * NP + (size_t)nacc + 4;
+  k_kpba_finish<<<dim3((unsigned)((PS + 255) / 256)), dim3(256), 0, st>>>(part, nwg, NP, nacc, sys);
 }
+void launch_kpba_finish(hipStream_t st, const double* part, int nwg, int C, double* sys) { launch_kpba_finish_sized(st, part, nwg, (6 * C + 15) / 16 * 16, C * kKbAcc, sys); }
 
 int launch_kpba_status(hipStream_t st, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, int* status, const double* sw, bool wide) {
   if (C < 2 || C > (wide ? kKtMaxCams : kKbMaxCams) || npts == 0 || npts > ((size_t)1 << 38)) return 1;

@@ -406,6 +406,240 @@ def refine_extrinsics_system(all_uvs, all_extrinsics, all_intrinsics, *, points,
     return out
 
 
+# ---------------------------------------------------------------- camera refinement with free intrinsics
+INTRINSIC_GROUPS = {"focal": (0, 1), "principal": (2, 3), "distortion": (4, 5)}   # columns of (fx fy cx cy k1 k2)
+MAX_REFINE_CAMERAS_FREE_INTRINSICS = 12
+
+
+@dataclass
+class CameraRefinement:
+    extrinsics: np.ndarray     # (C, 6)
+    intrinsics: list           # (camera_matrix, dist_coefs) per camera, in the format given: fx fy cx cy k1 k2 updated, the rest as given
+    points: np.ndarray         # (P, 3); NaN rows where point_status is not 1
+    cost: float                # robust cost + prior_cost
+    prior_cost: float          # 0.5 sum ((theta - theta_0) / std)^2 over the free intrinsic scalars
+    cost0: float
+    optimality: float          # inf-norm of the gradient over the free parameters (the prior's share included)
+    nfev: int
+    njev: int
+    status: int                # scipy's: 0 max_nfev, 1 gtol, 2 ftol, 3 xtol
+    message: str
+    success: bool
+    point_status: np.ndarray   # (P,): a key of REFINE_POINT_STATUS
+    held: np.ndarray           # (C, 12) bool in the order fx fy cx cy k1 k2 | rotation vector | translation: parameters that were not free
+    scale: float               # factor of the closing rescale about the gauge camera's centre
+    history: np.ndarray        # (evaluations, 3): cost (prior included), damping, accepted
+    info: dict                 # kernel_ms, reduce_ms, n_reduce, step_ms, n_step, group, gauge_camera, scale_camera
+
+
+def _free_intrinsics_mask(free_intrinsics, C):
+    """(C, 6) bool from a collection of group names or a (C, 6) boolean array"""
+    if isinstance(free_intrinsics, str):
+        free_intrinsics = (free_intrinsics,)
+    names = list(free_intrinsics) if not isinstance(free_intrinsics, np.ndarray) else None
+    if names is not None and all(isinstance(n, str) for n in names):
+        free = np.zeros((C, 6), dtype=bool)
+        for n in names:
+            if n not in INTRINSIC_GROUPS:
+                raise ValueError(f"free_intrinsics: unknown group {n!r}; the groups are {sorted(INTRINSIC_GROUPS)}")
+            free[:, INTRINSIC_GROUPS[n]] = True
+        return free
+    free = np.asarray(free_intrinsics)
+    if free.shape != (C, 6) or free.dtype != np.bool_:
+        raise ValueError(f"free_intrinsics must be a collection of {sorted(INTRINSIC_GROUPS)} or a ({C}, 6) bool array in the order fx fy cx cy k1 k2")
+    return free.copy()
+
+
+def _prior_weights(intrinsics_prior_std, C):
+    """None, or the (C, 6) plane of 1 / std^2 (0 where std is inf)"""
+    if intrinsics_prior_std is None:
+        return None
+    std = np.asarray(intrinsics_prior_std, dtype=np.float64)
+    if std.shape == (6,):
+        std = np.broadcast_to(std, (C, 6))
+    if std.shape != (C, 6):
+        raise ValueError(f"intrinsics_prior_std must be None, (6,) or ({C}, 6): one std per fx fy cx cy k1 k2")
+    if not (std > 0).all():   # (NaN compares false)
+        raise ValueError("intrinsics_prior_std must be positive (inf: no prior on that scalar)")
+    with np.errstate(over="ignore", divide="ignore"):
+        w = np.ascontiguousarray(1.0 / (std * std))
+    if np.isinf(w).any():
+        raise ValueError("intrinsics_prior_std is too small: 1 / std^2 is not finite")
+    return w
+
+
+def _held_bits12(held, C):
+    held = np.asarray(held)
+    if held.shape == (C, 12):
+        held = (held.astype(bool).astype(np.int32) << np.arange(12, dtype=np.int32)).sum(1)
+    bits = np.ascontiguousarray(held, dtype=np.int32)
+    if bits.shape != (C,):
+        raise ValueError("held must be (n_cameras, 12) bool or (n_cameras,) bit words, in the order fx fy cx cy k1 k2 | rotation vector | translation")
+    return bits
+
+
+def _refine_cameras_limit(who, C):
+    if not 2 <= C <= MAX_REFINE_CAMERAS_FREE_INTRINSICS:
+        raise NotImplementedError(f"{who}() takes 2 to {MAX_REFINE_CAMERAS_FREE_INTRINSICS} cameras, got {C}: 12 scalars per camera hold the reduced system to 144 rows; "
+                                  'refine_extrinsics(reduction="tiled") refines the extrinsics alone of up to 64 cameras')
+
+
+def _intrinsics_like(all_intrinsics, theta6):
+    out = []
+    for (K, d), t in zip(all_intrinsics, theta6):
+        K2 = np.array(K, dtype=np.float64)
+        K2[0, 0], K2[1, 1], K2[0, 2], K2[1, 2] = t[:4]
+        d2 = np.array(d, dtype=np.float64)
+        flat = d2.reshape(-1)   # (a view: (5,), (1, 5) and (5, 1) alike)
+        if flat.size < 2:
+            if np.any(t[4:6] != 0):
+                d2 = np.r_[flat, np.zeros(2 - flat.size)]
+                d2[:2] = t[4:6]
+            elif flat.size == 1:
+                flat[0] = t[4]
+        else:
+            flat[:2] = t[4:6]
+        out.append((K2, d2))
+    return out
+
+
+def refine_cameras(all_uvs, all_extrinsics, all_intrinsics, *, free_intrinsics=("focal",), intrinsics_prior_std=None, points=None, inliers=None, weights=None, gauge_camera=0, scale_camera=None,
+                   loss="soft_l1", f_scale=1.0, ftol=1e-8, xtol=1e-8, gtol=1e-8, max_nfev=100, verbose=0, device=0):
+    """`refine_extrinsics` with the intrinsics among the unknowns: free-point bundle adjustment over the extrinsics, the chosen intrinsic scalars
+    of every camera and every 3-D point.  For a rig whose intrinsics are only nominal, or a lens that was refocused: `refine_extrinsics` would
+    move the camera to absorb an error that belongs to fx, fy.
+
+        unc = calibration_uncertainty(...)                                   # from the board calibration, if there was one
+        res = refine_cameras(uvs, ext, intr, free_intrinsics=("focal", "principal"), intrinsics_prior_std=unc.intrinsics_std)
+        ext, intr = res.extrinsics, res.intrinsics
+
+    free_intrinsics: any subset of "focal" (fx, fy), "principal" (cx, cy), "distortion" (k1, k2), or a (C, 6) bool array in the order
+    fx fy cx cy k1 k2; () frees nothing: refine_extrinsics' problem through these kernels.  p1, p2, k3 stay constants.
+    intrinsics_prior_std: None, (6,) or (C, 6) positive numbers, inf = no prior on that scalar (CalibrationUncertainty.intrinsics_std passes
+    straight in): the cost gains 0.5 sum ((theta - theta_0) / std)^2 over the free intrinsic scalars, theta_0 the intrinsics given; plain
+    quadratic, never through the robust loss.  Keypoints alone determine intrinsics weakly (compact scenes moved fx, fy by 5 to 7 % at
+    0.3 px of noise): a prior is advised whenever one is known.
+    points, inliers, weights, gauge_camera, scale_camera, loss, f_scale, ftol, xtol, gtol, max_nfev, verbose: as refine_extrinsics takes
+    them.  The gauge is refine_extrinsics': the six extrinsics of gauge_camera and one translation scalar of scale_camera are held, the
+    closing rescale restores the baseline; the intrinsics of the gauge camera are free like any other camera's.  A camera that no used point
+    sees is held whole, all 12 scalars.
+    Returns a CameraRefinement; `cost` includes `prior_cost`.  ValueError: an unknown group, a mask of the wrong shape, a std that is zero,
+    negative or NaN, and what refine_extrinsics refuses.  NotImplementedError: fewer than 2 or more than 12 cameras (12 C <= 144 rows) --
+    refine_extrinsics(reduction="tiled") takes the extrinsics alone of up to 64.  Without a GPU: ops.McbaError -- there is no host path."""
+    from . import solver
+    from .triangulation import triangulate
+
+    if callable(loss) or loss not in ops.LOSSES:
+        raise ValueError(f"loss must be one of {sorted(ops.LOSSES)}")
+    if not f_scale > 0:
+        raise ValueError("`f_scale` must be positive.")
+    if int(max_nfev) < 2:
+        raise ValueError("max_nfev must be at least 2: the start and one trial are the least a run needs")
+    if min(ftol, xtol, gtol) < 0:
+        raise ValueError("ftol, xtol and gtol must not be negative")
+    uvs = _stack_uvs(all_uvs, all_extrinsics, all_intrinsics)
+    C, P = uvs.shape[:2]
+    _refine_cameras_limit("refine_cameras", C)
+    free = _free_intrinsics_mask(free_intrinsics, C)
+    pw = _prior_weights(intrinsics_prior_std, C)
+    if P < 1:
+        raise ValueError("refine_cameras() needs at least one point")
+    ext0 = np.ascontiguousarray(all_extrinsics, dtype=np.float64)
+    if ext0.shape != (C, 6) or not np.isfinite(ext0).all():
+        raise ValueError("all_extrinsics must be finite (rotation vector, translation) rows, one per camera")
+    gauge_camera = int(gauge_camera)
+    if not 0 <= gauge_camera < C:
+        raise ValueError("gauge_camera is not a camera of the rig")
+    centres = _camera_centres(ext0)
+    if scale_camera is None:
+        scale_camera = int(np.argmax(np.linalg.norm(centres - centres[gauge_camera], axis=1)))
+    scale_camera = int(scale_camera)
+    if not 0 <= scale_camera < C:
+        raise ValueError("scale_camera is not a camera of the rig")
+    if scale_camera == gauge_camera:
+        raise ValueError("gauge_camera == scale_camera: the scale is fixed by the distance between two different cameras")
+    if inliers is not None:
+        mask = np.asarray(inliers)
+        if mask.shape != (C, P) or mask.dtype != np.bool_:
+            raise ValueError(f"inliers must be the ({C}, {P}) bool mask of triangulate_consensus")
+        uvs = np.where(mask[:, :, None], uvs, np.nan)   # (a copy: the one that is uploaded)
+    w = _weight_plane(weights, C, P)
+    if points is None:
+        start_uvs = uvs if w is None else np.where((w > 0)[:, :, None], uvs, np.nan)
+        pts = np.ascontiguousarray(triangulate(list(start_uvs), all_extrinsics, all_intrinsics, device=device))
+    else:
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        if pts.shape != (P, 3):
+            raise ValueError("points must be (n_points, 3), one row per row of the cameras' uvs")
+    cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
+    d = -rodrigues(ext0[scale_camera, :3]) @ (centres[scale_camera] - centres[gauge_camera])
+    held12 = np.concatenate([~free, np.zeros((C, 6), dtype=bool)], axis=1)
+    held12[gauge_camera, 6:] = True
+    held12[scale_camera, 9 + int(np.argmax(np.abs(d)))] = True
+    held_bits = _held_bits12(held12, C)
+    cams, out, status, res = np.empty((C, 12)), np.empty((P, 3)), np.empty(P, np.int32), np.zeros(16)
+    hist = np.zeros((int(max_nfev) + 1, 3))
+    addr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+    ops.call("mcba_refine_cameras", C, P, uvs.ctypes.data, addr(w), cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, held_bits.ctypes.data, addr(pw), gauge_camera, scale_camera, ops.LOSSES[loss],
+             float(f_scale), float(ftol), float(xtol), float(gtol), int(max_nfev), int(device), cams.ctypes.data, out.ctypes.data, status.ctypes.data, res.ctypes.data, hist.ctypes.data, len(hist))
+    hist = hist[:min(int(res[7]), len(hist))].copy()
+    code = int(res[5])
+    if verbose == 2:
+        print("{0:^15}{1:^15}{2:^15}{3:^15}{4:^15}".format("Iteration", "Total nfev", "Cost", "Cost reduction", "Damping"))
+        it, last = 0, None
+        for k, (c, lam, acc) in enumerate(hist):
+            if acc:
+                print("{0:^15}{1:^15}{2:^15.4e}{3:^15}{4:^15.2e}".format(it, k + 1, c, "" if last is None else "%.2e" % (last - c), lam))
+                it, last = it + 1, c
+    if verbose >= 1:
+        print(solver.TERMINATION_MESSAGES[code])
+        print("Function evaluations {0}, initial cost {1:.4e}, final cost {2:.4e}, first-order optimality {3:.2e}.".format(int(res[3]), res[1], res[0], res[2]))
+    held = ((held_bits[:, None] >> np.arange(12)) & 1).astype(bool)
+    return CameraRefinement(extrinsics=cams[:, 6:].copy(), intrinsics=_intrinsics_like(all_intrinsics, cams[:, :6]), points=out, cost=float(res[0]), prior_cost=float(res[14]), cost0=float(res[1]),
+                            optimality=float(res[2]), nfev=int(res[3]), njev=int(res[4]), status=code, message=solver.TERMINATION_MESSAGES[code], success=code > 0, point_status=status, held=held,
+                            scale=float(res[6]), history=hist,
+                            info={"kernel_ms": float(res[8]), "reduce_ms": float(res[9]), "n_reduce": int(res[10]), "step_ms": float(res[11]), "n_step": int(res[12]), "group": int(res[13]),
+                                  "gauge_camera": gauge_camera, "scale_camera": scale_camera})
+
+
+def refine_cameras_system(all_uvs, all_extrinsics, all_intrinsics, *, points, held, lam, loss="soft_l1", f_scale=1.0, step=None, device=0, weights=None):
+    """One evaluation of refine_cameras laid open (`mcba_refine_cameras_system`; tests and diagnostics), the counterpart of
+    refine_extrinsics_system: the loop's own set-up and kernels run once at (all_extrinsics, all_intrinsics, points) and the damping lam, and
+    what they wrote comes back as it is.  held: (C, 12) bool or (C,) bit words in the order fx fy cx cy k1 k2 | rotation vector |
+    translation, taken as given -- no gauge, scale or blind-camera rule.  The prior does not enter: the kernels never see it.
+    step: None, or (cameras_trial (C, 12), dtheta (C, 12)): also the back-substitution, the trial cost under the trial intrinsics and extrinsics.
+    Returns a dict: point_status (P,); system (the raw NP NP + 102 C + 4 doubles, NP = 12 C rounded up to 16) and its views YY (NP, NP),
+    acc (C, 102) = U_c packed lower (78) | g_c (12) | sum_p Y_cp z_p (12), cost, count, gmax, tail; group, workgroups, NP, kernel_ms; with a
+    step trial_points (P, 3) and step4 = trial cost, sum dX^2, 0, sum X^2."""
+    if callable(loss) or loss not in ops.LOSSES:
+        raise ValueError(f"loss must be one of {sorted(ops.LOSSES)}")
+    uvs = _stack_uvs(all_uvs, all_extrinsics, all_intrinsics)
+    C, P = uvs.shape[:2]
+    _refine_cameras_limit("refine_cameras_system", C)
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.shape != (P, 3):
+        raise ValueError("points must be (n_points, 3), one row per row of the cameras' uvs")
+    held_bits = _held_bits12(held, C)
+    cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
+    NP = (12 * C + 15) // 16 * 16
+    status, system, info = np.empty(P, np.int32), np.empty(NP * NP + 102 * C + 4), np.zeros(4)
+    trial = step4 = cam_trial = dtheta = None
+    if step is not None:
+        cam_trial, dtheta = (np.ascontiguousarray(a, dtype=np.float64) for a in step)
+        if cam_trial.shape != (C, 12) or dtheta.shape != (C, 12):
+            raise ValueError("step must be (cameras_trial (n_cameras, 12), dtheta (n_cameras, 12))")
+        trial, step4 = np.empty((P, 3)), np.empty(4)
+    addr = lambda a: None if a is None else a.ctypes.data   # noqa: E731
+    w = _weight_plane(weights, C, P)
+    ops.call("mcba_refine_cameras_system", C, P, uvs.ctypes.data, addr(w), cam.ctypes.data, dist.ctypes.data, pts.ctypes.data, held_bits.ctypes.data, ops.LOSSES[loss], float(f_scale), float(lam),
+             int(device), addr(cam_trial), addr(dtheta), status.ctypes.data, system.ctypes.data, addr(trial), addr(step4), info.ctypes.data)
+    out = dict(point_status=status, system=system, YY=system[:NP * NP].reshape(NP, NP), acc=system[NP * NP:NP * NP + 102 * C].reshape(C, 102), cost=float(system[-4]), count=float(system[-3]),
+               gmax=float(system[-2]), tail=float(system[-1]), group=int(info[0]), workgroups=int(info[1]), NP=int(info[2]), kernel_ms=float(info[3]))
+    if step is not None:
+        out.update(trial_points=trial, step4=step4)
+    return out
+
+
 # ---------------------------------------------------------------- extrinsics from keypoints alone (SURVEY.md section 8f-14)
 RELATIVE_POSE_STATUS = {1: "ok", -1: "fewer than 8 common points", -2: "too few inliers", -3: "too few points for the scale"}
 MAX_HYPOTHESES = ops.TWOVIEW_MAX_HYPOTHESES

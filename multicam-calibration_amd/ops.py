@@ -138,6 +138,11 @@ SYMBOLS = [
                                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, ctypes.c_int]),
     ("mcba_refine_extrinsics_system_reduction", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                                                _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    # camera refinement with free intrinsics: 12 held bits per camera, a (C, 6) plane of prior weights (or NULL) behind held
+    ("mcba_refine_cameras", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, ctypes.c_int]),
+    ("mcba_refine_cameras_system", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _dp, _dp, _dp, _dp, _dp,
+                                                  _dp, _dp]),
     # two-view RANSAC: samples, inliers and the count / status tables by address like the doubles
     ("mcba_two_view_ransac", ctypes.c_int, [ctypes.c_size_t, _dp, _dp, _dp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("mcba_profile_enable", ctypes.c_int, [_h, ctypes.c_int]),
