@@ -728,6 +728,53 @@ int mcba_two_view_ransac(size_t n_points, const double* uv_a, const double* uv_b
                          double threshold, int undistort_iterations, int device, double* rt12, double* best4, unsigned char* inliers, double* points, double* essential_out, double* cost_out,
                          unsigned* count_out, int* status_out, double* kernel_ms);
 
+/* ---- camera resection (the reference resects only a planar board, through cv2.solvePnP): the pose x_cam = R X + t of each
+ * of C cameras from P known world points and that camera's own detections of them.  Stateless, host arrays in and out, a device ordinal.  Cameras
+ * are independent problems; the camera index is a grid dimension of the kernels.
+ * In: points (P, 3), a NaN row = unknown; uvs (C, P, 2) raw detections, NaN = unseen -- a point is usable for a camera when all five numbers are
+ * finite; cam12 (C, 12) and dist5 (C, 5) as everywhere (mcba_resect_ransac reads the intrinsics alone: the pose in cam12 is never looked at;
+ * mcba_resect_refine starts from it).
+ *
+ * mcba_resect_ransac: per camera H hypotheses from samples (C, H, MCBA_RESECT_SAMPLE) of indices into 0 .. P - 1, drawn by the caller.  A
+ * hypothesis is the 6-point DLT pose (Hartley-normalised 12 x 12 normal matrix, its smallest eigenvector, the left block projected onto a
+ * rotation) followed by exactly MCBA_RESECT_GN_ITERATIONS Gauss-Newton iterations on the same six points in normalised coordinates; it is void
+ * when anything is not finite, when the eigen-gap lambda_2 / lambda_12 of the normal matrix is below 1e-10 (the DLT start is not defined: six
+ * coplanar points) or when a sample point ends behind the camera.  Where every hypothesis of a camera is void, hypothesis 0 "wins" with cost
+ * +inf, no inliers and a NaN pose.  Every hypothesis is scored over every usable point by the truncated
+ * squared reprojection error of the undistorted pixels, sum min(e^2, threshold^2), a point with z <= 0 counting as e^2 = +inf; the lowest
+ * (cost, index) wins; inlier <=> e^2 <= threshold^2 and z > 0.  poses_in (C, H, 12; R row-major then t) or NULL: the generator is skipped and
+ * these poses are scored (tests and diagnostics; samples may then be NULL).
+ * A camera with fewer than MCBA_RESECT_SAMPLE usable points takes no part: nothing is launched for it, its rt12, best4[1] and tables are NaN /
+ * void (best4 = {-1, NaN, 0, usable}), its samples are not read.
+ * Out: rt12 (C, 12); best4 (C, 4) = {winning hypothesis, its cost, its inliers, usable points}; inliers (C, P) bytes; optional tables pose_out
+ * (C, H, 12), cost_out (C, H), count_out (C, H), status_out (C, H); kernel_ms (6 doubles or NULL): the call's kernels, then the stages prepare,
+ * hypotheses, score, finish, mask.  No sum uses atomics: two calls on the same input return the same bits.
+ * MCBA_ERR_ARG, checked before any device is touched and with nothing written: C < 1 or C > MCBA_RESECT_MAX_CAMERAS, P < 1, H < 1 or
+ * H > MCBA_RESECT_MAX_HYPOTHESES, a sample index outside 0 .. P - 1, not usable or repeated within a sample, threshold <= 0.
+ *
+ * mcba_resect_refine: the pose-only polish.  Per camera with active[c] != 0 (NULL: every camera) Levenberg-Marquardt on the six pose scalars
+ * over the points with mask[c, p] != 0 (and usable), the points fixed: f = detection - projection of the five-coefficient model on the raw
+ * detections, robust loss and f_scale as mcba_refine_extrinsics, Marquardt damping with its tenfold rule, a 6 x 6 solve on the host, one
+ * small device-to-host copy per evaluation.  Every camera has its own damping and stops on its own (scipy's status values: 1 gtol, 2 ftol,
+ * 3 xtol, 0 max_nfev); a stopped camera is not evaluated again.
+ * Out: extrinsics_out (C, 6) rotation vector, translation (an inactive camera: its start); result (C, 8) = {cost at the start, cost,
+ * optimality, nfev, njev, status, detections used, damping}, NaN rows for inactive cameras; system_out (C, MCBA_RESECT_SYSTEM) or NULL: the
+ * last linearisation -- upper triangle of J^T W J (21, row-major) | gradient (6) | robust cost | detections used; kernel_ms (2 doubles or
+ * NULL): the span of the call's kernels and host solves, the number of evaluations.
+ * MCBA_ERR_ARG: C outside 1 .. MCBA_RESECT_MAX_CAMERAS, P < 1, an unknown loss, f_scale <= 0, max_nfev < 1. */
+#define MCBA_RESECT_MAX_HYPOTHESES 4096
+#define MCBA_RESECT_MAX_CAMERAS 64
+#define MCBA_RESECT_SAMPLE 6
+#define MCBA_RESECT_GN_ITERATIONS 10
+#define MCBA_RESECT_CHUNK 64               /* hypotheses per workgroup of the scoring kernel (its second grid dimension counts chunks) */
+#define MCBA_RESECT_POINTS_PER_BLOCK 1024  /* points per workgroup of the scoring kernel */
+#define MCBA_RESECT_SYSTEM 29
+int mcba_resect_ransac(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, int n_hypotheses, const int* samples,
+                       const double* poses_in, double threshold, int undistort_iterations, int device, double* rt12, double* best4, unsigned char* inliers, double* pose_out, double* cost_out,
+                       unsigned* count_out, int* status_out, double* kernel_ms);
+int mcba_resect_refine(int n_cameras, size_t n_points, const double* points, const double* uvs, const unsigned char* mask, const double* cam12, const double* dist5, const int* active, int loss,
+                       double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* extrinsics_out, double* result, double* system_out, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,8 @@ Only what the hot path needs lives here:
              triangulate_consensus (per-detection inlier masks) -- SURVEY.md section 8f-9;
              refine_extrinsics (free-point bundle adjustment of the extrinsics on keypoint detections) -- SURVEY.md section 8f-12;
              estimate_relative_pose / extrinsics_from_keypoints (two-view RANSAC and a scale chain: extrinsics from keypoints alone) -- SURVEY.md section 8f-14;
-             refine_cameras (refine_extrinsics with free intrinsics and a Gaussian prior on them: 12 unknowns per camera, 2 to 12 cameras) -- SURVEY.md section 8f-15
+             refine_cameras (refine_extrinsics with free intrinsics and a Gaussian prior on them: 12 unknowns per camera, 2 to 12 cameras) -- SURVEY.md section 8f-15;
+             resect_camera / resect_cameras (resection: a camera's pose from known 3-D points and its own detections -- PnP RANSAC and a pose-only polish) -- SURVEY.md section 8f-16
   uncertainty.py  calibration_uncertainty (parameter covariance from the Schur system) -- SURVEY.md section 8f-10;
              triangulation_uncertainty (covariance of every triangulated point) -- SURVEY.md section 8f-11
              weights= on refine_triangulation / triangulate(refine=True) / triangulation_uncertainty / refine_extrinsics (per-detection confidence
@@ -29,6 +30,7 @@ from .triangulation import triangulate  # noqa: F401
 from . import geometry  # noqa: F401
 from .geometry import (project_points, project_to_cameras, apply_rigid_transform, keypoint_reprojection_errors, refine_triangulation, triangulate_consensus, refine_extrinsics, ExtrinsicsRefinement, rigid_transform_from_correspondences,  # noqa: F401
                        estimate_relative_pose, extrinsics_from_keypoints, KeypointExtrinsics, draw_samples, refine_cameras, CameraRefinement,
+                       resect_camera, resect_cameras, CameraResection, draw_resection_samples,
                        rodrigues, rodrigues_inv, get_transformation_matrix, get_transformation_vector, get_projection_matrix, euclidean_to_homogenous, homogeneous_to_euclidean)
 from .io import save_calibration, load_calibration  # noqa: F401
 from .diagnostics import reprojection_errors, undistort_points  # noqa: F401
@@ -43,5 +45,6 @@ __all__ = ["bundle_adjust", "bundle_adjustment", "serialize_params", "deserializ
            "detect_chessboard", "detect_chessboards", "reorder_chessboard_corners", "generate_chessboard_objpoints", "extend_grid", "summarize_detections",
            "geometry", "project_points", "project_to_cameras", "apply_rigid_transform", "keypoint_reprojection_errors", "refine_triangulation", "triangulate_consensus", "refine_extrinsics", "ExtrinsicsRefinement", "rigid_transform_from_correspondences",
            "estimate_relative_pose", "extrinsics_from_keypoints", "KeypointExtrinsics", "draw_samples", "refine_cameras", "CameraRefinement",
+           "resect_camera", "resect_cameras", "CameraResection", "draw_resection_samples",
            "rodrigues", "rodrigues_inv", "get_transformation_matrix", "get_transformation_vector", "get_projection_matrix", "euclidean_to_homogenous", "homogeneous_to_euclidean",
            "calibration_uncertainty", "CalibrationUncertainty", "triangulation_uncertainty", "TriangulationUncertainty"]

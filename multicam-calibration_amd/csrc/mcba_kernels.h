@@ -297,6 +297,31 @@ void launch_tv_finish(hipStream_t st, const double* part_c, const unsigned* part
 // inliers (M bytes), part_f: tv_pose_blocks(M) x 4 in-front counts; then win_idx[1] = the candidate, best4[3] = its count, rt12; points (M, 3), NaN for non-inliers
 void launch_tv_pose(hipStream_t st, const double* prep, size_t M, const double* F, const int* status, double threshold, const double* cand, unsigned* part_f, int* win_idx, double* best4, double* rt12,
                     unsigned char* inliers, double* points);
+// camera resection (mcba_resect.hip): the device side of mcba_resect_ransac and mcba_resect_refine, one launcher per stage,
+// every buffer the caller's.  C cameras (the grid's last dimension) of at least 6 usable points each, 1 <= H <= MCBA_RESECT_MAX_HYPOTHESES per camera.
+// Nothing is accumulated with atomics: the results depend on (P, H) alone.
+constexpr int kRsThreads = 256, kRsPPT = 4, kRsPoints = kRsThreads * kRsPPT;   // k_rs_score: points per lane and per workgroup
+constexpr int kRsChunk = 64;                                                    // hypotheses whose K [R | t] one workgroup of k_rs_score holds in LDS
+inline size_t rs_score_blocks(size_t P) { return (P + kRsPoints - 1) / kRsPoints; }
+inline size_t rs_pose_blocks(size_t P) { return (P + kRsThreads - 1) / kRsThreads; }
+// points (P, 3), uvs (C, P, 2), cams (C, 9) = fx fy cx cy k1 k2 p1 p2 k3.  prep: per camera 4 planes of P doubles (undistorted u, v; normalised x, y); usable (C, P)
+void launch_rs_prepare(hipStream_t st, const double* points, const double* uvs, size_t P, int C, const double* cams, int und_iters, double* prep, unsigned char* usable);
+// pose, KP (C, H, 12), status (C, H).  pose_in (C, H, 12) or nullptr: the generator is skipped, pose = pose_in (void where not finite)
+void launch_rs_hypotheses(hipStream_t st, const double* points, const double* prep, size_t P, int C, const int* samples, int H, const double* pose_in, const double* cams, double* pose, double* KP,
+                          int* status);
+// part_c, part_n: (C, rs_score_blocks(P), H) per-workgroup partial costs and inlier counts
+void launch_rs_score(hipStream_t st, const double* points, const double* prep, const unsigned char* usable, size_t P, int C, const double* KP, int H, double threshold, double* part_c,
+                     unsigned* part_n);
+// cost (C, H; +inf for a void hypothesis), count (C, H); then per camera the winner: win_idx (C), best4 (C, 4)[0 .. 2] = (index, cost, inliers), rt12 (C, 12) = its pose
+void launch_rs_finish(hipStream_t st, const double* part_c, const unsigned* part_n, size_t nblk, int C, int H, const double* pose, const int* status, double* cost, unsigned* count, int* win_idx,
+                      double* best4, double* rt12);
+// inliers (C, P) bytes: the winner's
+void launch_rs_mask(hipStream_t st, const double* points, const double* prep, const unsigned char* usable, size_t P, int C, const double* KP, const int* status, int H, double threshold,
+                    const int* win_idx, unsigned char* inliers);
+// the polish, one evaluation of n listed problems: ids (n) = the row of uvs / mask, tcs (n) = the camera at the pose to evaluate; part (n, rs_pose_blocks(P), 29);
+// sys (n, 29) = upper triangle of J^T W J | gradient | robust cost | detections used; cost_only: the last two alone, the others 0.  Non-zero: an unknown loss.
+int launch_rs_normal(hipStream_t st, int loss, bool cost_only, const double* points, const double* uvs, const unsigned char* mask, size_t P, int n, const int* ids, const TcCam* tcs, double f_scale,
+                     double* part, double* sys);
 // calibration uncertainty (mcba_cov.hip).  Non-zero: arguments out of range.
 // part: 2 x 1024 doubles of scratch; out[0] = sum rho' f^2, out[1] = present scalars of the residual vector res (NaN = missing)
 int launch_cov_wss(hipStream_t st, int loss, double f_scale, const double* res, size_t count, double* part, double* out);

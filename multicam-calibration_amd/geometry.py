@@ -16,7 +16,9 @@ GPU (`csrc/mcba_keypoints.hip`; no numpy fallback -- without a device every one 
   estimate_relative_pose         (`csrc/mcba_twoview.hip`; no counterpart in the reference) two-view RANSAC: the pose of one
                                  camera relative to another from the keypoints both detect, known intrinsics, nothing else
   extrinsics_from_keypoints      the rig's extrinsics from keypoints alone: a spanning tree of such pairs, a scale chain, refine_extrinsics
-The last five use the five-coefficient forward model on the RAW (distorted) detections: no undistortion iteration, so none of its truncation
+  resect_camera, resect_cameras  (`csrc/mcba_resect.hip`; the reference resects only a planar board) the pose of a camera from
+                                 known 3-D points and its own detections: PnP RANSAC (6-point DLT + Gauss-Newton hypotheses), a pose-only polish
+The refinements (refine_triangulation onwards; of the resection, its polish) use the five-coefficient forward model on the RAW (distorted) detections: no undistortion iteration, so none of its truncation
 error.  With p1 = p2 = k3 = 0 (all bundle_adjust returns) the model is project_points'.
 
 Host (numpy, the reference's formulas): rigid_transform_from_correspondences (returns (t, rmsd); the one in flatibration.py returns t alone),
@@ -838,6 +840,141 @@ def extrinsics_from_keypoints(all_uvs, all_intrinsics, *, threshold, root=0, n_h
     ext, pts, factor = _rescale_about(ext, pts, root, scale_camera, baseline)
     return KeypointExtrinsics(extrinsics=ext, points=pts, tree=tree, edges=edges, edge_inliers=edge_inliers, refinement=res, scale_camera=scale_camera,
                               info=dict(root=root, baseline=float(baseline), kernel_ms=kernel_ms, rescale=factor, reduction=reduction))
+
+
+# ---------------------------------------------------------------- camera resection
+RESECTION_STATUS = {1: "ok", -1: "fewer than 6 usable points", -2: "too few inliers"}
+MAX_RESECTION_HYPOTHESES = ops.RESECT_MAX_HYPOTHESES
+MAX_RESECTION_CAMERAS = ops.RESECT_MAX_CAMERAS
+
+
+def draw_resection_samples(n_usable, n_hypotheses, seed):
+    """(n_hypotheses, 6) int32: per hypothesis six different indices in 0 .. n_usable - 1, one
+    `np.random.default_rng(seed).choice(n_usable, 6, replace=False)` each from a generator of its own -- the global numpy generator is never
+    touched.  seed: anything default_rng takes (an int, a sequence of ints).  The indices count the camera's usable points in their order."""
+    if int(n_usable) < ops.RESECT_SAMPLE:
+        raise ValueError("a sample needs 6 different points")
+    rng = np.random.default_rng(seed)
+    return np.ascontiguousarray(np.stack([rng.choice(int(n_usable), ops.RESECT_SAMPLE, replace=False) for _ in range(int(n_hypotheses))]), dtype=np.int32)
+
+
+def _min_resection_inliers(n_usable):
+    return max(12, n_usable // 10)
+
+
+@dataclass
+class CameraResection:
+    extrinsics: np.ndarray     # (C, 6) rotation vector, translation of x_cam = R X + t; NaN rows where status is -1
+    inliers: np.ndarray        # (C, P) bool: the winning hypothesis' inliers
+    status: np.ndarray         # (C,) RESECTION_STATUS
+    n_usable: np.ndarray       # (C,) points with a finite position and a finite detection
+    n_inliers: np.ndarray      # (C,)
+    cost: np.ndarray           # (C,) the winner's truncated cost, sum min(e^2, threshold^2) in px^2
+    hypothesis: np.ndarray     # (C,) the winner's index, -1 where status is -1
+    refined_cost: np.ndarray   # (C,) the polish: robust cost 0.5 sum rho(f^2) over the inliers' raw detections at the result; NaN where it did not run
+    optimality: np.ndarray     # (C,) inf-norm of its gradient
+    nfev: np.ndarray           # (C,) its evaluations
+    lm_status: np.ndarray      # (C,) scipy's: 0 max_nfev, 1 gtol, 2 ftol, 3 xtol; -1 where it did not run
+    info: dict                 # samples (per camera, indices into 0 .. P - 1, None where status is -1), ransac_extrinsics (C, 6): the winning
+    #                            hypotheses before the polish, kernel_ms: dict(ransac=(total, prepare, hypotheses, score, finish, mask), polish=the span of its evaluations)
+
+
+def _resect(points, uvs, intr, seeds, threshold, n_hypotheses, undistort_iterations, refine, loss, f_scale, ftol, xtol, gtol, max_nfev, device):
+    if not threshold > 0:
+        raise ValueError("`threshold` (pixels) must be positive.")
+    H = int(n_hypotheses)
+    if not 1 <= H <= MAX_RESECTION_HYPOTHESES:
+        raise ValueError(f"n_hypotheses must be 1 .. {MAX_RESECTION_HYPOTHESES}")
+    if int(undistort_iterations) < 0:
+        raise ValueError("undistort_iterations must not be negative")
+    if loss not in ops.LOSSES:
+        raise ValueError(f"loss must be one of {sorted(ops.LOSSES)}")
+    if not f_scale > 0:
+        raise ValueError("`f_scale` must be positive.")
+    if int(max_nfev) < 2:
+        raise ValueError("max_nfev must be at least 2")
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3 or len(pts) == 0:
+        raise ValueError("points must be (n_points, 3), at least one")
+    if uvs.ndim != 3 or uvs.shape[1:] != (len(pts), 2) or len(uvs) != len(intr):
+        raise ValueError("one (n_points, 2) array of detections and one (camera_matrix, dist_coefs) per camera, matching points, required")
+    C, P = len(uvs), len(pts)
+    if not 1 <= C <= MAX_RESECTION_CAMERAS:
+        raise ValueError(f"1 .. {MAX_RESECTION_CAMERAS} cameras per call")
+    cam, dist = _cam_blocks([np.zeros(6)] * C, intr)
+    usable = np.isfinite(pts).all(1)[None, :] & np.isfinite(uvs).all(2)
+    n_usable = usable.sum(1)
+    samples, per_camera = np.zeros((C, H, ops.RESECT_SAMPLE), dtype=np.int32), [None] * C
+    for c in range(C):
+        if n_usable[c] >= ops.RESECT_SAMPLE:
+            samples[c] = np.flatnonzero(usable[c]).astype(np.int32)[draw_resection_samples(n_usable[c], H, seeds[c])]
+            per_camera[c] = samples[c]
+    rt, best, mask, ms = np.empty((C, 12)), np.empty((C, 4)), np.zeros((C, P), dtype=np.uint8), np.zeros(6)
+    ops.call("mcba_resect_ransac", C, P, pts.ctypes.data, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, H, samples.ctypes.data, None, float(threshold), int(undistort_iterations), int(device),
+             rt.ctypes.data, best.ctypes.data, mask.ctypes.data, None, None, None, None, ms.ctypes.data)
+    ext = np.full((C, 6), np.nan)
+    for c in range(C):
+        if np.isfinite(rt[c]).all():
+            ext[c] = np.r_[_rotation_vector(rt[c, :9].reshape(3, 3)), rt[c, 9:]]
+    n_in = best[:, 2].astype(np.int64)
+    status = np.where(n_usable < ops.RESECT_SAMPLE, -1, np.where(n_in >= np.maximum(12, n_usable // 10), 1, -2)).astype(np.int32)
+    out = CameraResection(extrinsics=ext, inliers=mask.astype(bool), status=status, n_usable=n_usable.astype(np.int64), n_inliers=n_in, cost=best[:, 1].copy(),
+                          hypothesis=best[:, 0].astype(np.int64), refined_cost=np.full(C, np.nan), optimality=np.full(C, np.nan), nfev=np.zeros(C, dtype=np.int64),
+                          lm_status=np.full(C, -1, dtype=np.int64), info=dict(samples=per_camera, ransac_extrinsics=ext.copy(), kernel_ms=dict(ransac=ms, polish=0.0)))
+    active = np.ascontiguousarray((status != -1) & np.isfinite(ext).all(1), dtype=np.int32)
+    if refine and active.any():
+        cam[:, 6:] = np.where(active[:, None] != 0, ext, 0.0)
+        new, res, pms = np.empty((C, 6)), np.empty((C, 8)), np.zeros(2)
+        ops.call("mcba_resect_refine", C, P, pts.ctypes.data, uvs.ctypes.data, mask.ctypes.data, cam.ctypes.data, dist.ctypes.data, active.ctypes.data, ops.LOSSES[loss], float(f_scale), float(ftol),
+                 float(xtol), float(gtol), int(max_nfev), int(device), new.ctypes.data, res.ctypes.data, None, pms.ctypes.data)
+        on = active != 0
+        out.extrinsics[on] = new[on]
+        out.refined_cost[on], out.optimality[on] = res[on, 1], res[on, 2]
+        out.nfev[on], out.lm_status[on] = res[on, 3].astype(np.int64), res[on, 5].astype(np.int64)
+        out.info["kernel_ms"]["polish"] = float(pms[0])
+        out.info["polish_evaluations"] = int(pms[1])
+    return out
+
+
+def resect_cameras(points, all_uvs, all_intrinsics, *, threshold, n_hypotheses=256, seed=0, undistort_iterations=5, refine=True, loss="soft_l1", f_scale=1.0, ftol=1e-8, xtol=1e-8, gtol=1e-8,
+                   max_nfev=50, device=0):
+    """Resection: the pose of every camera from known 3-D points and that camera's own 2-D detections of them -> `CameraResection`.
+    points: (P, 3) in the world frame, a NaN row = unknown; all_uvs: per camera (P, 2) raw detections, NaN = unseen; all_intrinsics: per
+    camera (camera_matrix, dist_coefs).  A point is usable for a camera when its position and its detection are finite.  The cameras are
+    independent problems solved in one call of the library (`mcba_resect_ransac`, `csrc/mcba_resect.hip`: the camera is a grid dimension);
+    camera c draws its samples from the seed `[seed, c]`, so row c equals `resect_camera(..., seed=[seed, c])`.  No camera's former pose is
+    an input: a knocked, refocused or newly added camera is placed against the points the others triangulate.
+
+    PnP RANSAC on the GPU: per camera `n_hypotheses` (at most 4096) poses, each the 6-point DLT of a host-drawn sample
+    (`draw_resection_samples(n_usable, n_hypotheses, seed)`) settled by ten Gauss-Newton iterations on its six points, each scored over all
+    usable points by the truncated squared reprojection error of the undistorted pixels, sum min(e^2, threshold^2), a point behind the
+    camera counting in full; the lowest (cost, index) wins, its inliers are e^2 <= threshold^2 in front of the camera.  `threshold` (pixels)
+    has no default: it is the detector's noise.  Seeded, without atomics: two calls return the same bits.
+
+    status (`RESECTION_STATUS`): 1 ok; -1 fewer than 6 usable points: the row is NaN, nothing is launched for that camera, the others are
+    unaffected; -2 fewer than max(12, a tenth of the usable points) inliers: the estimate is returned but not to be trusted -- coplanar
+    points end here, not in an exception: the 6-point DLT is degenerate for them, a sample whose DLT start is not defined (eigen-gap below
+    1e-10) is void, and with every hypothesis void the row is NaN and has no inlier.
+
+    refine=True: every camera of status 1 or -2 is polished on its inliers by a pose-only Levenberg-Marquardt (`mcba_resect_refine`): the
+    robust cost (`loss`, `f_scale`, as `refine_extrinsics`) of the raw detections under the five-coefficient model, the points fixed; ftol,
+    xtol, gtol, max_nfev and `lm_status` are scipy.optimize.least_squares'.  The cost never rises, every camera stops on its own.
+    refine=False: the winning hypotheses."""
+    uvs = np.ascontiguousarray(np.stack([np.asarray(u, dtype=np.float64) for u in all_uvs])) if len(all_uvs) else np.zeros((0, 0, 2))
+    return _resect(points, uvs, list(all_intrinsics), [[int(seed), c] for c in range(len(uvs))] if np.ndim(seed) == 0 else [list(np.ravel(seed)) + [c] for c in range(len(uvs))], threshold,
+                   n_hypotheses, undistort_iterations, refine, loss, f_scale, ftol, xtol, gtol, max_nfev, device)
+
+
+def resect_camera(points, uvs, intrinsics, *, threshold, n_hypotheses=256, seed=0, undistort_iterations=5, refine=True, loss="soft_l1", f_scale=1.0, ftol=1e-8, xtol=1e-8, gtol=1e-8, max_nfev=50,
+                  device=0, return_info=False):
+    """One camera of `resect_cameras`: (transform (6,), inliers (P,) bool), transform = (rotation vector, translation) of x_cam = R X + t,
+    the convention of `all_extrinsics` everywhere; NaN when fewer than 6 points are usable.  points: (P, 3), uvs: (P, 2) raw detections,
+    intrinsics: (camera_matrix, dist_coefs); the samples come from `seed` itself.  return_info=True: also the `CameraResection` of the one camera."""
+    u = np.asarray(uvs, dtype=np.float64)
+    if u.ndim != 2:
+        raise ValueError("uvs must be (n_points, 2)")
+    r = _resect(points, np.ascontiguousarray(u[None]), [intrinsics], [seed], threshold, n_hypotheses, undistort_iterations, refine, loss, f_scale, ftol, xtol, gtol, max_nfev, device)
+    return (r.extrinsics[0], r.inliers[0], r) if return_info else (r.extrinsics[0], r.inliers[0])
 
 
 # ---------------------------------------------------------------- host helpers (numpy; the reference's formulas)
