@@ -728,6 +728,28 @@ int mcba_two_view_ransac(size_t n_points, const double* uv_a, const double* uv_b
                          double threshold, int undistort_iterations, int device, double* rt12, double* best4, unsigned char* inliers, double* points, double* essential_out, double* cost_out,
                          unsigned* count_out, int* status_out, double* kernel_ms);
 
+/* ---- the five-point hypothesis generator of the two-view RANSAC (additive to ABI 7) ------------------------------------------
+ * mcba_two_view_ransac with another generator: samples (H, MCBA_TWOVIEW5_SAMPLE) ints, five correspondences each, drawn by the caller.  Per
+ * sample the essential matrices of the five points in normalised coordinates -- the null space of the 5 x 9 epipolar matrix, the ten cubic
+ * constraints, Gauss-Jordan, the degree-10 polynomial in one coordinate (and, in a second pass, in another), its real roots, a Gauss-Newton
+ * polish -- at most MCBA_TWOVIEW5_SLOTS of them, in ascending order of the root, each in mcba_two_view_ransac's convention (singular values
+ * 1, 1, 0, |E|_F = sqrt 2, the entry of largest magnitude positive) in the sample's leading slots; the other slots are void (status -1, E NaN).
+ * A sample is void as a whole when anything is not finite, when sigma_5 / sigma_1 of the 5 x 9 matrix is below 1e-7 or when a pivot of the
+ * elimination is below 1e-9 of the block's largest entry.  The live candidates are packed in slot order (a fixed-order prefix count, no
+ * atomics) and scored, won and voted on by mcba_two_view_ransac's own stages: the lowest (cost, 10 sample + slot) wins.
+ * Out as mcba_two_view_ransac, with best4[0] = 10 sample + slot of the winner and the optional tables in slot order: essential_out (10 H, 9),
+ * cost_out (10 H; +inf for a void slot), count_out (10 H), status_out (10 H).  Nothing live: slot 0 "wins" with cost +inf, no inliers, a NaN
+ * pose.  kernel_ms (6 doubles or NULL): the call's kernels, then prepare, hypotheses (with the compaction and the read-back of the packed
+ * count), score, finish, pose.  Two calls on the same input return the same bits.
+ * MCBA_ERR_ARG, checked before any device is touched and with nothing written: M < 8, H < 1 or H > MCBA_TWOVIEW5_MAX_SAMPLES, a sample index
+ * outside 0 .. M - 1 or repeated within a sample, threshold <= 0. */
+#define MCBA_TWOVIEW5_SAMPLE 5
+#define MCBA_TWOVIEW5_SLOTS 10
+#define MCBA_TWOVIEW5_MAX_SAMPLES 1024
+int mcba_two_view_ransac5(size_t n_points, const double* uv_a, const double* uv_b, const double* cam12, const double* dist5, int n_samples, const int* samples, double threshold,
+                          int undistort_iterations, int device, double* rt12, double* best4, unsigned char* inliers, double* points, double* essential_out, double* cost_out, unsigned* count_out,
+                          int* status_out, double* kernel_ms);
+
 /* ---- camera resection (the reference resects only a planar board, through cv2.solvePnP): the pose x_cam = R X + t of each
  * of C cameras from P known world points and that camera's own detections of them.  Stateless, host arrays in and out, a device ordinal.  Cameras
  * are independent problems; the camera index is a grid dimension of the kernels.

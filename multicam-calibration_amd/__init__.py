@@ -13,7 +13,7 @@ Only what the hot path needs lives here:
   geometry.py  project_points / project_to_cameras / apply_rigid_transform / keypoint_reprojection_errors / refine_triangulation and the reference's matrix helpers -- SURVEY.md section 8f-8;
              triangulate_consensus (per-detection inlier masks) -- SURVEY.md section 8f-9;
              refine_extrinsics (free-point bundle adjustment of the extrinsics on keypoint detections) -- SURVEY.md section 8f-12;
-             estimate_relative_pose / extrinsics_from_keypoints (two-view RANSAC and a scale chain: extrinsics from keypoints alone) -- SURVEY.md section 8f-14;
+             estimate_relative_pose / extrinsics_from_keypoints (two-view RANSAC and a scale chain: extrinsics from keypoints alone; solver="5point" for thin scenes) -- SURVEY.md sections 8f-14, 8f-17;
              refine_cameras (refine_extrinsics with free intrinsics and a Gaussian prior on them: 12 unknowns per camera, 2 to 12 cameras) -- SURVEY.md section 8f-15;
              resect_camera / resect_cameras (resection: a camera's pose from known 3-D points and its own detections -- PnP RANSAC and a pose-only polish) -- SURVEY.md section 8f-16
   uncertainty.py  calibration_uncertainty (parameter covariance from the Schur system) -- SURVEY.md section 8f-10;

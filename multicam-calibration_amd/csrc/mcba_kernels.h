@@ -297,6 +297,11 @@ void launch_tv_finish(hipStream_t st, const double* part_c, const unsigned* part
 // inliers (M bytes), part_f: tv_pose_blocks(M) x 4 in-front counts; then win_idx[1] = the candidate, best4[3] = its count, rt12; points (M, 3), NaN for non-inliers
 void launch_tv_pose(hipStream_t st, const double* prep, size_t M, const double* F, const int* status, double threshold, const double* cand, unsigned* part_f, int* win_idx, double* best4, double* rt12,
                     unsigned char* inliers, double* points);
+// the five-point generator (mcba_fivepoint.hip): 1 <= H <= MCBA_TWOVIEW5_MAX_SAMPLES samples of five correspondences.  E10, F10
+// (10 H, 9), status10 (10 H): the candidate table in slot order; Ep, Fp (10 H rows of room), stp, map: its live rows packed in index order, map[i] =
+// 10 sample + slot, n_packed[0] of them (at least 1: a void row 0 where nothing is live) -- the table launch_tv_score .. launch_tv_pose take
+void launch_tv5_hypotheses(hipStream_t st, const double* prep, size_t M, const int* samples, int H, const TvCams& cams, double* E10, double* F10, int* status10, double* Ep, double* Fp, int* stp,
+                           int* map, int* n_packed);
 // camera resection (mcba_resect.hip): the device side of mcba_resect_ransac and mcba_resect_refine, one launcher per stage,
 // every buffer the caller's.  C cameras (the grid's last dimension) of at least 6 usable points each, 1 <= H <= MCBA_RESECT_MAX_HYPOTHESES per camera.
 // Nothing is accumulated with atomics: the results depend on (P, H) alone.

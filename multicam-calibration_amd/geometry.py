@@ -645,16 +645,20 @@ def refine_cameras_system(all_uvs, all_extrinsics, all_intrinsics, *, points, he
 # ---------------------------------------------------------------- extrinsics from keypoints alone
 RELATIVE_POSE_STATUS = {1: "ok", -1: "fewer than 8 common points", -2: "too few inliers", -3: "too few points for the scale"}
 MAX_HYPOTHESES = ops.TWOVIEW_MAX_HYPOTHESES
+MAX_FIVEPOINT_SAMPLES = ops.TWOVIEW5_MAX_SAMPLES
+SOLVERS = ("8point", "5point")
 
 
-def draw_samples(n_common, n_hypotheses, seed):
-    """(n_hypotheses, 8) int32: per hypothesis eight different indices in 0 .. n_common - 1, one
-    `np.random.default_rng(seed).choice(n_common, 8, replace=False)` each from a generator of its own -- the global numpy generator is never
+def draw_samples(n_common, n_hypotheses, seed, size=8):
+    """(n_hypotheses, size) int32: per hypothesis `size` (8, or 5 for the five-point solver) different indices in 0 .. n_common - 1, one
+    `np.random.default_rng(seed).choice(n_common, size, replace=False)` each from a generator of its own -- the global numpy generator is never
     touched.  seed: anything default_rng takes (an int, a sequence of ints)."""
+    if int(size) not in (8, ops.TWOVIEW5_SAMPLE):
+        raise ValueError("size must be 8 (the 8-point solver) or 5 (the five-point solver)")
     if int(n_common) < 8:
         raise ValueError("a sample needs 8 different correspondences")
     rng = np.random.default_rng(seed)
-    return np.ascontiguousarray(np.stack([rng.choice(int(n_common), 8, replace=False) for _ in range(int(n_hypotheses))]), dtype=np.int32)
+    return np.ascontiguousarray(np.stack([rng.choice(int(n_common), int(size), replace=False) for _ in range(int(n_hypotheses))]), dtype=np.int32)
 
 
 def _rotation_vector(R):
@@ -673,7 +677,7 @@ def _intrinsics_rows(intrinsics_a, intrinsics_b):
 
 
 def estimate_relative_pose(uvs_a, uvs_b, intrinsics_a, intrinsics_b, *, threshold, n_hypotheses=512, seed=0, undistort_iterations=5, refine=False, loss="soft_l1", f_scale=1.0, device=0,
-                           return_info=False):
+                           return_info=False, solver="8point"):
     """The pose of camera b relative to camera a from the keypoints both detect, with known intrinsics and nothing else:
     (transform (6,), inliers (P,) bool), transform = the rotation vector and the UNIT translation of x_b = R x_a + t (a two-view geometry
     has no scale).  uvs_a, uvs_b: (P, 2) raw detections, NaN = unseen; intrinsics: (camera_matrix, dist_coefs) each.
@@ -683,16 +687,33 @@ def estimate_relative_pose(uvs_a, uvs_b, intrinsics_a, intrinsics_b, *, threshol
     Sampson distance of the undistorted pixels, sum min(e^2, threshold^2); the lowest (cost, index) wins, its inliers are e^2 <= threshold^2;
     of the four (R, t) of the winner the one with most inliers in front of both cameras is returned.  `threshold` (pixels) has no default: it
     is the detector's noise.  Seeded, without atomics: two calls return the same bits.  A planar scene or a purely rotating pair is
-    degenerate for the 8-point estimate: it shows as few inliers (status -2), not as an exception.
+    degenerate for the 8-point estimate: it shows as few inliers (status -2), not as an exception.  A THIN scene does not show: see `solver`.
+
+    solver="5point" (`mcba_two_view_ransac5`, `csrc/mcba_fivepoint.hip`): the hypotheses are the essential matrices
+    -- up to ten -- of `n_hypotheses` samples of FIVE correspondences (`draw_samples(..., size=5)`; at most 1024 samples), the minimal solver
+    for calibrated cameras; scoring, winner and vote are the same kernels.  This is the generator for THIN scenes -- keypoints of an animal on
+    an arena floor, a slab a few millimetres deep: there the 8-point estimate is not short of inliers but WRONG with status 1 (on the
+    project's slab scenes it keeps a quarter to a half of the points and an essential matrix up to 0.68 from the true one in Frobenius norm),
+    while the five-point winner keeps every point from an eighth of the samples.  Still out of scope, for either solver: the EXACTLY planar
+    cloud -- there the essential matrix has a twin that every point satisfies; on a prototype at depth sigma 0 the twin won two pairs of three,
+    at 1 mm the margins were thin, at 5 mm the right matrix won every pair with the second-best cost 1.07 to 1.41 x the winner's -- and the
+    purely rotating pair.  The default stays "8point": nothing changes for a caller who does not ask.
 
     refine=True: `refine_extrinsics` on the two cameras with the inlier mask (`loss`, `f_scale`), |t| renormalised to 1.
-    return_info=True: also a dict -- n_common, n_inliers, cost, hypothesis, n_in_front, points (P, 3: the two-view point of every inlier in
+    return_info=True: also a dict -- n_common, n_inliers, cost, hypothesis (the winner's index in the scored order; "5point": among the live
+    candidates), sample and slot ("5point": the winner is candidate `slot` of sample `sample`; "8point": sample = hypothesis, slot = 0),
+    n_scored (the candidates that were scored: n_hypotheses, or the live candidates of the five-point samples), n_in_front, points (P, 3: the two-view point of every inlier in
     camera a's frame at unit baseline, NaN elsewhere), status (`RELATIVE_POSE_STATUS`: 1 ok, -1 fewer than 8 common points: transform NaN,
     -2 fewer than max(16, a tenth of the common points) inliers: the estimate is returned but not to be trusted), samples, kernel_ms (the
     call's kernels, then prepare, hypotheses, score, finish, pose)."""
     if not threshold > 0:
         raise ValueError("`threshold` (pixels) must be positive.")
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    five = solver == "5point"
     H = int(n_hypotheses)
+    if five and not 1 <= H <= MAX_FIVEPOINT_SAMPLES:
+        raise ValueError(f"n_hypotheses counts samples for solver='5point' and must be 1 .. {MAX_FIVEPOINT_SAMPLES}")
     if not 1 <= H <= MAX_HYPOTHESES:
         raise ValueError(f"n_hypotheses must be 1 .. {MAX_HYPOTHESES}")
     if int(undistort_iterations) < 0:
@@ -704,20 +725,29 @@ def estimate_relative_pose(uvs_a, uvs_b, intrinsics_a, intrinsics_b, *, threshol
     idx = np.flatnonzero(np.isfinite(ua).all(1) & np.isfinite(ub).all(1))
     M = len(idx)
     transform, inliers, points = np.full(6, np.nan), np.zeros(P, dtype=bool), np.full((P, 3), np.nan)
-    info = dict(n_common=M, n_inliers=0, cost=np.nan, hypothesis=-1, n_in_front=0, points=points, status=-1, samples=None, kernel_ms=np.zeros(6))
+    info = dict(n_common=M, n_inliers=0, cost=np.nan, hypothesis=-1, sample=-1, slot=-1, n_scored=0, n_in_front=0, points=points, status=-1, samples=None, kernel_ms=np.zeros(6))
     if M >= 8:
         cam, dist = _intrinsics_rows(intrinsics_a, intrinsics_b)
         ca, cb = np.ascontiguousarray(ua[idx]), np.ascontiguousarray(ub[idx])
-        samples = draw_samples(M, H, seed)
         rt, best, mask, pts, ms = np.empty(12), np.empty(4), np.empty(M, dtype=np.uint8), np.empty((M, 3)), np.zeros(6)
-        ops.call("mcba_two_view_ransac", M, ca.ctypes.data, cb.ctypes.data, cam.ctypes.data, dist.ctypes.data, H, samples.ctypes.data, None, float(threshold), int(undistort_iterations), int(device),
-                 rt.ctypes.data, best.ctypes.data, mask.ctypes.data, pts.ctypes.data, None, None, None, None, ms.ctypes.data)
+        if five:
+            samples = draw_samples(M, H, seed, size=ops.TWOVIEW5_SAMPLE)
+            slot_status = np.empty(ops.TWOVIEW5_SLOTS * H, dtype=np.int32)
+            ops.call("mcba_two_view_ransac5", M, ca.ctypes.data, cb.ctypes.data, cam.ctypes.data, dist.ctypes.data, H, samples.ctypes.data, float(threshold), int(undistort_iterations), int(device),
+                     rt.ctypes.data, best.ctypes.data, mask.ctypes.data, pts.ctypes.data, None, None, None, slot_status.ctypes.data, ms.ctypes.data)
+            won = int(best[0])
+            place = dict(hypothesis=int((slot_status[:won] == 1).sum()), sample=won // ops.TWOVIEW5_SLOTS, slot=won % ops.TWOVIEW5_SLOTS, n_scored=max(1, int((slot_status == 1).sum())))
+        else:
+            samples = draw_samples(M, H, seed)
+            ops.call("mcba_two_view_ransac", M, ca.ctypes.data, cb.ctypes.data, cam.ctypes.data, dist.ctypes.data, H, samples.ctypes.data, None, float(threshold), int(undistort_iterations), int(device),
+                     rt.ctypes.data, best.ctypes.data, mask.ctypes.data, pts.ctypes.data, None, None, None, None, ms.ctypes.data)
+            place = dict(hypothesis=int(best[0]), sample=int(best[0]), slot=0, n_scored=H)
         inliers[idx] = mask.astype(bool)
         points[idx] = pts
         n_in = int(best[2])
         if np.isfinite(rt).all():
             transform = np.r_[_rotation_vector(rt[:9].reshape(3, 3)), rt[9:]]
-        info.update(n_inliers=n_in, cost=float(best[1]), hypothesis=int(best[0]), n_in_front=int(best[3]), status=1 if n_in >= _min_inliers(M) else -2, samples=samples, kernel_ms=ms)
+        info.update(n_inliers=n_in, cost=float(best[1]), n_in_front=int(best[3]), status=1 if n_in >= _min_inliers(M) else -2, samples=samples, kernel_ms=ms, **place)
         if refine and np.isfinite(transform).all():
             res = refine_extrinsics([ua, ub], np.stack([np.zeros(6), transform]), [intrinsics_a, intrinsics_b], inliers=np.stack([inliers, inliers]), gauge_camera=0, scale_camera=1, loss=loss,
                                     f_scale=f_scale, device=device)
@@ -751,7 +781,7 @@ def _rescale_about(ext, points, root, scale_camera, baseline):
 
 
 def extrinsics_from_keypoints(all_uvs, all_intrinsics, *, threshold, root=0, n_hypotheses=512, seed=0, baseline=1.0, scale_camera=None, refine=True, loss="soft_l1", f_scale=1.0, min_common=16,
-                              reduction=None, device=0, **refine_kwargs):
+                              reduction=None, device=0, solver="8point", **refine_kwargs):
     """The extrinsics of a rig from the pose estimator's keypoints alone -- known intrinsics, no board, no starting calibration -- as a
     `KeypointExtrinsics`: the initialiser in front of `refine_extrinsics` and `triangulate`.  all_uvs: per camera (P, 2) raw detections, NaN =
     unseen; all_intrinsics: per camera (camera_matrix, dist_coefs).  The frame is camera `root`'s (its extrinsics are the exact zero vector).
@@ -762,7 +792,9 @@ def extrinsics_from_keypoints(all_uvs, all_intrinsics, *, threshold, root=0, n_h
 
     1. the maximum spanning tree of the co-visibility counts (`calibration.get_camera_spanning_tree`'s rule on the (C, P) plane of seen
        points), edges in order of distance from `root`; a tree edge with fewer than `min_common` common points: ValueError naming the cameras;
-    2. `estimate_relative_pose` per tree edge (i, j), seed [seed, i, j], `threshold`, `n_hypotheses`; an edge of status -2 (too few inliers:
+    2. `estimate_relative_pose` per tree edge (i, j), seed [seed, i, j], `threshold`, `n_hypotheses`, `solver` ("8point", the default, or
+       "5point": the generator for thin scenes -- keypoints on an arena floor --, where the 8-point edges are wrong with status 1; see
+       `estimate_relative_pose`; with it `n_hypotheses` counts samples, at most 1024); an edge of status -2 (too few inliers:
        a planar scene, a pure rotation, a wrong threshold): ValueError;
     3. the scale chain, in tree order: the first edge has scale 1; for a later edge (i -> j), X = `triangulate` over the cameras placed so
        far, Y = the edge's two-view points in camera i's frame, s = median(|R_i X + t_i| / |Y|) over the edge's inliers with finite X,
@@ -791,6 +823,10 @@ def extrinsics_from_keypoints(all_uvs, all_intrinsics, *, threshold, root=0, n_h
     if reduction is None:
         reduction = "resident" if C <= MAX_REFINE_CAMERAS else "tiled"
     _reduction_limit("extrinsics_from_keypoints", reduction, C)
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    if solver == "5point" and not 1 <= int(n_hypotheses) <= MAX_FIVEPOINT_SAMPLES:
+        raise ValueError(f"n_hypotheses counts samples for solver='5point' and must be 1 .. {MAX_FIVEPOINT_SAMPLES}")
     seen = np.isfinite(uvs).all(-1)
     tree = [(int(i), int(j)) for i, j in _spanning_tree(seen, root)]
     for i, j in tree:
@@ -806,7 +842,7 @@ def extrinsics_from_keypoints(all_uvs, all_intrinsics, *, threshold, root=0, n_h
     T = {root: (np.eye(3), np.zeros(3))}
     edges, edge_inliers, kernel_ms = [], np.zeros((C, P), dtype=bool), 0.0
     for n, (i, j) in enumerate(tree):
-        tr, inl, info = estimate_relative_pose(uvs[i], uvs[j], intr[i], intr[j], threshold=threshold, n_hypotheses=n_hypotheses, seed=[int(seed), i, j], device=device, return_info=True)
+        tr, inl, info = estimate_relative_pose(uvs[i], uvs[j], intr[i], intr[j], threshold=threshold, n_hypotheses=n_hypotheses, seed=[int(seed), i, j], device=device, return_info=True, solver=solver)
         kernel_ms += float(info["kernel_ms"][0])
         edge = dict(cameras=(i, j), n_common=info["n_common"], n_inliers=info["n_inliers"], cost=info["cost"], scale=np.nan, status=info["status"])
         edges.append(edge)

@@ -146,6 +146,7 @@ SYMBOLS = [
     # two-view RANSAC: samples, inliers and the count / status tables by address like the doubles
     ("mcba_two_view_ransac", ctypes.c_int, [ctypes.c_size_t, _dp, _dp, _dp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     # camera resection: every array by address
+    ("mcba_two_view_ransac5", ctypes.c_int, [ctypes.c_size_t, _dp, _dp, _dp, _dp, ctypes.c_int, _dp, ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("mcba_resect_ransac", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("mcba_resect_refine", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                           ctypes.c_int, _dp, _dp, _dp, _dp]),
@@ -168,6 +169,7 @@ SYMBOLS = [
 
 LM_STATE = 32  # MCBA_LM_STATE of include/mcba.h
 TWOVIEW_MAX_HYPOTHESES, TWOVIEW_CHUNK, TWOVIEW_POINTS_PER_BLOCK = 4096, 64, 1024  # MCBA_TWOVIEW_* of include/mcba.h
+TWOVIEW5_SAMPLE, TWOVIEW5_SLOTS, TWOVIEW5_MAX_SAMPLES = 5, 10, 1024  # MCBA_TWOVIEW5_* of include/mcba.h
 RESECT_MAX_HYPOTHESES, RESECT_CHUNK, RESECT_POINTS_PER_BLOCK, RESECT_SAMPLE, RESECT_GN_ITERATIONS, RESECT_MAX_CAMERAS, RESECT_SYSTEM = 4096, 64, 1024, 6, 10, 64, 29  # MCBA_RESECT_* of include/mcba.h
 
 _lib = None
