@@ -3,6 +3,7 @@ absent; the oracle restates its two published algorithms) and against synthetic 
 import numpy as np
 import pytest
 
+import triangulate_bounds as tb
 from oracle import triangulate_oracle as tri
 from test_triangulate_cpu import scene
 
@@ -26,7 +27,9 @@ def test_matches_oracle_with_noise_and_missing_views(mc, C):
     assert np.array_equal(np.isnan(got), np.isnan(want))
     ok = ~np.isnan(want).any(1)
     # same algorithm in FP64: SVD by LAPACK vs one-sided Jacobi differ in the last bits, scaled by the DLT conditioning
+    # (this gate scales nothing -- 1e-8 of the scene, 8e-6 absolute; the bar that IS scaled, pair by pair, is triangulate_bounds.check below: DESIGN.md section 8f-4)
     assert np.abs(got[ok] - want[ok]).max() <= 1e-8 * np.abs(want[ok]).max()
+    tb.check("C=%d" % C, got, *tb.enclosure(uvs, ext, intr))
 
 
 def test_recovers_noise_free_points_and_tangential_distortion(mc):
@@ -36,6 +39,7 @@ def test_recovers_noise_free_points_and_tangential_distortion(mc):
     want = tri.triangulate(uvs, ext, intr_t)
     got = mc.triangulate(uvs, ext, intr_t)
     assert np.abs(got - want).max() <= 1e-8 * np.abs(want).max()
+    tb.check("five coefficients, C=5", got, *tb.enclosure(uvs, ext, intr_t))
 
 
 def test_argument_checks(mc):
@@ -64,7 +68,9 @@ def test_the_config5_rig_triangulates(mc):
     assert np.isnan(got[:9]).all() and np.abs(got[9:] - X[9:]).max() < 1e-8
     intr_t = [(K, np.array([d[0], d[1], 1e-3, -5e-4, 1e-3])) for K, d in intr]
     want = tri.triangulate(uvs, ext, intr_t)
-    assert np.abs(mc.triangulate(uvs, ext, intr_t) - want).max() <= 1e-8 * np.abs(want).max()
+    got = mc.triangulate(uvs, ext, intr_t)
+    assert np.abs(got - want).max() <= 1e-8 * np.abs(want).max()
+    tb.check("five coefficients, C=24", got, *tb.enclosure(uvs, ext, intr_t))
 
 
 def test_random_rigs_and_occlusion_patterns_vs_oracle(mc):
@@ -87,3 +93,4 @@ def test_random_rigs_and_occlusion_patterns_vs_oracle(mc):
         ok = ~np.isnan(want).any(1)
         if ok.any():
             assert np.abs(got[ok] - want[ok]).max() <= 1e-7 * max(1.0, np.abs(want[ok]).max()), (tag, np.abs(got[ok] - want[ok]).max())
+        tb.check(tag, got, *tb.enclosure(uvs, ext, intr))   # (noise-free cases: positions up to 0.72, the interval's asymmetry -- triangulate_bounds.check)

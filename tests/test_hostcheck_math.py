@@ -306,12 +306,16 @@ def test_triangulation_vs_oracle_with_noise_and_missing_views(hc, C):
     ok = ~np.isnan(want).any(1)
     print("triangulation, C = %d: max relative difference %.3g" % (C, np.abs(got[ok] - want[ok]).max() / np.abs(want[ok]).max()))
     assert np.abs(got[ok] - want[ok]).max() <= 1e-8 * np.abs(want[ok]).max()
+    import triangulate_bounds as tb
+
+    tb.check("C=%d" % C, got, *tb.enclosure(uvs, ext, intr))   # the bar that is scaled by each pair's conditioning (tests/triangulate_bounds.py)
 
 
 def test_triangulation_random_rigs_and_occlusion_patterns_vs_oracle(hc):
     """The 40-case sweep and the gate of test_gpu_triangulate.py::test_random_rigs_and_occlusion_patterns_vs_oracle."""
     from oracle import triangulate_oracle as tri
     from test_triangulate_cpu import scene
+    import triangulate_bounds as tb
 
     rng = np.random.default_rng(404)
     worst = 0.0
@@ -332,6 +336,7 @@ def test_triangulation_random_rigs_and_occlusion_patterns_vs_oracle(hc):
             rel = np.abs(got[ok] - want[ok]).max() / max(1.0, np.abs(want[ok]).max())
             worst = max(worst, rel)
             assert rel <= 1e-7, (tag, rel)
+        tb.check(tag, got, *tb.enclosure(uvs, ext, intr))
     print("triangulation sweep: worst relative difference %.3g" % worst)
 
 
