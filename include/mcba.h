@@ -797,6 +797,26 @@ int mcba_resect_ransac(int n_cameras, size_t n_points, const double* points, con
 int mcba_resect_refine(int n_cameras, size_t n_points, const double* points, const double* uvs, const unsigned char* mask, const double* cam12, const double* dist5, const int* active, int loss,
                        double f_scale, double ftol, double xtol, double gtol, int max_nfev, int device, double* extrinsics_out, double* result, double* system_out, double* kernel_ms);
 
+/* ---- the minimal generator of the resection: mcba_resect_ransac with P3P hypotheses, for point sets the 6-point DLT
+ * cannot start from (coplanar and nearly coplanar points) and for detections so often wrong that six clean ones are rarely drawn together.
+ * mcba_resect_ransac_p3p: the arguments of mcba_resect_ransac less poses_in.  samples (C, H, MCBA_RESECT_P3P_SAMPLE), H = n_hypotheses counts
+ * SAMPLES, 1 .. MCBA_RESECT_P3P_MAX_SAMPLES.  A sample's three points and unit bearings give Grunert's quartic; each real root (ascending)
+ * fills one of the sample's MCBA_RESECT_P3P_SLOTS slots with the pose of the two triangles' frames, settled by exactly MCBA_RESECT_P3P_POLISH
+ * Gauss-Newton iterations on the three points.  A slot is void when there is no such root, when the world points or the bearings are collinear
+ * (sine of the angle at the first point at most 1e-6), when a depth ratio is not positive, when anything is not finite or when a sample point
+ * ends behind the camera.  Equal candidates are not merged.  The table of 4 H slots per camera is scored, and the winner and its mask are found,
+ * exactly as mcba_resect_ransac does with 4 H hypotheses: best4[0] is the winning SLOT (its sample is best4[0] / 4), and the optional tables
+ * pose_out (C, 4 H, 12), cost_out, count_out, status_out (C, 4 H) have 4 H rows per camera.  A camera takes part with at least
+ * MCBA_RESECT_SAMPLE (6) usable points, as there.  kernel_ms: the same six slots.  Two calls on the same input return the same bits.
+ * MCBA_ERR_ARG, checked before any device is touched and with nothing written: as mcba_resect_ransac, with H > MCBA_RESECT_P3P_MAX_SAMPLES. */
+#define MCBA_RESECT_P3P_SAMPLE 3
+#define MCBA_RESECT_P3P_SLOTS 4
+#define MCBA_RESECT_P3P_POLISH 5
+#define MCBA_RESECT_P3P_MAX_SAMPLES 1024
+int mcba_resect_ransac_p3p(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, int n_hypotheses, const int* samples,
+                           double threshold, int undistort_iterations, int device, double* rt12, double* best4, unsigned char* inliers, double* pose_out, double* cost_out, unsigned* count_out,
+                           int* status_out, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,8 @@ Only what the hot path needs lives here:
              refine_extrinsics (free-point bundle adjustment of the extrinsics on keypoint detections) -- SURVEY.md section 8f-12;
              estimate_relative_pose / extrinsics_from_keypoints (two-view RANSAC and a scale chain: extrinsics from keypoints alone; solver="5point" for thin scenes) -- SURVEY.md sections 8f-14, 8f-17;
              refine_cameras (refine_extrinsics with free intrinsics and a Gaussian prior on them: 12 unknowns per camera, 2 to 12 cameras) -- SURVEY.md section 8f-15;
-             resect_camera / resect_cameras (resection: a camera's pose from known 3-D points and its own detections -- PnP RANSAC and a pose-only polish) -- SURVEY.md section 8f-16
+             resect_camera / resect_cameras (resection: a camera's pose from known 3-D points and its own detections -- PnP RANSAC and a pose-only polish) -- SURVEY.md section 8f-16;
+             solver="p3p" on either (a minimal 3-point generator for coplanar or nearly coplanar points and for heavy outlier shares) -- SURVEY.md section 8f-18
   uncertainty.py  calibration_uncertainty (parameter covariance from the Schur system) -- SURVEY.md section 8f-10;
              triangulation_uncertainty (covariance of every triangulated point) -- SURVEY.md section 8f-11
              weights= on refine_triangulation / triangulate(refine=True) / triangulation_uncertainty / refine_extrinsics (per-detection confidence

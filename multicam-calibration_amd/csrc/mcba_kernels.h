@@ -314,6 +314,9 @@ void launch_rs_prepare(hipStream_t st, const double* points, const double* uvs, 
 // pose, KP (C, H, 12), status (C, H).  pose_in (C, H, 12) or nullptr: the generator is skipped, pose = pose_in (void where not finite)
 void launch_rs_hypotheses(hipStream_t st, const double* points, const double* prep, size_t P, int C, const int* samples, int H, const double* pose_in, const double* cams, double* pose, double* KP,
                           int* status);
+// the P3P generator (mcba_resect_p3p.hip): samples (C, H, 3), 1 <= H <= MCBA_RESECT_P3P_MAX_SAMPLES; pose, KP (C, 4 H, 12),
+// status (C, 4 H): the candidates of sample h in slots 4 h .. 4 h + 3, void slots included -- the table launch_rs_score .. launch_rs_mask take with 4 H for H
+void launch_rs3_hypotheses(hipStream_t st, const double* points, const double* prep, size_t P, int C, const int* samples, int H, const double* cams, double* pose, double* KP, int* status);
 // part_c, part_n: (C, rs_score_blocks(P), H) per-workgroup partial costs and inlier counts
 void launch_rs_score(hipStream_t st, const double* points, const double* prep, const unsigned char* usable, size_t P, int C, const double* KP, int H, double threshold, double* part_c,
                      unsigned* part_n);

@@ -1,6 +1,8 @@
-// mcba_resect_api.hip -- mcba_resect_ransac and mcba_resect_refine of include/mcba.h: stateless, host arrays in and out,
-// a device ordinal, no handle.  The points, the detections and the samples go up once; the stages of csrc/mcba_resect.hip run on that copy, each
-// between two events.  Cameras with fewer than six usable points are left out before anything is uploaded: the kernels see the others, packed.
+// mcba_resect_api.hip -- mcba_resect_ransac, mcba_resect_ransac_p3p and mcba_resect_refine of include/mcba.h (SURVEY.md sections 8f-16, 8f-18):
+// stateless, host arrays in and out, a device ordinal, no handle.  The points, the detections and the samples go up once; the stages of
+// csrc/mcba_resect.hip run on that copy, each between two events; the two RANSAC entries are one body (resect_ransac) that differs in the
+// generator it launches: k_rs_hypotheses, or k_rs3_hypotheses of csrc/mcba_resect_p3p.hip with four table rows per sample.
+// Cameras with fewer than six usable points are left out before anything is uploaded: the kernels see the others, packed.
 // The polish's loop is rs_lm of mcba_resect_math.h, driven here against the kernels: one launch pair and one small copy back per evaluation.
 #include "mcba_handle.h"
 #include "mcba_resect_math.h"
@@ -52,20 +54,28 @@ struct ResectBackEnd {
   }
 };
 
-}  // namespace
+// What tells the two generators of the RANSAC apart: indices per sample, rows of the pose table per sample, the bound on n_hypotheses.
+struct Generator {
+  const char* who;
+  int size, slots, max_h;
+  const char* range;
+};
+constexpr Generator kDlt6{"mcba_resect_ransac", MCBA_RESECT_SAMPLE, 1, MCBA_RESECT_MAX_HYPOTHESES, ": 1 .. MCBA_RESECT_MAX_HYPOTHESES (4096) hypotheses required"};
+constexpr Generator kP3p{"mcba_resect_ransac_p3p", MCBA_RESECT_P3P_SAMPLE, MCBA_RESECT_P3P_SLOTS, MCBA_RESECT_P3P_MAX_SAMPLES, ": 1 .. MCBA_RESECT_P3P_MAX_SAMPLES (1024) samples required"};
 
-extern "C" {
-
-int mcba_resect_ransac(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, int n_hypotheses, const int* samples,
-                       const double* poses_in, double threshold, int undistort_iterations, int device, double* rt12, double* best4, unsigned char* inliers, double* pose_out, double* cost_out,
-                       unsigned* count_out, int* status_out, double* kernel_ms) {
+// The body of mcba_resect_ransac and mcba_resect_ransac_p3p: the checks, the upload, the stages between their events, the download.
+// n_hypotheses counts samples; the table that the scorer sees has H = n_hypotheses g.slots rows per camera.
+int resect_ransac(const Generator& g, int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, int n_hypotheses, const int* samples,
+                  const double* poses_in, double threshold, int undistort_iterations, int device, double* rt12, double* best4, unsigned char* inliers, double* pose_out, double* cost_out,
+                  unsigned* count_out, int* status_out, double* kernel_ms) {
+  auto bad = [&](const char* what) { return fail(MCBA_ERR_ARG, (std::string(g.who) + what).c_str()); };
   if (!points || !uvs || !cam12 || !dist5 || !rt12 || !best4 || !inliers || (!samples && !poses_in) || undistort_iterations < 0)
-    return fail(MCBA_ERR_ARG, "mcba_resect_ransac: non-NULL arrays (samples or poses_in), undistort_iterations >= 0 required");
-  if (n_cameras < 1 || n_cameras > MCBA_RESECT_MAX_CAMERAS) return fail(MCBA_ERR_ARG, "mcba_resect_ransac: 1 .. MCBA_RESECT_MAX_CAMERAS (64) cameras required");
-  if (n_points < 1) return fail(MCBA_ERR_ARG, "mcba_resect_ransac: at least one point required");
-  if (n_hypotheses < 1 || n_hypotheses > MCBA_RESECT_MAX_HYPOTHESES) return fail(MCBA_ERR_ARG, "mcba_resect_ransac: 1 .. MCBA_RESECT_MAX_HYPOTHESES (4096) hypotheses required");
-  if (!(threshold > 0.0)) return fail(MCBA_ERR_ARG, "mcba_resect_ransac: threshold (pixels) must be positive");
-  const int C = n_cameras, H = n_hypotheses;
+    return bad(g.slots == 1 ? ": non-NULL arrays (samples or poses_in), undistort_iterations >= 0 required" : ": non-NULL arrays, undistort_iterations >= 0 required");
+  if (n_cameras < 1 || n_cameras > MCBA_RESECT_MAX_CAMERAS) return bad(": 1 .. MCBA_RESECT_MAX_CAMERAS (64) cameras required");
+  if (n_points < 1) return bad(": at least one point required");
+  if (n_hypotheses < 1 || n_hypotheses > g.max_h) return bad(g.range);
+  if (!(threshold > 0.0)) return bad(": threshold (pixels) must be positive");
+  const int C = n_cameras, S = n_hypotheses, H = S * g.slots;
   const size_t P = n_points;
   // the usable points of every camera; the cameras that take part
   std::vector<unsigned char> use((size_t)C * P);
@@ -81,13 +91,13 @@ int mcba_resect_ransac(int n_cameras, size_t n_points, const double* points, con
   }
   if (!poses_in)
     for (int c : act)
-      for (int h = 0; h < H; ++h) {
-        const int* s = samples + MCBA_RESECT_SAMPLE * ((size_t)c * H + h);
-        for (int k = 0; k < MCBA_RESECT_SAMPLE; ++k) {
-          if (s[k] < 0 || (size_t)s[k] >= P) return fail(MCBA_ERR_ARG, "mcba_resect_ransac: a sample index is outside 0 .. n_points - 1");
-          if (!use[(size_t)c * P + s[k]]) return fail(MCBA_ERR_ARG, "mcba_resect_ransac: a sampled point is not usable for its camera");
+      for (int h = 0; h < S; ++h) {
+        const int* s = samples + g.size * ((size_t)c * S + h);
+        for (int k = 0; k < g.size; ++k) {
+          if (s[k] < 0 || (size_t)s[k] >= P) return bad(": a sample index is outside 0 .. n_points - 1");
+          if (!use[(size_t)c * P + s[k]]) return bad(": a sampled point is not usable for its camera");
           for (int j = 0; j < k; ++j)
-            if (s[j] == s[k]) return fail(MCBA_ERR_ARG, "mcba_resect_ransac: an index is repeated within a sample");
+            if (s[j] == s[k]) return bad(": an index is repeated within a sample");
         }
       }
   if (int rc = stateless_device(device)) return rc;
@@ -130,9 +140,10 @@ int mcba_resect_ransac(int n_cameras, size_t n_points, const double* points, con
     for (int a = 0; a < Ca; ++a)
       if (int rc = call.put(d_pin + 12 * HH * a, poses_in + 12 * HH * act[a], 12 * HH)) return rc;
   } else {
-    if (int rc = call.scratch(&d_smp, MCBA_RESECT_SAMPLE * HH * Ca)) return rc;
+    const size_t per = (size_t)g.size * S;   // indices per camera
+    if (int rc = call.scratch(&d_smp, per * Ca)) return rc;
     for (int a = 0; a < Ca; ++a)
-      if (int rc = call.put(d_smp + MCBA_RESECT_SAMPLE * HH * a, samples + MCBA_RESECT_SAMPLE * HH * act[a], MCBA_RESECT_SAMPLE * HH)) return rc;
+      if (int rc = call.put(d_smp + per * a, samples + per * act[a], per)) return rc;
   }
   if (int rc = call.scratch(&d_prep, 4 * P * Ca)) return rc;
   if (int rc = call.scratch(&d_use, P * Ca)) return rc;
@@ -158,7 +169,8 @@ int mcba_resect_ransac(int n_cameras, size_t n_points, const double* points, con
   mcba::launch_rs_prepare(nullptr, d_pts, d_uv, P, Ca, d_cams, undistort_iterations, d_prep, d_use);
   if (int rc = check_launch()) return rc;
   HIPCHK(hipEventRecord(ev[0], nullptr));
-  mcba::launch_rs_hypotheses(nullptr, d_pts, d_prep, P, Ca, d_smp, H, d_pin, d_cams, d_pose, d_KP, d_st);
+  if (g.slots == 1) mcba::launch_rs_hypotheses(nullptr, d_pts, d_prep, P, Ca, d_smp, H, d_pin, d_cams, d_pose, d_KP, d_st);
+  else mcba::launch_rs3_hypotheses(nullptr, d_pts, d_prep, P, Ca, d_smp, S, d_cams, d_pose, d_KP, d_st);
   if (int rc = check_launch()) return rc;
   HIPCHK(hipEventRecord(ev[1], nullptr));
   mcba::launch_rs_score(nullptr, d_pts, d_prep, d_use, P, Ca, d_KP, H, threshold, d_pc, d_pn);
@@ -197,6 +209,24 @@ int mcba_resect_ransac(int n_cameras, size_t n_points, const double* points, con
       if (int rc = call.download(status_out + HH * c, d_st + HH * a, HH)) return rc;
   }
   return MCBA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcba_resect_ransac(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, int n_hypotheses, const int* samples,
+                       const double* poses_in, double threshold, int undistort_iterations, int device, double* rt12, double* best4, unsigned char* inliers, double* pose_out, double* cost_out,
+                       unsigned* count_out, int* status_out, double* kernel_ms) {
+  return resect_ransac(kDlt6, n_cameras, n_points, points, uvs, cam12, dist5, n_hypotheses, samples, poses_in, threshold, undistort_iterations, device, rt12, best4, inliers, pose_out, cost_out,
+                       count_out, status_out, kernel_ms);
+}
+
+int mcba_resect_ransac_p3p(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, int n_hypotheses, const int* samples,
+                           double threshold, int undistort_iterations, int device, double* rt12, double* best4, unsigned char* inliers, double* pose_out, double* cost_out, unsigned* count_out,
+                           int* status_out, double* kernel_ms) {
+  return resect_ransac(kP3p, n_cameras, n_points, points, uvs, cam12, dist5, n_hypotheses, samples, nullptr, threshold, undistort_iterations, device, rt12, best4, inliers, pose_out, cost_out,
+                       count_out, status_out, kernel_ms);
 }
 
 int mcba_resect_refine(int n_cameras, size_t n_points, const double* points, const double* uvs, const unsigned char* mask, const double* cam12, const double* dist5, const int* active, int loss,

@@ -152,16 +152,17 @@ MCBA_HD void rs_camera_point(const double* pose, const double* X, double* Xc) {
   Xc[2] = fma(pose[6], X[0], fma(pose[7], X[1], fma(pose[8], X[2], pose[11])));
 }
 
-// One Gauss-Newton iteration on the six points: residuals pi(R X + t) - x in normalised coordinates (12), unknowns (omega, delta) of the
-// left-multiplicative update R <- exp(omega) R, t <- exp(omega) t + delta, the 6 x 6 normal equations solved by chol_solve<6>.  step6: the
-// step taken (tests: how far the last one still moved).
+// One Gauss-Newton iteration on N sample points (6: a DLT hypothesis; 3: a P3P candidate, mcba_resect_p3p_math.h): residuals pi(R X + t) - x
+// in normalised coordinates (2 N), unknowns (omega, delta) of the left-multiplicative update R <- exp(omega) R, t <- exp(omega) t + delta, the
+// 6 x 6 normal equations solved by chol_solve<6>.  step6: the step taken (tests: how far the last one still moved).
+template <int N>
 MCBA_HD void rs_gauss_newton_step(const double* X, const double* x, double* pose, double* step6) {
   double A[21], g[6];
 #pragma unroll
   for (int i = 0; i < 21; ++i) A[i] = 0.0;
 #pragma unroll
   for (int i = 0; i < 6; ++i) g[i] = 0.0;
-  for (int k = 0; k < 6; ++k) {
+  for (int k = 0; k < N; ++k) {
     double Xc[3];
     rs_camera_point(pose, X + 3 * k, Xc);
     const double iz = 1.0 / Xc[2], px = Xc[0] * iz, py = Xc[1] * iz;
@@ -198,7 +199,7 @@ MCBA_HD void rs_gauss_newton_step(const double* X, const double* x, double* pose
 MCBA_HD int rs_hypothesis(const double* X, const double* x, double* S, double* V, double* pose, double* step6) {
   bool ok = rs_dlt(X, x, S, V, pose);
   for (int i = 0; i < 6; ++i) step6[i] = 0.0;
-  for (int it = 0; it < kRsGnIterations; ++it) rs_gauss_newton_step(X, x, pose, step6);
+  for (int it = 0; it < kRsGnIterations; ++it) rs_gauss_newton_step<kRsSample>(X, x, pose, step6);
 #pragma unroll
   for (int i = 0; i < 12; ++i) ok = ok && rs_finite(pose[i]);
   for (int k = 0; k < 6; ++k) {

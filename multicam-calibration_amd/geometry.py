@@ -882,16 +882,21 @@ def extrinsics_from_keypoints(all_uvs, all_intrinsics, *, threshold, root=0, n_h
 RESECTION_STATUS = {1: "ok", -1: "fewer than 6 usable points", -2: "too few inliers"}
 MAX_RESECTION_HYPOTHESES = ops.RESECT_MAX_HYPOTHESES
 MAX_RESECTION_CAMERAS = ops.RESECT_MAX_CAMERAS
+RESECTION_SOLVERS = ("dlt6", "p3p")     # the hypothesis generators of resect_camera / resect_cameras (SURVEY.md sections 8f-16, 8f-18)
+MAX_RESECTION_P3P_SAMPLES = ops.RESECT_P3P_MAX_SAMPLES
 
 
-def draw_resection_samples(n_usable, n_hypotheses, seed):
-    """(n_hypotheses, 6) int32: per hypothesis six different indices in 0 .. n_usable - 1, one
-    `np.random.default_rng(seed).choice(n_usable, 6, replace=False)` each from a generator of its own -- the global numpy generator is never
-    touched.  seed: anything default_rng takes (an int, a sequence of ints).  The indices count the camera's usable points in their order."""
-    if int(n_usable) < ops.RESECT_SAMPLE:
-        raise ValueError("a sample needs 6 different points")
+def draw_resection_samples(n_usable, n_hypotheses, seed, size=6):
+    """(n_hypotheses, size) int32: per hypothesis `size` different indices in 0 .. n_usable - 1, one
+    `np.random.default_rng(seed).choice(n_usable, size, replace=False)` each from a generator of its own -- the global numpy generator is never
+    touched.  seed: anything default_rng takes (an int, a sequence of ints).  The indices count the camera's usable points in their order.
+    size: 6 (the samples of solver="dlt6") or 3 (solver="p3p")."""
+    if size not in (ops.RESECT_SAMPLE, ops.RESECT_P3P_SAMPLE):
+        raise ValueError("size must be 6 (dlt6) or 3 (p3p)")
+    if int(n_usable) < size:
+        raise ValueError(f"a sample needs {size} different points")
     rng = np.random.default_rng(seed)
-    return np.ascontiguousarray(np.stack([rng.choice(int(n_usable), ops.RESECT_SAMPLE, replace=False) for _ in range(int(n_hypotheses))]), dtype=np.int32)
+    return np.ascontiguousarray(np.stack([rng.choice(int(n_usable), size, replace=False) for _ in range(int(n_hypotheses))]), dtype=np.int32)
 
 
 def _min_resection_inliers(n_usable):
@@ -906,7 +911,7 @@ class CameraResection:
     n_usable: np.ndarray       # (C,) points with a finite position and a finite detection
     n_inliers: np.ndarray      # (C,)
     cost: np.ndarray           # (C,) the winner's truncated cost, sum min(e^2, threshold^2) in px^2
-    hypothesis: np.ndarray     # (C,) the winner's index, -1 where status is -1
+    hypothesis: np.ndarray     # (C,) the winner's index, -1 where status is -1; solver="p3p": its slot, the sample is hypothesis // 4
     refined_cost: np.ndarray   # (C,) the polish: robust cost 0.5 sum rho(f^2) over the inliers' raw detections at the result; NaN where it did not run
     optimality: np.ndarray     # (C,) inf-norm of its gradient
     nfev: np.ndarray           # (C,) its evaluations
@@ -915,12 +920,16 @@ class CameraResection:
     #                            hypotheses before the polish, kernel_ms: dict(ransac=(total, prepare, hypotheses, score, finish, mask), polish=the span of its evaluations)
 
 
-def _resect(points, uvs, intr, seeds, threshold, n_hypotheses, undistort_iterations, refine, loss, f_scale, ftol, xtol, gtol, max_nfev, device):
+def _resect(points, uvs, intr, seeds, threshold, n_hypotheses, undistort_iterations, refine, loss, f_scale, ftol, xtol, gtol, max_nfev, device, solver="dlt6"):
     if not threshold > 0:
         raise ValueError("`threshold` (pixels) must be positive.")
+    if solver not in RESECTION_SOLVERS:
+        raise ValueError(f"solver must be one of {RESECTION_SOLVERS}")
     H = int(n_hypotheses)
-    if not 1 <= H <= MAX_RESECTION_HYPOTHESES:
-        raise ValueError(f"n_hypotheses must be 1 .. {MAX_RESECTION_HYPOTHESES}")
+    p3p = solver == "p3p"
+    size, h_max = (ops.RESECT_P3P_SAMPLE, MAX_RESECTION_P3P_SAMPLES) if p3p else (ops.RESECT_SAMPLE, MAX_RESECTION_HYPOTHESES)
+    if not 1 <= H <= h_max:
+        raise ValueError(f"n_hypotheses must be 1 .. {h_max}" + (" samples with solver=\"p3p\"" if p3p else ""))
     if int(undistort_iterations) < 0:
         raise ValueError("undistort_iterations must not be negative")
     if loss not in ops.LOSSES:
@@ -940,14 +949,18 @@ def _resect(points, uvs, intr, seeds, threshold, n_hypotheses, undistort_iterati
     cam, dist = _cam_blocks([np.zeros(6)] * C, intr)
     usable = np.isfinite(pts).all(1)[None, :] & np.isfinite(uvs).all(2)
     n_usable = usable.sum(1)
-    samples, per_camera = np.zeros((C, H, ops.RESECT_SAMPLE), dtype=np.int32), [None] * C
+    samples, per_camera = np.zeros((C, H, size), dtype=np.int32), [None] * C
     for c in range(C):
         if n_usable[c] >= ops.RESECT_SAMPLE:
-            samples[c] = np.flatnonzero(usable[c]).astype(np.int32)[draw_resection_samples(n_usable[c], H, seeds[c])]
+            samples[c] = np.flatnonzero(usable[c]).astype(np.int32)[draw_resection_samples(n_usable[c], H, seeds[c], size=size)]
             per_camera[c] = samples[c]
     rt, best, mask, ms = np.empty((C, 12)), np.empty((C, 4)), np.zeros((C, P), dtype=np.uint8), np.zeros(6)
-    ops.call("mcba_resect_ransac", C, P, pts.ctypes.data, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, H, samples.ctypes.data, None, float(threshold), int(undistort_iterations), int(device),
-             rt.ctypes.data, best.ctypes.data, mask.ctypes.data, None, None, None, None, ms.ctypes.data)
+    if p3p:
+        ops.call("mcba_resect_ransac_p3p", C, P, pts.ctypes.data, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, H, samples.ctypes.data, float(threshold), int(undistort_iterations), int(device),
+                 rt.ctypes.data, best.ctypes.data, mask.ctypes.data, None, None, None, None, ms.ctypes.data)
+    else:
+        ops.call("mcba_resect_ransac", C, P, pts.ctypes.data, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, H, samples.ctypes.data, None, float(threshold), int(undistort_iterations), int(device),
+                 rt.ctypes.data, best.ctypes.data, mask.ctypes.data, None, None, None, None, ms.ctypes.data)
     ext = np.full((C, 6), np.nan)
     for c in range(C):
         if np.isfinite(rt[c]).all():
@@ -973,7 +986,7 @@ def _resect(points, uvs, intr, seeds, threshold, n_hypotheses, undistort_iterati
 
 
 def resect_cameras(points, all_uvs, all_intrinsics, *, threshold, n_hypotheses=256, seed=0, undistort_iterations=5, refine=True, loss="soft_l1", f_scale=1.0, ftol=1e-8, xtol=1e-8, gtol=1e-8,
-                   max_nfev=50, device=0):
+                   max_nfev=50, device=0, solver="dlt6"):
     """Resection: the pose of every camera from known 3-D points and that camera's own 2-D detections of them -> `CameraResection`.
     points: (P, 3) in the world frame, a NaN row = unknown; all_uvs: per camera (P, 2) raw detections, NaN = unseen; all_intrinsics: per
     camera (camera_matrix, dist_coefs).  A point is usable for a camera when its position and its detection are finite.  The cameras are
@@ -995,21 +1008,35 @@ def resect_cameras(points, all_uvs, all_intrinsics, *, threshold, n_hypotheses=2
     refine=True: every camera of status 1 or -2 is polished on its inliers by a pose-only Levenberg-Marquardt (`mcba_resect_refine`): the
     robust cost (`loss`, `f_scale`, as `refine_extrinsics`) of the raw detections under the five-coefficient model, the points fixed; ftol,
     xtol, gtol, max_nfev and `lm_status` are scipy.optimize.least_squares'.  The cost never rises, every camera stops on its own.
-    refine=False: the winning hypotheses."""
+    refine=False: the winning hypotheses.
+
+    solver (`RESECTION_SOLVERS`): "dlt6", the default, is the generator above.  "p3p" (`mcba_resect_ransac_p3p`, `csrc/mcba_resect_p3p.hip`,
+    SURVEY.md section 8f-18) draws `n_hypotheses` (at most 1024) SAMPLES of three points (`draw_resection_samples(..., size=3)`); each gives up
+    to four poses -- the real roots of Grunert's quartic, settled by five Gauss-Newton iterations on the three points --, all of them scored
+    like any hypothesis: four table slots per sample, `hypothesis` is the winning slot and `hypothesis // 4` its sample.  Scoring, status
+    rules (a camera still needs 6 usable points) and the polish are the same.  Use "p3p" where the points lie in or near a plane (floor marks,
+    arena landmarks, an animal flatter than the noise: the 6-point DLT has no defined start there, and between 0.05 mm of depth and the noise
+    it can win with a wrong pose and status 1), and where more than about a third of the detections are wrong (a clean 3-point sample is
+    drawn 1 / (1 - outlier share)^3 times as often as a clean 6-point one).  Use "dlt6" otherwise: six points average the noise of a
+    hypothesis, and a sample costs one slot of scoring, not four.  Caveat: a plane seen nearly fronto-parallel from far away has a second pose
+    of almost equal reprojection cost; the scorer picks the lower cost and promises nothing more."""
     uvs = np.ascontiguousarray(np.stack([np.asarray(u, dtype=np.float64) for u in all_uvs])) if len(all_uvs) else np.zeros((0, 0, 2))
     return _resect(points, uvs, list(all_intrinsics), [[int(seed), c] for c in range(len(uvs))] if np.ndim(seed) == 0 else [list(np.ravel(seed)) + [c] for c in range(len(uvs))], threshold,
-                   n_hypotheses, undistort_iterations, refine, loss, f_scale, ftol, xtol, gtol, max_nfev, device)
+                   n_hypotheses, undistort_iterations, refine, loss, f_scale, ftol, xtol, gtol, max_nfev, device, solver)
 
 
 def resect_camera(points, uvs, intrinsics, *, threshold, n_hypotheses=256, seed=0, undistort_iterations=5, refine=True, loss="soft_l1", f_scale=1.0, ftol=1e-8, xtol=1e-8, gtol=1e-8, max_nfev=50,
-                  device=0, return_info=False):
+                  device=0, return_info=False, solver="dlt6"):
     """One camera of `resect_cameras`: (transform (6,), inliers (P,) bool), transform = (rotation vector, translation) of x_cam = R X + t,
     the convention of `all_extrinsics` everywhere; NaN when fewer than 6 points are usable.  points: (P, 3), uvs: (P, 2) raw detections,
-    intrinsics: (camera_matrix, dist_coefs); the samples come from `seed` itself.  return_info=True: also the `CameraResection` of the one camera."""
+    intrinsics: (camera_matrix, dist_coefs); the samples come from `seed` itself.  return_info=True: also the `CameraResection` of the one camera.
+    solver: "dlt6" or "p3p" as there -- "p3p" for coplanar or nearly coplanar points and for heavy outlier shares, `n_hypotheses` (at most
+    1024) then counts 3-point samples of up to four poses each; a nearly fronto-parallel distant plane has a second pose of almost equal
+    cost, and the lower cost wins."""
     u = np.asarray(uvs, dtype=np.float64)
     if u.ndim != 2:
         raise ValueError("uvs must be (n_points, 2)")
-    r = _resect(points, np.ascontiguousarray(u[None]), [intrinsics], [seed], threshold, n_hypotheses, undistort_iterations, refine, loss, f_scale, ftol, xtol, gtol, max_nfev, device)
+    r = _resect(points, np.ascontiguousarray(u[None]), [intrinsics], [seed], threshold, n_hypotheses, undistort_iterations, refine, loss, f_scale, ftol, xtol, gtol, max_nfev, device, solver)
     return (r.extrinsics[0], r.inliers[0], r) if return_info else (r.extrinsics[0], r.inliers[0])
 
 

@@ -148,6 +148,8 @@ SYMBOLS = [
     # camera resection: every array by address
     ("mcba_two_view_ransac5", ctypes.c_int, [ctypes.c_size_t, _dp, _dp, _dp, _dp, ctypes.c_int, _dp, ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("mcba_resect_ransac", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    # the P3P generator: mcba_resect_ransac's arguments less poses_in
+    ("mcba_resect_ransac_p3p", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, ctypes.c_int, _dp, ctypes.c_double, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("mcba_resect_refine", ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
                                           ctypes.c_int, _dp, _dp, _dp, _dp]),
     ("mcba_profile_enable", ctypes.c_int, [_h, ctypes.c_int]),
@@ -171,6 +173,7 @@ LM_STATE = 32  # MCBA_LM_STATE of include/mcba.h
 TWOVIEW_MAX_HYPOTHESES, TWOVIEW_CHUNK, TWOVIEW_POINTS_PER_BLOCK = 4096, 64, 1024  # MCBA_TWOVIEW_* of include/mcba.h
 TWOVIEW5_SAMPLE, TWOVIEW5_SLOTS, TWOVIEW5_MAX_SAMPLES = 5, 10, 1024  # MCBA_TWOVIEW5_* of include/mcba.h
 RESECT_MAX_HYPOTHESES, RESECT_CHUNK, RESECT_POINTS_PER_BLOCK, RESECT_SAMPLE, RESECT_GN_ITERATIONS, RESECT_MAX_CAMERAS, RESECT_SYSTEM = 4096, 64, 1024, 6, 10, 64, 29  # MCBA_RESECT_* of include/mcba.h
+RESECT_P3P_SAMPLE, RESECT_P3P_SLOTS, RESECT_P3P_MAX_SAMPLES, RESECT_P3P_POLISH = 3, 4, 1024, 5  # MCBA_RESECT_P3P_* of include/mcba.h
 
 _lib = None
 
