@@ -573,7 +573,8 @@ int mcba_detect_anchor(int height, int width, int channels, const unsigned char*
  * The call linearises x[slot] with curvature floor 1 into the handle's own buffers and reduces with lambda = 0: a linearisation or reduced
  * system the caller had is gone afterwards (call mcba_linearize again); the handle's curvature floor, loss and parameters are untouched.
  * Either output may be NULL.  info8 = {sigma2, m, p, frames without data, failing pivot (-1 = none), kernel_ms of the covariance kernels,
- * 0, 0}.  MCBA_ERR_NONFINITE with info8[4] >= 0: S_g is not positive definite at that pivot (the message names camera and parameter).
+ * frames per workgroup of k_cov_frames (8 or 4; 0 when frame_cov is NULL), ld (the row stride of the camera block on the device, n rounded up
+ * to 64)}.  MCBA_ERR_NONFINITE with info8[4] >= 0: S_g is not positive definite at that pivot (the message names camera and parameter).
  * MCBA_ERR_ARG: a sparse-Schur handle, a tabulated loss, a numeric x_scale or frozen coordinates, gauge_camera out of range. */
 int mcba_covariance(mcba_handle* h, int slot, int gauge_camera, double sigma2_in, double* cam_cov, double* frame_cov, double* info8);
 
@@ -592,7 +593,9 @@ int mcba_covariance(mcba_handle* h, int slot, int gauge_camera, double sigma2_in
  * views_out (P): cameras that see the point.  status_out (P): 1 ok; -1 fewer than two views or a NaN in the point; -2 degenerate: a pivot of
  * the scaled factor whose square is below 1e-12 (two cameras with one centre, a point on the baseline).  Both terms are NaN unless the
  * status is 1, and such a point leaves the pooled sums.
- * info8 = {sigma2, m, 3 P_u, points of status -1, points of status -2, kernel_ms, 0, 0}; kernel_ms may be NULL.  n_points == 0 returns at once.
+ * info8 = {sigma2, m, 3 P_u, points of status -1, points of status -2, kernel_ms, points per workgroup of k_tricov_cal (16, 10 or 5; 0 without
+ * cam_cov), ld (the row stride of the uploaded cam_cov, 12 C rounded up to 64)}; kernel_ms may be NULL.  n_points == 0 returns at once with
+ * info8 = {sigma2_in, 0 ..}.
  * The environment variable MCBA_TRICOV_G (5, 10 or 16), read per call, forces the number of points a workgroup of the calibration term takes. */
 int mcba_triangulation_covariance(int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, const double* cam_cov, int loss, double f_scale,
                                   double sigma2_in, int device, double* det6, double* cal6, int* views_out, int* status_out, double* info8, double* kernel_ms);

@@ -102,7 +102,7 @@ int mcba_covariance(mcba_handle* h, int slot, int gauge_camera, double sigma2_in
   float ms = 0.f;
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
   if (e != hipSuccess) { g_err = std::string("mcba_covariance: ") + hipGetErrorString(e); return done(MCBA_ERR_HIP); }
-  info8[0] = sigma2; info8[1] = m; info8[2] = p; info8[3] = ndeg; info8[4] = pivot; info8[5] = ms; info8[6] = info8[7] = 0.0;
+  info8[0] = sigma2; info8[1] = m; info8[2] = p; info8[3] = ndeg; info8[4] = pivot; info8[5] = ms; info8[6] = frame_cov ? G : 0; info8[7] = ld;
   if (pivot >= 0) {
     const int cam = pivot / h->cw, par = pivot % h->cw + (12 - h->cw);
     g_err = "mcba_covariance: the gauge-fixed Schur complement is not positive definite: pivot " + std::to_string(pivot) + " (camera " + std::to_string(cam) + ", parameter " + std::to_string(par) + ")";

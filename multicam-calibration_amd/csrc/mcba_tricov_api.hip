@@ -75,7 +75,7 @@ int mcba_triangulation_covariance_weighted(int n_cameras, size_t n_points, const
   HIPCHK(call.stop(&ms));
   if (kernel_ms) *kernel_ms = ms;
   if (int rc = call.download(info8, d_info, (size_t)5)) return rc;
-  info8[5] = ms;
+  info8[5] = ms; info8[6] = G; info8[7] = ld;
   if (int rc = call.download(det6, d_det, 6 * n_points)) return rc;
   if (int rc = call.download(views_out, d_views, n_points)) return rc;
   if (int rc = call.download(status_out, d_status, n_points)) return rc;

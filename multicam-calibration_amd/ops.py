@@ -778,7 +778,8 @@ class Problem:
 
     def covariance(self, slot, gauge_camera, sigma2=None, frames=True):
         """Covariance of the camera system and of every frame pose at x[slot] (include/mcba.h: mcba_covariance).  Returns (cam_cov (n, n) in the
-        order of `cam_index`, frame_cov (F, 6, 6) or None, info (8,) = sigma2, m, p, frames without data, failing pivot, kernel_ms, 0, 0).
+        order of `cam_index`, frame_cov (F, 6, 6) or None, info (8,) = sigma2, m, p, frames without data, failing pivot, kernel_ms, frames per
+        workgroup of k_cov_frames (0 without frames), ld of the device's camera block).
         ValueError if the gauge-fixed Schur complement is not positive definite.  The handle's linearisation is gone afterwards."""
         if self._loss_fn is not None:
             raise ValueError("covariance: named losses only (a callable loss is set)")

@@ -31,7 +31,7 @@ class CalibrationUncertainty:
     sigma2: float
     n_residuals: int
     n_free: int
-    info: dict                       # n_degenerate_frames, kernel_ms
+    info: dict                       # n_degenerate_frames, kernel_ms, group (frames per workgroup of k_cov_frames; 0 without frame blocks), ld (row stride of the camera block on the device)
 
 
 def calibration_uncertainty(all_calib_uvs, all_extrinsics, all_intrinsics, calib_objpoints, calib_poses, *, gauge_camera=0, loss="soft_l1", f_scale=1.0, sigma=None,
@@ -95,7 +95,7 @@ def calibration_uncertainty(all_calib_uvs, all_extrinsics, all_intrinsics, calib
         with np.errstate(invalid="ignore"):
             pose_std = np.sqrt(np.diagonal(frames, axis1=1, axis2=2))
     return CalibrationUncertainty(camera_covariance=full, intrinsics_std=std[:, :6].copy(), extrinsics_std=std[:, 6:].copy(), camera_correlation=corr, pose_covariance=frames,
-                                  pose_std=pose_std, sigma2=sigma2, n_residuals=m, n_free=p, info={"n_degenerate_frames": int(info[3]), "kernel_ms": float(info[5])})
+                                  pose_std=pose_std, sigma2=sigma2, n_residuals=m, n_free=p, info={"n_degenerate_frames": int(info[3]), "kernel_ms": float(info[5]), "group": int(info[6]), "ld": int(info[7])})
 
 
 POINT_STATUS = {1: "ok", -1: "too few views", -2: "degenerate"}
@@ -112,7 +112,7 @@ class TriangulationUncertainty:
     sigma2: float
     n_residuals: int
     n_free: int
-    info: dict                         # n_unusable, n_degenerate, kernel_ms
+    info: dict                         # n_unusable, n_degenerate, kernel_ms, group (points per workgroup of k_tricov_cal; 0 without a camera covariance), ld (row stride of the uploaded camera covariance)
 
 
 def _camera_covariance(camera_covariance, C):
@@ -202,4 +202,4 @@ def triangulation_uncertainty(points, all_uvs, all_extrinsics, all_intrinsics, *
     with np.errstate(invalid="ignore"):
         std = np.sqrt(np.diagonal(total, axis1=1, axis2=2))
     return TriangulationUncertainty(covariance=total, std=std, detection_covariance=det3, calibration_covariance=cal3, n_views=views, status=status, sigma2=sigma2, n_residuals=m,
-                                    n_free=nfree, info={"n_unusable": int(info[3]), "n_degenerate": int(info[4]), "kernel_ms": float(info[5])})
+                                    n_free=nfree, info={"n_unusable": int(info[3]), "n_degenerate": int(info[4]), "kernel_ms": float(info[5]), "group": int(info[6]), "ld": int(info[7])})

@@ -3,7 +3,12 @@
 Metric, for the camera block and every frame block: max |Sigma_gpu - Sigma_ref| / sqrt(Sigma_ref,ii Sigma_ref,jj), and the same on the
 standard deviations.  Bound: 64 cond_2(H_scaled) 2.2e-16 with cond_2 from the oracle -- the forward-error form for inverting a matrix whose
 entries carry a few eps of summation error; two float64 host algorithms on the oracle's own H differ by 0.1 .. 2.4 cond eps at these shapes,
-64 leaves the GPU's different summation order a factor of about 25.  Every case prints its figures before it asserts."""
+64 leaves the GPU's different summation order a factor of about 25.  Every case prints its figures before it asserts.
+
+Every case also asserts the launch shape the call reports (info["group"], info["ld"]) against covariance_oracle.expected_group / expected_ld, and holds
+the frame stage on its own -- the returned blocks against the long-double evaluation of sigma2 V_f^-1 + Y_f Sigma_cc Y_f^T at the camera covariance
+the GPU itself returned -- to covariance_oracle.FRAME_BOUND_FACTOR cond_2(V_f) eps, orders below the end-to-end bound.  The edges of the launches
+(frames without data at group edges, the two halves against the device's own input, the error paths) are in tests/test_gpu_covariance_edges.py."""
 import os
 
 import numpy as np
@@ -31,6 +36,24 @@ def check_against(u, o, label, skip_frames=()):
     assert e_cam <= o["bound"] and e_fr <= o["bound"] and e_std <= o["bound"]
 
 
+def check_launch_shape(u, n, label, force=0, frames=True):
+    """the group and row stride the call says it launched against the LDS formula of the kernel's comment"""
+    print(f"{label}: n {n} group {u.info['group']} (expected {cvo.expected_group(n, force) if frames else 0}) ld {u.info['ld']} (expected {cvo.expected_ld(n)})")
+    assert u.info["group"] == (cvo.expected_group(n, force) if frames else 0) and u.info["ld"] == cvo.expected_ld(n)
+
+
+def check_frame_stage(u, o, label):
+    """the frame blocks against the long-double frame stage fed the camera covariance the GPU returned, in units of cond_2(V_f) eps"""
+    ref, cond_v = cvo.frame_reference(o, u.camera_covariance, u.sigma2)
+    e = cvo.frame_stage_error(u.pose_covariance, ref, cond_v)
+    print(f"{label}: frame stage {e:.3g} cond(V_f) eps (bound {cvo.FRAME_BOUND_FACTOR:g}; cond(V_f) {np.nanmin(cond_v):.3g} .. {np.nanmax(cond_v):.3g}): {e * np.nanmax(cond_v) / (cvo.BOUND_FACTOR * o['cond']):.2g} of the end-to-end bound")
+    assert e <= cvo.FRAME_BOUND_FACTOR
+
+
+def system_size(pr):
+    return (6 if pr["kwargs"]["fix_intrinsics"] else 12) * pr["uvs"].shape[0]
+
+
 def check_exact(u, o, C):
     cam = u.camera_covariance
     d = np.sqrt(np.diagonal(cam))
@@ -55,21 +78,28 @@ def test_cases_match_the_oracle(name):
     pr, o = cvo.case(name)
     if name == "c3_f30_missing_cauchy_gauge2":
         assert pr["uvs"].shape[1] == 25   # the frames the filter keeps
+    assert pr["uvs"].shape[1] == cvo.KEPT_FRAMES.get(name, pr["uvs"].shape[1])
     u = run(pr)
+    check_launch_shape(u, system_size(pr), name)
     check_against(u, o, name)
     check_exact(u, o, pr["uvs"].shape[0])
+    check_frame_stage(u, o, name)
 
 
 @gpu
 def test_four_frame_workgroups_match_the_oracle(monkeypatch):
-    """k_cov_frames with 4 frames per workgroup -- the shape of rigs beyond about 26 cameras, which no test-sized problem reaches -- forced at
-    C = 2, F = 130 and at n = 120 (MCBA_COV_FRAMES_G, read per call)."""
+    """k_cov_frames with 4 frames per workgroup -- the shape of rigs of 27 cameras and more, which "c27_f5_missing" and "c40_f9_missing_huber_fs07"
+    reach unforced -- forced at C = 2, F = 130 and at n = 120 (MCBA_COV_FRAMES_G, read per call): the small-n end of that shape, one and two
+    panels, and F = 3, 4, 5: one short of, at and one past a group of 4."""
     monkeypatch.setenv("MCBA_COV_FRAMES_G", "4")
-    for name in ("c2_f130", "c10_f8"):
+    for name in ("c2_f130", "c10_f8", "c2_f3", "c2_f4", "c2_f5"):
         pr, o = cvo.case(name)
         u = run(pr)
+        check_launch_shape(u, system_size(pr), name + " (G = 4)", force=4)
+        assert u.info["group"] == 4
         check_against(u, o, name + " (G = 4)")
         check_exact(u, o, pr["uvs"].shape[0])
+        check_frame_stage(u, o, name + " (G = 4)")
 
 
 @gpu
@@ -77,6 +107,7 @@ def test_frame_covariance_can_be_left_out():
     pr, o = cvo.case("c2_f4")
     u = run(pr, frame_covariance=False)
     assert u.pose_covariance is None and u.pose_std is None
+    check_launch_shape(u, 24, "c2_f4 without frame blocks", frames=False)
     assert cvo.rel_err(u.camera_covariance, o["camera_covariance"]) <= o["bound"]
 
 

@@ -1,6 +1,7 @@
 """triangulation_uncertainty on the GPU (csrc/mcba_tricov.hip through mcba_triangulation_covariance) against tests/tricov_oracle.py, at the smallest
 shapes at which the kernels can go wrong: one point; n = 36 (no multiple of 16 or 32), n = 72 (a full 64-column panel and a partial one), n = 144,
-n = 288; one lane and one point past a wavefront and past a 16-point group; the smaller groups forced.
+n = 288; one lane and one point past a wavefront and past a 16-point group; the smaller groups forced -- and reached unforced at 30, 48, 49 and 64
+cameras (tricov_oracle.WIDE_CASES: n = 768 = ld, twelve panels of diag_blocks), every case asserting the group the call reports.
 
 Metric and bound are the oracle's (its docstring derives both factors): detection term max |got - ref|_ij / sqrt(ref_ii ref_jj) <= k cond_2(H_s) eps,
 calibration term |got - ref|_ij <= k cond_2(H_s) eps sqrt(T_ii T_jj), k = 64, or 2000 for the two cases of the "outlier" scene.  Every case prints its
@@ -45,10 +46,14 @@ def check_exact(u, o):
 def test_cases_match_the_oracle(name):
     """every case with its dense random positive semi-definite camera covariance and without one"""
     i, o = tco.case(name)
+    C = len(i["ext"])
     u = run(i)
+    print(f"{name}: {C} cameras, group {u.info['group']} (expected {tco.expected_group(C)}), ld {u.info['ld']}")
+    assert u.info["group"] == tco.expected_group(C) and u.info["ld"] == (12 * C + 63) // 64 * 64
     tco.check_against_oracle(name, as_dict(u), o)
     check_exact(u, o)
     alone = run(i, with_cov=False)
+    assert alone.info["group"] == 0 and alone.info["ld"] == u.info["ld"]
     tco.check_against_oracle(name + " (no camera covariance)", as_dict(alone), o, with_cov=False)
     check_exact(alone, o)
     assert alone.calibration_covariance is None and np.array_equal(alone.covariance, alone.detection_covariance, equal_nan=True)
@@ -73,6 +78,7 @@ def test_smaller_groups_match_the_oracle(monkeypatch, group):
     for name in ("three", "twelve", "c3_p17"):
         i, o = tco.case(name)
         u = run(i)
+        assert u.info["group"] == int(group) == tco.expected_group(len(i["ext"]), force=int(group))
         tco.check_against_oracle(f"{name} (G = {group})", as_dict(u), o)
         check_exact(u, o)
 
@@ -205,3 +211,26 @@ def test_bundle_adjust_to_point_uncertainty():
     ok = ref["status"] == 1
     print(f"std (detection) {np.sqrt(np.diagonal(u.detection_covariance[ok], axis1=1, axis2=2)).mean(0)}, std (calibration) {np.sqrt(np.diagonal(u.calibration_covariance[ok], axis1=1, axis2=2)).mean(0)}")
     assert ok.sum() > 100 and (np.diagonal(u.calibration_covariance[ok], axis1=1, axis2=2) > 0).all()
+
+
+@gpu
+def test_calibration_to_point_uncertainty_at_27_cameras():
+    """calibration_uncertainty (k_cov_frames in its four-frame shape) -> triangulation_uncertainty(camera_covariance=unc) at 27 cameras on the board
+    corners of two frames: the oracle fed the same Sigma_cc within the bound, both calls reporting their natural groups, a calibration term that is
+    not zero.  The camera covariance of a real calibration: strongly correlated, the gauge camera's rows zero."""
+    import covariance_oracle as cvo
+
+    pr, _ = cvo.case("c27_f5_missing")
+    unc = m.calibration_uncertainty(pr["uvs"], pr["extrinsics"], pr["intrinsics"], pr["obj"], pr["poses"], **pr["kwargs"])
+    assert unc.info["group"] == 4 == cvo.expected_group(324)
+    frames = [1, 4]
+    pts = np.concatenate([pr["obj"] @ ks.rodrigues(pr["poses"][f][:3]).T + pr["poses"][f][3:] for f in frames])
+    det = [np.concatenate([pr["uvs"][c, f] for f in frames]) for c in range(27)]
+    sigma = float(np.sqrt(unc.sigma2))
+    u = triangulation_uncertainty(pts, det, pr["extrinsics"], pr["intrinsics"], camera_covariance=unc, sigma=sigma)
+    ref = tco.uncertainty(pts, det, pr["extrinsics"], pr["intrinsics"], camera_covariance=unc.camera_covariance, sigma=sigma)
+    assert u.info["group"] == 16 == tco.expected_group(27) and u.info["ld"] == 384
+    tco.check_against_oracle("calibration_uncertainty(27, 5), two boards", as_dict(u), ref)
+    check_exact(u, ref)
+    ok = ref["status"] == 1
+    assert ok.sum() == 108 and (np.diagonal(u.calibration_covariance[ok], axis1=1, axis2=2) > 0).all()

@@ -40,6 +40,20 @@ def test_cases_match_the_oracle(name):
 
 
 @gpu
+def test_wide_rig_takes_the_one_tile_weighted_kernel_unforced():
+    """49 cameras (tricov_oracle's "c49_p11", arctan): the weighted instantiation of k_tricov_cal at one row tile, five points per workgroup because
+    nothing larger fits -- not forced; against the oracle of the 147 virtual cameras, T Sigma T^T for the camera covariance"""
+    i, _ = tco.case("c49_p11")
+    w = wo.draw_levels(49, 11, 9049)
+    assert wo.usable_fraction(i["uvs"], w) == 1.0
+    o = wo.uncertainty_virtual(i["points"], i["uvs"], i["ext"], i["intr"], w, camera_covariance=i["camera_covariance"], sigma=tco.SIGMA, loss=i["loss"], f_scale=i["f_scale"])
+    u = run(dict(i, weights=w))
+    print(f"c49_p11, weighted: group {u.info['group']}, ld {u.info['ld']}")
+    assert u.info["group"] == 5 == tco.expected_group(49) and u.info["ld"] == 640
+    tco.check_against_oracle("c49_p11, weighted", as_dict(u), o)
+
+
+@gpu
 @pytest.mark.parametrize("name", wo.POOLED_CASES)
 def test_pooled_sigma_matches_the_oracle(name):
     i, o = wo.tricov_case(name)

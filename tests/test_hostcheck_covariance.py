@@ -62,6 +62,7 @@ def host_covariance(hc, o, C, F, cw, gauge, sigma2):
 def test_host_build_matches_the_oracle(hc, name):
     pr, o = cvo.case(name)
     C, F = pr["uvs"].shape[:2]
+    assert F == cvo.KEPT_FRAMES.get(name, F)
     kw = pr["kwargs"]
     cam, fr, flag = host_covariance(hc, o, C, F, 6 if kw["fix_intrinsics"] else 12, kw["gauge_camera"], o["sigma2"])
     e_cam, e_fr = cvo.rel_err(cam, o["camera_covariance"]), cvo.rel_err(fr, o["pose_covariance"])
@@ -73,6 +74,49 @@ def test_host_build_matches_the_oracle(hc, name):
     assert np.array_equal(cam, cam.T) and np.array_equal(fr, fr.transpose(0, 2, 1))
     assert (cam[o["held"]] == 0.0).all() and (cam[:, o["held"]] == 0.0).all()
     assert (np.linalg.eigvalsh(fr) > 0).all()
+    # the frame stage alone, from the host build's own camera covariance: in units of cond_2(V_f) eps (covariance_oracle.FRAME_BOUND_FACTOR)
+    ref, cond_v = cvo.frame_reference(o, cam, o["sigma2"])
+    e_stage = cvo.frame_stage_error(fr, ref, cond_v)
+    print(f"{name}: frame stage {e_stage:.3g} cond(V_f) eps (bound {cvo.FRAME_BOUND_FACTOR:g}), cond(V_f) {np.nanmin(cond_v):.3g} .. {np.nanmax(cond_v):.3g}")
+    assert e_stage <= cvo.FRAME_BOUND_FACTOR
+
+
+@pytest.mark.parametrize("name", sorted(cvo.CASES))
+def test_frame_stage_host_spread(name):
+    """the number FRAME_BOUND_FACTOR is 25 times of: two float64 numpy evaluations of the frame-stage formula against the long-double one, in
+    units of cond_2(V_f) eps, and the long-double one against the oracle's own blocks within the oracle's bound"""
+    pr, o = cvo.case(name)
+    ref, cond_v = cvo.frame_reference(o, o["camera_covariance"], o["sigma2"])
+    spread = [cvo.frame_stage_error(cvo.frame_reference(o, o["camera_covariance"], o["sigma2"], np.float64, how)[0], ref, cond_v) for how in ("cho_solve", "inverse")]
+    good = ~o["nodata"]
+    e_oracle = cvo.rel_err(ref[good], o["pose_covariance"][good])
+    print(f"{name}: cho_solve {spread[0]:.3g} inverse {spread[1]:.3g} cond(V_f) eps; long double against the oracle {e_oracle:.3g} (bound {o['bound']:.3g})")
+    assert max(spread) <= cvo.FRAME_HOST_SPREAD and cvo.FRAME_BOUND_FACTOR == 25 * cvo.FRAME_HOST_SPREAD == 450
+    assert e_oracle <= o["bound"]
+    assert cvo.FRAME_BOUND_FACTOR * np.nanmax(cond_v) <= 0.02 * cvo.BOUND_FACTOR * o["cond"]   # the stage bound is what it is for: far below the end-to-end one
+
+
+def test_expected_group_switches_where_the_lds_formula_says():
+    """k_cov_frames takes 8 frames per workgroup up to n = 312 (26 cameras: 152 640 B of the 160 KiB) and 4 from n = 324 (164 928 B) to the cap;
+    every 6-wide system (at most 26 cameras, n = 156) takes 8; a forced group wins where it fits"""
+    assert cvo.frames_lds(312, 8) == 152640 and cvo.frames_lds(324, 8) == 164928 and cvo.LDS_LIMIT == 163840
+    for C in range(2, 41):
+        assert cvo.expected_group(12 * C) == (8 if 12 * C <= 312 else 4), C
+    for C in range(2, 27):
+        assert cvo.expected_group(6 * C) == 8, C
+    assert cvo.expected_group(24, force=4) == 4 and cvo.expected_group(120, force=4) == 4 and cvo.expected_group(480, force=8) == 4 and cvo.expected_group(480, force=5) == 4
+    assert [cvo.expected_ld(n) for n in (24, 96, 156, 192, 312, 324, 480)] == [64, 128, 192, 192, 320, 384, 512]
+
+
+def test_long_double_inverse():
+    """inverse_longdouble on a Hilbert-like matrix against numpy's float64 inverse (cond 5e5: agreement to cond eps), and A A^-1 = I in long double"""
+    n = 6
+    A = 1.0 / (np.arange(n)[:, None] + np.arange(n)[None, :] + 1.0) + np.eye(n) * 1e-3
+    Ai = cvo.inverse_longdouble(A)
+    assert np.abs(Ai @ A.astype(np.longdouble) - np.eye(n)).max() <= 1e-13
+    assert np.abs(Ai.astype(np.float64) - np.linalg.inv(A)).max() <= 1e-9 * np.abs(Ai).max()
+    with pytest.raises(np.linalg.LinAlgError):
+        cvo.inverse_longdouble(np.array([[1.0, 2.0], [2.0, 1.0]]))
 
 
 def test_frame_without_data_and_failing_pivot(hc):

@@ -2,7 +2,7 @@
 (tests/hostcheck/tricov_hostcheck.cpp, plain -O2) and held, without a GPU, to the bound of the GPU tier (tests/test_gpu_tricov.py) against
 tests/tricov_oracle.py on every case: detection term max |got - ref|_ij / sqrt(ref_ii ref_jj) <= k cond_2(H_scaled) 2.2e-16, calibration term
 |got - ref|_ij <= k cond_2(H_scaled) 2.2e-16 sqrt(T_ii T_jj), T = |G| |Sigma_cc| |G|^T; k = 64, or 2000 for the two cases of the "outlier" scene (the
-oracle's docstring derives both)."""
+oracle's docstring derives both; the wide robust cases of tricov_oracle.ROBUST_CASES are held to 2000 as well)."""
 import ctypes
 import os
 import subprocess

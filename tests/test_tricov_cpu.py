@@ -74,11 +74,21 @@ def test_two_host_formulations_agree_within_the_bound(name):
     det, cal = tco.formulation_spread(name)
     ok = o["status"] == 1
     print(f"{name} ({i['loss']}): usable {ok.sum()} / {len(ok)}, cond {np.nanmin(o['cond']):.3g} .. {np.nanmax(o['cond']):.3g}, spread detection {det:.3g} calibration {cal:.3g} x 64 cond eps")
-    limit = 2 * tco.HOST_SPREAD if name.startswith("outlier") else 1.0
-    assert np.array_equal(o["bound"][ok], (tco.ROBUST_BOUND_FACTOR if name.startswith("outlier") else tco.BOUND_FACTOR) * o["cond"][ok] * tco.EPS)
+    robust = name in tco.ROBUST_CASES
+    assert robust == name.startswith("outlier") or name in tco.WIDE_CASES
+    limit = 2 * tco.HOST_SPREAD if robust else 1.0
+    assert np.array_equal(o["bound"][ok], (tco.ROBUST_BOUND_FACTOR if robust else tco.BOUND_FACTOR) * o["cond"][ok] * tco.EPS)
     assert det <= limit and cal <= limit
     assert tco.ROBUST_BOUND_FACTOR == 25 * tco.HOST_SPREAD * tco.BOUND_FACTOR == 2000
     assert np.array_equal(o["detection"], o["detection"].transpose(0, 2, 1), equal_nan=True)
+
+
+def test_expected_group_switches_where_the_lds_formula_says():
+    """k_tricov_cal takes 16 points per workgroup up to 29 cameras, 10 up to 48 and 5 up to the cap of 64; a forced group wins where it fits"""
+    assert tco.LDS_LIMIT == 163840 and tco.cal_lds(768, 5) <= tco.LDS_LIMIT < tco.cal_lds(768, 10)
+    for C in range(2, 65):
+        assert tco.expected_group(C) == (16 if C <= 29 else 10 if C <= 48 else 5), C
+    assert tco.expected_group(3, force=5) == 5 and tco.expected_group(12, force=10) == 10 and tco.expected_group(64, force=16) == 5 and tco.expected_group(3, force=8) == 16
 
 
 def test_argument_refusals_come_before_the_device():
