@@ -820,6 +820,30 @@ int mcba_resect_ransac_p3p(int n_cameras, size_t n_points, const double* points,
                            double threshold, int undistort_iterations, int device, double* rt12, double* best4, unsigned char* inliers, double* pose_out, double* cost_out, unsigned* count_out,
                            int* status_out, double* kernel_ms);
 
+/* ---- Trajectory smoothing (Python: trajectory.smooth_trajectories).  Stateless.  Per track k of n_tracks (tracks are
+ * independent), frames t = 0 .. n_frames - 1, unknowns x_t in R^3:
+ *   minimise 0.5 f^2 sum_t rho(d_t^2 / f^2) + 0.5 / a_k^2 sum_{t=1}^{T-2} |x_{t-1} - 2 x_t + x_{t+1}|^2,  d_t^2 = (x_t - p_t)^T Sigma_t^-1 (x_t - p_t)
+ * points (T, K, 3) = p, cov6 (T, K, 6) = Sigma packed 00 01 02 11 12 22, accel_std (K) = a (positive, finite), f = f_scale > 0, loss 0 linear,
+ * 1 soft_l1, 2 huber (scipy's rho).  A frame is usable when p and Sigma are finite and Sigma is positive definite (every pivot of its
+ * Jacobi-scaled 3 x 3 Cholesky factor has a square >= 1e-12, the rule of mcba_triangulation_covariance) with a finite inverse; an unusable frame
+ * has no data term.  IRLS: weights w_t = rho'(d_t^2 / f^2) start at 1, or at weights_in (T, K; finite, >= 0; NULL = none); every iteration is
+ * one solve of the block-pentadiagonal normal equations by a recursive partitioned elimination (separators of two consecutive frames, `segment`
+ * pairs of frames between them: 0 = the default, else 2 .. 64) and one small download.  A track stops after solve number i >= 2 when
+ * max |x_new - x_old| < xtol max |x_new|, or at max_iterations >= 1; the linear loss is one solve.  max_iterations == 1 with weights_in is one
+ * evaluation laid open: one solve with exactly those weights.
+ * out_points (T, K, 3): every frame filled for a track of status 1, NaN otherwise.  out_weights (T, K): rho' at the result, 0 on unusable frames.
+ * out_d2 (T, K): d_t^2 at the result, NaN on unusable frames.  status (K): 1 ok, -1 fewer than two usable frames (never launched), -2 the square
+ * of a pivot of a Jacobi-scaled 6 x 6 block fell below 1e-12.  n_usable, n_iterations (K).  history (max_iterations, K, 2): per solve the
+ * objective at its result and its step max |x_new - x_old| (infinite for the first), NaN where a track no longer ran.
+ * info8 = {levels, segment, tracks per chunk, chunks, kernel ms, most solves of a track, device bytes of a chunk, 0}: tracks are solved in chunks
+ * that fit a device-memory budget (MCBA_SMOOTH_BUDGET_MB, default 8192; the result does not depend on it).  kernel_ms may be NULL.
+ * Two calls on the same input return the same bits.  MCBA_ERR_ARG, checked before any device is touched and with nothing written: n_frames == 0
+ * or above 2^31, n_tracks < 1, a NULL array, a loss outside 0 .. 2, f_scale or an accel_std not positive and finite, a negative or non-finite
+ * weight, max_iterations < 1, xtol < 0, segment outside {0, 2 .. 64}. */
+int mcba_smooth_trajectories(size_t n_frames, int n_tracks, const double* points, const double* cov6, const double* accel_std, const double* weights_in, int loss, double f_scale,
+                             int max_iterations, double xtol, int segment, int device, double* out_points, double* out_weights, double* out_d2, int* status, int* n_usable, int* n_iterations,
+                             double* history, double* info8, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

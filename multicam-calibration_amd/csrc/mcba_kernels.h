@@ -353,6 +353,16 @@ int tricov_group(int n, int lds_limit, int force_g);   // points per workgroup o
 int launch_tricov_cal(hipStream_t st, int loss, const double* uvs, const double* pts, size_t npts, const TcCam* cams, int C, double f_scale, const double* hinv, const int* status, const double* Sig,
                       int ld, const double* info, double* det6, double* cal6, int G, const double* sw = nullptr);
 
+// ---- trajectory smoothing (mcba_smooth.hip).  SmLevel, SmData: mcba_smooth_math.h.  A chunk of K tracks, (T, K, .) planes
+struct SmLevel;
+struct SmData;
+int smooth_eval_blocks(size_t T);   // workgroups of k_smooth_eval per track: part holds 4 doubles for each
+// p, winv, w from the raw points, packed covariances and start weights (w_in NULL: 1); n_usable (K)
+void launch_smooth_prepare(hipStream_t st, size_t T, int K, const double* pts, const double* cov6, const double* w_in, double* p, double* winv, double* w, int* n_usable);
+// one linear solve (every level up, every level down) of the nact tracks of list, then res (nact, 4) = objective, step, max |x|, 0; bad (K) is
+// set to 1 where a pivot was refused
+int launch_smooth_solve(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad, double* part, double* res);
+
 // ---- free-point bundle adjustment of the extrinsics (mcba_kpba.hip).  uvs (C, P, 2) raw detections (NaN = unseen), pts
 // (P, 3), cams: TcCam table in device memory, 2 <= C <= 24, held (C): bit i = scalar i of the camera is not free.  Non-zero: arguments out of range.
 int kpba_group(int C, int lds_limit, int force_g);   // points per group of k_kpba_reduce (64, 32 or 16; 0: no shape fits)
