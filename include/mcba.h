@@ -844,6 +844,23 @@ int mcba_smooth_trajectories(size_t n_frames, int n_tracks, const double* points
                              int max_iterations, double xtol, int segment, int device, double* out_points, double* out_weights, double* out_d2, int* status, int* n_usable, int* n_iterations,
                              double* history, double* info8, double* kernel_ms);
 
+/* ---- Trajectory uncertainty (Python: trajectory.trajectory_uncertainty).  Stateless, additive to ABI 7.  Per track let
+ *   A = blockdiag(w_t Sigma_t^-1) + a_k^-2 (D2^T D2 (x) I3)
+ * be exactly the matrix of mcba_smooth_trajectories (same points, cov6, accel_std, usable-frame rule and segment; w_t = weights (T, K; finite,
+ * >= 0), NULL = 1, and 0 on unusable frames whatever is passed) and Z = A^-1.  out_cov6 (T, K, 6) = Z_tt packed 00 01 02 11 12 22 for every
+ * frame, unusable ones included (there: the interpolation uncertainty).  out_lag9 ((T - 1), K, 9; NULL = not computed) = Z_{t,t+1} row-major,
+ * rows of frame t; it is not symmetric.  Cov(x_{t+1} - x_t) = Z_tt + Z_{t+1,t+1} - Z_{t,t+1} - Z_{t,t+1}^T is left to the caller: it cancels.
+ * With weights = the out_weights of a robust solve this is the weighted-least-squares covariance at those weights, not a Hessian-based one (no
+ * rho'' term).  One elimination of every level as in the smoother, then a selected inversion of every level top down; no atomics, two calls on
+ * the same input return the same bits, and the chunking over tracks (MCBA_SMOOTH_BUDGET_MB) does not change them.
+ * status (K): 1 ok, -1 fewer than two usable frames (never launched), -2 a refused pivot; a track of status -1 or -2 is NaN throughout.
+ * n_usable (K).  info8 = {levels, segment, tracks per chunk, chunks, kernel ms, 1, device bytes of a chunk, kernel ms of the selected inversion
+ * alone}.  kernel_ms may be NULL.  MCBA_ERR_ARG, checked before any device is touched and with nothing written: n_frames == 0 or above 2^31,
+ * n_tracks < 1, a NULL array other than weights and out_lag9, an accel_std not positive and finite, a negative or non-finite weight, segment
+ * outside {0, 2 .. 64}. */
+int mcba_smooth_covariance(size_t n_frames, int n_tracks, const double* points, const double* cov6, const double* accel_std, const double* weights, int segment, int device,
+                           double* out_cov6, double* out_lag9, int* status, int* n_usable, double* info8, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

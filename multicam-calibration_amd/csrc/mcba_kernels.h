@@ -363,6 +363,11 @@ void launch_smooth_prepare(hipStream_t st, size_t T, int K, const double* pts, c
 // set to 1 where a pivot was refused
 int launch_smooth_solve(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad, double* part, double* res);
 
+// ---- trajectory uncertainty (mcba_smooth_cov.hip).  The elimination alone, every level up (bad as above); then the
+// selected inversion, every level down: z[l] = the SM_ZC planes of level l >= 1 (mcba_smooth_cov_math.h), cov6 (T, K, 6), lag9 (T - 1, K, 9) or null
+int launch_smooth_cov_reduce(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad);
+int launch_smooth_selinv(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, double* const* z, double* cov6, double* lag9, int K, const int* list, int nact);
+
 // ---- free-point bundle adjustment of the extrinsics (mcba_kpba.hip).  uvs (C, P, 2) raw detections (NaN = unseen), pts
 // (P, 3), cams: TcCam table in device memory, 2 <= C <= 24, held (C): bit i = scalar i of the camera is not free.  Non-zero: arguments out of range.
 int kpba_group(int C, int lds_limit, int force_g);   // points per group of k_kpba_reduce (64, 32 or 16; 0: no shape fits)

@@ -1,5 +1,6 @@
 """smooth_trajectories -- the fixed-interval smoother of keypoint tracks: T frames x K keypoints of triangulated points and their per-frame
-covariances in, gap-free tracks out.  It fills the frames fewer than two cameras saw, trusts each frame exactly as much
+covariances in, gap-free tracks out; trajectory_uncertainty -- the covariance of every smoothed point and, on request,
+of neighbouring frames (section 8f-20).  It fills the frames fewer than two cameras saw, trusts each frame exactly as much
 as `triangulation_uncertainty` says, and with a robust loss discounts gross triangulation errors.
 
 The reference has no counterpart (its flatibration tutorial loads keypoints that an outside tool smoothed in time).  Everything runs on the GPU:
@@ -27,6 +28,19 @@ class TrajectorySmoothing:
     cost: np.ndarray          # (K,): the objective at the result, NaN unless the status is 1
     history: np.ndarray       # (iterations, K, 2): per solve the objective at its result and its step max |x_new - x_old| (inf for the first); NaN where a track no longer ran
     info: dict                # kernel_ms, levels, segment, tracks_per_chunk, chunks, device_bytes
+    covariance: np.ndarray = None      # uncertainty=True or "lag": TrajectoryUncertainty.covariance at the returned weights
+    std: np.ndarray = None             # ... and its std
+    lag_covariance: np.ndarray = None  # uncertainty="lag": TrajectoryUncertainty.lag_covariance
+
+
+@dataclass
+class TrajectoryUncertainty:
+    covariance: np.ndarray      # (T, K, 3, 3): Z_tt of every frame, unusable ones included (there: the interpolation uncertainty); NaN unless the status is 1
+    std: np.ndarray             # (T, K, 3): the square roots of its diagonal
+    lag_covariance: np.ndarray  # (T - 1, K, 3, 3): Z_{t,t+1}, rows of frame t (not symmetric); None unless lag=True
+    status: np.ndarray          # (K,): a key of TRAJECTORY_STATUS
+    n_usable: np.ndarray        # (K,)
+    info: dict                  # kernel_ms, levels, segment, tracks_per_chunk, chunks, device_bytes
 
 
 def _covariance_planes(covariance, T, K):
@@ -42,7 +56,26 @@ def _covariance_planes(covariance, T, K):
     raise ValueError(f"covariance must be ({T}, {K}, 3, 3), or a scalar, ({K},) or ({T}, {K}) standard deviation; got {cov.shape}")
 
 
-def smooth_trajectories(points, covariance, *, accel_std, loss="linear", f_scale=3.0, weights_in=None, max_iterations=50, xtol=1e-8, segment=None, device=0):
+def _track_arguments(points, covariance, accel_std):
+    """the arrays every call of this module takes, checked: points (T, K, 3), cov6 (T, K, 6), accel_std (K,)"""
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.ndim != 3 or pts.shape[2] != 3:
+        raise ValueError("points must be (T, K, 3)")
+    T, K = pts.shape[:2]
+    if T == 0 or K == 0:
+        raise ValueError("points must hold at least one frame and one track")
+    cov6 = _covariance_planes(covariance, T, K)
+    acc = np.asarray(accel_std, dtype=np.float64)
+    if acc.shape not in ((), (K,)):
+        raise ValueError(f"accel_std must be a scalar or ({K},)")
+    acc = np.ascontiguousarray(np.broadcast_to(acc, (K,)))
+    with np.errstate(over="ignore", divide="ignore"):
+        if not (np.isfinite(acc).all() and (acc > 0).all() and np.isfinite(1.0 / (acc * acc)).all()):
+            raise ValueError("accel_std must be positive and finite")
+    return pts, cov6, acc
+
+
+def smooth_trajectories(points, covariance, *, accel_std, loss="linear", f_scale=3.0, weights_in=None, max_iterations=50, xtol=1e-8, segment=None, device=0, uncertainty=False):
     """Smooth K independent keypoint tracks of T frames.  Per track k, with unknowns x_t in R^3, minimise
 
         0.5 f^2 sum_t rho(d_t^2 / f^2) + 0.5 / a_k^2 sum_{t=1}^{T-2} |x_{t-1} - 2 x_t + x_{t+1}|^2,    d_t^2 = (x_t - p_t)^T Sigma_t^-1 (x_t - p_t)
@@ -66,26 +99,20 @@ def smooth_trajectories(points, covariance, *, accel_std, loss="linear", f_scale
 
     status (TRAJECTORY_STATUS): -1 fewer than two usable frames (the system is positive definite exactly from two on); -2 a pivot of a
     Jacobi-scaled 6 x 6 block whose square fell below 1e-12.  Such a track is NaN; the others are unaffected.
+    uncertainty: True or "lag" -- after the solve, trajectory_uncertainty() at the returned weights with the same segment and device fills
+    covariance and std (and, for "lag", lag_covariance).  False (the default): the three fields are None and the call is the solve alone.
+
     ValueError (before a device is touched): wrong shapes, T == 0 or K == 0, accel_std <= 0 or not finite, f_scale <= 0, a loss outside the
-    three, a negative or non-finite weights_in, max_iterations < 1, segment out of range.  Without a GPU: ops.McbaError -- there is no host path."""
+    three, a negative or non-finite weights_in, max_iterations < 1, segment out of range, uncertainty not one of False, True, "lag".
+    Without a GPU: ops.McbaError -- there is no host path."""
+    if not any(uncertainty is u for u in (False, True)) and uncertainty != "lag":
+        raise ValueError('uncertainty must be False, True or "lag"')
     if callable(loss) or loss not in LOSSES:
         if loss in ("cauchy", "arctan"):
             raise ValueError(f"smooth_trajectories: loss {loss!r} is not convex -- the reweighting loop is a majorise-minimise scheme only for linear, soft_l1 and huber")
         raise ValueError(f"loss must be one of {sorted(LOSSES)}")
-    pts = np.ascontiguousarray(points, dtype=np.float64)
-    if pts.ndim != 3 or pts.shape[2] != 3:
-        raise ValueError("points must be (T, K, 3)")
+    pts, cov6, acc = _track_arguments(points, covariance, accel_std)
     T, K = pts.shape[:2]
-    if T == 0 or K == 0:
-        raise ValueError("points must hold at least one frame and one track")
-    cov6 = _covariance_planes(covariance, T, K)
-    acc = np.asarray(accel_std, dtype=np.float64)
-    if acc.shape not in ((), (K,)):
-        raise ValueError(f"accel_std must be a scalar or ({K},)")
-    acc = np.ascontiguousarray(np.broadcast_to(acc, (K,)))
-    with np.errstate(over="ignore", divide="ignore"):
-        if not (np.isfinite(acc).all() and (acc > 0).all() and np.isfinite(1.0 / (acc * acc)).all()):
-            raise ValueError("accel_std must be positive and finite")
     if not (np.isfinite(f_scale) and f_scale > 0):
         raise ValueError("`f_scale` must be positive.")
     win = None
@@ -115,6 +142,62 @@ def smooth_trajectories(points, covariance, *, accel_std, loss="linear", f_scale
     cost = np.full(K, np.nan)
     ran = (status == 1) & (nit > 0)
     cost[ran] = hist[nit[ran] - 1, np.flatnonzero(ran), 0]
-    return TrajectorySmoothing(points=out, weights=w, mahalanobis2=d2, status=status, n_usable=nus, n_iterations=nit, cost=cost, history=hist,
-                               info={"kernel_ms": float(info[4]), "levels": int(info[0]), "segment": int(info[1]), "tracks_per_chunk": int(info[2]), "chunks": int(info[3]),
-                                     "device_bytes": int(info[6])})
+    res = TrajectorySmoothing(points=out, weights=w, mahalanobis2=d2, status=status, n_usable=nus, n_iterations=nit, cost=cost, history=hist, info=_info(info))
+    if uncertainty is not False:
+        u = _uncertainty(pts, cov6, acc, w, uncertainty == "lag", segment, device)
+        res.covariance, res.std, res.lag_covariance = u.covariance, u.std, u.lag_covariance
+    return res
+
+
+def _info(info8):
+    return {"kernel_ms": float(info8[4]), "levels": int(info8[0]), "segment": int(info8[1]), "tracks_per_chunk": int(info8[2]), "chunks": int(info8[3]), "device_bytes": int(info8[6])}
+
+
+_SYM = np.array([[0, 1, 2], [1, 3, 4], [2, 4, 5]])
+
+
+def trajectory_uncertainty(points, covariance, *, accel_std, weights=None, lag=False, segment=None, device=0):
+    """The covariance of every smoothed point.  Per track let A = blockdiag(w_t Sigma_t^-1) + a^-2 (D2^T D2 (x) I3) be
+    exactly the matrix of smooth_trajectories (same arguments, same usable-frame rule, w_t = 0 on unusable frames) and Z = A^-1.  Returned:
+
+        covariance[t, k] = Z_tt for every frame -- on an unusable frame it is the interpolation uncertainty of the filled point;
+        std[t, k] = the square roots of its diagonal;
+        lag_covariance[t, k] = Z_{t,t+1}, t = 0 .. T - 2 (lag=True only; not symmetric, rows belong to frame t).
+
+    The covariance of a frame-to-frame displacement is  Cov(x_{t+1} - x_t) = Z_tt + Z_{t+1,t+1} - Z_{t,t+1} - Z_{t,t+1}^T;  it is left to the
+    caller because it cancels: form it where the precision it needs is known.
+
+    For the linear loss (weights=None) Z is the exact posterior covariance under the second-difference prior.  For soft_l1 / huber pass
+    weights = result.weights = rho'(d^2 / f^2): Z is then the weighted-least-squares covariance at those weights.  The rho'' term of a
+    Hessian-based covariance is out of scope.  covariance takes the three forms of smooth_trajectories.
+
+    Everything runs on the GPU: the elimination of the smoother once, then a selected inversion over the same separator tree.  Two calls return
+    the same bits, whatever the chunking.  status as in smooth_trajectories; a track of status -1 or -2 is NaN throughout.
+    ValueError (before a device is touched): wrong shapes, T == 0 or K == 0, accel_std <= 0 or not finite, a negative or non-finite weight,
+    segment out of range.  Without a GPU: ops.McbaError -- there is no host path."""
+    pts, cov6, acc = _track_arguments(points, covariance, accel_std)
+    T, K = pts.shape[:2]
+    win = None
+    if weights is not None:
+        win = np.ascontiguousarray(weights, dtype=np.float64)
+        if win.shape != (T, K):
+            raise ValueError(f"weights must be ({T}, {K})")
+        if not (np.isfinite(win).all() and (win >= 0).all()):
+            raise ValueError("weights must be finite and not negative")
+    if segment is not None and not SEGMENT_MIN <= int(segment) <= SEGMENT_MAX:
+        raise ValueError(f"segment must be None or {SEGMENT_MIN} .. {SEGMENT_MAX}")
+    return _uncertainty(pts, cov6, acc, win, bool(lag), segment, device)
+
+
+def _uncertainty(pts, cov6, acc, win, lag, segment, device):
+    """the call itself, on checked arrays: points (T, K, 3), cov6 (T, K, 6), acc (K,), win (T, K) or None"""
+    T, K = pts.shape[:2]
+    c6, l9 = np.empty((T, K, 6)), np.empty((T - 1, K, 9)) if lag else None
+    status, nus, info = np.empty(K, np.int32), np.empty(K, np.int32), np.zeros(8)
+    ms = ctypes.c_double(0.0)
+    ops.call("mcba_smooth_covariance", T, K, pts.ctypes.data, cov6.ctypes.data, acc.ctypes.data, None if win is None else win.ctypes.data, 0 if segment is None else int(segment), int(device),
+             c6.ctypes.data, None if l9 is None else l9.ctypes.data, status.ctypes.data, nus.ctypes.data, info.ctypes.data, ctypes.addressof(ms))
+    full = np.ascontiguousarray(c6[..., _SYM])
+    with np.errstate(invalid="ignore"):
+        std = np.sqrt(full[..., (0, 1, 2), (0, 1, 2)])
+    return TrajectoryUncertainty(covariance=full, std=std, lag_covariance=None if l9 is None else l9.reshape(T - 1, K, 3, 3), status=status, n_usable=nus, info=_info(info))
