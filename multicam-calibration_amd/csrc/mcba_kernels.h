@@ -356,16 +356,15 @@ int launch_tricov_cal(hipStream_t st, int loss, const double* uvs, const double*
 // ---- trajectory smoothing (mcba_smooth.hip).  SmLevel, SmData: mcba_smooth_math.h.  A chunk of K tracks, (T, K, .) planes
 struct SmLevel;
 struct SmData;
-int smooth_eval_blocks(size_t T);   // workgroups of k_smooth_eval per track: part holds 4 doubles for each
 // p, winv, w from the raw points, packed covariances and start weights (w_in NULL: 1); n_usable (K)
 void launch_smooth_prepare(hipStream_t st, size_t T, int K, const double* pts, const double* cov6, const double* w_in, double* p, double* winv, double* w, int* n_usable);
-// one linear solve (every level up, every level down) of the nact tracks of list, then res (nact, 4) = objective, step, max |x|, 0; bad (K) is
-// set to 1 where a pivot was refused
+// the elimination alone, every level up, of the nact tracks of list; bad (K) is set to 1 where a pivot was refused
+int launch_smooth_reduce(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad);
+// one linear solve (launch_smooth_reduce, then every level down) of the nact tracks of list, then res (nact, 4) = objective, step, max |x|, 0
 int launch_smooth_solve(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad, double* part, double* res);
 
-// ---- trajectory uncertainty (mcba_smooth_cov.hip).  The elimination alone, every level up (bad as above); then the
-// selected inversion, every level down: z[l] = the SM_ZC planes of level l >= 1 (mcba_smooth_cov_math.h), cov6 (T, K, 6), lag9 (T - 1, K, 9) or null
-int launch_smooth_cov_reduce(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad);
+// ---- trajectory uncertainty (mcba_smooth_cov.hip).  After launch_smooth_reduce: the selected inversion, every level
+// down: z[l] = the SM_ZC planes of level l >= 1 (mcba_smooth_cov_math.h), cov6 (T, K, 6), lag9 (T - 1, K, 9) or null
 int launch_smooth_selinv(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, double* const* z, double* cov6, double* lag9, int K, const int* list, int nact);
 
 // ---- free-point bundle adjustment of the extrinsics (mcba_kpba.hip).  uvs (C, P, 2) raw detections (NaN = unseen), pts

@@ -87,33 +87,38 @@ __global__ __launch_bounds__(256) void k_smooth_final(SmData td, const int* __re
   }
 }
 
-int smooth_eval_blocks(size_t T) { return (int)((T + 255) / 256); }
-
 void launch_smooth_prepare(hipStream_t st, size_t T, int K, const double* pts, const double* cov6, const double* w_in, double* p, double* winv, double* w, int* n_usable) {
   const size_t count = T * K;
   k_smooth_prepare<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st>>>(count, pts, cov6, w_in, p, winv, w);
   k_smooth_count<<<dim3((unsigned)K), dim3(256), 0, st>>>(T, K, winv, n_usable);
 }
 
-// one linear solve of the nact running tracks of `list` (positions in the chunk of K tracks), then their sums: res (nact, 4)
-int launch_smooth_solve(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad, double* part, double* res) {
+// the elimination of the nact running tracks of `list` (positions in the chunk of K tracks), every level up: the factors stay in lv[.].fac, lv[.].sep
+int launch_smooth_reduce(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad) {
   if (levels < 1 || levels > SM_MAX_LEVELS || nact < 1 || nact > K) return 1;
   const SmLevel none{};
   for (int l = 0; l < levels; ++l) {
-    const int nq = smooth_lanes(lv[l]);
-    const size_t lanes = (size_t)nq * nact;
-    if ((lanes + 63) / 64 > 0x7fffffffu) return 1;
-    const dim3 grid((unsigned)((lanes + 63) / 64));
+    int nq;
+    unsigned blocks;
+    if (!smooth_grid(lv[l], nact, nq, blocks)) return 1;
     const SmLevel& nx = l + 1 < levels ? lv[l + 1] : none;
-    if (l == 0) k_smooth_reduce<true><<<grid, dim3(64), 0, st>>>(lv[0], nx, td, K, list, nact, nq, bad);
-    else k_smooth_reduce<false><<<grid, dim3(64), 0, st>>>(lv[l], nx, td, K, list, nact, nq, bad);
+    if (l == 0) k_smooth_reduce<true><<<dim3(blocks), dim3(64), 0, st>>>(lv[0], nx, td, K, list, nact, nq, bad);
+    else k_smooth_reduce<false><<<dim3(blocks), dim3(64), 0, st>>>(lv[l], nx, td, K, list, nact, nq, bad);
   }
+  return 0;
+}
+
+// one linear solve of the nact running tracks of `list`, then their sums: res (nact, 4)
+int launch_smooth_solve(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad, double* part, double* res) {
+  if (launch_smooth_reduce(st, lv, levels, td, K, list, nact, bad)) return 1;
+  const SmLevel none{};
   for (int l = levels - 1; l >= 0; --l) {
-    const int nq = smooth_lanes(lv[l]);
-    const dim3 grid((unsigned)(((size_t)nq * nact + 63) / 64));
+    int nq;
+    unsigned blocks;
+    if (!smooth_grid(lv[l], nact, nq, blocks)) return 1;
     const SmLevel& up = l + 1 < levels ? lv[l + 1] : none;
-    if (l == 0) k_smooth_backsub<true><<<grid, dim3(64), 0, st>>>(lv[0], up, td, K, list, nact, nq);
-    else k_smooth_backsub<false><<<grid, dim3(64), 0, st>>>(lv[l], up, td, K, list, nact, nq);
+    if (l == 0) k_smooth_backsub<true><<<dim3(blocks), dim3(64), 0, st>>>(lv[0], up, td, K, list, nact, nq);
+    else k_smooth_backsub<false><<<dim3(blocks), dim3(64), 0, st>>>(lv[l], up, td, K, list, nact, nq);
   }
   const int nblk = smooth_eval_blocks(td.T);
   if ((size_t)nblk * nact > 0x7fffffffu) return 1;

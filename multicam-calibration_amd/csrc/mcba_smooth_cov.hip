@@ -1,9 +1,8 @@
 // mcba_smooth_cov.hip -- trajectory uncertainty: the band of the inverse of the smoother's system, by selected inversion
 // over the separator tree of its elimination.  Per-lane arithmetic: mcba_smooth_cov_math.h (host-checked).  No atomics: every word has one writer.
-//   k_smooth_cov_reduce  lane = (segment, track): smooth_reduce_lane of mcba_smooth_math.h as it is, in the geometry of k_smooth_reduce (whose
-//                        template lives in mcba_smooth.hip and is not visible here); the right-hand side rides along unused
-//   k_smooth_selinv      lane = (segment, track), laid out as k_smooth_backsub: the segment's diagonal and sub-diagonal blocks of the inverse from
-//                        its separators'; level 0 writes the frames' covariances and, on request, the lag-one blocks
+// The elimination is the smoother's own: launch_smooth_reduce of mcba_smooth.hip (the right-hand side rides along unused).
+//   k_smooth_selinv  lane = (segment, track), laid out as k_smooth_backsub: the segment's diagonal and sub-diagonal blocks of the inverse from
+//                    its separators'; level 0 writes the frames' covariances and, on request, the lag-one blocks
 #include <hip/hip_runtime.h>
 
 #include "mcba_device.h"
@@ -11,13 +10,6 @@
 #include "mcba_smooth_cov_math.h"
 
 namespace mcba {
-
-template <bool LEVEL0>
-__global__ __launch_bounds__(64) void k_smooth_cov_reduce(SmLevel lv, SmLevel nx, SmData td, int K, const int* __restrict__ list, int nact, int nq, int* __restrict__ bad) {
-  const size_t gid = (size_t)blockIdx.x * 64 + threadIdx.x;
-  if (gid >= (size_t)nq * nact) return;
-  smooth_reduce_lane<LEVEL0>(lv, nx, td, K, list[gid % nact], (int)(gid / nact), bad);
-}
 
 // the lane's state is about 195 doubles: it wants the whole register file, as k_smooth_reduce, and still spills
 template <bool LEVEL0>
@@ -28,41 +20,18 @@ __global__ __launch_bounds__(64) void k_smooth_selinv(SmLevel lv, SmLevel up, Sm
   smooth_selinv_lane<LEVEL0>(lv, up, td, z, zup, cov6, lag9, K, list[gid % nact], (int)(gid / nact));
 }
 
-static int smooth_cov_grid(const SmLevel& lv, int nact, dim3& grid, int& nq) {
-  nq = smooth_lanes(lv);
-  const size_t lanes = (size_t)nq * nact;
-  if ((lanes + 63) / 64 > 0x7fffffffu) return 1;
-  grid = dim3((unsigned)((lanes + 63) / 64));
-  return 0;
-}
-
-// the elimination of the nact running tracks of `list`, every level up: the factors stay in lv[.].fac, lv[.].sep
-int launch_smooth_cov_reduce(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad) {
-  if (levels < 1 || levels > SM_MAX_LEVELS || nact < 1 || nact > K) return 1;
-  const SmLevel none{};
-  for (int l = 0; l < levels; ++l) {
-    dim3 grid;
-    int nq;
-    if (smooth_cov_grid(lv[l], nact, grid, nq)) return 1;
-    const SmLevel& nx = l + 1 < levels ? lv[l + 1] : none;
-    if (l == 0) k_smooth_cov_reduce<true><<<grid, dim3(64), 0, st>>>(lv[0], nx, td, K, list, nact, nq, bad);
-    else k_smooth_cov_reduce<false><<<grid, dim3(64), 0, st>>>(lv[l], nx, td, K, list, nact, nq, bad);
-  }
-  return 0;
-}
-
 // the selected inversion, every level down.  z[l]: the SM_ZC planes of level l >= 1 (z[0] unused); cov6 (T, K, 6), lag9 (T - 1, K, 9) or null
 int launch_smooth_selinv(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, double* const* z, double* cov6, double* lag9, int K, const int* list, int nact) {
   if (levels < 1 || levels > SM_MAX_LEVELS || nact < 1 || nact > K) return 1;
   const SmLevel none{};
   for (int l = levels - 1; l >= 0; --l) {
-    dim3 grid;
     int nq;
-    if (smooth_cov_grid(lv[l], nact, grid, nq)) return 1;
+    unsigned blocks;
+    if (!smooth_grid(lv[l], nact, nq, blocks)) return 1;
     const SmLevel& up = l + 1 < levels ? lv[l + 1] : none;
     const double* zup = l + 1 < levels ? z[l + 1] : nullptr;
-    if (l == 0) k_smooth_selinv<true><<<grid, dim3(64), 0, st>>>(lv[0], up, td, nullptr, zup, cov6, lag9, K, list, nact, nq);
-    else k_smooth_selinv<false><<<grid, dim3(64), 0, st>>>(lv[l], up, td, z[l], zup, nullptr, nullptr, K, list, nact, nq);
+    if (l == 0) k_smooth_selinv<true><<<dim3(blocks), dim3(64), 0, st>>>(lv[0], up, td, nullptr, zup, cov6, lag9, K, list, nact, nq);
+    else k_smooth_selinv<false><<<dim3(blocks), dim3(64), 0, st>>>(lv[l], up, td, z[l], zup, nullptr, nullptr, K, list, nact, nq);
   }
   return 0;
 }

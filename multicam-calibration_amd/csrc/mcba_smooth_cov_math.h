@@ -20,6 +20,13 @@ namespace mcba {
 
 constexpr int SM_ZC = 57;   // per block of a level >= 1: Zd (21) | Zs (36)
 
+// device doubles (and ints, counted as doubles) one chunk of K tracks of the covariance call needs.  (Approximate on purpose, and reported as
+// device_bytes: the weights plane is counted whether given or not, the lag plane as T rows, not T - 1)
+inline size_t smooth_cov_chunk_doubles(size_t T, int K, int segment, bool lag) {
+  SmLevel lv[SM_MAX_LEVELS];
+  return (size_t)T * K * (20 + 6 + (lag ? 9 : 0)) + (size_t)K * 4 + smooth_carve(T, segment, K, lv, SM_ZC, nullptr, nullptr);
+}
+
 MCBA_HD constexpr int sm_sym(int a, int b) { return a >= b ? sm_tri(a, b) : sm_tri(b, a); }
 
 // L^T x = y in place; b has stride `st`

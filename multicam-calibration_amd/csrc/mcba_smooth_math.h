@@ -72,6 +72,46 @@ inline int smooth_plan(size_t T, int segment, int K, SmLevel* lv) {
 }
 // the lanes (segments) one track has on a level: the segments with a left separator, the last of which may be empty, and the first
 MCBA_HD int smooth_lanes(const SmLevel& lv) { return lv.m == lv.n ? 1 : lv.n / (lv.m + 1) + 1; }
+// the launch of a level for nact running tracks: nq = its lanes per track, blocks = workgroups of 64 lanes.  False: the grid would not fit
+inline bool smooth_grid(const SmLevel& lv, int nact, int& nq, unsigned& blocks) {
+  nq = smooth_lanes(lv);
+  const size_t b = ((size_t)nq * nact + 63) / 64;
+  blocks = (unsigned)b;
+  return b <= 0x7fffffffu;
+}
+inline int smooth_eval_blocks(size_t T) { return (int)((T + 255) / 256); }   // workgroups of k_smooth_eval per track: part holds 4 doubles for each
+
+// the plan and the level storage of a chunk of K tracks, in one walk: per level fac, from level 1 on sep, then `extra` doubles per node (the
+// smoother's solution, 6; the SM_ZC planes of mcba_smooth_cov_math.h).  Returns the doubles it takes, 0 where smooth_plan returns no levels.
+// base null: counts only.  Otherwise lv[l].fac and lv[l].sep are set and aux[l] is the level's extra plane (aux[0] = nullptr)
+inline size_t smooth_carve(size_t T, int segment, int K, SmLevel* lv, int extra, double* base, double** aux, int* levels = nullptr) {
+  const int L = smooth_plan(T, segment, K, lv);
+  if (levels) *levels = L;
+  size_t n = 0;
+  for (int l = 0; l < L; ++l) {
+    const size_t part[3] = {lv[l].NS * SM_FAC, l ? lv[l].NS * SM_SEP : 0, l ? lv[l].NS * extra : 0};
+    if (base) {
+      lv[l].fac = base + n;
+      lv[l].sep = l ? base + n + part[0] : nullptr;
+      aux[l] = l ? base + n + part[0] + part[1] : nullptr;
+    }
+    n += part[0] + part[1] + part[2];
+  }
+  return n;
+}
+// tracks per chunk of K tracks under a budget in bytes, one track taking per_track doubles: as many as fit, at least one; and the chunks
+inline int smooth_chunk_tracks(double budget_bytes, size_t per_track, size_t K, int& nchunks) {
+  const double fit = floor(budget_bytes / ((double)per_track * sizeof(double)));
+  const int Kc = (int)((double)K < fit ? (double)K : fit > 1.0 ? fit : 1.0);
+  nchunks = (int)((K + Kc - 1) / Kc);
+  return Kc;
+}
+// device doubles (and ints, counted as doubles) one chunk of K tracks of the smoother needs.  (Approximate on purpose, and reported as
+// device_bytes: the weights plane is counted whether given or not)
+inline size_t smooth_chunk_doubles(size_t T, int K, int segment) {
+  SmLevel lv[SM_MAX_LEVELS];
+  return (size_t)T * K * 24 + (size_t)K * 8 + (size_t)4 * smooth_eval_blocks(T) * K + smooth_carve(T, segment, K, lv, 6, nullptr, nullptr);
+}
 
 MCBA_HD size_t sm_node(const SmLevel& lv, long long j, int K, int k) {
   const long long q = j / (lv.m + 1), i = j % (lv.m + 1);

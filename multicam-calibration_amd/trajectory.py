@@ -75,6 +75,23 @@ def _track_arguments(points, covariance, accel_std):
     return pts, cov6, acc
 
 
+def _weights_argument(weights, name, T, K):
+    """a (T, K) weights array under its parameter's name, checked; None stays None"""
+    if weights is None:
+        return None
+    win = np.ascontiguousarray(weights, dtype=np.float64)
+    if win.shape != (T, K):
+        raise ValueError(f"{name} must be ({T}, {K})")
+    if not (np.isfinite(win).all() and (win >= 0).all()):
+        raise ValueError(f"{name} must be finite and not negative")
+    return win
+
+
+def _check_segment(segment):
+    if segment is not None and not SEGMENT_MIN <= int(segment) <= SEGMENT_MAX:
+        raise ValueError(f"segment must be None or {SEGMENT_MIN} .. {SEGMENT_MAX}")
+
+
 def smooth_trajectories(points, covariance, *, accel_std, loss="linear", f_scale=3.0, weights_in=None, max_iterations=50, xtol=1e-8, segment=None, device=0, uncertainty=False):
     """Smooth K independent keypoint tracks of T frames.  Per track k, with unknowns x_t in R^3, minimise
 
@@ -115,20 +132,13 @@ def smooth_trajectories(points, covariance, *, accel_std, loss="linear", f_scale
     T, K = pts.shape[:2]
     if not (np.isfinite(f_scale) and f_scale > 0):
         raise ValueError("`f_scale` must be positive.")
-    win = None
-    if weights_in is not None:
-        win = np.ascontiguousarray(weights_in, dtype=np.float64)
-        if win.shape != (T, K):
-            raise ValueError(f"weights_in must be ({T}, {K})")
-        if not (np.isfinite(win).all() and (win >= 0).all()):
-            raise ValueError("weights_in must be finite and not negative")
+    win = _weights_argument(weights_in, "weights_in", T, K)
     max_iterations = int(max_iterations)
     if max_iterations < 1:
         raise ValueError("max_iterations must be at least 1")
     if not xtol >= 0:
         raise ValueError("xtol must not be negative")
-    if segment is not None and not SEGMENT_MIN <= int(segment) <= SEGMENT_MAX:
-        raise ValueError(f"segment must be None or {SEGMENT_MIN} .. {SEGMENT_MAX}")
+    _check_segment(segment)
 
     out, w, d2 = np.empty((T, K, 3)), np.empty((T, K)), np.empty((T, K))
     status, nus, nit = np.empty(K, np.int32), np.empty(K, np.int32), np.empty(K, np.int32)
@@ -177,15 +187,8 @@ def trajectory_uncertainty(points, covariance, *, accel_std, weights=None, lag=F
     segment out of range.  Without a GPU: ops.McbaError -- there is no host path."""
     pts, cov6, acc = _track_arguments(points, covariance, accel_std)
     T, K = pts.shape[:2]
-    win = None
-    if weights is not None:
-        win = np.ascontiguousarray(weights, dtype=np.float64)
-        if win.shape != (T, K):
-            raise ValueError(f"weights must be ({T}, {K})")
-        if not (np.isfinite(win).all() and (win >= 0).all()):
-            raise ValueError("weights must be finite and not negative")
-    if segment is not None and not SEGMENT_MIN <= int(segment) <= SEGMENT_MAX:
-        raise ValueError(f"segment must be None or {SEGMENT_MIN} .. {SEGMENT_MAX}")
+    win = _weights_argument(weights, "weights", T, K)
+    _check_segment(segment)
     return _uncertainty(pts, cov6, acc, win, bool(lag), segment, device)
 
 

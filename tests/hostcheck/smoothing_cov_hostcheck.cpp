@@ -1,4 +1,4 @@
-// Host build of csrc/mcba_smooth_cov_math.h -- the per-lane text of csrc/mcba_smooth_cov.hip (k_smooth_cov_reduce, k_smooth_selinv) -- for g++:
+// Host build of csrc/mcba_smooth_cov_math.h -- the per-lane text of k_smooth_selinv (csrc/mcba_smooth_cov.hip) behind k_smooth_reduce -- for g++:
 // serial loops over the lanes in the kernels' order (prepare, every level up, every level down, tracks fastest), the level plan and the statuses
 // of mcba_smooth_cov_api.hip.  tests/test_hostcheck_smoothing_cov.py compiles this as a shared library (plain -O2) and holds it to the GPU tier's
 // bar; with -DSMOOTH_COV_HOSTCHECK_MAIN it is a stand-alone program that reads a scene file, which the same test builds with
@@ -20,20 +20,10 @@ extern "C" int hc_smooth_covariance(size_t T, int K, const double* points, const
   const size_t TK = T * K;
   SmLevel lv[SM_MAX_LEVELS];
   double* zc[SM_MAX_LEVELS];
-  const int levels = smooth_plan(T, segment, K, lv);
-  if (levels < 1) return 1;
-  std::vector<std::vector<double>> store;
-  for (int l = 0; l < levels; ++l) {   // NaN-filled: whatever reads a word nobody wrote shows
-    store.emplace_back(lv[l].NS * SM_FAC, nan);
-    lv[l].fac = store.back().data();
-    zc[l] = nullptr;
-    if (l) {
-      store.emplace_back(lv[l].NS * SM_SEP, nan);
-      lv[l].sep = store.back().data();
-      store.emplace_back(lv[l].NS * SM_ZC, nan);
-      zc[l] = store.back().data();
-    }
-  }
+  int levels = 0;
+  std::vector<double> store(smooth_carve(T, segment, K, lv, SM_ZC, nullptr, nullptr), nan);   // NaN-filled: whatever reads a word nobody wrote shows
+  if (store.empty()) return 1;
+  smooth_carve(T, segment, K, lv, SM_ZC, store.data(), zc, &levels);
   std::vector<double> p(3 * TK), winv(6 * TK), w(TK), ia2(K), oc(6 * TK, nan), ol(out_lag9 ? 9 * (T - 1) * K : 0, nan);
   std::vector<int> bad(K, 0), list;
   for (int k = 0; k < K; ++k) { ia2[k] = 1.0 / (accel_std[k] * accel_std[k]); n_usable[k] = 0; }
@@ -75,6 +65,25 @@ extern "C" int hc_smooth_covariance(size_t T, int K, const double* points, const
   }
   for (int i = 0; i < 8; ++i) info8[i] = 0.0;
   info8[0] = levels; info8[1] = segment; info8[2] = K; info8[3] = 1;
+  return 0;
+}
+
+// the chunk rule and the carve of the C call: out4 = tracks per chunk, chunks, device bytes, levels; offs (3 per level) = where fac, sep and the
+// SM_ZC planes of each level of a chunk of that many tracks start in its storage, in doubles (-1: none); total = the doubles of that storage
+extern "C" int hc_smooth_chunks(size_t T, int K, int segment, double budget_mb, int lag, double* out4, long long* offs, long long* total) {
+  if (segment == 0) segment = SM_SEGMENT_DEFAULT;
+  int nchunks = 0, levels = 0;
+  const int Kc = smooth_chunk_tracks(budget_mb * 1048576.0, smooth_cov_chunk_doubles(T, 1, segment, lag != 0), (size_t)K, nchunks);
+  SmLevel lv[SM_MAX_LEVELS];
+  double* zc[SM_MAX_LEVELS];
+  std::vector<double> store(smooth_carve(T, segment, Kc, lv, SM_ZC, nullptr, nullptr));
+  *total = (long long)smooth_carve(T, segment, Kc, lv, SM_ZC, store.data(), zc, &levels);
+  for (int l = 0; l < levels; ++l) {
+    offs[3 * l] = lv[l].fac - store.data();
+    offs[3 * l + 1] = lv[l].sep ? lv[l].sep - store.data() : -1;
+    offs[3 * l + 2] = zc[l] ? zc[l] - store.data() : -1;
+  }
+  out4[0] = Kc; out4[1] = nchunks; out4[2] = (double)smooth_cov_chunk_doubles(T, Kc, segment, lag != 0) * sizeof(double); out4[3] = levels;
   return 0;
 }
 

@@ -20,19 +20,12 @@ extern "C" int hc_smooth_trajectories(size_t T, int K, const double* points, con
   const double nan = std::nan("");
   const size_t TK = T * K;
   SmLevel lv[SM_MAX_LEVELS];
-  const int levels = smooth_plan(T, segment, K, lv);
-  if (levels < 1) return 1;
-  std::vector<std::vector<double>> store;
-  for (int l = 0; l < levels; ++l) {   // NaN-filled: whatever reads a word nobody wrote shows
-    store.emplace_back(lv[l].NS * SM_FAC, nan);
-    lv[l].fac = store.back().data();
-    if (l) {
-      store.emplace_back(lv[l].NS * SM_SEP, nan);
-      lv[l].sep = store.back().data();
-      store.emplace_back(lv[l].NS * 6, nan);
-      lv[l].x = store.back().data();
-    }
-  }
+  double* aux[SM_MAX_LEVELS];
+  int levels = 0;
+  std::vector<double> store(smooth_carve(T, segment, K, lv, 6, nullptr, nullptr), nan);   // NaN-filled: whatever reads a word nobody wrote shows
+  if (store.empty()) return 1;
+  smooth_carve(T, segment, K, lv, 6, store.data(), aux, &levels);
+  for (int l = 1; l < levels; ++l) lv[l].x = aux[l];
   std::vector<double> p(3 * TK), winv(6 * TK), w(TK), x(3 * TK, 0.0), d2(TK, 0.0), dx(TK, nan), ia2(K);
   std::vector<int> bad(K, 0), list, stat(K, SM_OK);
   for (int k = 0; k < K; ++k) { ia2[k] = 1.0 / (accel_std[k] * accel_std[k]); n_usable[k] = 0; n_iterations[k] = 0; }
@@ -89,6 +82,25 @@ extern "C" int hc_smooth_trajectories(size_t T, int K, const double* points, con
   }
   for (int i = 0; i < 8; ++i) info8[i] = 0.0;
   info8[0] = levels; info8[1] = segment; info8[2] = K; info8[3] = 1;
+  return 0;
+}
+
+// the chunk rule and the carve of the C call: out4 = tracks per chunk, chunks, device bytes, levels; offs (3 per level) = where fac, sep and the
+// extra plane of each level of a chunk of that many tracks start in its storage, in doubles (-1: none); total = the doubles of that storage
+extern "C" int hc_smooth_chunks(size_t T, int K, int segment, double budget_mb, double* out4, long long* offs, long long* total) {
+  if (segment == 0) segment = SM_SEGMENT_DEFAULT;
+  int nchunks = 0, levels = 0;
+  const int Kc = smooth_chunk_tracks(budget_mb * 1048576.0, smooth_chunk_doubles(T, 1, segment), (size_t)K, nchunks);
+  SmLevel lv[SM_MAX_LEVELS];
+  double* aux[SM_MAX_LEVELS];
+  std::vector<double> store(smooth_carve(T, segment, Kc, lv, 6, nullptr, nullptr));
+  *total = (long long)smooth_carve(T, segment, Kc, lv, 6, store.data(), aux, &levels);
+  for (int l = 0; l < levels; ++l) {
+    offs[3 * l] = lv[l].fac - store.data();
+    offs[3 * l + 1] = lv[l].sep ? lv[l].sep - store.data() : -1;
+    offs[3 * l + 2] = aux[l] ? aux[l] - store.data() : -1;
+  }
+  out4[0] = Kc; out4[1] = nchunks; out4[2] = (double)smooth_chunk_doubles(T, Kc, segment) * sizeof(double); out4[3] = levels;
   return 0;
 }
 

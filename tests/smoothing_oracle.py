@@ -379,3 +379,60 @@ def check_robust(name, case, got, xtol=1e-8):
         else:
             left_out += 1
     return left_out
+
+
+# ---------------------------------------------------------------- the level plan and the chunk rule of both trajectory calls
+SEGMENT_DEFAULT, MAX_LEVELS = 16, 40
+FAC, SEP, X_EXTRA, ZC_EXTRA = 63, 90, 6, 57   # doubles per node: factors; separator planes (levels >= 1); then the solution or the Zd | Zs planes
+
+
+def plan(T, segment, K):
+    """the levels of T frames and K tracks: a list of (n, m, nq, NS), or None past MAX_LEVELS"""
+    n, levels = (T + 1) // 2, []
+    while True:
+        if len(levels) == MAX_LEVELS:
+            return None
+        m = n if n <= segment + 1 else segment
+        nq = (n - 1) // (m + 1) + 1
+        levels.append((n, m, nq, (m + 1) * nq * K))
+        if m == n:
+            return levels
+        n //= m + 1
+
+
+def level_doubles(T, segment, K, extra):
+    """the level storage of one chunk: per level NS (FAC + (SEP + extra from level 1 on))"""
+    return sum(NS * (FAC + (SEP + extra if l else 0)) for l, (_, _, _, NS) in enumerate(plan(T, segment, K) or []))
+
+
+def check_carve(levels, extra, offs, total):
+    """offs (3 per level: the starts of fac, sep and the extra plane in doubles, -1 for none) tile [0, total) in that order, level after level,
+    without gap or overlap: level 0 has fac alone"""
+    cur = 0
+    for l, (_, _, _, NS) in enumerate(levels):
+        fac, sep, aux = (int(v) for v in offs[3 * l:3 * l + 3])
+        assert fac == cur, (l, fac, cur)
+        cur += NS * FAC
+        if l == 0:
+            assert sep == -1 and aux == -1
+            continue
+        assert sep == cur and aux == cur + NS * SEP, (l, sep, aux, cur)
+        cur += NS * (SEP + extra)
+    assert cur == total, (cur, total)
+
+
+def chunk_doubles(T, K, segment, kind, lag=False):
+    """device doubles (and ints, counted as doubles) one chunk of K tracks needs; kind: "smooth" or "cov" """
+    if kind == "smooth":
+        return T * K * 24 + K * 8 + 4 * ((T + 255) // 256) * K + level_doubles(T, segment, K, X_EXTRA)
+    assert kind == "cov"
+    return T * K * (20 + 6 + (9 if lag else 0)) + K * 4 + level_doubles(T, segment, K, ZC_EXTRA)
+
+
+def expected_chunks(T, K, segment, budget_mb, kind, lag=False):
+    """(tracks_per_chunk, chunks, device_bytes, levels) of smooth_trajectories (kind "smooth") or trajectory_uncertainty ("cov") under a
+    budget of budget_mb MiB: as many tracks per chunk as fit, at least one, at most K; device_bytes is what the widest chunk takes"""
+    segment = segment or SEGMENT_DEFAULT
+    per_track = float(chunk_doubles(T, 1, segment, kind, lag)) * 8
+    Kc = int(min(float(K), max(1.0, np.floor(budget_mb * 1048576.0 / per_track))))
+    return Kc, (K + Kc - 1) // Kc, chunk_doubles(T, Kc, segment, kind, lag) * 8, len(plan(T, segment, Kc))

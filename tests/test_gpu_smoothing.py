@@ -88,6 +88,22 @@ def test_chunks_over_tracks_return_the_same_bits(monkeypatch):
     assert whole["status"][3] == -1 and np.array_equal(whole["points"][:, 0], whole["points"][:, 2]) and whole["n_iterations"][0] != whole["n_iterations"][1]
 
 
+def test_a_chunk_in_which_no_track_is_launched(monkeypatch):
+    """one track per chunk, the middle one without a usable frame: its chunk launches nothing, beside two chunks whose IRLS loops run"""
+    s = so.scene(40, 3, seed=2)
+    s["points"][:, 1] = np.nan
+    case = dict(points=s["points"], cov=s["cov"], accel_std=0.1, loss="soft_l1", f_scale=3.0, segment=3)
+    whole = run(case)
+    monkeypatch.setenv("MCBA_SMOOTH_BUDGET_MB", "0.001")
+    parts = run(case)
+    print(whole["info"], parts["info"], parts["n_iterations"])
+    assert whole["info"]["chunks"] == 1 and parts["info"]["chunks"] == 3 and parts["info"]["tracks_per_chunk"] == 1
+    assert all(np.array_equal(whole[f], parts[f], equal_nan=True) for f in FIELDS)
+    assert list(parts["status"]) == [1, -1, 1] and (parts["n_iterations"][[0, 2]] > 1).all() and parts["n_iterations"][1] == 0
+    assert np.isnan(parts["points"][:, 1]).all() and np.isnan(parts["mahalanobis2"][:, 1]).all() and np.isnan(parts["cost"][1]) and (parts["weights"][:, 1] == 0).all()
+    assert np.isfinite(parts["points"][:, [0, 2]]).all()
+
+
 def test_refused_pivot_and_isotropic_forms():
     s = so.scene(40, 2, seed=2)
     from multicam_calibration_amd import smooth_trajectories

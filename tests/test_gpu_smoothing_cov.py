@@ -94,6 +94,22 @@ def test_chunks_over_tracks_return_the_same_bits(monkeypatch):
     assert np.array_equal(whole["lag_covariance"][:, 0], whole["lag_covariance"][:, 4]) and np.isfinite(whole["covariance"][:, [0, 1, 2, 4]]).all()
 
 
+def test_a_chunk_in_which_no_track_is_launched(monkeypatch):
+    """one track per chunk, the middle one without a usable frame: its chunk launches nothing"""
+    s = so.scene(40, 3, seed=2)
+    s["points"][:, 1] = np.nan
+    case = dict(points=s["points"], cov=s["cov"], accel_std=0.1, segment=3)
+    whole = run(case)
+    monkeypatch.setenv("MCBA_SMOOTH_BUDGET_MB", "0.001")
+    parts = run(case)
+    print(whole["info"], parts["info"])
+    assert whole["info"]["chunks"] == 1 and parts["info"]["chunks"] == 3 and parts["info"]["tracks_per_chunk"] == 1
+    assert same(whole, parts)
+    assert list(parts["status"]) == [1, -1, 1] and list(parts["n_usable"]) == [40, 0, 40]
+    assert np.isnan(parts["covariance"][:, 1]).all() and np.isnan(parts["std"][:, 1]).all() and np.isnan(parts["lag_covariance"][:, 1]).all()
+    assert np.isfinite(parts["covariance"][:, [0, 2]]).all() and np.isfinite(parts["lag_covariance"][:, [0, 2]]).all()
+
+
 def test_long_tracks_default_segment_against_segment_two():
     """5000 frames x 7 tracks: the default segment against segment=2 within the sum of the two bars, the condition number and max|zhat| taken
     from the first 400 frames (the system is local: neither grows with the length of a stationary scene); that sub-case against the reference"""

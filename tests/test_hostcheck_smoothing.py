@@ -29,6 +29,7 @@ def hc(tmp_path_factory):
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", lib, SRC])
     h = ctypes.CDLL(lib)
     h.hc_smooth_trajectories.argtypes = [ctypes.c_size_t, ctypes.c_int, V, V, V, V, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int, V, V, V, V, V, V, V, V]
+    h.hc_smooth_chunks.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_double, V, V, V]
     return h
 
 
@@ -102,6 +103,27 @@ def test_refused_pivot_is_status_minus_two(hc):
     print(got["status"], got["n_usable"])
     assert got["status"][0] == so.STATUS_PIVOT and np.isnan(got["points"][:, 0]).all() and np.isnan(got["mahalanobis2"][:, 0]).all() and (got["weights"][:, 0] == 0).all()
     assert got["status"][1] == 1 and np.array_equal(got["points"][:, 1], alone["points"][:, 0])
+
+
+CHUNK_SHAPES = [(T, 2) for T in (1, 2, 3, 5, 333)] + [(400, None), (5000, None)]   # the shortest tracks, five levels, the default segment
+
+
+@pytest.mark.parametrize("T,segment", CHUNK_SHAPES)
+def test_chunk_rule_and_carve_against_the_oracle(hc, T, segment):
+    """the tracks-per-chunk rule, the byte count and the level carve that the C call uses (mcba_smooth_math.h), against so.expected_chunks: one
+    chunk, the budgets of the GPU tier, and one at which a chunk is a single track"""
+    for K in (1, 5, 20):
+        for budget in (8192.0, 0.5, 0.2, 0.001):
+            out4, offs, total = np.full(4, 7.0), np.full(3 * so.MAX_LEVELS, 7, np.int64), np.full(1, 7, np.int64)
+            assert hc.hc_smooth_chunks(T, K, segment or 0, budget, out4.ctypes.data, offs.ctypes.data, total.ctypes.data) == 0
+            want = so.expected_chunks(T, K, segment, budget, "smooth")
+            assert tuple(int(v) for v in out4) == want, (K, budget, out4, want)
+            if budget == 8192.0:
+                assert want[:2] == (K, 1)
+            if budget == 0.001:
+                assert want[:2] == (1, K)
+            so.check_carve(so.plan(T, segment or so.SEGMENT_DEFAULT, want[0]), so.X_EXTRA, offs, int(total[0]))
+            assert int(total[0]) == so.level_doubles(T, segment or so.SEGMENT_DEFAULT, want[0], so.X_EXTRA)
 
 
 def test_stand_alone_program_under_sanitizers(hc, tmp_path):

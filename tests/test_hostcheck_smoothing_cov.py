@@ -30,6 +30,7 @@ def hc(tmp_path_factory):
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", lib, SRC])
     h = ctypes.CDLL(lib)
     h.hc_smooth_covariance.argtypes = [ctypes.c_size_t, ctypes.c_int, V, V, V, V, ctypes.c_int, V, V, V, V, V]
+    h.hc_smooth_chunks.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, V, V, V]
     return h
 
 
@@ -97,6 +98,28 @@ def test_refused_pivot_is_status_minus_two(hc):
     alone = run(hc, s["points"][:, 1:], s["cov"][:, 1:], 0.1, segment=3)
     assert got["status"][0] == so.STATUS_PIVOT and np.isnan(got["covariance"][:, 0]).all() and np.isnan(got["lag_covariance"][:, 0]).all()
     assert got["status"][1] == 1 and np.array_equal(got["covariance"][:, 1], alone["covariance"][:, 0]) and np.array_equal(got["lag_covariance"][:, 1], alone["lag_covariance"][:, 0])
+
+
+CHUNK_SHAPES = [(T, 2) for T in (1, 2, 3, 5, 333)] + [(400, None), (5000, None)]   # the shortest tracks, five levels, the default segment
+
+
+@pytest.mark.parametrize("T,segment", CHUNK_SHAPES)
+def test_chunk_rule_and_carve_against_the_oracle(hc, T, segment):
+    """the tracks-per-chunk rule, the byte count and the level carve that the C call uses (mcba_smooth_math.h, mcba_smooth_cov_math.h), against
+    so.expected_chunks, with and without the lag plane: one chunk, the budgets of the GPU tier, and one at which a chunk is a single track"""
+    for K in (1, 5, 20):
+        for budget in (8192.0, 0.5, 0.2, 0.001):
+            for lag in (False, True):
+                out4, offs, total = np.full(4, 7.0), np.full(3 * so.MAX_LEVELS, 7, np.int64), np.full(1, 7, np.int64)
+                assert hc.hc_smooth_chunks(T, K, segment or 0, budget, int(lag), out4.ctypes.data, offs.ctypes.data, total.ctypes.data) == 0
+                want = so.expected_chunks(T, K, segment, budget, "cov", lag)
+                assert tuple(int(v) for v in out4) == want, (K, budget, lag, out4, want)
+                if budget == 8192.0:
+                    assert want[:2] == (K, 1)
+                if budget == 0.001:
+                    assert want[:2] == (1, K)
+                so.check_carve(so.plan(T, segment or so.SEGMENT_DEFAULT, want[0]), so.ZC_EXTRA, offs, int(total[0]))
+                assert int(total[0]) == so.level_doubles(T, segment or so.SEGMENT_DEFAULT, want[0], so.ZC_EXTRA)
 
 
 def test_stand_alone_program_under_sanitizers(hc, tmp_path):
