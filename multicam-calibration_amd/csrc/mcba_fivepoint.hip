@@ -4,7 +4,7 @@
 //   k_tv5_hypotheses  lane = sample: fp_candidates on the five sampled correspondences, tv_fundamental per slot; a table of 10 H rows (E, F,
 //                     status), the live candidates of a sample in its leading slots.  The work space of a sample (FpWork: two 10 x 20 matrices and
 //                     the basis, 436 doubles, indexed at run time) is in scratch: H is 1024 at most, this is not the hot kernel
-//   k_tv5_compact     one workgroup: the live slots packed, order-preserving, into the table k_tv_score, k_tv_finish, k_tv_winner and the pose
+//   k_tv5_compact     one workgroup: the live slots packed, order-preserving, into the table k_hyp_score, k_hyp_finish, k_tv_winner and the pose
 //                     kernels of mcba_twoview.hip see; lane t counts the live slots of its contiguous run, the runs' counts are prefix-summed in
 //                     lane order, lane t writes its run.  map[i] = 10 sample + slot of packed row i.  No atomics: the order is the table's.
 //                     Nothing live: row 0 is slot 0 (void, NaN), so that "hypothesis 0 wins with nothing" as in mcba_two_view_ransac
@@ -43,18 +43,18 @@ __global__ __launch_bounds__(64) void k_tv5_hypotheses(const double* __restrict_
 }
 
 // S = 10 H slots.  Ep, Fp (n, 9), stp (n), map (n), n_packed[0] = n >= 1
-__global__ __launch_bounds__(kTvThreads) void k_tv5_compact(const double* __restrict__ E10, const double* __restrict__ F10, const int* __restrict__ status10, int S, double* __restrict__ Ep,
+__global__ __launch_bounds__(kHypThreads) void k_tv5_compact(const double* __restrict__ E10, const double* __restrict__ F10, const int* __restrict__ status10, int S, double* __restrict__ Ep,
                                                             double* __restrict__ Fp, int* __restrict__ stp, int* __restrict__ map, int* __restrict__ n_packed) {
-  __shared__ int s_n[kTvThreads];
+  __shared__ int s_n[kHypThreads];
   const int tid = threadIdx.x;
-  const int run = (S + kTvThreads - 1) / kTvThreads, s0 = tid * run, s1 = s0 + run < S ? s0 + run : S;
+  const int run = (S + kHypThreads - 1) / kHypThreads, s0 = tid * run, s1 = s0 + run < S ? s0 + run : S;
   int n = 0;
   for (int s = s0; s < s1; ++s) n += status10[s] == TV_OK ? 1 : 0;
   s_n[tid] = n;
   __syncthreads();
   if (tid == 0) {   // exclusive prefix in lane order (256 additions)
     int acc = 0;
-    for (int t = 0; t < kTvThreads; ++t) { const int c = s_n[t]; s_n[t] = acc; acc += c; }
+    for (int t = 0; t < kHypThreads; ++t) { const int c = s_n[t]; s_n[t] = acc; acc += c; }
     n_packed[0] = acc > 0 ? acc : 1;
     if (acc == 0) {
       for (int i = 0; i < 9; ++i) { Ep[i] = E10[i]; Fp[i] = F10[i]; }
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(kTvThreads) void k_tv5_compact(const double* __rest
 void launch_tv5_hypotheses(hipStream_t st, const double* prep, size_t M, const int* samples, int H, const TvCams& cams, double* E10, double* F10, int* status10, double* Ep, double* Fp, int* stp,
                            int* map, int* n_packed) {
   k_tv5_hypotheses<<<dim3((unsigned)((H + 63) / 64)), dim3(64), 0, st>>>(prep, M, samples, H, cams, E10, F10, status10);
-  k_tv5_compact<<<dim3(1), dim3(kTvThreads), 0, st>>>(E10, F10, status10, FP_SLOTS * H, Ep, Fp, stp, map, n_packed);
+  k_tv5_compact<<<dim3(1), dim3(kHypThreads), 0, st>>>(E10, F10, status10, FP_SLOTS * H, Ep, Fp, stp, map, n_packed);
 }
 
 }  // namespace mcba

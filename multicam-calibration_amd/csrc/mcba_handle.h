@@ -288,6 +288,33 @@ struct StatelessCall {
   }
 };
 
+// The N events that separate the N + 1 stages of a stateless call between its start() and its stop(), released on every path out:
+// create() before start(), mark() after each stage but the last, fill() after stop()
+template <int N>
+struct StageEvents {
+  hipEvent_t ev[N] = {};
+  int marked = 0;
+  ~StageEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  hipError_t create() {
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < N && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+    return e;
+  }
+  hipError_t mark() { return hipEventRecord(ev[marked++], nullptr); }
+  // kernel_ms[0] = total, kernel_ms[1 .. N + 1] = the stages, from e0 over the marks to e1; nothing is written unless every span was read
+  hipError_t fill(const StatelessCall& call, double total, double* kernel_ms) const {
+    double ms[N + 2] = {total};
+    for (int i = 0; i <= N; ++i) {
+      float span = 0.f;
+      hipError_t e = hipEventElapsedTime(&span, i == 0 ? call.e0 : ev[i - 1], i == N ? call.e1 : ev[i]);
+      if (e != hipSuccess) return e;
+      ms[1 + i] = span;
+    }
+    for (int i = 0; i < N + 2; ++i) kernel_ms[i] = ms[i];
+    return hipSuccess;
+  }
+};
+
 // The per-detection weights of a stateless keypoint call, count = C P of them, as the kernels read them: the plane of
 // sqrt(w), 0 for a zero or NaN weight (the detection is unseen), uploaded once beside the detections.  weights NULL: *d_sw = nullptr, the
 // unweighted kernels.  check_weights (before the device is touched, with the other arguments): MCBA_ERR_ARG for a negative or infinite weight.

@@ -278,23 +278,26 @@ int launch_tri_refine(hipStream_t st, int loss, const double* uvs, const double*
 enum ConsensusForm { CONSENSUS_AUTO = -1, CONSENSUS_LANE = 0, CONSENSUS_WAVE = 1, CONSENSUS_LANE_SEARCH = 2 };
 int launch_consensus(hipStream_t st, int form, int loss, const double* uvs, size_t npts, const KpCam* cams, int C, double threshold, int min_views, int und_iters, double f_scale,
                      int max_iterations, double* out, unsigned long long* mask, double* hyp, double* info);
+// hypothesis scoring (mcba_hyp_score.h): the one launch shape of the two RANSAC pipelines below, and the finish kernel they share
+constexpr int kHypThreads = 256, kHypPPT = 4, kHypPoints = kHypThreads * kHypPPT;   // k_hyp_score: points per lane and per workgroup
+constexpr int kHypChunk = 64;                                                        // hypotheses that one workgroup of k_hyp_score holds in LDS
+inline size_t hyp_score_blocks(size_t n) { return (n + kHypPoints - 1) / kHypPoints; }     // workgroups of k_hyp_score per camera
+inline size_t hyp_point_blocks(size_t n) { return (n + kHypThreads - 1) / kHypThreads; }   // workgroups of a lane = point kernel per camera
+// part_c, part_n (C, nblk, H) -> cost (C, H; +inf for a void hypothesis: status != 1), count (C, H)
+void launch_hyp_finish(hipStream_t st, const double* part_c, const unsigned* part_n, size_t nblk, int C, int H, const int* status, double* cost, unsigned* count);
 // two-view RANSAC (mcba_twoview.hip): the device side of mcba_two_view_ransac, one launcher per stage, every buffer the
 // caller's.  M >= 8 common points, 1 <= H <= MCBA_TWOVIEW_MAX_HYPOTHESES.  Nothing is accumulated with atomics: the results depend on (M, H) alone.
-constexpr int kTvThreads = 256, kTvPPT = 4, kTvPoints = kTvThreads * kTvPPT;   // k_tv_score: points per lane and per workgroup
-constexpr int kTvChunk = 64;                                                    // hypotheses whose F one workgroup of k_tv_score holds in LDS
-struct TvCams { double ka[4], da[5], kb[4], db[5]; };                           // (fx fy cx cy), (k1 k2 p1 p2 k3) of camera a and of camera b
-inline size_t tv_score_blocks(size_t M) { return (M + kTvPoints - 1) / kTvPoints; }
-inline size_t tv_pose_blocks(size_t M) { return (M + kTvThreads - 1) / kTvThreads; }
+struct TvCams { double ka[4], da[5], kb[4], db[5]; };   // (fx fy cx cy), (k1 k2 p1 p2 k3) of camera a and of camera b
 // prep: 8 planes of M doubles (undistorted pixels a.x a.y b.x b.y, normalised a.x a.y b.x b.y)
 void launch_tv_prepare(hipStream_t st, const double* uv_a, const double* uv_b, size_t M, const TvCams& cams, int und_iters, double* prep);
 // E, F (H, 9), status (H).  e_in (H, 9) or nullptr: the generator is skipped, E = e_in (void where not finite)
 void launch_tv_hypotheses(hipStream_t st, const double* prep, size_t M, const int* samples, int H, const double* e_in, const TvCams& cams, double* E, double* F, int* status);
-// part_c, part_n: tv_score_blocks(M) x H per-workgroup partial costs and inlier counts
+// part_c, part_n: hyp_score_blocks(M) x H per-workgroup partial costs and inlier counts
 void launch_tv_score(hipStream_t st, const double* prep, size_t M, const double* F, int H, double threshold, double* part_c, unsigned* part_n);
 // cost (H; +inf for a void hypothesis), count (H); then the winner: win_idx[0], best4[0 .. 2] = (index, cost, inliers), cand (4 x 12) = its four (R, t)
 void launch_tv_finish(hipStream_t st, const double* part_c, const unsigned* part_n, size_t nblk, int H, const double* E, const int* status, double* cost, unsigned* count, int* win_idx, double* best4,
                       double* cand);
-// inliers (M bytes), part_f: tv_pose_blocks(M) x 4 in-front counts; then win_idx[1] = the candidate, best4[3] = its count, rt12; points (M, 3), NaN for non-inliers
+// inliers (M bytes), part_f: hyp_point_blocks(M) x 4 in-front counts; then win_idx[1] = the candidate, best4[3] = its count, rt12; points (M, 3), NaN for non-inliers
 void launch_tv_pose(hipStream_t st, const double* prep, size_t M, const double* F, const int* status, double threshold, const double* cand, unsigned* part_f, int* win_idx, double* best4, double* rt12,
                     unsigned char* inliers, double* points);
 // the five-point generator (mcba_fivepoint.hip): 1 <= H <= MCBA_TWOVIEW5_MAX_SAMPLES samples of five correspondences.  E10, F10
@@ -305,10 +308,6 @@ void launch_tv5_hypotheses(hipStream_t st, const double* prep, size_t M, const i
 // camera resection (mcba_resect.hip): the device side of mcba_resect_ransac and mcba_resect_refine, one launcher per stage,
 // every buffer the caller's.  C cameras (the grid's last dimension) of at least 6 usable points each, 1 <= H <= MCBA_RESECT_MAX_HYPOTHESES per camera.
 // Nothing is accumulated with atomics: the results depend on (P, H) alone.
-constexpr int kRsThreads = 256, kRsPPT = 4, kRsPoints = kRsThreads * kRsPPT;   // k_rs_score: points per lane and per workgroup
-constexpr int kRsChunk = 64;                                                    // hypotheses whose K [R | t] one workgroup of k_rs_score holds in LDS
-inline size_t rs_score_blocks(size_t P) { return (P + kRsPoints - 1) / kRsPoints; }
-inline size_t rs_pose_blocks(size_t P) { return (P + kRsThreads - 1) / kRsThreads; }
 // points (P, 3), uvs (C, P, 2), cams (C, 9) = fx fy cx cy k1 k2 p1 p2 k3.  prep: per camera 4 planes of P doubles (undistorted u, v; normalised x, y); usable (C, P)
 void launch_rs_prepare(hipStream_t st, const double* points, const double* uvs, size_t P, int C, const double* cams, int und_iters, double* prep, unsigned char* usable);
 // pose, KP (C, H, 12), status (C, H).  pose_in (C, H, 12) or nullptr: the generator is skipped, pose = pose_in (void where not finite)
@@ -317,7 +316,7 @@ void launch_rs_hypotheses(hipStream_t st, const double* points, const double* pr
 // the P3P generator (mcba_resect_p3p.hip): samples (C, H, 3), 1 <= H <= MCBA_RESECT_P3P_MAX_SAMPLES; pose, KP (C, 4 H, 12),
 // status (C, 4 H): the candidates of sample h in slots 4 h .. 4 h + 3, void slots included -- the table launch_rs_score .. launch_rs_mask take with 4 H for H
 void launch_rs3_hypotheses(hipStream_t st, const double* points, const double* prep, size_t P, int C, const int* samples, int H, const double* cams, double* pose, double* KP, int* status);
-// part_c, part_n: (C, rs_score_blocks(P), H) per-workgroup partial costs and inlier counts
+// part_c, part_n: (C, hyp_score_blocks(P), H) per-workgroup partial costs and inlier counts
 void launch_rs_score(hipStream_t st, const double* points, const double* prep, const unsigned char* usable, size_t P, int C, const double* KP, int H, double threshold, double* part_c,
                      unsigned* part_n);
 // cost (C, H; +inf for a void hypothesis), count (C, H); then per camera the winner: win_idx (C), best4 (C, 4)[0 .. 2] = (index, cost, inliers), rt12 (C, 12) = its pose
@@ -326,7 +325,7 @@ void launch_rs_finish(hipStream_t st, const double* part_c, const unsigned* part
 // inliers (C, P) bytes: the winner's
 void launch_rs_mask(hipStream_t st, const double* points, const double* prep, const unsigned char* usable, size_t P, int C, const double* KP, const int* status, int H, double threshold,
                     const int* win_idx, unsigned char* inliers);
-// the polish, one evaluation of n listed problems: ids (n) = the row of uvs / mask, tcs (n) = the camera at the pose to evaluate; part (n, rs_pose_blocks(P), 29);
+// the polish, one evaluation of n listed problems: ids (n) = the row of uvs / mask, tcs (n) = the camera at the pose to evaluate; part (n, hyp_point_blocks(P), 29);
 // sys (n, 29) = upper triangle of J^T W J | gradient | robust cost | detections used; cost_only: the last two alone, the others 0.  Non-zero: an unknown loss.
 int launch_rs_normal(hipStream_t st, int loss, bool cost_only, const double* points, const double* uvs, const unsigned char* mask, size_t P, int n, const int* ids, const TcCam* tcs, double f_scale,
                      double* part, double* sys);

@@ -5,12 +5,9 @@
 //                       camera (SoA), a usable flag (point and detection finite)
 //   k_rs_hypotheses     lane = (camera, hypothesis): rs_hypothesis on the 6 sampled points -- DLT, then ten Gauss-Newton iterations -- and
 //                       K [R | t].  The two 12 x 12 work matrices (288 doubles) are in scratch: H is a few thousand at most, not the hot kernel
-//   k_rs_score          the hot one, k_tv_score's shape: a workgroup keeps kRsPoints points of one camera in registers (kRsPPT per lane: X, Y, Z,
-//                       undistorted u, v, the flag) and loops over a chunk of kRsChunk hypotheses whose K [R | t] sits in LDS; grid = (point
-//                       blocks, chunks, cameras); per hypothesis the inlier count and the truncated cost, lane -> wavefront (shuffles) ->
-//                       workgroup (waves in index order) -> one partial per (workgroup, hypothesis, camera)
-//   k_rs_finish         workgroup = (hypothesis, camera): lane t sums the partials of workgroups t, t + 256, ... in order, then a fixed LDS tree
-//   k_rs_winner         workgroup = camera: the lowest (cost, index); its pose
+//   k_hyp_score         the hot one (mcba_hyp_score.h) with RsScore: K [R | t] against X, Y, Z and the undistorted u, v of the camera's usable
+//                       points, the truncated reprojection cost; then k_hyp_finish of mcba_twoview.hip (launch_hyp_finish) with grid (H, C)
+//   k_rs_winner         workgroup = camera: the lowest (cost, index), hyp_argmin; its pose
 //   k_rs_mask           lane = (camera, point): the winner's inlier mask, with the scorer's own inline function
 //   k_rs_normal         the polish: lane = (listed camera, point) over the masked points, rs_normal_item; kRsSys sums per workgroup in the
 //                       scorer's order; COST_ONLY: the robust cost and the count alone (a trial pose)
@@ -18,23 +15,23 @@
 // No atomics, floating-point or other: every sum has a fixed order, the results depend on (P, H) alone, bit for bit.
 #include <hip/hip_runtime.h>
 #include <math.h>
-// No contraction beyond the fma() calls the text spells out: k_rs_score and k_rs_mask must judge a point alike to the last bit.
+// No contraction beyond the fma() calls the text spells out: k_hyp_score<RsScore> and k_rs_mask must judge a point alike to the last bit.
 #pragma clang fp contract(off)
-#include "mcba_kernels.h"
-#include "mcba_device.h"
+#include "mcba_hyp_score.h"
 #include "mcba_resect_math.h"
 #include "../../include/mcba.h"
 
-static_assert(mcba::kRsPoints == MCBA_RESECT_POINTS_PER_BLOCK && mcba::kRsChunk == MCBA_RESECT_CHUNK, "include/mcba.h names the launch shape of k_rs_score");
+static_assert(mcba::kHypPoints == MCBA_RESECT_POINTS_PER_BLOCK && mcba::kHypChunk == MCBA_RESECT_CHUNK, "include/mcba.h names the launch shape of k_hyp_score");
+static_assert(mcba::RS_OK == mcba::TV_OK, "k_hyp_finish tells a live hypothesis of either pipeline by the one status");
 static_assert(mcba::kRsSample == MCBA_RESECT_SAMPLE && mcba::kRsGnIterations == MCBA_RESECT_GN_ITERATIONS, "include/mcba.h names the sample size and the Gauss-Newton iterations of a hypothesis");
 static_assert(mcba::kRsSys == MCBA_RESECT_SYSTEM, "include/mcba.h names the length of a camera's normal system");
 
 namespace mcba {
 
 // cams: (C, 9) = fx fy cx cy k1 k2 p1 p2 k3.  prep: per camera 4 planes of P doubles (undistorted u, v; normalised x, y); usable: (C, P)
-__global__ __launch_bounds__(kRsThreads) void k_rs_prepare(const double* __restrict__ points, const double* __restrict__ uvs, size_t P, const double* __restrict__ cams, int und_iters,
+__global__ __launch_bounds__(kHypThreads) void k_rs_prepare(const double* __restrict__ points, const double* __restrict__ uvs, size_t P, const double* __restrict__ cams, int und_iters,
                                                            double* __restrict__ prep, unsigned char* __restrict__ usable) {
-  const size_t p = (size_t)blockIdx.x * kRsThreads + threadIdx.x;
+  const size_t p = (size_t)blockIdx.x * kHypThreads + threadIdx.x;
   const int c = blockIdx.y;
   if (p >= P) return;
   const double u = uvs[2 * ((size_t)c * P + p)], v = uvs[2 * ((size_t)c * P + p) + 1];
@@ -80,118 +77,41 @@ __global__ __launch_bounds__(64) void k_rs_hypotheses(const double* __restrict__
   status[ch] = st;
 }
 
-// grid: (rs_score_blocks(P), ceil(H / kRsChunk), C).  part_c, part_n: (C, blocks, H)
-__global__ __launch_bounds__(kRsThreads) void k_rs_score(const double* __restrict__ points, const double* __restrict__ prep, const unsigned char* __restrict__ usable, size_t P,
-                                                         const double* __restrict__ KP, int H, double t2, double* __restrict__ part_c, unsigned* __restrict__ part_n) {
-  __shared__ double s_P[kRsChunk * 12];
-  __shared__ double s_c[kRsThreads / 64][kRsChunk];
-  __shared__ unsigned s_n[kRsThreads / 64][kRsChunk];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int c = blockIdx.z;
-  const int h0 = blockIdx.y * kRsChunk, nh = H - h0 < kRsChunk ? H - h0 : kRsChunk;
-  for (int i = tid; i < 12 * nh; i += kRsThreads) s_P[i] = KP[12 * ((size_t)c * H + h0) + i];
-  double X[kRsPPT], Y[kRsPPT], Z[kRsPPT], u[kRsPPT], v[kRsPPT];
-  bool ok[kRsPPT];
-  const size_t p0 = (size_t)blockIdx.x * kRsPoints;
-  const double* pu = prep + (size_t)c * 4 * P;
-#pragma unroll
-  for (int j = 0; j < kRsPPT; ++j) {
-    const size_t p = p0 + (size_t)j * kRsThreads + tid;
-    ok[j] = p < P && usable[(size_t)c * P + (p < P ? p : 0)] != 0;
-    X[j] = ok[j] ? points[3 * p] : 0.0;
-    Y[j] = ok[j] ? points[3 * p + 1] : 0.0;
-    Z[j] = ok[j] ? points[3 * p + 2] : 0.0;
-    u[j] = ok[j] ? pu[p] : 0.0;
-    v[j] = ok[j] ? pu[P + p] : 0.0;
+// k_hyp_score's resection model: a hypothesis is K [R | t] (12 doubles), a point is X, Y, Z and the camera's undistorted u, v (planes 0, 1 of
+// its prep); a point that is not usable for the camera is not ok
+struct RsScore {
+  static constexpr int kDoubles = 12;
+  static constexpr bool kCameras = true;
+  struct Point { double X, Y, Z, u, v; bool ok; };
+  const double* __restrict__ points;
+  const double* __restrict__ prep;
+  const unsigned char* __restrict__ usable;
+  size_t P;
+  __device__ __forceinline__ Point load(int c, size_t p) const {
+    const bool ok = p < P && usable[(size_t)c * P + (p < P ? p : 0)] != 0;
+    const double* pu = prep + (size_t)c * 4 * P;
+    return {ok ? points[3 * p] : 0.0, ok ? points[3 * p + 1] : 0.0, ok ? points[3 * p + 2] : 0.0, ok ? pu[p] : 0.0, ok ? pu[P + p] : 0.0, ok};
   }
-  __syncthreads();
-  for (int h = 0; h < nh; ++h) {
-    double kp[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) kp[i] = s_P[12 * h + i];
-    double cs = 0.0;
-    unsigned n = 0;
-#pragma unroll
-    for (int j = 0; j < kRsPPT; ++j) {
-      const double e2 = rs_error2(kp, X[j], Y[j], Z[j], u[j], v[j]);
-      cs += ok[j] ? tv_cost_term(e2, t2) : 0.0;
-      n += ok[j] && tv_inlier(e2, t2) ? 1u : 0u;
-    }
-    cs = wave_sum(cs);
-    n = wave_sum(n);
-    if (lane == 0) { s_c[wave][h] = cs; s_n[wave][h] = n; }
-  }
-  __syncthreads();
-  const size_t row = ((size_t)c * gridDim.x + blockIdx.x) * H + h0;
-  for (int h = tid; h < nh; h += kRsThreads) {
-    double cs = s_c[0][h];
-    unsigned n = s_n[0][h];
-#pragma unroll
-    for (int w = 1; w < kRsThreads / 64; ++w) { cs += s_c[w][h]; n += s_n[w][h]; }
-    part_c[row + h] = cs;
-    part_n[row + h] = n;
-  }
-}
+  static __device__ __forceinline__ double error2(const double* kp, const Point& q) { return rs_error2(kp, q.X, q.Y, q.Z, q.u, q.v); }
+};
 
-// grid (H, C): lane t sums the partials of workgroups t, t + 256, ... in order, then a fixed LDS tree
-__global__ __launch_bounds__(kRsThreads) void k_rs_finish(const double* __restrict__ part_c, const unsigned* __restrict__ part_n, size_t nblk, int H, const int* __restrict__ status,
-                                                          double* __restrict__ cost, unsigned* __restrict__ count) {
-  __shared__ double s_c[kRsThreads];
-  __shared__ unsigned long long s_n[kRsThreads];
-  const int h = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
-  double cs = 0.0;
-  unsigned long long n = 0;
-  for (size_t bk = tid; bk < nblk; bk += kRsThreads) {
-    cs += part_c[((size_t)c * nblk + bk) * H + h];
-    n += part_n[((size_t)c * nblk + bk) * H + h];
-  }
-  s_c[tid] = cs;
-  s_n[tid] = n;
-  __syncthreads();
-  for (int s = kRsThreads / 2; s >= 1; s >>= 1) {
-    if (tid < s) { s_c[tid] += s_c[tid + s]; s_n[tid] += s_n[tid + s]; }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const bool ok = status[(size_t)c * H + h] == RS_OK;
-    cost[(size_t)c * H + h] = ok ? s_c[0] : __builtin_inf();
-    count[(size_t)c * H + h] = ok ? (unsigned)s_n[0] : 0u;
-  }
-}
-
-// workgroup = camera: the lowest (cost, index) -- a total order, so the tree's shape does not matter.  best4: (C, 4), slot 3 is the host's
-__global__ __launch_bounds__(kRsThreads) void k_rs_winner(const double* __restrict__ cost, const unsigned* __restrict__ count, int H, const double* __restrict__ pose, int* __restrict__ win_idx,
-                                                          double* __restrict__ best4, double* __restrict__ rt12) {
-  __shared__ double s_c[kRsThreads];
-  __shared__ int s_h[kRsThreads];
+// workgroup = camera: the winner (hyp_argmin) and its pose.  best4: (C, 4), slot 3 is the host's
+__global__ __launch_bounds__(kHypThreads) void k_rs_winner(const double* __restrict__ cost, const unsigned* __restrict__ count, int H, const double* __restrict__ pose, int* __restrict__ win_idx,
+                                                           double* __restrict__ best4, double* __restrict__ rt12) {
   const int tid = threadIdx.x, c = blockIdx.x;
-  double bc = __builtin_inf();
-  int bh = 0x7fffffff;
-  for (int h = tid; h < H; h += kRsThreads) {
-    const double cs = cost[(size_t)c * H + h];
-    const bool take = tv_before(cs, h, bc, bh);
-    bc = take ? cs : bc;
-    bh = take ? h : bh;
-  }
-  s_c[tid] = bc;
-  s_h[tid] = bh;
-  __syncthreads();
-  for (int s = kRsThreads / 2; s >= 1; s >>= 1) {
-    if (tid < s && tv_before(s_c[tid + s], s_h[tid + s], s_c[tid], s_h[tid])) { s_c[tid] = s_c[tid + s]; s_h[tid] = s_h[tid + s]; }
-    __syncthreads();
-  }
-  const int w = s_h[0];   // (H >= 1: hypothesis 0 beats the initial (inf, INT_MAX) even when it is void)
+  double bc;
+  const int w = hyp_argmin(cost + (size_t)c * H, H, bc);
   if (tid == 0) {
     win_idx[c] = w;
-    best4[4 * c] = (double)w; best4[4 * c + 1] = s_c[0]; best4[4 * c + 2] = (double)count[(size_t)c * H + w]; best4[4 * c + 3] = 0.0;
+    best4[4 * c] = (double)w; best4[4 * c + 1] = bc; best4[4 * c + 2] = (double)count[(size_t)c * H + w]; best4[4 * c + 3] = 0.0;
   }
   if (tid < 12) rt12[12 * c + tid] = pose[12 * ((size_t)c * H + w) + tid];
 }
 
-__global__ __launch_bounds__(kRsThreads) void k_rs_mask(const double* __restrict__ points, const double* __restrict__ prep, const unsigned char* __restrict__ usable, size_t P,
+__global__ __launch_bounds__(kHypThreads) void k_rs_mask(const double* __restrict__ points, const double* __restrict__ prep, const unsigned char* __restrict__ usable, size_t P,
                                                         const double* __restrict__ KP, const int* __restrict__ status, int H, double t2, const int* __restrict__ win_idx,
                                                         unsigned char* __restrict__ inliers) {
-  const size_t p = (size_t)blockIdx.x * kRsThreads + threadIdx.x;
+  const size_t p = (size_t)blockIdx.x * kHypThreads + threadIdx.x;
   const int c = blockIdx.y;
   if (p >= P) return;
   const size_t cw = (size_t)c * H + win_idx[c];
@@ -204,19 +124,19 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_mask(const double* __restrict
   inliers[(size_t)c * P + p] = ok && tv_inlier(e2, t2) ? 1 : 0;
 }
 
-// grid: (rs_pose_blocks(P), n).  ids (n): the camera of each listed problem (rows of uvs / mask); tcs (n): its camera at the pose to evaluate.
+// grid: (hyp_point_blocks(P), n).  ids (n): the camera of each listed problem (rows of uvs / mask); tcs (n): its camera at the pose to evaluate.
 // part: (n, blocks, kRsSys), COST_ONLY: slots 27, 28 alone are written
 template <int LOSS, bool COST_ONLY>
-__global__ __launch_bounds__(kRsThreads) void k_rs_normal(const double* __restrict__ points, const double* __restrict__ uvs, const unsigned char* __restrict__ mask, size_t P,
+__global__ __launch_bounds__(kHypThreads) void k_rs_normal(const double* __restrict__ points, const double* __restrict__ uvs, const unsigned char* __restrict__ mask, size_t P,
                                                           const int* __restrict__ ids, const TcCam* __restrict__ tcs, double fs2, double inv_fs2, double* __restrict__ part) {
   constexpr int NV = COST_ONLY ? 2 : kRsSys, V0 = COST_ONLY ? 27 : 0;
-  __shared__ double s_v[kRsThreads / 64][NV];
+  __shared__ double s_v[kHypThreads / 64][NV];
   __shared__ TcCam s_tc;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int k = blockIdx.y, c = ids[k];
   if (tid < 30) reinterpret_cast<double*>(&s_tc)[tid] = reinterpret_cast<const double*>(tcs + k)[tid];
   __syncthreads();
-  const size_t p = (size_t)blockIdx.x * kRsThreads + tid;
+  const size_t p = (size_t)blockIdx.x * kHypThreads + tid;
   double acc[kRsSys];
 #pragma unroll
   for (int i = 0; i < kRsSys; ++i) acc[i] = 0.0;
@@ -240,7 +160,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_normal(const double* __restri
   if (tid < NV) {
     double s = s_v[0][tid];
 #pragma unroll
-    for (int w = 1; w < kRsThreads / 64; ++w) s += s_v[w][tid];
+    for (int w = 1; w < kHypThreads / 64; ++w) s += s_v[w][tid];
     part[((size_t)k * gridDim.x + blockIdx.x) * kRsSys + V0 + tid] = s;
   }
 }
@@ -257,7 +177,7 @@ __global__ __launch_bounds__(64) void k_rs_normal_finish(const double* __restric
 
 // ---------------------------------------------------------------- launch wrappers
 void launch_rs_prepare(hipStream_t st, const double* points, const double* uvs, size_t P, int C, const double* cams, int und_iters, double* prep, unsigned char* usable) {
-  k_rs_prepare<<<dim3((unsigned)rs_pose_blocks(P), (unsigned)C), dim3(kRsThreads), 0, st>>>(points, uvs, P, cams, und_iters, prep, usable);
+  k_rs_prepare<<<dim3((unsigned)hyp_point_blocks(P), (unsigned)C), dim3(kHypThreads), 0, st>>>(points, uvs, P, cams, und_iters, prep, usable);
 }
 
 void launch_rs_hypotheses(hipStream_t st, const double* points, const double* prep, size_t P, int C, const int* samples, int H, const double* pose_in, const double* cams, double* pose, double* KP,
@@ -267,31 +187,30 @@ void launch_rs_hypotheses(hipStream_t st, const double* points, const double* pr
 
 void launch_rs_score(hipStream_t st, const double* points, const double* prep, const unsigned char* usable, size_t P, int C, const double* KP, int H, double threshold, double* part_c,
                      unsigned* part_n) {
-  k_rs_score<<<dim3((unsigned)rs_score_blocks(P), (unsigned)((H + kRsChunk - 1) / kRsChunk), (unsigned)C), dim3(kRsThreads), 0, st>>>(points, prep, usable, P, KP, H, threshold * threshold, part_c,
-                                                                                                                                        part_n);
+  launch_hyp_score(st, RsScore{points, prep, usable, P}, P, C, KP, H, threshold, part_c, part_n);
 }
 
 void launch_rs_finish(hipStream_t st, const double* part_c, const unsigned* part_n, size_t nblk, int C, int H, const double* pose, const int* status, double* cost, unsigned* count, int* win_idx,
                       double* best4, double* rt12) {
-  k_rs_finish<<<dim3((unsigned)H, (unsigned)C), dim3(kRsThreads), 0, st>>>(part_c, part_n, nblk, H, status, cost, count);
-  k_rs_winner<<<dim3((unsigned)C), dim3(kRsThreads), 0, st>>>(cost, count, H, pose, win_idx, best4, rt12);
+  launch_hyp_finish(st, part_c, part_n, nblk, C, H, status, cost, count);
+  k_rs_winner<<<dim3((unsigned)C), dim3(kHypThreads), 0, st>>>(cost, count, H, pose, win_idx, best4, rt12);
 }
 
 void launch_rs_mask(hipStream_t st, const double* points, const double* prep, const unsigned char* usable, size_t P, int C, const double* KP, const int* status, int H, double threshold,
                     const int* win_idx, unsigned char* inliers) {
-  k_rs_mask<<<dim3((unsigned)rs_pose_blocks(P), (unsigned)C), dim3(kRsThreads), 0, st>>>(points, prep, usable, P, KP, status, H, threshold * threshold, win_idx, inliers);
+  k_rs_mask<<<dim3((unsigned)hyp_point_blocks(P), (unsigned)C), dim3(kHypThreads), 0, st>>>(points, prep, usable, P, KP, status, H, threshold * threshold, win_idx, inliers);
 }
 
 template <int LOSS>
 static void rs_normal_launch(hipStream_t st, bool cost_only, dim3 grid, const double* points, const double* uvs, const unsigned char* mask, size_t P, const int* ids, const TcCam* tcs, double fs2,
                              double* part) {
-  if (cost_only) k_rs_normal<LOSS, true><<<grid, dim3(kRsThreads), 0, st>>>(points, uvs, mask, P, ids, tcs, fs2, 1.0 / fs2, part);
-  else k_rs_normal<LOSS, false><<<grid, dim3(kRsThreads), 0, st>>>(points, uvs, mask, P, ids, tcs, fs2, 1.0 / fs2, part);
+  if (cost_only) k_rs_normal<LOSS, true><<<grid, dim3(kHypThreads), 0, st>>>(points, uvs, mask, P, ids, tcs, fs2, 1.0 / fs2, part);
+  else k_rs_normal<LOSS, false><<<grid, dim3(kHypThreads), 0, st>>>(points, uvs, mask, P, ids, tcs, fs2, 1.0 / fs2, part);
 }
 
 int launch_rs_normal(hipStream_t st, int loss, bool cost_only, const double* points, const double* uvs, const unsigned char* mask, size_t P, int n, const int* ids, const TcCam* tcs, double f_scale,
                      double* part, double* sys) {
-  const size_t nblk = rs_pose_blocks(P);
+  const size_t nblk = hyp_point_blocks(P);
   const dim3 grid((unsigned)nblk, (unsigned)n);
   const double fs2 = f_scale * f_scale;
   switch (loss) {

@@ -5,6 +5,7 @@
 // Cameras with fewer than six usable points are left out before anything is uploaded: the kernels see the others, packed.
 // The polish's loop is rs_lm of mcba_resect_math.h, driven here against the kernels: one launch pair and one small copy back per evaluation.
 #include "mcba_handle.h"
+#include "mcba_ransac_host.h"
 #include "mcba_resect_math.h"
 
 using namespace mcba_internal;
@@ -54,18 +55,12 @@ struct ResectBackEnd {
   }
 };
 
-// What tells the two generators of the RANSAC apart: indices per sample, rows of the pose table per sample, the bound on n_hypotheses.
-struct Generator {
-  const char* who;
-  int size, slots, max_h;
-  const char* range;
-};
-constexpr Generator kDlt6{"mcba_resect_ransac", MCBA_RESECT_SAMPLE, 1, MCBA_RESECT_MAX_HYPOTHESES, ": 1 .. MCBA_RESECT_MAX_HYPOTHESES (4096) hypotheses required"};
-constexpr Generator kP3p{"mcba_resect_ransac_p3p", MCBA_RESECT_P3P_SAMPLE, MCBA_RESECT_P3P_SLOTS, MCBA_RESECT_P3P_MAX_SAMPLES, ": 1 .. MCBA_RESECT_P3P_MAX_SAMPLES (1024) samples required"};
+constexpr mcba::Generator kDlt6{"mcba_resect_ransac", MCBA_RESECT_SAMPLE, 1, MCBA_RESECT_MAX_HYPOTHESES, ": 1 .. MCBA_RESECT_MAX_HYPOTHESES (4096) hypotheses required"};
+constexpr mcba::Generator kP3p{"mcba_resect_ransac_p3p", MCBA_RESECT_P3P_SAMPLE, MCBA_RESECT_P3P_SLOTS, MCBA_RESECT_P3P_MAX_SAMPLES, ": 1 .. MCBA_RESECT_P3P_MAX_SAMPLES (1024) samples required"};
 
 // The body of mcba_resect_ransac and mcba_resect_ransac_p3p: the checks, the upload, the stages between their events, the download.
 // n_hypotheses counts samples; the table that the scorer sees has H = n_hypotheses g.slots rows per camera.
-int resect_ransac(const Generator& g, int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, int n_hypotheses, const int* samples,
+int resect_ransac(const mcba::Generator& g, int n_cameras, size_t n_points, const double* points, const double* uvs, const double* cam12, const double* dist5, int n_hypotheses, const int* samples,
                   const double* poses_in, double threshold, int undistort_iterations, int device, double* rt12, double* best4, unsigned char* inliers, double* pose_out, double* cost_out,
                   unsigned* count_out, int* status_out, double* kernel_ms) {
   auto bad = [&](const char* what) { return fail(MCBA_ERR_ARG, (std::string(g.who) + what).c_str()); };
@@ -89,17 +84,10 @@ int resect_ransac(const Generator& g, int n_cameras, size_t n_points, const doub
     }
     if (n_use[c] >= (size_t)MCBA_RESECT_SAMPLE) act.push_back(c);
   }
+  std::string msg;
   if (!poses_in)
     for (int c : act)
-      for (int h = 0; h < S; ++h) {
-        const int* s = samples + g.size * ((size_t)c * S + h);
-        for (int k = 0; k < g.size; ++k) {
-          if (s[k] < 0 || (size_t)s[k] >= P) return bad(": a sample index is outside 0 .. n_points - 1");
-          if (!use[(size_t)c * P + s[k]]) return bad(": a sampled point is not usable for its camera");
-          for (int j = 0; j < k; ++j)
-            if (s[j] == s[k]) return bad(": an index is repeated within a sample");
-        }
-      }
+      if (!mcba::samples_ok(g.who, samples + (size_t)g.size * S * c, (size_t)S, g.size, P, use.data() + (size_t)c * P, &msg)) return fail(MCBA_ERR_ARG, msg.c_str());
   if (int rc = stateless_device(device)) return rc;
   const double nan = __builtin_nan("");
   for (int c = 0; c < C; ++c) {
@@ -122,7 +110,7 @@ int resect_ransac(const Generator& g, int n_cameras, size_t n_points, const doub
     for (int i = 0; i < 4; ++i) cams9[9 * (size_t)a + i] = cam12[12 * (size_t)act[a] + i];
     for (int i = 0; i < 5; ++i) cams9[9 * (size_t)a + 4 + i] = dist5[5 * (size_t)act[a] + i];
   }
-  const size_t nblk = mcba::rs_score_blocks(P);
+  const size_t nblk = mcba::hyp_score_blocks(P);
   StatelessCall call;
   double *d_pts = nullptr, *d_uv = nullptr, *d_cams = nullptr, *d_pin = nullptr, *d_prep = nullptr, *d_pose = nullptr, *d_KP = nullptr, *d_pc = nullptr, *d_cost = nullptr, *d_best = nullptr,
          *d_rt = nullptr;
@@ -158,40 +146,27 @@ int resect_ransac(const Generator& g, int n_cameras, size_t n_points, const doub
   if (int rc = call.scratch(&d_best, (size_t)4 * Ca)) return rc;
   if (int rc = call.scratch(&d_rt, (size_t)12 * Ca)) return rc;
   if (int rc = call.scratch(&d_inl, P * Ca)) return rc;
-  // the call's own events bracket the whole; four more separate the stages
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  struct EventGuard {
-    hipEvent_t* e;
-    ~EventGuard() { for (int i = 0; i < 4; ++i) if (e[i]) (void)hipEventDestroy(e[i]); }
-  } guard{ev};
-  for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&ev[i]));
+  StageEvents<4> stages;   // the call's own events bracket the whole; four more separate the stages
+  HIPCHK(stages.create());
   HIPCHK(call.start());
   mcba::launch_rs_prepare(nullptr, d_pts, d_uv, P, Ca, d_cams, undistort_iterations, d_prep, d_use);
   if (int rc = check_launch()) return rc;
-  HIPCHK(hipEventRecord(ev[0], nullptr));
+  HIPCHK(stages.mark());
   if (g.slots == 1) mcba::launch_rs_hypotheses(nullptr, d_pts, d_prep, P, Ca, d_smp, H, d_pin, d_cams, d_pose, d_KP, d_st);
   else mcba::launch_rs3_hypotheses(nullptr, d_pts, d_prep, P, Ca, d_smp, S, d_cams, d_pose, d_KP, d_st);
   if (int rc = check_launch()) return rc;
-  HIPCHK(hipEventRecord(ev[1], nullptr));
+  HIPCHK(stages.mark());
   mcba::launch_rs_score(nullptr, d_pts, d_prep, d_use, P, Ca, d_KP, H, threshold, d_pc, d_pn);
   if (int rc = check_launch()) return rc;
-  HIPCHK(hipEventRecord(ev[2], nullptr));
+  HIPCHK(stages.mark());
   mcba::launch_rs_finish(nullptr, d_pc, d_pn, nblk, Ca, H, d_pose, d_st, d_cost, d_cnt, d_win, d_best, d_rt);
   if (int rc = check_launch()) return rc;
-  HIPCHK(hipEventRecord(ev[3], nullptr));
+  HIPCHK(stages.mark());
   mcba::launch_rs_mask(nullptr, d_pts, d_prep, d_use, P, Ca, d_KP, d_st, H, threshold, d_win, d_inl);
   if (int rc = check_launch()) return rc;
   double total = 0.0;
   HIPCHK(call.stop(&total));
-  if (kernel_ms) {
-    const hipEvent_t seq[6] = {call.e0, ev[0], ev[1], ev[2], ev[3], call.e1};
-    kernel_ms[0] = total;
-    for (int i = 0; i < 5; ++i) {
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, seq[i], seq[i + 1]));
-      kernel_ms[1 + i] = ms;
-    }
-  }
+  if (kernel_ms) HIPCHK(stages.fill(call, total, kernel_ms));
   for (int a = 0; a < Ca; ++a) {
     const size_t c = (size_t)act[a];
     double b4[4];
@@ -239,7 +214,7 @@ int mcba_resect_refine(int n_cameras, size_t n_points, const double* points, con
   if (max_nfev < 1) return fail(MCBA_ERR_ARG, "mcba_resect_refine: max_nfev must be at least 1");
   if (int rc = stateless_device(device)) return rc;
   const int C = n_cameras;
-  const size_t P = n_points, nblk = mcba::rs_pose_blocks(P);
+  const size_t P = n_points, nblk = mcba::hyp_point_blocks(P);
   std::vector<mcba::RsCamera> cams((size_t)C);
   int n_act = 0;
   for (int c = 0; c < C; ++c) {

@@ -4,7 +4,7 @@
 //                       Grunert's quartic, its real roots, per root the pose from the two triangles' frames and five Gauss-Newton iterations
 //                       -- and K [R | t]; slots 4 h .. 4 h + 3 of the (C, 4 H, 12) table, void slots included.  No work matrices: a lane's
 //                       state is its 3 points, the quartic and one pose at a time
-// The table is scored in place by k_rs_score, k_rs_finish, k_rs_winner and k_rs_mask of mcba_resect.hip with 4 H for H: a void slot costs
+// The table is scored in place by k_hyp_score, k_hyp_finish, k_rs_winner and k_rs_mask (mcba_resect.hip) with 4 H for H: a void slot costs
 // +inf there, so nothing is compacted and the cameras' different live counts need no bookkeeping.  No atomics.
 #include <hip/hip_runtime.h>
 #include <math.h>

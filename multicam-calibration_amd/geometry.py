@@ -649,6 +649,12 @@ MAX_FIVEPOINT_SAMPLES = ops.TWOVIEW5_MAX_SAMPLES
 SOLVERS = ("8point", "5point")
 
 
+def _draw(n, n_hypotheses, seed, size):
+    """the drawer behind draw_samples and draw_resection_samples: one generator, one choice() without replacement per hypothesis, in order"""
+    rng = np.random.default_rng(seed)
+    return np.ascontiguousarray(np.stack([rng.choice(int(n), int(size), replace=False) for _ in range(int(n_hypotheses))]), dtype=np.int32)
+
+
 def draw_samples(n_common, n_hypotheses, seed, size=8):
     """(n_hypotheses, size) int32: per hypothesis `size` (8, or 5 for the five-point solver) different indices in 0 .. n_common - 1, one
     `np.random.default_rng(seed).choice(n_common, size, replace=False)` each from a generator of its own -- the global numpy generator is never
@@ -657,8 +663,7 @@ def draw_samples(n_common, n_hypotheses, seed, size=8):
         raise ValueError("size must be 8 (the 8-point solver) or 5 (the five-point solver)")
     if int(n_common) < 8:
         raise ValueError("a sample needs 8 different correspondences")
-    rng = np.random.default_rng(seed)
-    return np.ascontiguousarray(np.stack([rng.choice(int(n_common), int(size), replace=False) for _ in range(int(n_hypotheses))]), dtype=np.int32)
+    return _draw(n_common, n_hypotheses, seed, size)
 
 
 def _rotation_vector(R):
@@ -895,8 +900,7 @@ def draw_resection_samples(n_usable, n_hypotheses, seed, size=6):
         raise ValueError("size must be 6 (dlt6) or 3 (p3p)")
     if int(n_usable) < size:
         raise ValueError(f"a sample needs {size} different points")
-    rng = np.random.default_rng(seed)
-    return np.ascontiguousarray(np.stack([rng.choice(int(n_usable), size, replace=False) for _ in range(int(n_hypotheses))]), dtype=np.int32)
+    return _draw(n_usable, n_hypotheses, seed, size)
 
 
 def _min_resection_inliers(n_usable):

@@ -5,7 +5,7 @@ hypotheses, score, finish, mask): the median of `reps` calls after one that warm
 of the detections missing, one detection displaced by N(0, 40^2) px on 15 % of the points); every camera is resected against the true points.
 
 How to read it: the generator stage (k_rs3_hypotheses against k_rs_hypotheses) at equal sample count; the whole RANSAC at equal sample count,
-where "p3p" fills and scores FOUR table slots per sample -- 4 x the work of k_rs_score, k_rs_finish and k_rs_winner -- so at equal sample count
+where "p3p" fills and scores FOUR table slots per sample -- 4 x the work of k_hyp_score, k_hyp_finish and k_rs_winner -- so at equal sample count
 it is the dearer call whenever the scorer dominates.  What "p3p" buys is that far fewer samples are needed.
 
   python scripts/p3p_resection_timing.py [--out DIR] [--reps R] [--big-reps R]"""

@@ -1,7 +1,7 @@
 """Camera resection on the MI355X: writes profiles/resection_timing.json.
 Per shape (cameras x points x hypotheses; by default 6 x 200 000 x 512 and 24 x 20 000 x 256) a fresh child process: the call time of
 resect_cameras with and without the polish, the kernel time of mcba_resect_ransac per stage (HIP events: prepare, hypotheses, score, finish, mask)
-and the span and the evaluations of mcba_resect_refine; for k_rs_score the achieved FP64 rate from the operation count below.
+and the span and the evaluations of mcba_resect_refine; for the scorer (k_hyp_score with RsScore; key k_rs_score) the achieved FP64 rate from the operation count below.
 Scene: scripts/consensus_timing.py's (0.3 px noise, 10 % of the detections missing, one detection displaced by N(0, 40^2) px on 15 % of the points);
 every camera is resected against the true points.  The call does not exist in earlier versions: the numbers are recorded, nothing is compared.
 
@@ -15,7 +15,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-# FP64 operations of k_rs_score per (point, hypothesis), counted from the text of rs_error2 and tv_cost_term (a model, not a profile): three rows of
+# FP64 operations of the scorer per (point, hypothesis), counted from the text of rs_error2 and tv_cost_term (a model, not a profile): three rows of
 # K [R | t] 9 fma, fast_rcp 1 rcp + 3 fma, the two differences 2 fma, their squares 1 fma + 1 mul, the truncated sum 1 add:
 # 15 fma + 1 mul + 1 add + 1 rcp = 18 instructions, 33 flops (an fma counts two)
 SCORE_INSTRUCTIONS, SCORE_FLOPS = 18, 33

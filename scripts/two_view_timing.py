@@ -1,6 +1,6 @@
 """Extrinsics from keypoints on the MI355X: writes profiles/two_view_timing.json.
   pair   one camera pair, 200 000 common points x 512 hypotheses: call time of estimate_relative_pose, kernel time of mcba_two_view_ransac per
-         stage (HIP events: prepare, hypotheses, score, finish, pose), and for k_tv_score the achieved FP64 rate from the operation count below
+         stage (HIP events: prepare, hypotheses, score, finish, pose), and for the scorer (k_hyp_score with TvScore; key k_tv_score) the achieved FP64 rate from the operation count below
   rig    a 6-camera rig at 200 000 points: call time of extrinsics_from_keypoints with and without the refinement, the two-view kernels' share
 Scene: scripts/consensus_timing.py's (0.3 px noise, 10 % of the detections missing, one detection displaced by N(0, 40^2) px on 15 % of the points).
 
@@ -13,7 +13,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-# FP64 operations of k_tv_score per (point, hypothesis), counted from the text of tv_sampson2 and tv_cost_term (a model, not a profile):
+# FP64 operations of the scorer per (point, hypothesis), counted from the text of tv_sampson2 and tv_cost_term (a model, not a profile):
 # F x_a 6 fma, the first two of F^T x_b 4 fma, the numerator 2 fma, the denominator 3 fma + 1 mul, its square 1 mul, fast_rcp 1 rcp + 3 fma,
 # the quotient 1 mul, the truncated sum 1 add: 18 fma + 3 mul + 1 add + 1 rcp = 23 instructions, 41 flops (an fma counts two)
 SCORE_INSTRUCTIONS, SCORE_FLOPS = 23, 41

@@ -8,10 +8,21 @@
 #include <cstdint>
 #include <vector>
 #include "../../multicam-calibration_amd/csrc/mcba_resect_math.h"
+#include "../../multicam-calibration_amd/csrc/mcba_ransac_host.h"
 
 using namespace mcba;
 
 extern "C" {
+
+// The check that mcba_resect_ransac and mcba_resect_ransac_p3p make of a camera's table of host-drawn samples before the upload
+// (csrc/mcba_ransac_host.h), the same text.  usable: a byte per point, or NULL.  Returns 1 for a table that passes; 0 with the message in msg
+// (cap bytes of room, NUL-terminated).
+int hc_samples_ok(const char* who, const int* samples, size_t rows, int size, size_t limit, const unsigned char* usable, char* msg, size_t cap) {
+  std::string m;
+  const bool ok = samples_ok(who, samples, rows, size, limit, usable, &m);
+  snprintf(msg, cap, "%s", m.c_str());
+  return ok ? 1 : 0;
+}
 
 // out4: 4 planes of P doubles (undistorted u, v; normalised x, y), usable: P bytes
 void hc_rs_prepare(size_t P, const double* points, const double* uv, const double* cam12, const double* dist5, int und_iters, double* out4, unsigned char* usable) {
@@ -190,6 +201,8 @@ int main(int argc, char** argv) {
        fread(smp.data(), 4, smp.size(), fh) == smp.size();
   fclose(fh);
   if (!ok) return 2;
+  char msg[128];
+  if (!hc_samples_ok("main", smp.data(), (size_t)H, 6, (size_t)P, nullptr, msg, sizeof msg)) return 6;
   std::vector<double> rt(12), best(4), pose(12 * H), cost(H);
   std::vector<unsigned char> inl(P);
   std::vector<unsigned> cnt(H);

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <vector>
 #include "../../multicam-calibration_amd/csrc/mcba_twoview_math.h"
+#include "../../multicam-calibration_amd/csrc/mcba_ransac_host.h"
 
 using namespace mcba;
 
@@ -17,6 +18,15 @@ static void intrinsics_of(const double* cam12, const double* dist5, double ka[4]
 }
 
 extern "C" {
+
+// The check that mcba_two_view_ransac and mcba_two_view_ransac5 make of their table of host-drawn samples before the upload (csrc/mcba_ransac_host.h), the same text.  usable: a byte
+// per point, or NULL.  Returns 1 for a table that passes; 0 with the message in msg (cap bytes of room, NUL-terminated).
+int hc_samples_ok(const char* who, const int* samples, size_t rows, int size, size_t limit, const unsigned char* usable, char* msg, size_t cap) {
+  std::string m;
+  const bool ok = samples_ok(who, samples, rows, size, limit, usable, &m);
+  snprintf(msg, cap, "%s", m.c_str());
+  return ok ? 1 : 0;
+}
 
 // out8: 8 planes of M doubles (undistorted pixels a.x a.y b.x b.y, normalised a.x a.y b.x b.y)
 void hc_tv_prepare(size_t M, const double* uv_a, const double* uv_b, const double* cam12, const double* dist5, int und_iters, double* out8) {
@@ -121,6 +131,8 @@ int main(int argc, char** argv) {
        fread(smp.data(), 4, smp.size(), fh) == smp.size();
   fclose(fh);
   if (!ok) return 2;
+  char msg[128];
+  if (!hc_samples_ok("main", smp.data(), (size_t)H, 8, (size_t)M, nullptr, msg, sizeof msg)) return 6;
   std::vector<double> rt(12), best(4), pts(3 * M), E(9 * H), cost(H);
   std::vector<unsigned char> inl(M);
   std::vector<unsigned> cnt(H);

@@ -1,7 +1,7 @@
 """mcba_two_view_ransac5 (csrc/mcba_fivepoint.hip) and solver="5point" of the two public functions above it on the GPU,
 held to tests/fivepoint_oracle.py by the rules of that module's docstring: the candidate table at its launch edges (one sample; 7, 64 and 103
 samples -- a lane short of, at and past a wavefront of samples, the packed table short of, across and over several chunks of the scoring grid;
-8 points; 1024 + 1 points, a second workgroup of k_tv_score), the scores of the packed table through twoview_oracle.check_scores and the winner
+8 points; 1024 + 1 points, a second workgroup of the scorer), the scores of the packed table through twoview_oracle.check_scores and the winner
 and pose through check_pose (the oracle scoring the very table that came back), bitwise repeatability, solver="8point" bit-identical to no
 keyword, the chain on a thin scene against the optimum reached from the true extrinsics, every tree edge of "thin6", and the error paths.
 Output buffers start as sentinels."""

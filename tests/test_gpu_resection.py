@@ -156,6 +156,31 @@ def test_hypotheses_at_the_launch_boundaries(H):
     assert (g["count"][0][ok] <= o["n_usable"]).all() and (g["cost"][0][ok] <= THR ** 2 * o["n_usable"]).all()
 
 
+def finish_scene():
+    """(X, uvs (2, P, 2), intrs, poses (2, 5, 12)): cameras 1 and 2 of a three-camera scene (0.3 px noise) at 257 workgroups + 1 point; per camera
+    the true pose and four perturbed ones (rotation vector by 1e-4 rad, translation by 0.5 scene units per coordinate, normal, seeded)"""
+    uvs, ext, intr, X = scene(C=3, P=257 * PPB + 1, seed=5, noise=0.3)
+    rng = np.random.default_rng(11)
+    poses = np.empty((2, 5, 12))
+    for a, c in enumerate((1, 2)):
+        for h in range(5):
+            e = ext[c] + (rng.normal(size=6) * np.r_[[1e-4] * 3, [0.5] * 3] if h else 0.0)
+            poses[a, h] = np.r_[ks.rodrigues(e[:3]).ravel(), e[3:]]
+    return X, np.stack([np.array(uvs[1]), np.array(uvs[2])]), [intr[1], intr[2]], poses
+
+
+def test_finish_past_one_partial_per_lane_with_a_second_camera():
+    """k_hyp_finish with more partials than lanes (257 workgroups + 1 point: lane 0 sums two) AND a camera index above 0, in one call: C = 2,
+    H = 5 poses handed in.  Each camera's row is held to the oracle as in test_scoring_and_winner_with_poses_handed_in."""
+    X, uvs, intrs, poses = finish_scene()
+    g = call(X, uvs, intrs, None, THR, poses_in=poses)
+    assert np.array_equal(g["pose"], poses)
+    for a in range(2):
+        o = ro.ransac(X, uvs[a], intrs[a], None, THR, poses_in=poses[a])
+        check_camera(f"257 workgroups + 1 point, camera {a}", row(g, a), None, o, with_hypotheses=False)
+        assert g["best"][a, 3] == len(X)
+
+
 def test_cameras_of_different_usable_counts_in_one_call():
     """C = 1, 2, 3: the third camera sees 4 points (status -1, NaN, nothing launched for it), the second about half; every row equals its single-camera call bit for bit"""
     uvs, ext, intr, X = scene(C=3, P=PPB + 37, seed=9, noise=0.3)

@@ -37,6 +37,7 @@ def hc(tmp_path_factory):
     h = ctypes.CDLL(lib)
     h.hc_resect_ransac.argtypes = [ctypes.c_size_t, V, V, V, V, ctypes.c_int, V, V, ctypes.c_double, ctypes.c_int, V, V, V, V, V, V, V]
     h.hc_rs_prepare.argtypes = [ctypes.c_size_t, V, V, V, V, ctypes.c_int, V, V]
+    h.hc_samples_ok.argtypes = [ctypes.c_char_p, V, ctypes.c_size_t, ctypes.c_int, ctypes.c_size_t, V, ctypes.c_char_p, ctypes.c_size_t]
     h.hc_resect_refine.argtypes = [ctypes.c_int, ctypes.c_size_t, V, V, V, V, V, V, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, V, V, V, V]
     return h
 
@@ -174,6 +175,36 @@ def test_bad_arguments_write_nothing(hc):
     for kw in (dict(H=0), dict(threshold=0.0), dict(samples=bad)):
         rc, g = run(hc, c["points"], c["uv"], c["intr"], kw.get("samples", smp), kw.get("threshold", ro.THRESHOLD), H=kw.get("H"))
         assert rc == 1 and (g["rt12"] == 7.0).all() and (g["best"] == 7.0).all() and (g["cost"] == 7.0).all()
+
+
+def samples_ok(hc, who, samples, limit, usable=None):
+    """the verdict and the message of csrc/mcba_ransac_host.h's samples_ok on an (rows, size) table"""
+    smp = np.ascontiguousarray(samples, dtype=np.int32)
+    msg = ctypes.create_string_buffer(b"?" * 255, 256)
+    ok = hc.hc_samples_ok(who.encode(), P(smp), smp.shape[0], smp.shape[1], limit, P(usable), msg, 256)
+    return bool(ok), msg.value.decode()
+
+
+def test_sample_check_verdicts_and_messages(hc):
+    """The check both resection entries make of a camera's samples: a valid table passes with no message; an index equal to the limit, a negative
+    one, a point that is not usable for the camera and a repeat within a row fail with the entry's name in front of today's texts.  A point out of
+    range is reported as such before its flag is looked up, an unusable point before a repeat."""
+    rng = np.random.default_rng(5)
+    good = np.stack([rng.choice(30, 6, replace=False) for _ in range(9)]).astype(np.int32)
+    usable = np.ones(30, np.uint8)
+    assert samples_ok(hc, "mcba_resect_ransac", good, 30, usable) == (True, "")
+    assert samples_ok(hc, "mcba_resect_ransac_p3p", good[:, :3], 30) == (True, "")
+    for who in ("mcba_resect_ransac", "mcba_resect_ransac_p3p"):
+        bad = good.copy()
+        bad[8, 5] = 30
+        assert samples_ok(hc, who, bad, 30, usable) == (False, who + ": a sample index is outside 0 .. n_points - 1")
+        bad[8, 5] = -1
+        assert samples_ok(hc, who, bad, 30, usable) == (False, who + ": a sample index is outside 0 .. n_points - 1")
+        bad[8, 5] = bad[8, 1]
+        assert samples_ok(hc, who, bad, 30, usable) == (False, who + ": an index is repeated within a sample")
+        off = usable.copy()
+        off[bad[8, 1]] = 0
+        assert samples_ok(hc, who, bad, 30, off) == (False, who + ": a sampled point is not usable for its camera")
 
 
 @pytest.mark.parametrize("loss", ["linear", "soft_l1", "huber", "cauchy", "arctan"])

@@ -34,6 +34,7 @@ def hc(tmp_path_factory):
     h = ctypes.CDLL(lib)
     h.hc_two_view_ransac.argtypes = [ctypes.c_size_t, V, V, V, V, ctypes.c_int, V, V, ctypes.c_double, ctypes.c_int, V, V, V, V, V, V, V, V]
     h.hc_tv_prepare.argtypes = [ctypes.c_size_t, V, V, V, V, ctypes.c_int, V]
+    h.hc_samples_ok.argtypes = [ctypes.c_char_p, V, ctypes.c_size_t, ctypes.c_int, ctypes.c_size_t, V, ctypes.c_char_p, ctypes.c_size_t]
     return h
 
 
@@ -105,6 +106,31 @@ def test_bad_arguments_write_nothing(hc):
         n = kw.get("n", len(ua))
         rc, g = run(hc, np.ascontiguousarray(ua[:n]), np.ascontiguousarray(ub[:n]), ia, ib, smp, kw.get("threshold", tvo.THRESHOLD), H=kw.get("H"))
         assert rc == 1 and (g["rt12"] == 7.0).all() and (g["best"] == 7.0).all() and (g["points"] == 7.0).all()
+
+
+def samples_ok(hc, who, samples, limit, usable=None):
+    """the verdict and the message of csrc/mcba_ransac_host.h's samples_ok on an (rows, size) table"""
+    smp = np.ascontiguousarray(samples, dtype=np.int32)
+    msg = ctypes.create_string_buffer(b"?" * 255, 256)
+    ok = hc.hc_samples_ok(who.encode(), P(smp), smp.shape[0], smp.shape[1], limit, P(usable), msg, 256)
+    return bool(ok), msg.value.decode()
+
+
+def test_sample_check_verdicts_and_messages(hc):
+    """The check both two-view entries make of their samples: a valid table passes with no message; an index equal to the limit, a negative one
+    and a repeat within a row fail with the entry's name in front of today's texts.  A repeat across rows is no fault."""
+    good = tvo.draw_samples(40, 7, 3)
+    assert samples_ok(hc, "mcba_two_view_ransac", good, 40) == (True, "")
+    assert samples_ok(hc, "mcba_two_view_ransac5", good[:, :5], int(good[:, :5].max()) + 1) == (True, "")
+    assert samples_ok(hc, "mcba_two_view_ransac", np.stack([good[0], good[0]]), 40) == (True, "")
+    for who in ("mcba_two_view_ransac", "mcba_two_view_ransac5"):
+        bad = good.copy()
+        bad[6, 7] = 40
+        assert samples_ok(hc, who, bad, 40) == (False, who + ": a sample index is outside 0 .. n_points - 1")
+        bad[6, 7] = -1
+        assert samples_ok(hc, who, bad, 40) == (False, who + ": a sample index is outside 0 .. n_points - 1")
+        bad[6, 7] = bad[6, 0]
+        assert samples_ok(hc, who, bad, 40) == (False, who + ": an index is repeated within a sample")
 
 
 def test_stand_alone_program_under_sanitizers(tmp_path):

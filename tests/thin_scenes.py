@@ -5,7 +5,7 @@ import numpy as np
 
 import multicam_calibration_amd as m
 
-# name -> (C, P, seed, noise in px, zs in mm).  "thin3_1025": one point past a workgroup of k_tv_score (1024 + 1)
+# name -> (C, P, seed, noise in px, zs in mm).  "thin3_1025": one point past a workgroup of the scorer (1024 + 1)
 SCENES = {"thin3": (3, 200, 13, 0.3, 5.0), "thin6": (6, 300, 16, 0.3, 5.0), "thin3_1025": (3, 1025, 13, 0.3, 5.0)}
 
 
