@@ -861,6 +861,41 @@ int mcba_smooth_trajectories(size_t n_frames, int n_tracks, const double* points
 int mcba_smooth_covariance(size_t n_frames, int n_tracks, const double* points, const double* cov6, const double* accel_std, const double* weights, int segment, int device,
                            double* out_cov6, double* out_lag9, int* status, int* n_usable, double* info8, double* kernel_ms);
 
+/* ---- Trajectory refinement (Python: trajectory.refine_trajectories).  Stateless, additive to ABI 7.  Per track k of
+ * n_tracks (tracks are independent), frames t = 0 .. T - 1, unknowns x_t in R^3:
+ *   minimise 0.5 sum_t sum_{c sees (t,k)} f^2 [rho(ru^2 / f^2) + rho(rv^2 / f^2)] + 0.5 / a_k^2 sum_{t=1}^{T-2} |x_{t-1} - 2 x_t + x_{t+1}|^2,
+ *   (ru, rv) = sqrt(w_ctk) (detection - projection_c(x_t)) / pixel_std_c
+ * uvs (C, T, K, 2) raw detections (NaN = unseen), cam12 (C, 12), dist5 (C, 5) or NULL: the cameras of mcba_triangulate_refine (the
+ * five-coefficient forward model), 1 <= C <= 64; weights (C, T, K) or NULL = 1: finite and >= 0, a zero or NaN weight = unseen; pixel_std (C)
+ * positive; start (T, K, 3); accel_std (K) = a; loss 0 linear, 1 soft_l1, 2 huber (scipy's rho), f = f_scale in units of pixel_std.
+ * A frame is usable when two cameras or more see it, single when exactly one does.  A track runs when it has two usable frames or more and a
+ * finite start.  Gauss-Newton in step form: per iteration one linearisation (H_t with the curvature weights of mcba_triangulate_refine, the
+ * gradient G of the whole objective), one solve (blockdiag(H_t) + a^-2 D2^T D2 (x) I3) d = -G by the elimination of mcba_smooth_trajectories
+ * (`segment` as there), one evaluation of the objective at x + alpha d for alpha = 1, 1/2, 1/4, 1/8, and one small download: the largest alpha
+ * whose objective is not above the current one is taken (none: the track stops where it is, alpha 0), and the track stops when
+ * alpha max |d| < xtol max |x| or after max_iterations >= 1.  The objective never rises.
+ * out_points (T, K, 3), information (T, K, 6) = H_t at the returned points packed 00 01 02 11 12 22; status (K): 1 ok, -1 fewer than two usable
+ * frames, -2 a refused 6 x 6 pivot, -3 a non-finite start (-1 and -3: never launched); every track whose status is not 1 is NaN throughout.
+ * n_usable, n_single, n_iterations (K); cost (K) the objective at the result; history (max_iterations, K, 3) = the objective after the
+ * iteration, the accepted step alpha max |d|, alpha; NaN where a track no longer ran.  out_cov6 (T, K, 6) and out_lag9 (T - 1, K, 9), both or
+ * the second may be NULL: Z_tt and Z_{t,t+1} of the inverse of the Gauss-Newton matrix at the returned points, as mcba_smooth_covariance
+ * lays them out -- the covariance in units where pixel_std is the detection noise.  info8 = {levels, segment, tracks per chunk, chunks, kernel
+ * ms, most iterations of a track, device bytes of a chunk, kernel ms of the covariance alone}; chunks as in mcba_smooth_trajectories
+ * (MCBA_SMOOTH_BUDGET_MB).  No atomics: two calls return the same bits, whatever the chunking.  MCBA_ERR_ARG, checked before any device is
+ * touched and with nothing written: n_frames == 0 or above 2^31, n_tracks < 1, n_cameras outside 1 .. 64, a NULL array other than dist5,
+ * weights, out_cov6, out_lag9, kernel_ms (out_lag9 without out_cov6), a loss outside 0 .. 2, f_scale, a pixel_std or an accel_std not positive
+ * and finite, a negative or infinite weight, max_iterations < 1, xtol < 0, segment outside {0, 2 .. 64}. */
+int mcba_refine_trajectories(size_t n_frames, int n_tracks, int n_cameras, const double* uvs, const double* cam12, const double* dist5, const double* weights, const double* pixel_std,
+                             const double* start, const double* accel_std, int loss, double f_scale, int max_iterations, double xtol, int segment, int device, double* out_points,
+                             double* information, int* status, int* n_usable, int* n_single, int* n_iterations, double* cost, double* history, double* out_cov6, double* out_lag9, double* info8,
+                             double* kernel_ms);
+/* One evaluation of that loop laid open, at `points` and before anything is accepted: information (T, K, 6) = H, gradient (T, K, 3) = G,
+ * step (T, K, 3) = d, data_cost and penalty_cost (K) = the two terms of the objective at the points, trial_costs (K, 4) = the objective at
+ * x + alpha d for alpha = 1, 1/2, 1/4, 1/8; status, n_usable, n_single as above.  Arguments, errors and info8 as above. */
+int mcba_refine_trajectories_system(size_t n_frames, int n_tracks, int n_cameras, const double* uvs, const double* cam12, const double* dist5, const double* weights, const double* pixel_std,
+                                    const double* points, const double* accel_std, int loss, double f_scale, int segment, int device, double* information, double* gradient, double* step,
+                                    int* status, int* n_usable, int* n_single, double* data_cost, double* penalty_cost, double* trial_costs, double* info8, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

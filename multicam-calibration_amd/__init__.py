@@ -23,7 +23,8 @@ Only what the hot path needs lives here:
              weights: a detection of weight w enters the cost as if it and fx, fy, cx, cy of its camera were multiplied by sqrt(w)) -- SURVEY.md section 8f-13
   trajectory.py  smooth_trajectories (the fixed-interval smoother of keypoint tracks: gaps filled, every frame trusted as its covariance says,
              gross errors discounted by a robust loss) -- SURVEY.md section 8f-19; trajectory_uncertainty (the covariance of every
-             smoothed point and of neighbouring frames, by selected inversion) -- section 8f-20
+             smoothed point and of neighbouring frames, by selected inversion) -- section 8f-20; refine_trajectories (the tracks refined on
+             the raw detections: Gauss-Newton on the reprojection cost plus the smoothness prior, single-camera frames used) -- section 8f-21
   synth.py   deterministic synthetic board detections for tests and bench
 """
 from . import synth  # noqa: F401
@@ -43,6 +44,7 @@ from .detection import detect_chessboard, detect_chessboards, reorder_chessboard
 from .uncertainty import calibration_uncertainty, CalibrationUncertainty, triangulation_uncertainty, TriangulationUncertainty  # noqa: F401
 from . import trajectory  # noqa: F401
 from .trajectory import smooth_trajectories, TrajectorySmoothing, trajectory_uncertainty, TrajectoryUncertainty  # noqa: F401
+from .trajectory import refine_trajectories, refine_trajectories_system, TrajectoryRefinement, TrajectoryRefinementSystem, TRAJECTORY_REFINE_STATUS  # noqa: F401
 from .calibration import calibrate, get_intrinsics, estimate_pose, estimate_all_extrinsics, consensus_calib_poses, get_camera_spanning_tree, estimate_pairwise_camera_transform  # noqa: F401
 
 __all__ = ["bundle_adjust", "bundle_adjustment", "serialize_params", "deserialize_params", "ops", "solver", "synth", "calibration", "calibrate", "triangulate", "get_intrinsics",
@@ -54,4 +56,5 @@ __all__ = ["bundle_adjust", "bundle_adjustment", "serialize_params", "deserializ
            "resect_camera", "resect_cameras", "CameraResection", "draw_resection_samples",
            "rodrigues", "rodrigues_inv", "get_transformation_matrix", "get_transformation_vector", "get_projection_matrix", "euclidean_to_homogenous", "homogeneous_to_euclidean",
            "calibration_uncertainty", "CalibrationUncertainty", "triangulation_uncertainty", "TriangulationUncertainty",
-           "trajectory", "smooth_trajectories", "TrajectorySmoothing", "trajectory_uncertainty", "TrajectoryUncertainty"]
+           "trajectory", "smooth_trajectories", "TrajectorySmoothing", "trajectory_uncertainty", "TrajectoryUncertainty",
+           "refine_trajectories", "refine_trajectories_system", "TrajectoryRefinement", "TrajectoryRefinementSystem", "TRAJECTORY_REFINE_STATUS"]

@@ -358,13 +358,27 @@ struct SmData;
 // p, winv, w from the raw points, packed covariances and start weights (w_in NULL: 1); n_usable (K)
 void launch_smooth_prepare(hipStream_t st, size_t T, int K, const double* pts, const double* cov6, const double* w_in, double* p, double* winv, double* w, int* n_usable);
 // the elimination alone, every level up, of the nact tracks of list; bad (K) is set to 1 where a pivot was refused
-int launch_smooth_reduce(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad);
+int launch_smooth_reduce(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad, bool rhs = false);
+// the back-substitution alone, every level down.  rhs (both): level 0 in the right-hand-side mode of mcba_smooth_math.h (SmData::rhs)
+int launch_smooth_backsub(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, bool rhs = false);
 // one linear solve (launch_smooth_reduce, then every level down) of the nact tracks of list, then res (nact, 4) = objective, step, max |x|, 0
 int launch_smooth_solve(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad, double* part, double* res);
 
 // ---- trajectory uncertainty (mcba_smooth_cov.hip).  After launch_smooth_reduce: the selected inversion, every level
 // down: z[l] = the SM_ZC planes of level l >= 1 (mcba_smooth_cov_math.h), cov6 (T, K, 6), lag9 (T - 1, K, 9) or null
 int launch_smooth_selinv(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, double* const* z, double* cov6, double* lag9, int K, const int* list, int nact);
+
+// ---- trajectory refinement (mcba_traj_refine.hip).  TrData: mcba_traj_refine_math.h, the planes of a chunk of K tracks;
+// cams: a KpCam table in device memory, 1 <= C <= kKpMaxCams; loss: linear, soft_l1 or huber.  Non-zero: arguments out of range
+struct TrData;
+// per track its usable frames (two cameras or more), its single ones (exactly one) and the non-finite coordinates of its start (K each)
+int launch_traj_count(hipStream_t st, const TrData& rd, int C, int K, int* n_usable, int* n_single, int* n_bad);
+// H and G at x for the tracks with run[k] != 0
+int launch_traj_linearise(hipStream_t st, int loss, const TrData& rd, const KpCam* cams, int C, int K, const int* run);
+// res (nact, TR_SUMS) of the nact tracks of list from x and d; part: TR_SUMS smooth_eval_blocks(T) nact doubles of scratch
+int launch_traj_trial(hipStream_t st, int loss, const TrData& rd, const KpCam* cams, int C, int K, const int* list, int nact, double* part, double* res);
+// x <- x + alpha[k] d for every track of the chunk (alpha 0: untouched)
+int launch_traj_apply(hipStream_t st, const TrData& rd, int K, const double* alpha);
 
 // ---- free-point bundle adjustment of the extrinsics (mcba_kpba.hip).  uvs (C, P, 2) raw detections (NaN = unseen), pts
 // (P, 3), cams: TcCam table in device memory, 2 <= C <= 24, held (C): bit i = scalar i of the camera is not free.  Non-zero: arguments out of range.

@@ -43,18 +43,18 @@ __global__ __launch_bounds__(256) void k_smooth_count(size_t T, int K, const dou
 
 // lane -> (segment q, position kk in the list of running tracks), tracks fastest.  No launch bound beyond the workgroup size: the lane's
 // state is about 150 doubles and wants the whole register file
-template <bool LEVEL0>
+template <bool LEVEL0, bool RHS = false>
 __global__ __launch_bounds__(64) void k_smooth_reduce(SmLevel lv, SmLevel nx, SmData td, int K, const int* __restrict__ list, int nact, int nq, int* __restrict__ bad) {
   const size_t gid = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (gid >= (size_t)nq * nact) return;
-  smooth_reduce_lane<LEVEL0>(lv, nx, td, K, list[gid % nact], (int)(gid / nact), bad);
+  smooth_reduce_lane<LEVEL0, RHS>(lv, nx, td, K, list[gid % nact], (int)(gid / nact), bad);
 }
 
-template <bool LEVEL0>
+template <bool LEVEL0, bool RHS = false>
 __global__ __launch_bounds__(64) void k_smooth_backsub(SmLevel lv, SmLevel up, SmData td, int K, const int* __restrict__ list, int nact, int nq) {
   const size_t gid = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (gid >= (size_t)nq * nact) return;
-  smooth_backsub_lane<LEVEL0>(lv, up, td, K, list[gid % nact], (int)(gid / nact));
+  smooth_backsub_lane<LEVEL0, RHS>(lv, up, td, K, list[gid % nact], (int)(gid / nact));
 }
 
 __global__ __launch_bounds__(256) void k_smooth_eval(SmData td, int K, const int* __restrict__ list, int nblk, double* __restrict__ part) {
@@ -94,7 +94,8 @@ void launch_smooth_prepare(hipStream_t st, size_t T, int K, const double* pts, c
 }
 
 // the elimination of the nact running tracks of `list` (positions in the chunk of K tracks), every level up: the factors stay in lv[.].fac, lv[.].sep
-int launch_smooth_reduce(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad) {
+// rhs: level 0 in the right-hand-side mode (SmData::rhs)
+int launch_smooth_reduce(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad, bool rhs) {
   if (levels < 1 || levels > SM_MAX_LEVELS || nact < 1 || nact > K) return 1;
   const SmLevel none{};
   for (int l = 0; l < levels; ++l) {
@@ -102,8 +103,25 @@ int launch_smooth_reduce(hipStream_t st, const SmLevel* lv, int levels, const Sm
     unsigned blocks;
     if (!smooth_grid(lv[l], nact, nq, blocks)) return 1;
     const SmLevel& nx = l + 1 < levels ? lv[l + 1] : none;
-    if (l == 0) k_smooth_reduce<true><<<dim3(blocks), dim3(64), 0, st>>>(lv[0], nx, td, K, list, nact, nq, bad);
+    if (l == 0 && rhs) k_smooth_reduce<true, true><<<dim3(blocks), dim3(64), 0, st>>>(lv[0], nx, td, K, list, nact, nq, bad);
+    else if (l == 0) k_smooth_reduce<true><<<dim3(blocks), dim3(64), 0, st>>>(lv[0], nx, td, K, list, nact, nq, bad);
     else k_smooth_reduce<false><<<dim3(blocks), dim3(64), 0, st>>>(lv[l], nx, td, K, list, nact, nq, bad);
+  }
+  return 0;
+}
+
+// the back-substitution after launch_smooth_reduce, every level down; rhs as there (level 0 then writes the solution alone)
+int launch_smooth_backsub(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, bool rhs) {
+  if (levels < 1 || levels > SM_MAX_LEVELS || nact < 1 || nact > K) return 1;
+  const SmLevel none{};
+  for (int l = levels - 1; l >= 0; --l) {
+    int nq;
+    unsigned blocks;
+    if (!smooth_grid(lv[l], nact, nq, blocks)) return 1;
+    const SmLevel& up = l + 1 < levels ? lv[l + 1] : none;
+    if (l == 0 && rhs) k_smooth_backsub<true, true><<<dim3(blocks), dim3(64), 0, st>>>(lv[0], up, td, K, list, nact, nq);
+    else if (l == 0) k_smooth_backsub<true><<<dim3(blocks), dim3(64), 0, st>>>(lv[0], up, td, K, list, nact, nq);
+    else k_smooth_backsub<false><<<dim3(blocks), dim3(64), 0, st>>>(lv[l], up, td, K, list, nact, nq);
   }
   return 0;
 }
@@ -111,15 +129,7 @@ int launch_smooth_reduce(hipStream_t st, const SmLevel* lv, int levels, const Sm
 // one linear solve of the nact running tracks of `list`, then their sums: res (nact, 4)
 int launch_smooth_solve(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad, double* part, double* res) {
   if (launch_smooth_reduce(st, lv, levels, td, K, list, nact, bad)) return 1;
-  const SmLevel none{};
-  for (int l = levels - 1; l >= 0; --l) {
-    int nq;
-    unsigned blocks;
-    if (!smooth_grid(lv[l], nact, nq, blocks)) return 1;
-    const SmLevel& up = l + 1 < levels ? lv[l + 1] : none;
-    if (l == 0) k_smooth_backsub<true><<<dim3(blocks), dim3(64), 0, st>>>(lv[0], up, td, K, list, nact, nq);
-    else k_smooth_backsub<false><<<dim3(blocks), dim3(64), 0, st>>>(lv[l], up, td, K, list, nact, nq);
-  }
+  if (launch_smooth_backsub(st, lv, levels, td, K, list, nact)) return 1;
   const int nblk = smooth_eval_blocks(td.T);
   if ((size_t)nblk * nact > 0x7fffffffu) return 1;
   k_smooth_eval<<<dim3((unsigned)(nblk * nact)), dim3(256), 0, st>>>(td, K, list, nblk, part);

@@ -22,7 +22,10 @@ inline int smooth_check_common(const char* who, const char* weights_name, size_t
   return MCBA_OK;
 }
 
-// One call's walk over its chunks.  setup() once, then per chunk c < nchunks: begin(c), the entry's own launches on list, scatter() per output
+// One call's walk over its chunks.  setup() once, then per chunk c < nchunks: begin(c), the entry's own launches on list, scatter() per output.
+// What every trajectory call shares is setup_shared() / begin_shared(): the budget and the chunk width, the levels, 1 / a^2, the list, d_bad, the
+// events.  setup() / begin() add the data planes of the two calls that take points and covariances (upload, prepare, count); a call with data
+// planes of its own (mcba_traj_refine_api.hip) uses the shared pair and fills h_list itself
 struct SmoothChunks {
   StatelessCall call;        // every device buffer of the call, and the events e0, e1 around its launches
   hipEvent_t e2 = nullptr;   // a third event for a call that times a part of its bracket: created by that call, released here
@@ -47,18 +50,11 @@ struct SmoothChunks {
 
   // per_track: the device doubles one track takes (the entry's *_chunk_doubles at K = 1); extra: doubles per separator node beyond fac and sep.
   // The buffers are sized for the widest chunk: a narrower last one re-plans its levels inside them
-  int setup(const char* who_, size_t T_, size_t K_, int segment_, const double* points_, const double* cov6_, const double* accel_std_, const double* weights_, size_t per_track, int extra_) {
-    who = who_; T = T_; K = K_; segment = segment_; points = points_; cov6 = cov6_; accel_std = accel_std_; weights = weights_; extra = extra_;
+  int setup_shared(const char* who_, size_t T_, size_t K_, int segment_, const double* accel_std_, size_t per_track, int extra_) {
+    who = who_; T = T_; K = K_; segment = segment_; accel_std = accel_std_; extra = extra_;
     double budget_mb = 8192.0;
     if (const char* e = getenv("MCBA_SMOOTH_BUDGET_MB")) { const double v = atof(e); if (v > 0.0) budget_mb = v; }
     Kc = mcba::smooth_chunk_tracks(budget_mb * 1048576.0, per_track, K, nchunks);
-    const size_t TK = T * Kc;
-    if (int rc = call.scratch(&d_pts, 3 * TK)) return rc;
-    if (int rc = call.scratch(&d_cov, 6 * TK)) return rc;
-    if (weights) if (int rc = call.scratch(&d_win, TK)) return rc;
-    if (int rc = call.scratch(&d_p, 3 * TK)) return rc;
-    if (int rc = call.scratch(&d_winv, 6 * TK)) return rc;
-    if (int rc = call.scratch(&d_w, TK)) return rc;
     if (int rc = call.scratch(&d_ia2, (size_t)Kc)) return rc;
     if (int rc = call.scratch(&d_nus, (size_t)Kc)) return rc;
     if (int rc = call.scratch(&d_list, (size_t)Kc)) return rc;
@@ -68,6 +64,18 @@ struct SmoothChunks {
     if (int rc = call.scratch(&d_lev, lev_doubles)) return rc;
     HIPCHK(hipEventCreate(&call.e0));
     HIPCHK(hipEventCreate(&call.e1));
+    return MCBA_OK;
+  }
+  int setup(const char* who_, size_t T_, size_t K_, int segment_, const double* points_, const double* cov6_, const double* accel_std_, const double* weights_, size_t per_track, int extra_) {
+    points = points_; cov6 = cov6_; weights = weights_;
+    if (int rc = setup_shared(who_, T_, K_, segment_, accel_std_, per_track, extra_)) return rc;
+    const size_t TK = T * Kc;
+    if (int rc = call.scratch(&d_pts, 3 * TK)) return rc;
+    if (int rc = call.scratch(&d_cov, 6 * TK)) return rc;
+    if (weights) if (int rc = call.scratch(&d_win, TK)) return rc;
+    if (int rc = call.scratch(&d_p, 3 * TK)) return rc;
+    if (int rc = call.scratch(&d_winv, 6 * TK)) return rc;
+    if (int rc = call.scratch(&d_w, TK)) return rc;
     return MCBA_OK;
   }
 
@@ -81,11 +89,21 @@ struct SmoothChunks {
 
   int tracks_of(int c) const { return (int)std::min<size_t>(Kc, K - (size_t)c * Kc); }   // (the last chunk may be narrower)
 
-  int begin(int c) {
+  // the chunk's tracks, its levels, 1 / a^2 on the device, d_bad cleared
+  int begin_shared(int c) {
     k0 = (size_t)c * Kc;
     kc = tracks_of(c);
     tk = T * kc;
     mcba::smooth_carve(T, segment, kc, lv, extra, d_lev, aux, &levels);
+    h_ia2.resize(kc);
+    for (int k = 0; k < kc; ++k) h_ia2[k] = 1.0 / (accel_std[k0 + k] * accel_std[k0 + k]);
+    if (int rc = call.put(d_ia2, h_ia2.data(), (size_t)kc)) return rc;
+    HIPCHK(hipMemset(d_bad, 0, kc * sizeof(int)));
+    return MCBA_OK;
+  }
+
+  int begin(int c) {
+    if (int rc = begin_shared(c)) return rc;
     // gather the chunk's tracks (all of them: the arrays as they are)
     const double *s_pts = points, *s_cov = cov6, *s_win = weights;
     if (kc != (int)K) {
@@ -98,13 +116,9 @@ struct SmoothChunks {
       }
       s_pts = h_pts.data(); s_cov = h_cov.data(); s_win = weights ? h_win.data() : nullptr;
     }
-    h_ia2.resize(kc);
-    for (int k = 0; k < kc; ++k) h_ia2[k] = 1.0 / (accel_std[k0 + k] * accel_std[k0 + k]);
     if (int rc = call.put(d_pts, s_pts, 3 * tk)) return rc;
     if (int rc = call.put(d_cov, s_cov, 6 * tk)) return rc;
     if (s_win) if (int rc = call.put(d_win, s_win, tk)) return rc;
-    if (int rc = call.put(d_ia2, h_ia2.data(), (size_t)kc)) return rc;
-    HIPCHK(hipMemset(d_bad, 0, kc * sizeof(int)));
     td = mcba::SmData{T, d_p, d_winv, d_w, d_ia2, nullptr, nullptr, nullptr, mcba::SM_LOSS_LINEAR, 1.0, 1.0};
     HIPCHK(hipEventRecord(call.e0, nullptr));
     mcba::launch_smooth_prepare(nullptr, T, kc, d_pts, d_cov, s_win ? d_win : nullptr, d_p, d_winv, d_w, d_nus);

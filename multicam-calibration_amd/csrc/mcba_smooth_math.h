@@ -51,6 +51,9 @@ struct SmData {
   double* dx;           // (T, K): max |x_new - x_old| of the frame's three coordinates
   int loss;
   double f2, inv_f2;    // f_scale^2 and its reciprocal
+  // the right-hand-side mode of level 0 (RHS: mcba_traj_refine_math.h): winv is then the packed diagonal block itself (weight 1, w unread), the
+  // right-hand side is -rhs, and the solution goes to x and nowhere else
+  const double* rhs;    // (T, K, 3): the gradient the solve steps against
 };
 
 MCBA_HD bool sm_finite(double v) { return v - v == 0.0; }
@@ -221,7 +224,7 @@ MCBA_HD void sm_e0_scalars(const SmData& td, int k, long long j, double& e00, do
 }
 
 // ---- block j of a level: D (21), r (6), E (36: the coupling to block j - 1, zero for j = 0)
-template <bool LEVEL0>
+template <bool LEVEL0, bool RHS = false>
 MCBA_HD void smooth_load(const SmLevel& lv, const SmData& td, int K, int k, long long j, double* D, double* r, double* E) {
   if (LEVEL0) {
     const double ia2 = td.ia2[k];
@@ -234,18 +237,23 @@ MCBA_HD void smooth_load(const SmLevel& lv, const SmData& td, int K, int k, long
       const long long t = 2 * j + f;
       if ((size_t)t < td.T) {
         const size_t idx = (size_t)t * K + k;
-        const double w = td.w[idx];
         double wi[6], p[3];
+        if (RHS) {
 #pragma unroll
-        for (int e = 0; e < 6; ++e) wi[e] = w * td.winv[6 * idx + e];
+          for (int e = 0; e < 6; ++e) wi[e] = td.winv[6 * idx + e];
+        } else {
+          const double w = td.w[idx];
 #pragma unroll
-        for (int e = 0; e < 3; ++e) p[e] = td.p[3 * idx + e];
+          for (int e = 0; e < 6; ++e) wi[e] = w * td.winv[6 * idx + e];
+#pragma unroll
+          for (int e = 0; e < 3; ++e) p[e] = td.p[3 * idx + e];
+        }
         const double pd = ia2 * sm_pen_diag(t, td.T);
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
 #pragma unroll
           for (int b = 0; b <= a; ++b) D[sm_tri(3 * f + a, 3 * f + b)] = sym3(wi, a, b) + (a == b ? pd : 0.0);
-          r[3 * f + a] = fma(sym3(wi, a, 0), p[0], fma(sym3(wi, a, 1), p[1], sym3(wi, a, 2) * p[2]));
+          r[3 * f + a] = RHS ? -td.rhs[3 * idx + a] : fma(sym3(wi, a, 0), p[0], fma(sym3(wi, a, 1), p[1], sym3(wi, a, 2) * p[2]));
         }
       } else {   // the phantom frame of an odd T
 #pragma unroll
@@ -271,7 +279,7 @@ MCBA_HD void smooth_load(const SmLevel& lv, const SmData& td, int K, int k, long
 }
 
 // ---- reduce: segment q of track k on level lv; nx = the next level (untouched on the last one).  bad[k] = 1 on a refused pivot
-template <bool LEVEL0>
+template <bool LEVEL0, bool RHS = false>
 MCBA_HD void smooth_reduce_lane(const SmLevel& lv, const SmLevel& nx, const SmData& td, int K, int k, int q, int* bad) {
   const int m = lv.m, n = lv.n;
   const long long j0 = (long long)q * (m + 1);
@@ -282,7 +290,7 @@ MCBA_HD void smooth_reduce_lane(const SmLevel& lv, const SmLevel& nx, const SmDa
   for (int e = 0; e < 27; ++e) CL[e] = 0.0;
   if (len > 0) {
     double D[21], g[6], G[36], E[36];
-    smooth_load<LEVEL0>(lv, td, K, k, j0, D, g, E);
+    smooth_load<LEVEL0, RHS>(lv, td, K, k, j0, D, g, E);
 #pragma unroll
     for (int e = 0; e < 36; ++e) G[e] = hasL ? E[e] : 0.0;
     bool isbad = false;
@@ -318,7 +326,7 @@ MCBA_HD void smooth_reduce_lane(const SmLevel& lv, const SmLevel& nx, const SmDa
       const long long jn = j0 + i + 1;
       if (jn < n) {
         double rn[6];
-        smooth_load<LEVEL0>(lv, td, K, k, jn, D, rn, E);
+        smooth_load<LEVEL0, RHS>(lv, td, K, k, jn, D, rn, E);
         double Et[36];   // L^-1 E^T
 #pragma unroll
         for (int r = 0; r < 6; ++r) {
@@ -377,9 +385,18 @@ MCBA_HD void smooth_reduce_lane(const SmLevel& lv, const SmLevel& nx, const SmDa
 }
 
 // ---- the solution of block j: levels >= 1 keep it in lv.x; level 0 writes the frames' x, dx, d2 and the new weights
-template <bool LEVEL0>
+template <bool LEVEL0, bool RHS = false>
 MCBA_HD void smooth_store_x(const SmLevel& lv, const SmData& td, int K, int k, long long j, const double* x) {
-  if (LEVEL0) {
+  if (LEVEL0 && RHS) {
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+      const long long t = 2 * j + f;
+      if ((size_t)t >= td.T) continue;
+      const size_t idx = (size_t)t * K + k;
+#pragma unroll
+      for (int e = 0; e < 3; ++e) td.x[3 * idx + e] = x[3 * f + e];
+    }
+  } else if (LEVEL0) {
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
       const long long t = 2 * j + f;
@@ -411,7 +428,7 @@ MCBA_HD void smooth_store_x(const SmLevel& lv, const SmData& td, int K, int k, l
 }
 
 // ---- back-substitution: segment q of track k on level lv; up = the level above (the solution of this level's separators)
-template <bool LEVEL0>
+template <bool LEVEL0, bool RHS = false>
 MCBA_HD void smooth_backsub_lane(const SmLevel& lv, const SmLevel& up, const SmData& td, int K, int k, int q) {
   const int m = lv.m, n = lv.n;
   const long long j0 = (long long)q * (m + 1);
@@ -430,7 +447,7 @@ MCBA_HD void smooth_backsub_lane(const SmLevel& lv, const SmLevel& up, const SmD
     const size_t nd = sm_node(up, q, K, k);
 #pragma unroll
     for (int e = 0; e < 6; ++e) xn[e] = up.x[(size_t)e * up.NS + nd];
-    smooth_store_x<LEVEL0>(lv, td, K, k, j0 + m, xn);
+    smooth_store_x<LEVEL0, RHS>(lv, td, K, k, j0 + m, xn);
   }
   for (int i = len - 1; i >= 0; --i) {
     const long long j = j0 + i;
@@ -469,7 +486,7 @@ MCBA_HD void smooth_backsub_lane(const SmLevel& lv, const SmLevel& up, const SmD
       for (int e = 0; e < 6; ++e) v[e] -= u[e];
     }
     sm_bwd6(L, v);
-    smooth_store_x<LEVEL0>(lv, td, K, k, j, v);
+    smooth_store_x<LEVEL0, RHS>(lv, td, K, k, j, v);
 #pragma unroll
     for (int e = 0; e < 6; ++e) xn[e] = v[e];
   }

@@ -157,6 +157,11 @@ SYMBOLS = [
                                                 _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     # trajectory uncertainty: every array by address; weights and out_lag9 may be NULL
     ("mcba_smooth_covariance", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    # trajectory refinement: every array by address; dist5, weights, out_cov6, out_lag9 may be NULL
+    ("mcba_refine_trajectories", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double,
+                                                ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    ("mcba_refine_trajectories_system", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                                       _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("mcba_profile_enable", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_stride", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_read", ctypes.c_int, [_h, _dp, _ip, ctypes.c_int, _ip]),

@@ -1,6 +1,7 @@
 """smooth_trajectories -- the fixed-interval smoother of keypoint tracks: T frames x K keypoints of triangulated points and their per-frame
 covariances in, gap-free tracks out; trajectory_uncertainty -- the covariance of every smoothed point and, on request,
-of neighbouring frames (section 8f-20).  It fills the frames fewer than two cameras saw, trusts each frame exactly as much
+of neighbouring frames (section 8f-20); refine_trajectories -- the same tracks refined on the raw detections, the maximum-likelihood fit of what
+was measured (section 8f-21).  The smoother fills the frames fewer than two cameras saw, trusts each frame exactly as much
 as `triangulation_uncertainty` says, and with a robust loss discounts gross triangulation errors.
 
 The reference has no counterpart (its flatibration tutorial loads keypoints that an outside tool smoothed in time).  Everything runs on the GPU:
@@ -11,8 +12,10 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import ops
+from .triangulation import _cam_blocks
 
 TRAJECTORY_STATUS = {1: "ok", -1: "fewer than two usable frames", -2: "a block pivot below the threshold"}
+TRAJECTORY_REFINE_STATUS = {1: "ok", -1: "fewer than two usable frames", -2: "a block pivot below the threshold", -3: "a non-finite start"}
 LOSSES = {"linear": 0, "soft_l1": 1, "huber": 2}
 SEGMENT_MIN, SEGMENT_MAX = 2, 64
 
@@ -204,3 +207,162 @@ def _uncertainty(pts, cov6, acc, win, lag, segment, device):
     with np.errstate(invalid="ignore"):
         std = np.sqrt(full[..., (0, 1, 2), (0, 1, 2)])
     return TrajectoryUncertainty(covariance=full, std=std, lag_covariance=None if l9 is None else l9.reshape(T - 1, K, 3, 3), status=status, n_usable=nus, info=_info(info))
+
+
+@dataclass
+class TrajectoryRefinement:
+    points: np.ndarray        # (T, K, 3): every frame filled for a track of status 1, NaN otherwise
+    information: np.ndarray   # (T, K, 3, 3): H_t, the Gauss-Newton matrix of the frame's detections at the result (rank 2 on a single frame, 0 on an unseen one)
+    status: np.ndarray        # (K,): a key of TRAJECTORY_REFINE_STATUS
+    n_usable: np.ndarray      # (K,): frames two cameras or more see
+    n_single: np.ndarray      # (K,): frames exactly one camera sees
+    n_iterations: np.ndarray  # (K,): linear solves done
+    cost: np.ndarray          # (K,): the objective at the result, NaN unless the status is 1
+    history: np.ndarray       # (iterations, K, 3): per iteration the objective after it, the accepted step alpha max |d| and alpha; NaN where a track no longer ran
+    info: dict                # kernel_ms, levels, segment, tracks_per_chunk, chunks, device_bytes
+    covariance: np.ndarray = None      # uncertainty=True or "lag": (T, K, 3, 3), Z_tt of the inverse of the Gauss-Newton matrix at the result
+    std: np.ndarray = None             # ... and the square roots of its diagonal
+    lag_covariance: np.ndarray = None  # uncertainty="lag": (T - 1, K, 3, 3), Z_{t,t+1}, rows of frame t
+
+
+@dataclass
+class TrajectoryRefinementSystem:
+    information: np.ndarray   # (T, K, 3, 3): H_t at the given points
+    gradient: np.ndarray      # (T, K, 3): G, the gradient of the whole objective
+    step: np.ndarray          # (T, K, 3): d, the solution of (blockdiag(H) + a^-2 D2^T D2 (x) I3) d = -G
+    data_cost: np.ndarray     # (K,): the data term of the objective at the points
+    penalty_cost: np.ndarray  # (K,): its smoothness term
+    trial_costs: np.ndarray   # (K, 4): the objective at x + alpha d, alpha = 1, 1/2, 1/4, 1/8
+    status: np.ndarray        # (K,): a key of TRAJECTORY_REFINE_STATUS
+    n_usable: np.ndarray      # (K,)
+    n_single: np.ndarray      # (K,)
+    info: dict                # as TrajectoryRefinement.info
+
+
+def _refine_arguments(start, all_uvs, all_extrinsics, all_intrinsics, accel_std, pixel_std, loss, f_scale, weights, segment):
+    """the checked arrays both refinement calls take: start (T, K, 3), uvs (C, T, K, 2), cam (C, 12), dist (C, 5), acc (K,), pstd (C,), w (C, T, K) or None"""
+    if callable(loss) or loss not in LOSSES:
+        if loss in ("cauchy", "arctan"):
+            raise ValueError(f"refine_trajectories: loss {loss!r} is not convex -- the backtracking Gauss-Newton loop is for linear, soft_l1 and huber")
+        raise ValueError(f"loss must be one of {sorted(LOSSES)}")
+    pts = np.ascontiguousarray(start, dtype=np.float64)
+    if pts.ndim != 3 or pts.shape[2] != 3:
+        raise ValueError("start must be (T, K, 3)")
+    T, K = pts.shape[:2]
+    if T == 0 or K == 0:
+        raise ValueError("start must hold at least one frame and one track")
+    if len(all_extrinsics) != len(all_intrinsics) or len(all_extrinsics) < 1:
+        raise ValueError("one (camera_matrix, dist_coefs) per entry of all_extrinsics, at least one camera")
+    C = len(all_extrinsics)
+    if C > 64:
+        raise ValueError("refine_trajectories supports at most 64 cameras")
+    if len(all_uvs) != C:
+        raise ValueError(f"all_uvs must be ({C}, {T}, {K}, 2), or a list of {C} arrays ({T}, {K}, 2)")
+    uvs = [np.asarray(u, dtype=np.float64) for u in all_uvs]
+    if any(u.shape != (T, K, 2) for u in uvs):
+        raise ValueError(f"all_uvs must be ({C}, {T}, {K}, 2), or a list of {C} arrays ({T}, {K}, 2)")
+    uvs = np.ascontiguousarray(np.stack(uvs))
+    cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
+    acc = np.asarray(accel_std, dtype=np.float64)
+    if acc.shape not in ((), (K,)):
+        raise ValueError(f"accel_std must be a scalar or ({K},)")
+    acc = np.ascontiguousarray(np.broadcast_to(acc, (K,)))
+    pstd = np.asarray(pixel_std, dtype=np.float64)
+    if pstd.shape not in ((), (C,)):
+        raise ValueError(f"pixel_std must be a scalar or ({C},)")
+    pstd = np.ascontiguousarray(np.broadcast_to(pstd, (C,)))
+    with np.errstate(over="ignore", divide="ignore"):
+        if not (np.isfinite(acc).all() and (acc > 0).all() and np.isfinite(1.0 / (acc * acc)).all()):
+            raise ValueError("accel_std must be positive and finite")
+        if not (np.isfinite(pstd).all() and (pstd > 0).all() and np.isfinite(1.0 / pstd).all()):
+            raise ValueError("pixel_std must be positive and finite")
+    if not (np.isfinite(f_scale) and f_scale > 0):
+        raise ValueError("`f_scale` must be positive.")
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (C, T, K):
+            raise ValueError(f"weights must be ({C}, {T}, {K}): one per camera, frame and track, got {w.shape}")
+        if (w < 0).any() or np.isinf(w).any():
+            raise ValueError("weights must be finite and not negative (0 or NaN: the detection is unseen)")
+    _check_segment(segment)
+    return pts, uvs, cam, dist, acc, pstd, w
+
+
+def refine_trajectories(start, all_uvs, all_extrinsics, all_intrinsics, *, accel_std, pixel_std=1.0, loss="linear", f_scale=3.0, weights=None, max_iterations=30, xtol=1e-8, segment=None,
+                        device=0, uncertainty=False):
+    """Refine K independent keypoint tracks of T frames on their raw detections.  Per track k, with unknowns x_t in
+    R^3, minimise
+
+        0.5 sum_t sum_{c sees (t,k)} f^2 [rho(ru^2 / f^2) + rho(rv^2 / f^2)] + 0.5 / a_k^2 sum_{t=1}^{T-2} |x_{t-1} - 2 x_t + x_{t+1}|^2,
+        (ru, rv) = sqrt(w_ctk) (detection - projection_c(x_t)) / pixel_std_c
+
+    start (T, K, 3): where the iteration begins -- the intended start is `smooth_trajectories(...).points`, which has every frame filled.
+    all_uvs (C, T, K, 2) or a list of C arrays (T, K, 2): raw detections, NaN = unseen.  all_extrinsics, all_intrinsics: the cameras as
+    `refine_triangulation` takes them (the five-coefficient forward model), at most 64.  accel_std: a, a scalar or (K,).  pixel_std: the
+    detection noise in pixels, a scalar or (C,).  loss: scipy's "linear", "soft_l1" or "huber" rho per scalar residual, f = f_scale in units
+    of pixel_std; "cauchy" and "arctan" are refused.  weights: None or (C, T, K) per-detection weights as `refine_triangulation` takes them
+    (0 or NaN: the detection is unseen).
+
+    A frame is usable when two cameras or more see it and single when exactly one does; a single frame still pins two of the point's three
+    coordinates, which the two-stage chain triangulate -> smooth_trajectories discards.  A track runs when it has at least two usable frames
+    (they pin the motions linear in time, the null space of the smoothness term) and its start is finite throughout.
+
+    Gauss-Newton in step form: per iteration one linearisation, one solve of the block-pentadiagonal system by the smoother's elimination
+    (`segment` as there), one evaluation of the objective at x + alpha d for alpha = 1, 1/2, 1/4, 1/8: the largest alpha whose objective is
+    not above the current one is taken (none: the track stops where it is, alpha = 0 in its history), and a track stops when
+    alpha max |d| < xtol max |x| or after max_iterations.  The objective never rises.  Two calls return the same bits, whatever the chunking.
+
+    status (TRAJECTORY_REFINE_STATUS): -1 fewer than two usable frames; -2 a refused 6 x 6 pivot; -3 a non-finite start.  Such a track is NaN
+    throughout; the others are unaffected.
+    uncertainty: True or "lag" -- covariance and std (and, for "lag", lag_covariance) are Z_tt (and Z_{t,t+1}) of the inverse of the
+    Gauss-Newton matrix blockdiag(H_t) + a^-2 D2^T D2 (x) I3 at the returned points: the covariance in units where pixel_std is the detection noise.
+
+    ValueError (before a device is touched): wrong shapes, T == 0 or K == 0, more than 64 cameras, accel_std, pixel_std or f_scale not positive
+    and finite, a loss outside the three, a negative or infinite weight, max_iterations < 1, xtol < 0, segment out of range, uncertainty not one
+    of False, True, "lag".  Without a GPU: ops.McbaError -- there is no host path."""
+    if not any(uncertainty is u for u in (False, True)) and uncertainty != "lag":
+        raise ValueError('uncertainty must be False, True or "lag"')
+    pts, uvs, cam, dist, acc, pstd, w = _refine_arguments(start, all_uvs, all_extrinsics, all_intrinsics, accel_std, pixel_std, loss, f_scale, weights, segment)
+    C, T, K = uvs.shape[:3]
+    max_iterations = int(max_iterations)
+    if max_iterations < 1:
+        raise ValueError("max_iterations must be at least 1")
+    if not xtol >= 0:
+        raise ValueError("xtol must not be negative")
+    out, h6 = np.empty((T, K, 3)), np.empty((T, K, 6))
+    status, nus, nsg, nit = (np.empty(K, np.int32) for _ in range(4))
+    cost, hist, info = np.empty(K), np.empty((max_iterations, K, 3)), np.zeros(8)
+    c6 = np.empty((T, K, 6)) if uncertainty is not False else None
+    l9 = np.empty((T - 1, K, 9)) if uncertainty == "lag" else None
+    ms = ctypes.c_double(0.0)
+    ops.call("mcba_refine_trajectories", T, K, C, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, None if w is None else w.ctypes.data, pstd.ctypes.data, pts.ctypes.data, acc.ctypes.data,
+             LOSSES[loss], float(f_scale), max_iterations, float(xtol), 0 if segment is None else int(segment), int(device), out.ctypes.data, h6.ctypes.data, status.ctypes.data, nus.ctypes.data,
+             nsg.ctypes.data, nit.ctypes.data, cost.ctypes.data, hist.ctypes.data, None if c6 is None else c6.ctypes.data, None if l9 is None else l9.ctypes.data, info.ctypes.data,
+             ctypes.addressof(ms))
+    res = TrajectoryRefinement(points=out, information=np.ascontiguousarray(h6[..., _SYM]), status=status, n_usable=nus, n_single=nsg, n_iterations=nit, cost=cost,
+                               history=np.ascontiguousarray(hist[:int(nit.max())]), info=_info(info))
+    if c6 is not None:
+        res.covariance = np.ascontiguousarray(c6[..., _SYM])
+        with np.errstate(invalid="ignore"):
+            res.std = np.sqrt(res.covariance[..., (0, 1, 2), (0, 1, 2)])
+        res.lag_covariance = None if l9 is None else l9.reshape(T - 1, K, 3, 3)
+    return res
+
+
+def refine_trajectories_system(points, all_uvs, all_extrinsics, all_intrinsics, *, accel_std, pixel_std=1.0, loss="linear", f_scale=3.0, weights=None, segment=None, device=0):
+    """One evaluation of refine_trajectories laid open, at `points` (T, K, 3) and before anything is accepted: the information blocks H_t, the
+    gradient G of the whole objective, the step d of (blockdiag(H) + a^-2 D2^T D2 (x) I3) d = -G, the data and the smoothness term of the objective
+    at the points and the objective at x + alpha d for alpha = 1, 1/2, 1/4, 1/8 -- what a test holds against a dense oracle.  Arguments, statuses
+    and errors as refine_trajectories; a track whose status is not 1 is NaN throughout."""
+    pts, uvs, cam, dist, acc, pstd, w = _refine_arguments(points, all_uvs, all_extrinsics, all_intrinsics, accel_std, pixel_std, loss, f_scale, weights, segment)
+    C, T, K = uvs.shape[:3]
+    h6, g, d = np.empty((T, K, 6)), np.empty((T, K, 3)), np.empty((T, K, 3))
+    status, nus, nsg = (np.empty(K, np.int32) for _ in range(3))
+    dc, pc, tc, info = np.empty(K), np.empty(K), np.empty((K, 4)), np.zeros(8)
+    ms = ctypes.c_double(0.0)
+    ops.call("mcba_refine_trajectories_system", T, K, C, uvs.ctypes.data, cam.ctypes.data, dist.ctypes.data, None if w is None else w.ctypes.data, pstd.ctypes.data, pts.ctypes.data,
+             acc.ctypes.data, LOSSES[loss], float(f_scale), 0 if segment is None else int(segment), int(device), h6.ctypes.data, g.ctypes.data, d.ctypes.data, status.ctypes.data,
+             nus.ctypes.data, nsg.ctypes.data, dc.ctypes.data, pc.ctypes.data, tc.ctypes.data, info.ctypes.data, ctypes.addressof(ms))
+    return TrajectoryRefinementSystem(information=np.ascontiguousarray(h6[..., _SYM]), gradient=g, step=d, data_cost=dc, penalty_cost=pc, trial_costs=tc, status=status, n_usable=nus,
+                                      n_single=nsg, info=_info(info))
