@@ -896,6 +896,60 @@ int mcba_refine_trajectories_system(size_t n_frames, int n_tracks, int n_cameras
                                     const double* points, const double* accel_std, int loss, double f_scale, int segment, int device, double* information, double* gradient, double* step,
                                     int* status, int* n_usable, int* n_single, double* data_cost, double* penalty_cost, double* trial_costs, double* info8, double* kernel_ms);
 
+/* ---- Skeleton-constrained keypoint refinement (Python: skeleton.refine_skeleton).  Stateless, additive to ABI 7.  Frames
+ * are independent.  The skeleton is a forest over the n_keypoints = K keypoints, 1 <= K <= 64, passed as parent (K) in the caller's numbering
+ * (-1 = root) with bone_length (K) = L_k and bone_std (K) = s_k of the bone (k, parent[k]), both positive and finite, in the points' unit; the
+ * entries of a root are ignored.  The call checks that the parents form a forest and derives the processing order, the depth levels and the child
+ * lists itself.  Per frame, over the positions x_k of its active keypoints:
+ *   minimise 0.5 sum_k sum_{c sees k} f^2 [rho(ru^2 / f^2) + rho(rv^2 / f^2)] + 0.5 sum_{active bones} ((|x_k - x_parent(k)| - L_k) / s_k)^2,
+ *   (ru, rv) = sqrt(w_ctk) (detection - projection_c(x_k)) / pixel_std_c
+ * uvs (C, T, K, 2) raw detections (NaN = unseen), cam12 (C, 12), dist5 (C, 5) or NULL: the cameras of mcba_triangulate_refine (the
+ * five-coefficient forward model), 1 <= C <= 64; weights (C, T, K) or NULL = 1: finite and >= 0, a zero or NaN weight = unseen; pixel_std (C)
+ * positive; start (T, K, 3); loss 0 .. 4 = linear, soft_l1, huber, cauchy, arctan (scipy's rho), f = f_scale in units of pixel_std; the bone
+ * term is always quadratic.
+ * A keypoint is usable in a frame with two views or more and a finite start, single with exactly one view and a finite start; with no view or a
+ * non-finite start it is out of the frame and its bones are dropped there, which may split a tree.  A connected piece of what is left is fitted
+ * when it holds a usable keypoint.  keypoint_status (T, K): 2 fitted as usable, 1 fitted as single, -1 out of the frame, -2 in a piece without a
+ * usable keypoint; every keypoint not fitted is NaN in every output.  A single keypoint has two solutions (its ray meets the sphere about its
+ * neighbour twice): the fit goes to the one near the start.
+ * Levenberg-Marquardt per frame, the iteration of mcba_triangulate_refine with the frame's whole objective: Marquardt's damping lam diag(H) from
+ * 1e-4, divided by 10 on acceptance (floor 1e-12), times 10 on rejection; a trial is accepted when the objective is not larger (NaN compares
+ * false, a refused 3 x 3 pivot is a rejected step), so the result is never worse than the start.  The Gauss-Newton matrix of a bone with
+ * direction u is + u u^T / s^2 on both diagonal blocks and - u u^T / s^2 off the diagonal (its second-order term is left out); the system is
+ * eliminated leaf to root on the forest, without fill.  A frame stops, frame_status (T) = 1, when a step has max |d| < xtol max |x| over its
+ * active keypoints (accepted or not) or the damping reaches 1e12; at max_iterations >= 1 trials, frame_status = 0; -1: nothing to fit.
+ * out_points (T, K, 3); n_iterations (T) trials made; cost, cost_start (T) the objective at the result and at the start; bone_residual (T, K) =
+ * (|x_k - x_parent(k)| - L_k) / s_k at the result, NaN for a root and for a bone dropped in the frame.  out_cov6, information (T, K, 6) and
+ * direction (T, K, 3): all three or none (NULL).  information = the diagonal block of the Gauss-Newton matrix at the result, bones included,
+ * undamped, packed 00 01 02 11 12 22; direction = u of the bone (k, parent[k]), NaN where dropped; out_cov6 = the keypoint's 3 x 3 block of the
+ * inverse of that matrix (selected inversion root to leaf), in units where pixel_std is the detection noise; a refused pivot there makes the
+ * piece's blocks NaN.  info8 = {levels of the forest, frames per workgroup, frames per chunk, chunks, kernel ms, most iterations of a frame,
+ * device bytes of a chunk, 0}.  No atomics: two calls return the same bits, and a frame's result does not depend on the frames around it.
+ * MCBA_ERR_ARG, checked before any device is touched and with nothing written: n_frames == 0 or above 2^31, n_keypoints outside 1 .. 64,
+ * n_cameras outside 1 .. 64, a NULL array other than dist5, weights, kernel_ms and the three optional outputs, a parent outside -1 .. K - 1 or
+ * equal to its keypoint, a cycle, a bone_length or bone_std of a keypoint with a parent not positive and finite, a loss outside 0 .. 4, f_scale
+ * or a pixel_std not positive and finite, a negative or infinite weight, max_iterations < 1, xtol < 0. */
+int mcba_refine_skeleton(size_t n_frames, int n_keypoints, int n_cameras, const double* uvs, const double* cam12, const double* dist5, const double* weights, const double* pixel_std,
+                         const double* start, const int* parent, const double* bone_length, const double* bone_std, int loss, double f_scale, int max_iterations, double xtol, int device,
+                         double* out_points, int* keypoint_status, int* frame_status, int* n_iterations, double* cost, double* cost_start, double* bone_residual, double* out_cov6,
+                         double* information, double* direction, double* info8, double* kernel_ms);
+/* One evaluation of that loop laid open, at `points` with the damping lam >= 0 and before anything is accepted: information (T, K, 6) and
+ * direction (T, K, 3) as above, gradient (T, K, 3) of the whole objective, step (T, K, 3) = the solution d of the damped system, data_cost and
+ * bone_cost (T) = the two terms of the objective at the points, trial_cost (T) = the objective at x + d; keypoint_status as above, frame_status
+ * 1 or -1.  Arguments, errors and info8 as above. */
+int mcba_refine_skeleton_system(size_t n_frames, int n_keypoints, int n_cameras, const double* uvs, const double* cam12, const double* dist5, const double* weights, const double* pixel_std,
+                                const double* points, const int* parent, const double* bone_length, const double* bone_std, int loss, double f_scale, double lam, int device, double* information,
+                                double* gradient, double* direction, double* step, int* keypoint_status, int* frame_status, double* data_cost, double* bone_cost, double* trial_cost,
+                                double* info8, double* kernel_ms);
+/* Bone lengths from located keypoints (Python: skeleton.estimate_bone_lengths).  Stateless, additive to ABI 7.  points (T, K, 3), NaN = missing;
+ * bones (E, 2) pairs of keypoints, 1 <= E <= 65535.  One kernel writes the (E, T) plane of distances sqrt(dx dx + dy dy + dz dz) -- plain
+ * products and sums in that order, no fused multiply-add --, NaN where an end has a NaN; the exact radix select of mcba_keypoint_errors then runs
+ * twice.  length (E) = the exact nan-median of the bone's distances (the mean of the two middle values for an even count), std (E) = 1.4826 times
+ * the exact nan-median of |distance - length|, count (E) = the frames that have both ends; a bone with none has NaN, NaN, 0.  MCBA_ERR_ARG,
+ * checked before any device is touched and with nothing written: n_frames == 0 or above 2^31, n_keypoints < 1, n_bones outside 1 .. 65535, a NULL
+ * array other than kernel_ms, a bone's keypoint outside 0 .. K - 1. */
+int mcba_bone_lengths(size_t n_frames, int n_keypoints, const double* points, int n_bones, const int* bones, int device, double* length, double* std, int* count, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,8 @@ Only what the hot path needs lives here:
              gross errors discounted by a robust loss) -- SURVEY.md section 8f-19; trajectory_uncertainty (the covariance of every
              smoothed point and of neighbouring frames, by selected inversion) -- section 8f-20; refine_trajectories (the tracks refined on
              the raw detections: Gauss-Newton on the reprojection cost plus the smoothness prior, single-camera frames used) -- section 8f-21
+  skeleton.py  refine_skeleton (the keypoints of a frame refined together, joined by bones of known length: a keypoint one camera saw is located,
+             the others get tighter) and estimate_bone_lengths (exact medians of the bone lengths and their spread) -- SURVEY.md section 8f-22
   synth.py   deterministic synthetic board detections for tests and bench
 """
 from . import synth  # noqa: F401
@@ -45,6 +47,8 @@ from .uncertainty import calibration_uncertainty, CalibrationUncertainty, triang
 from . import trajectory  # noqa: F401
 from .trajectory import smooth_trajectories, TrajectorySmoothing, trajectory_uncertainty, TrajectoryUncertainty  # noqa: F401
 from .trajectory import refine_trajectories, refine_trajectories_system, TrajectoryRefinement, TrajectoryRefinementSystem, TRAJECTORY_REFINE_STATUS  # noqa: F401
+from . import skeleton  # noqa: F401
+from .skeleton import refine_skeleton, refine_skeleton_system, estimate_bone_lengths, SkeletonRefinement, SkeletonSystem, BoneLengths  # noqa: F401
 from .calibration import calibrate, get_intrinsics, estimate_pose, estimate_all_extrinsics, consensus_calib_poses, get_camera_spanning_tree, estimate_pairwise_camera_transform  # noqa: F401
 
 __all__ = ["bundle_adjust", "bundle_adjustment", "serialize_params", "deserialize_params", "ops", "solver", "synth", "calibration", "calibrate", "triangulate", "get_intrinsics",
@@ -57,4 +61,5 @@ __all__ = ["bundle_adjust", "bundle_adjustment", "serialize_params", "deserializ
            "rodrigues", "rodrigues_inv", "get_transformation_matrix", "get_transformation_vector", "get_projection_matrix", "euclidean_to_homogenous", "homogeneous_to_euclidean",
            "calibration_uncertainty", "CalibrationUncertainty", "triangulation_uncertainty", "TriangulationUncertainty",
            "trajectory", "smooth_trajectories", "TrajectorySmoothing", "trajectory_uncertainty", "TrajectoryUncertainty",
-           "refine_trajectories", "refine_trajectories_system", "TrajectoryRefinement", "TrajectoryRefinementSystem", "TRAJECTORY_REFINE_STATUS"]
+           "refine_trajectories", "refine_trajectories_system", "TrajectoryRefinement", "TrajectoryRefinementSystem", "TRAJECTORY_REFINE_STATUS",
+           "skeleton", "refine_skeleton", "refine_skeleton_system", "estimate_bone_lengths", "SkeletonRefinement", "SkeletonSystem", "BoneLengths"]

@@ -380,6 +380,18 @@ int launch_traj_trial(hipStream_t st, int loss, const TrData& rd, const KpCam* c
 // x <- x + alpha[k] d for every track of the chunk (alpha 0: untouched)
 int launch_traj_apply(hipStream_t st, const TrData& rd, int K, const double* alpha);
 
+// ---- skeleton-constrained keypoint refinement (mcba_skeleton.hip).  SkArgs, SkPlan: mcba_skeleton_math.h -- the planes of
+// a launch (device memory) and the forest plan (plan_dev: a copy in device memory); cams: a KpCam table in device memory, 1 <= C <= kKpMaxCams;
+// loss: LOSS_LINEAR .. LOSS_ARCTAN.  Non-zero: arguments out of range
+struct SkArgs;
+struct SkPlan;
+// every frame of a.T: the loop (a.system == 0; with a.cov the marginal covariance at the result) or one evaluation laid open (a.system != 0)
+int launch_skel_refine(hipStream_t st, int loss, const SkArgs& a, const SkPlan* plan_dev, int K, const KpCam* cams, int C);
+// dist (E, T): the distance between the two ends of bone e = bones[2 e], bones[2 e + 1] in frame t of pts (T, K, 3), NaN where an end has a NaN
+int launch_skel_dist(hipStream_t st, const double* pts, const int* bones, size_t T, int K, int E, double* dist);
+// dist <- |dist - the median of its bone| with sel the states of launch_select over dist (two per bone)
+int launch_skel_absdev(hipStream_t st, double* dist, const SelState* sel, size_t T, int E);
+
 // ---- free-point bundle adjustment of the extrinsics (mcba_kpba.hip).  uvs (C, P, 2) raw detections (NaN = unseen), pts
 // (P, 3), cams: TcCam table in device memory, 2 <= C <= 24, held (C): bit i = scalar i of the camera is not free.  Non-zero: arguments out of range.
 int kpba_group(int C, int lds_limit, int force_g);   // points per group of k_kpba_reduce (64, 32 or 16; 0: no shape fits)

@@ -162,6 +162,11 @@ SYMBOLS = [
                                                 ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     ("mcba_refine_trajectories_system", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                                        _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    # skeleton-constrained refinement: every array by address (parent and the statuses, int*, like the doubles); dist5, weights and
+    # the three covariance outputs may be NULL
+    ("mcba_refine_skeleton", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, ctypes.c_int] + [_dp] * 9 + [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int] + [_dp] * 12),
+    ("mcba_refine_skeleton_system", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, ctypes.c_int] + [_dp] * 9 + [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int] + [_dp] * 11),
+    ("mcba_bone_lengths", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, _dp, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),
     ("mcba_profile_enable", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_stride", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_read", ctypes.c_int, [_h, _dp, _ip, ctypes.c_int, _ip]),

@@ -1,0 +1,156 @@
+// Host build of csrc/mcba_skeleton_math.h -- everything csrc/mcba_skeleton.hip computes -- for g++: skel_frame, the procedure of a frame, run by a
+// context whose each() is a serial loop over the frame's lanes per phase (the kernel's is one thread per lane and a barrier) and whose any() is
+// the frame's own word; the forest plan; the distance of estimate_bone_lengths.  tests/test_hostcheck_skeleton.py compiles this as a shared
+// library (plain -O2) and holds it to the GPU tier's rules.  With SKELETON_HOSTCHECK_MAIN it is a stand-alone program that runs a small frame
+// set through every path (for a sanitizer build: g++ -fsanitize=address,undefined -DSKELETON_HOSTCHECK_MAIN).
+#include <cmath>
+#include <cstddef>
+#include <cstdio>
+#include <cstring>
+#include <type_traits>
+#include <vector>
+#include "../../multicam-calibration_amd/csrc/mcba_skeleton_math.h"
+
+using namespace mcba;
+
+namespace {
+
+// one frame at a time: K lanes, planes of stride K
+struct HostCtx {
+  int K;
+  size_t t;
+  std::vector<SkLane> lanes;
+  std::vector<double> planes;
+  std::vector<int> cls;
+  SkFrameState fs;
+  double* history;   // (max_iterations) of the frame or null: the objective after every trial
+  HostCtx(int K_, size_t t_, double* history_) : K(K_), t(t_), lanes(K_), planes((size_t)SK_PLANES * K_, std::nan("")), cls(K_, 0), fs{}, history(history_) {
+    for (int k = 0; k < K; ++k) { lanes[k] = SkLane{}; lanes[k].k = k; }
+  }
+  template <class F>
+  void each(F&& f) {
+    const int it = fs.it;
+    const SkShared sh{planes.data(), cls.data(), K};
+    for (int k = 0; k < K; ++k) f(lanes[k], sh, fs, t);
+    if (history && fs.it != it) history[fs.it - 1] = fs.cost;
+  }
+  template <class P>
+  bool any(P&& pred) { return pred(fs); }
+};
+
+template <class F>
+void with_loss5(int loss, F&& f) {
+  if (loss == LOSS_LINEAR) f(std::integral_constant<int, LOSS_LINEAR>{});
+  else if (loss == LOSS_SOFT_L1) f(std::integral_constant<int, LOSS_SOFT_L1>{});
+  else if (loss == LOSS_HUBER) f(std::integral_constant<int, LOSS_HUBER>{});
+  else if (loss == LOSS_CAUCHY) f(std::integral_constant<int, LOSS_CAUCHY>{});
+  else f(std::integral_constant<int, LOSS_ARCTAN>{});
+}
+
+}  // namespace
+
+// the arguments of mcba_refine_skeleton (system == 0) or mcba_refine_skeleton_system (system != 0: max_iterations and xtol unused, lam the
+// damping); cov6, information and direction as there; history (T, max_iterations) or null.  Outputs of the other mode may be null
+extern "C" int hc_refine_skeleton(int system, size_t T, int K, int C, const double* uvs, const double* cam12, const double* dist5, const double* weights, const double* pixel_std,
+                                  const double* start, const int* parent, const double* bone_length, const double* bone_std, int loss, double f_scale, int max_iterations, double xtol, double lam,
+                                  double* out_points, int* keypoint_status, int* frame_status, int* n_iterations, double* cost, double* cost_start, double* bone_residual, double* out_cov6,
+                                  double* information, double* direction, double* gradient, double* step, double* data_cost, double* bone_cost, double* trial_cost, double* history, int* levels) {
+  SkPlan plan;
+  if (int rc = skel_plan(K, parent, bone_length, bone_std, plan)) return rc;
+  if (T < 1 || C < 1 || C > kKpMaxCams || loss < 0 || loss > 4 || !(f_scale > 0.0) || (!system && max_iterations < 1)) return 10;
+  *levels = plan.levels;
+  const size_t TK = T * K;
+  std::vector<KpCam> cams(C);
+  for (int c = 0; c < C; ++c) make_kp_cam(cam12 + 12 * c, dist5 ? dist5 + 5 * c : nullptr, cams[c]);
+  std::vector<double> sw((size_t)C * TK);
+  for (int c = 0; c < C; ++c)
+    for (size_t i = 0; i < TK; ++i) {
+      const double w = weights ? weights[c * TK + i] : 1.0;
+      sw[c * TK + i] = w > 0.0 ? sqrt(w) * (1.0 / pixel_std[c]) : 0.0;
+    }
+  SkArgs a{};
+  a.T = T; a.det = uvs; a.sw = sw.data(); a.start = start;
+  a.fs2 = f_scale * f_scale; a.inv_fs2 = 1.0 / a.fs2; a.lam0 = system ? lam : SK_LAM_START; a.xtol = xtol;
+  a.max_iterations = system ? 1 : max_iterations; a.system = system ? 1 : 0; a.cov = out_cov6 ? 1 : 0;
+  a.points = out_points; a.kstatus = keypoint_status; a.fstatus = frame_status; a.nit = n_iterations; a.cost = cost; a.cost0 = cost_start; a.bone_res = bone_residual;
+  a.info6 = information; a.dir = direction; a.cov6 = out_cov6; a.grad = gradient; a.step = step; a.data_cost = data_cost; a.bone_cost = bone_cost; a.trial_cost = trial_cost;
+  for (size_t t = 0; t < T; ++t) {
+    HostCtx cx(K, t, history && !system ? history + t * (size_t)max_iterations : nullptr);
+    with_loss5(loss, [&](auto L) { skel_frame<decltype(L)::value>(cx, plan, cams.data(), C, a); });
+  }
+  return 0;
+}
+
+// the forest plan: level, order (K), child_start (K + 1), child (K), out2 = (levels, frames per workgroup); the return code of skel_plan
+extern "C" int hc_skel_plan(int K, const int* parent, const double* bone_length, const double* bone_std, int* level, int* order, int* child_start, int* child, int* out2) {
+  SkPlan plan;
+  if (int rc = skel_plan(K, parent, bone_length, bone_std, plan)) return rc;
+  for (int k = 0; k < K; ++k) { level[k] = plan.level[k]; order[k] = plan.order[k]; child_start[k] = plan.child_start[k]; child[k] = plan.child[k]; }
+  child_start[K] = plan.child_start[K];
+  out2[0] = plan.levels; out2[1] = skel_frames_per_group(K);
+  return 0;
+}
+
+// dist (E, T) of points (T, K, 3) and bones (E, 2)
+extern "C" void hc_bone_distances(size_t T, int K, const double* points, int E, const int* bones, double* dist) {
+  for (int e = 0; e < E; ++e)
+    for (size_t t = 0; t < T; ++t) dist[(size_t)e * T + t] = skel_distance(points + 3 * (t * K + bones[2 * e]), points + 3 * (t * K + bones[2 * e + 1]));
+}
+
+#ifdef SKELETON_HOSTCHECK_MAIN
+// a stand-alone run of every path on a small synthetic set: three cameras on a circle looking at the origin, a tree of five keypoints, frames
+// with a single-view keypoint, an unseen one and a NaN start
+int main() {
+  const int K = 5, C = 3;
+  const size_t T = 6;
+  const int parent[K] = {-1, 0, 1, 1, 3};
+  const double L[K] = {0.0, 20.0, 15.0, 25.0, 10.0}, s[K] = {0.0, 0.5, 0.5, 0.5, 0.5};
+  double cam12[C * 12], pstd[C] = {0.5, 0.5, 0.5};
+  for (int c = 0; c < C; ++c) {
+    const double ang = 2.0943951023931953 * c;
+    const double v[12] = {1500.0, 1500.0, 640.0, 512.0, -0.05, 0.01, 0.0, ang, 0.0, 0.0, 0.0, 600.0};
+    memcpy(cam12 + 12 * c, v, sizeof(v));
+  }
+  std::vector<KpCam> cams(C);
+  for (int c = 0; c < C; ++c) make_kp_cam(cam12 + 12 * c, nullptr, cams[c]);
+  std::vector<double> truth(3 * T * K), start(3 * T * K), uvs(2 * C * T * K);
+  unsigned long long rs = 12345;
+  auto rnd = [&]() { rs = rs * 6364136223846793005ull + 1442695040888963407ull; return (double)(rs >> 11) / 9007199254740992.0 - 0.5; };
+  for (size_t t = 0; t < T; ++t)
+    for (int k = 0; k < K; ++k) {
+      double* x = &truth[3 * (t * K + k)];
+      if (parent[k] < 0) { x[0] = 20 * rnd(); x[1] = 20 * rnd(); x[2] = 20 * rnd(); }
+      else {
+        double v[3] = {rnd(), rnd(), rnd()};
+        const double n = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        for (int e = 0; e < 3; ++e) x[e] = truth[3 * (t * K + parent[k]) + e] + L[k] * v[e] / n;
+      }
+      for (int e = 0; e < 3; ++e) start[3 * (t * K + k) + e] = x[e] + 0.6 * rnd();
+      for (int c = 0; c < C; ++c) {
+        double u, v;
+        project5<false>(cams[c], x, u, v);
+        uvs[2 * ((c * T + t) * K + k)] = u + rnd();
+        uvs[2 * ((c * T + t) * K + k) + 1] = v + rnd();
+      }
+    }
+  const double nan = std::nan("");
+  for (int c = 1; c < C; ++c) uvs[2 * ((c * T + 1) * K + 4)] = nan;           // frame 1: keypoint 4 seen by camera 0 only
+  for (int c = 0; c < C; ++c) uvs[2 * ((c * T + 2) * K + 1) + 1] = nan;       // frame 2: keypoint 1 unseen
+  start[3 * (3 * K + 2)] = nan;                                               // frame 3: a NaN start
+  std::vector<double> pts(3 * T * K), cost(T), cost0(T), bres(T * K), c6(6 * T * K), h6(6 * T * K), dir(3 * T * K), g(3 * T * K), d(3 * T * K), dc(T), bc(T), tc(T), hist(T * 50);
+  std::vector<int> kst(T * K), fst(T), nit(T);
+  int levels = 0, bad = 0;
+  for (int loss = 0; loss < 5; ++loss) {
+    bad |= hc_refine_skeleton(0, T, K, C, uvs.data(), cam12, nullptr, nullptr, pstd, start.data(), parent, L, s, loss, 3.0, 50, 1e-8, 0.0, pts.data(), kst.data(), fst.data(), nit.data(), cost.data(),
+                              cost0.data(), bres.data(), c6.data(), h6.data(), dir.data(), nullptr, nullptr, nullptr, nullptr, nullptr, hist.data(), &levels);
+    for (size_t t = 0; t < T; ++t) {
+      printf("loss %d frame %zu: status %d, %d iterations, cost %.6g <- %.6g\n", loss, t, fst[t], nit[t], cost[t], cost0[t]);
+      if (!(cost[t] <= cost0[t])) bad |= 64;
+    }
+    bad |= hc_refine_skeleton(1, T, K, C, uvs.data(), cam12, nullptr, nullptr, pstd, start.data(), parent, L, s, loss, 3.0, 1, 0.0, 1e-4, nullptr, kst.data(), fst.data(), nullptr, nullptr, nullptr,
+                              nullptr, nullptr, h6.data(), dir.data(), g.data(), d.data(), dc.data(), bc.data(), tc.data(), nullptr, &levels);
+  }
+  printf("levels %d, %s\n", levels, bad ? "FAILED" : "ok");
+  return bad;
+}
+#endif
