@@ -950,6 +950,44 @@ int mcba_refine_skeleton_system(size_t n_frames, int n_keypoints, int n_cameras,
  * array other than kernel_ms, a bone's keypoint outside 0 .. K - 1. */
 int mcba_bone_lengths(size_t n_frames, int n_keypoints, const double* points, int n_bones, const int* bones, int device, double* length, double* std, int* count, double* kernel_ms);
 
+/* ---- skeleton trajectories (Python: skeleton.refine_skeleton_trajectories) -------------------------------------
+ * Stateless, additive to ABI 7.  The tracks of mcba_refine_trajectories joined inside every frame by the bones of mcba_refine_skeleton: one problem
+ * per call over x_{t,k}, t < n_frames, of the running tracks (two usable frames or more and a finite start, as there),
+ *   the data term and the second-difference prior of mcba_refine_trajectories + 0.5 sum_t sum_{active bones} ((|x_tk - x_tp| - L_k) / s_k)^2,
+ * a bone (k, parent[k]) being active, in every frame, when both its tracks run.  Arrays as mcba_refine_trajectories (uvs (C, T, K, 2), start
+ * (T, K, 3), accel_std (K), weights (C, T, K) or NULL, pixel_std (C), loss 0 .. 2) and mcba_refine_skeleton (parent, bone_length, bone_std (K):
+ * a forest over at most 64 keypoints).  Gauss-Newton in step form on the call's objective: per iteration the system (M + B) d = -G -- M the
+ * tracks' block-pentadiagonal matrices, B the bones' Gauss-Newton terms -- is solved by conjugate gradients preconditioned with M (one
+ * elimination of the smoother per iteration, one re-solve from its factors per CG iteration) until r^T z <= cg_tol^2 r0^T z0 or cg_max
+ * iterations; the largest alpha of 1, 1/2, 1/4, 1/8 whose objective is not above the current one is taken (none: the call stops where it is), and
+ * the call stops when alpha max |d| < xtol max |x| or after max_iterations.
+ * Outputs: out_points (T, K, 3); information (T, K, 6) = H of the data term at the returned points, packed 00 01 02 11 12 22; status, n_usable,
+ * n_single (K) as mcba_refine_trajectories (1, -1, -2, -3; a start whose objective is not finite gives every running track -3); converged (1) =
+ * the call stopped on a small step or on nothing accepted; n_iterations (1); cost, cost_start (1); history (max_iterations, 4) = objective,
+ * accepted step, alpha, CG iterations of that solve, NaN beyond n_iterations (an iteration that ends on a refused pivot or on an objective that
+ * is not finite accepts nothing and is not counted, in n_iterations or in the CG total); bone_residual (T, K) and direction (T, K, 3) of bone (k, parent[k])
+ * at the returned points, NaN where the bone is not active; info8 = levels, segment, running tracks, CG iterations in all, kernel ms, outer
+ * iterations, device bytes, 0.  Whatever belongs to a track that is not 1 is NaN.
+ * MCBA_ERR_ARG, before any device is touched and with nothing written: the checks of the two calls above, cg_tol outside (0, 1), cg_max < 1, and a
+ * call that does not fit the budget MCBA_SMOOTH_BUDGET_MB whole (bones couple the tracks: it cannot run in chunks). */
+int mcba_refine_skeleton_trajectories(size_t n_frames, int n_keypoints, int n_cameras, const double* uvs, const double* cam12, const double* dist5, const double* weights,
+                                      const double* pixel_std, const double* start, const double* accel_std, const int* parent, const double* bone_length, const double* bone_std, int loss,
+                                      double f_scale, int max_iterations, double xtol, double cg_tol, int cg_max, int segment, int device, double* out_points, double* information, int* status,
+                                      int* n_usable, int* n_single, int* converged, int* n_iterations, double* cost, double* cost_start, double* history, double* bone_residual,
+                                      double* direction, double* info8, double* kernel_ms);
+/* One evaluation of that loop laid open, at `points` and before anything is accepted: information and direction as above, gradient (T, K, 3) of the
+ * whole objective, step (T, K, 3) = the iterate of the preconditioned recurrence for (M + B) d = -G when it ended, cg_iterations (1), cg_residual
+ * (1) = sqrt(r^T z / r0^T z0) of the recurrence then, data_cost, penalty_cost, bone_cost (1 each) = the three terms of the objective at the points,
+ * trial_costs (4) = the objective at x + alpha d for alpha = 1, 1/2, 1/4, 1/8.  resolve_check: NULL, or (2, T, K, 3) for tests -- the solution of
+ * M z = -G by the elimination and back-substitution, then by the re-solve from the stored factors and the same back-substitution after the
+ * right-hand-side halves of every stored record were overwritten with NaN (tracks that do not run: unwritten).  Arguments, errors and info8 as
+ * above. */
+int mcba_refine_skeleton_trajectories_system(size_t n_frames, int n_keypoints, int n_cameras, const double* uvs, const double* cam12, const double* dist5, const double* weights,
+                                             const double* pixel_std, const double* points, const double* accel_std, const int* parent, const double* bone_length, const double* bone_std,
+                                             int loss, double f_scale, double cg_tol, int cg_max, int segment, int device, double* information, double* gradient, double* direction,
+                                             double* step, int* status, int* n_usable, int* n_single, int* cg_iterations, double* cg_residual, double* data_cost, double* penalty_cost,
+                                             double* bone_cost, double* trial_costs, double* resolve_check, double* info8, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

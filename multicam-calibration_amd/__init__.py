@@ -26,7 +26,8 @@ Only what the hot path needs lives here:
              smoothed point and of neighbouring frames, by selected inversion) -- section 8f-20; refine_trajectories (the tracks refined on
              the raw detections: Gauss-Newton on the reprojection cost plus the smoothness prior, single-camera frames used) -- section 8f-21
   skeleton.py  refine_skeleton (the keypoints of a frame refined together, joined by bones of known length: a keypoint one camera saw is located,
-             the others get tighter) and estimate_bone_lengths (exact medians of the bone lengths and their spread) -- SURVEY.md section 8f-22
+             the others get tighter) and estimate_bone_lengths (exact medians of the bone lengths and their spread) -- SURVEY.md section 8f-22; refine_skeleton_trajectories (the tracks of a recording refined together: the
+             detections, the time prior and the bones in one fit, conjugate gradients preconditioned by the smoother's elimination) -- section 8f-23
   synth.py   deterministic synthetic board detections for tests and bench
 """
 from . import synth  # noqa: F401
@@ -49,6 +50,7 @@ from .trajectory import smooth_trajectories, TrajectorySmoothing, trajectory_unc
 from .trajectory import refine_trajectories, refine_trajectories_system, TrajectoryRefinement, TrajectoryRefinementSystem, TRAJECTORY_REFINE_STATUS  # noqa: F401
 from . import skeleton  # noqa: F401
 from .skeleton import refine_skeleton, refine_skeleton_system, estimate_bone_lengths, SkeletonRefinement, SkeletonSystem, BoneLengths  # noqa: F401
+from .skeleton import refine_skeleton_trajectories, refine_skeleton_trajectories_system, SkeletonTrajectoryRefinement, SkeletonTrajectorySystem  # noqa: F401
 from .calibration import calibrate, get_intrinsics, estimate_pose, estimate_all_extrinsics, consensus_calib_poses, get_camera_spanning_tree, estimate_pairwise_camera_transform  # noqa: F401
 
 __all__ = ["bundle_adjust", "bundle_adjustment", "serialize_params", "deserialize_params", "ops", "solver", "synth", "calibration", "calibrate", "triangulate", "get_intrinsics",
@@ -62,4 +64,5 @@ __all__ = ["bundle_adjust", "bundle_adjustment", "serialize_params", "deserializ
            "calibration_uncertainty", "CalibrationUncertainty", "triangulation_uncertainty", "TriangulationUncertainty",
            "trajectory", "smooth_trajectories", "TrajectorySmoothing", "trajectory_uncertainty", "TrajectoryUncertainty",
            "refine_trajectories", "refine_trajectories_system", "TrajectoryRefinement", "TrajectoryRefinementSystem", "TRAJECTORY_REFINE_STATUS",
-           "skeleton", "refine_skeleton", "refine_skeleton_system", "estimate_bone_lengths", "SkeletonRefinement", "SkeletonSystem", "BoneLengths"]
+           "skeleton", "refine_skeleton", "refine_skeleton_system", "estimate_bone_lengths", "SkeletonRefinement", "SkeletonSystem", "BoneLengths",
+           "refine_skeleton_trajectories", "refine_skeleton_trajectories_system", "SkeletonTrajectoryRefinement", "SkeletonTrajectorySystem"]

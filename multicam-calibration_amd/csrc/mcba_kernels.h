@@ -361,6 +361,9 @@ void launch_smooth_prepare(hipStream_t st, size_t T, int K, const double* pts, c
 int launch_smooth_reduce(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad, bool rhs = false);
 // the back-substitution alone, every level down.  rhs (both): level 0 in the right-hand-side mode of mcba_smooth_math.h (SmData::rhs)
 int launch_smooth_backsub(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, bool rhs = false);
+// after launch_smooth_reduce(rhs = true): the forward pass again for the right-hand side td.rhs holds now, from the stored factors; done: null or a
+// device word that, non-zero, makes the launches return at once.  launch_smooth_backsub(rhs = true) follows
+int launch_smooth_resolve(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, const int* done);
 // one linear solve (launch_smooth_reduce, then every level down) of the nact tracks of list, then res (nact, 4) = objective, step, max |x|, 0
 int launch_smooth_solve(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, int* bad, double* part, double* res);
 
@@ -391,6 +394,21 @@ int launch_skel_refine(hipStream_t st, int loss, const SkArgs& a, const SkPlan* 
 int launch_skel_dist(hipStream_t st, const double* pts, const int* bones, size_t T, int K, int E, double* dist);
 // dist <- |dist - the median of its bone| with sel the states of launch_select over dist (two per bone)
 int launch_skel_absdev(hipStream_t st, double* dist, const SelState* sel, size_t T, int E);
+
+// ---- skeleton trajectories (mcba_skeltraj.hip).  SktData: mcba_skeltraj_math.h, the planes of the call over K <= 64
+// tracks, its active forest (device memory) and run (K).  Every launch is flat over (frame, keypoint) and takes part: one double per workgroup
+// of 256 lanes (SKT_SUMS for the trial).  Non-zero: arguments out of range
+struct SktData;
+// after launch_traj_linearise: the bones' gradient into G, q = G, dir and bres
+int launch_skt_linearise(hipStream_t st, const SktData& sd, int K);
+// after the first solve M z = -G: p = z, d = 0, sc (CG_DOUBLES) and w (CG_INTS) set for a new solve
+int launch_skt_cg_start(hipStream_t st, const SktData& sd, int K, double* part, double* sc, int* w);
+// one iteration of the preconditioned recurrence: operator, step, the re-solve of td (rhs = q, x = z) from the factors in lv, direction.  Every
+// kernel of it but the back-substitution returns at once when w[CG_DONE] is set; the last iteration sets it (tol2 = cg_tol^2, cg_max)
+int launch_skt_cg_iteration(hipStream_t st, const SktData& sd, int K, const SmLevel* lv, int levels, const SmData& td, const int* list, int nact, double tol2, int cg_max, double* part,
+                            double* sc, int* w);
+// res (SKT_SUMS) of the whole call from x and d
+int launch_skt_trial(hipStream_t st, int loss, const SktData& sd, const KpCam* cams, int C, int K, double* part, double* res);
 
 // ---- free-point bundle adjustment of the extrinsics (mcba_kpba.hip).  uvs (C, P, 2) raw detections (NaN = unseen), pts
 // (P, 3), cams: TcCam table in device memory, 2 <= C <= 24, held (C): bit i = scalar i of the camera is not free.  Non-zero: arguments out of range.

@@ -4,6 +4,7 @@
 //   k_smooth_prepare   lane = (frame, track): usable flag, Sigma^-1 (packed), the start weights
 //   k_smooth_count     workgroup = track: its usable frames
 //   k_smooth_reduce    lane = (segment, track), tracks fastest: forward elimination through the segment's interior, the Schur terms of its separators
+//   k_smooth_resolve   lane = (segment, track): the forward pass alone for a new right-hand side, from the stored factors
 //   k_smooth_backsub   lane = (segment, track): the interior's solution from its separators'; level 0 also writes d^2, the new weights, the step
 //   k_smooth_eval      workgroup = 256 frames of a track: the sums of the objective, the largest step and coordinate; k_smooth_final adds them
 #include <hip/hip_runtime.h>
@@ -48,6 +49,16 @@ __global__ __launch_bounds__(64) void k_smooth_reduce(SmLevel lv, SmLevel nx, Sm
   const size_t gid = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (gid >= (size_t)nq * nact) return;
   smooth_reduce_lane<LEVEL0, RHS>(lv, nx, td, K, list[gid % nact], (int)(gid / nact), bad);
+}
+
+// the forward pass again for a new right-hand side, the factors of k_smooth_reduce in place (smooth_resolve_lane).  done: null, or a word in
+// device memory: non-zero = the caller's iteration has ended and the launch returns at once
+template <bool LEVEL0>
+__global__ __launch_bounds__(64) void k_smooth_resolve(SmLevel lv, SmLevel nx, SmData td, int K, const int* __restrict__ list, int nact, int nq, const int* __restrict__ done) {
+  if (done && *done) return;
+  const size_t gid = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (gid >= (size_t)nq * nact) return;
+  smooth_resolve_lane<LEVEL0>(lv, nx, td, K, list[gid % nact], (int)(gid / nact));
 }
 
 template <bool LEVEL0, bool RHS = false>
@@ -106,6 +117,22 @@ int launch_smooth_reduce(hipStream_t st, const SmLevel* lv, int levels, const Sm
     if (l == 0 && rhs) k_smooth_reduce<true, true><<<dim3(blocks), dim3(64), 0, st>>>(lv[0], nx, td, K, list, nact, nq, bad);
     else if (l == 0) k_smooth_reduce<true><<<dim3(blocks), dim3(64), 0, st>>>(lv[0], nx, td, K, list, nact, nq, bad);
     else k_smooth_reduce<false><<<dim3(blocks), dim3(64), 0, st>>>(lv[l], nx, td, K, list, nact, nq, bad);
+  }
+  return 0;
+}
+
+// after launch_smooth_reduce(rhs = true): the forward pass of every level again for the right-hand side td.rhs now holds; launch_smooth_backsub(rhs =
+// true) follows it
+int launch_smooth_resolve(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, const int* done) {
+  if (levels < 1 || levels > SM_MAX_LEVELS || nact < 1 || nact > K) return 1;
+  const SmLevel none{};
+  for (int l = 0; l < levels; ++l) {
+    int nq;
+    unsigned blocks;
+    if (!smooth_grid(lv[l], nact, nq, blocks)) return 1;
+    const SmLevel& nx = l + 1 < levels ? lv[l + 1] : none;
+    if (l == 0) k_smooth_resolve<true><<<dim3(blocks), dim3(64), 0, st>>>(lv[0], nx, td, K, list, nact, nq, done);
+    else k_smooth_resolve<false><<<dim3(blocks), dim3(64), 0, st>>>(lv[l], nx, td, K, list, nact, nq, done);
   }
   return 0;
 }

@@ -22,6 +22,13 @@ inline int smooth_check_common(const char* who, const char* weights_name, size_t
   return MCBA_OK;
 }
 
+// the device-memory budget of one chunk in bytes: MCBA_SMOOTH_BUDGET_MB, 8192 where it is unset or not positive
+inline double smooth_budget_bytes() {
+  double budget_mb = 8192.0;
+  if (const char* e = getenv("MCBA_SMOOTH_BUDGET_MB")) { const double v = atof(e); if (v > 0.0) budget_mb = v; }
+  return budget_mb * 1048576.0;
+}
+
 // One call's walk over its chunks.  setup() once, then per chunk c < nchunks: begin(c), the entry's own launches on list, scatter() per output.
 // What every trajectory call shares is setup_shared() / begin_shared(): the budget and the chunk width, the levels, 1 / a^2, the list, d_bad, the
 // events.  setup() / begin() add the data planes of the two calls that take points and covariances (upload, prepare, count); a call with data
@@ -52,9 +59,7 @@ struct SmoothChunks {
   // The buffers are sized for the widest chunk: a narrower last one re-plans its levels inside them
   int setup_shared(const char* who_, size_t T_, size_t K_, int segment_, const double* accel_std_, size_t per_track, int extra_) {
     who = who_; T = T_; K = K_; segment = segment_; accel_std = accel_std_; extra = extra_;
-    double budget_mb = 8192.0;
-    if (const char* e = getenv("MCBA_SMOOTH_BUDGET_MB")) { const double v = atof(e); if (v > 0.0) budget_mb = v; }
-    Kc = mcba::smooth_chunk_tracks(budget_mb * 1048576.0, per_track, K, nchunks);
+    Kc = mcba::smooth_chunk_tracks(smooth_budget_bytes(), per_track, K, nchunks);
     if (int rc = call.scratch(&d_ia2, (size_t)Kc)) return rc;
     if (int rc = call.scratch(&d_nus, (size_t)Kc)) return rc;
     if (int rc = call.scratch(&d_list, (size_t)Kc)) return rc;

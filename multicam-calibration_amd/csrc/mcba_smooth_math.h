@@ -384,6 +384,102 @@ MCBA_HD void smooth_reduce_lane(const SmLevel& lv, const SmLevel& nx, const SmDa
   }
 }
 
+// ---- the right-hand side alone of block j of a level: level 0 in its right-hand-side mode (-rhs, zero on the phantom frame), a level >= 1 as
+// smooth_load sums it
+template <bool LEVEL0>
+MCBA_HD void smooth_load_rhs(const SmLevel& lv, const SmData& td, int K, int k, long long j, double* r) {
+  if (LEVEL0) {
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {
+      const long long t = 2 * j + f;
+      const bool in = (size_t)t < td.T;
+      const size_t idx = in ? (size_t)t * K + k : 0;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) r[3 * f + a] = in ? -td.rhs[3 * idx + a] : 0.0;
+    }
+  } else {
+    const size_t nd = sm_node(lv, j, K, k);
+#pragma unroll
+    for (int e = 0; e < 6; ++e) r[e] = lv.sep[(size_t)(21 + e) * lv.NS + nd] + lv.sep[(size_t)(48 + e) * lv.NS + nd];
+  }
+}
+
+// ---- re-solve: the forward pass of smooth_reduce_lane for a new right-hand side of a matrix it has already eliminated (level 0: in its
+// right-hand-side mode).  From the stored L and L^-1 G and the coupling E formed again (level 0: its three scalars; above: the level's own
+// record) it rewrites L^-1 g per interior block and the right-hand-side halves of the separator records (base 21 .. 26, cl 48 .. 53), and
+// nothing else: smooth_backsub_lane follows it unchanged.  The step to the next block is r_{i+1} - E_{i+1} (L^-T L^-1 g_i): one back
+// substitution with L in place of the six forward ones that make L^-1 E^T, so the result agrees with a fresh elimination to rounding, not in bits
+template <bool LEVEL0>
+MCBA_HD void smooth_resolve_lane(const SmLevel& lv, const SmLevel& nx, const SmData& td, int K, int k, int q) {
+  const int m = lv.m, n = lv.n;
+  const long long j0 = (long long)q * (m + 1);
+  const bool hasL = q > 0;
+  const int len = n - j0 < m ? (int)(n - j0) : m;
+  double CLr[6];
+#pragma unroll
+  for (int e = 0; e < 6; ++e) CLr[e] = 0.0;
+  if (len > 0) {
+    double g[6];
+    smooth_load_rhs<LEVEL0>(lv, td, K, k, j0, g);
+    for (int i = 0; i < len; ++i) {
+      const size_t nd = sm_node(lv, j0 + i, K, k);
+      double L[21];
+#pragma unroll
+      for (int e = 0; e < 21; ++e) L[e] = lv.fac[(size_t)e * lv.NS + nd];
+      sm_fwd6(L, g);
+#pragma unroll
+      for (int e = 0; e < 6; ++e) lv.fac[(size_t)(57 + e) * lv.NS + nd] = g[e];
+      if (hasL) {
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+          double v = CLr[a];
+#pragma unroll
+          for (int r = 0; r < 6; ++r) v = fma(-lv.fac[(size_t)(21 + r * 6 + a) * lv.NS + nd], g[r], v);
+          CLr[a] = v;
+        }
+      }
+      const long long jn = j0 + i + 1;
+      if (jn < n) {
+        double rn[6], w[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) w[e] = g[e];
+        sm_bwd6(L, w);
+        smooth_load_rhs<LEVEL0>(lv, td, K, k, jn, rn);
+        if (LEVEL0) {
+          double e00, e01, e11;
+          sm_e0_scalars(td, k, jn, e00, e01, e11);
+#pragma unroll
+          for (int a = 0; a < 3; ++a) {
+            rn[a] -= fma(e00, w[a], e01 * w[3 + a]);
+            rn[3 + a] = fma(-e11, w[3 + a], rn[3 + a]);
+          }
+        } else {
+          const size_t ne = sm_node(lv, jn, K, k);
+#pragma unroll
+          for (int r = 0; r < 6; ++r) {
+            double v = rn[r];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) v = fma(-lv.sep[(size_t)(54 + r * 6 + c) * lv.NS + ne], w[c], v);
+            rn[r] = v;
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 6; ++e) g[e] = rn[e];
+        if (i + 1 == len) {   // block jn is the right separator: block q of the next level
+          const size_t ns = sm_node(nx, q, K, k);
+#pragma unroll
+          for (int e = 0; e < 6; ++e) nx.sep[(size_t)(21 + e) * nx.NS + ns] = g[e];
+        }
+      }
+    }
+  }
+  if (hasL) {   // (an empty last segment hands its separator zeros)
+    const size_t ns = sm_node(nx, q - 1, K, k);
+#pragma unroll
+    for (int e = 0; e < 6; ++e) nx.sep[(size_t)(48 + e) * nx.NS + ns] = CLr[e];
+  }
+}
+
 // ---- the solution of block j: levels >= 1 keep it in lv.x; level 0 writes the frames' x, dx, d2 and the new weights
 template <bool LEVEL0, bool RHS = false>
 MCBA_HD void smooth_store_x(const SmLevel& lv, const SmData& td, int K, int k, long long j, const double* x) {

@@ -167,6 +167,11 @@ SYMBOLS = [
     ("mcba_refine_skeleton", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, ctypes.c_int] + [_dp] * 9 + [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int] + [_dp] * 12),
     ("mcba_refine_skeleton_system", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, ctypes.c_int] + [_dp] * 9 + [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int] + [_dp] * 11),
     ("mcba_bone_lengths", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, _dp, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),
+    # skeleton trajectories: every array by address; dist5 and weights may be NULL
+    ("mcba_refine_skeleton_trajectories", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, ctypes.c_int] + [_dp] * 10 + [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double,
+                                                         ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_dp] * 14),
+    ("mcba_refine_skeleton_trajectories_system", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, ctypes.c_int] + [_dp] * 10 + [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                                                ctypes.c_int, ctypes.c_int] + [_dp] * 16),
     ("mcba_profile_enable", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_stride", ctypes.c_int, [_h, ctypes.c_int]),
     ("mcba_profile_read", ctypes.c_int, [_h, _dp, _ip, ctypes.c_int, _ip]),

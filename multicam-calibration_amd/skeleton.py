@@ -277,3 +277,151 @@ def refine_skeleton_system(points, all_uvs, all_extrinsics, all_intrinsics, *, b
              p(h6), p(g), p(u3), p(d), p(kst), p(fst), p(dc), p(bc), p(tc), p(info), ctypes.addressof(ms))
     return SkeletonSystem(information=np.ascontiguousarray(h6[..., _SYM]), gradient=g, direction=_per_bone_out(u3, child), step=d, data_cost=dc, bone_cost=bc, trial_cost=tc,
                           keypoint_status=kst, frame_status=fst, parent=parent, info=_info(info))
+
+
+@dataclass
+class SkeletonTrajectoryRefinement:
+    points: np.ndarray         # (T, K, 3): NaN for a track whose status is not 1
+    status: np.ndarray         # (K,): a key of trajectory.TRAJECTORY_REFINE_STATUS
+    n_usable: np.ndarray       # (K,): frames two cameras or more see
+    n_single: np.ndarray       # (K,): frames exactly one camera sees
+    converged: bool            # the call stopped on a small step or on nothing accepted, not on the iteration limit alone
+    n_iterations: int          # outer (Gauss-Newton) iterations made
+    cost: float                # the call's objective at the result
+    cost_start: float          # ... at the start
+    history: np.ndarray        # (n_iterations, 4): objective, accepted step, alpha, CG iterations of that solve
+    bone_residual: np.ndarray  # (T, E): (|x_a - x_b| - L) / s at the result, NaN for a bone that was dropped
+    information: np.ndarray    # (T, K, 3, 3): H of the data term at the result (the prior and the bones are rebuilt from accel_std and direction)
+    direction: np.ndarray      # (T, E, 3): the unit vector of every bone from its parent end to its child end (`parent`), NaN where dropped
+    parent: np.ndarray         # (K,): as SkeletonRefinement.parent
+    info: dict                 # kernel_ms, levels, segment, cg_iterations_total, running_tracks, device_bytes
+
+
+@dataclass
+class SkeletonTrajectorySystem:
+    information: np.ndarray    # (T, K, 3, 3): H of the data term at the points
+    gradient: np.ndarray       # (T, K, 3): of the whole objective
+    direction: np.ndarray      # (T, E, 3)
+    step: np.ndarray           # (T, K, 3): the iterate of the preconditioned recurrence for (M + B) d = -G when it ended
+    cg_iterations: int
+    cg_residual: float         # sqrt(r^T z / r0^T z0) of the recurrence when it ended
+    data_cost: float
+    penalty_cost: float
+    bone_cost: float
+    trial_costs: np.ndarray    # (4,): the objective at x + alpha d, alpha = 1, 1/2, 1/4, 1/8
+    status: np.ndarray         # (K,)
+    n_usable: np.ndarray       # (K,)
+    n_single: np.ndarray       # (K,)
+    parent: np.ndarray         # (K,)
+    info: dict
+    resolve_check: np.ndarray = None   # resolve_check=True: (2, T, K, 3), M z = -G by the elimination and again by the re-solve from its factors
+
+
+def _trajectory_arguments(start, all_uvs, all_extrinsics, all_intrinsics, accel_std, bones, bone_length, bone_std, pixel_std, loss, f_scale, weights, cg_tol, cg_max, segment):
+    """_arguments plus what the time prior and the inner solve take: acc (K,), cg_max"""
+    from .trajectory import _check_segment
+    if not callable(loss) and loss in ("cauchy", "arctan"):
+        raise ValueError(f"refine_skeleton_trajectories: loss {loss!r} is not convex -- the backtracking Gauss-Newton loop is for linear, soft_l1 and huber")
+    args = _arguments(start, all_uvs, all_extrinsics, all_intrinsics, bones, bone_length, bone_std, pixel_std, loss, f_scale, weights)
+    K = args[0].shape[1]
+    acc = np.asarray(accel_std, dtype=np.float64)
+    if acc.shape not in ((), (K,)):
+        raise ValueError(f"accel_std must be a scalar or ({K},)")
+    acc = np.ascontiguousarray(np.broadcast_to(acc, (K,)))
+    with np.errstate(over="ignore", divide="ignore"):
+        if not (np.isfinite(acc).all() and (acc > 0).all() and np.isfinite(1.0 / (acc * acc)).all()):
+            raise ValueError("accel_std must be positive and finite")
+    if not 0.0 < cg_tol < 1.0:
+        raise ValueError("cg_tol must lie inside (0, 1)")
+    cg_max = int(cg_max)
+    if cg_max < 1:
+        raise ValueError("cg_max must be at least 1")
+    _check_segment(segment)
+    return args + (acc, cg_max)
+
+
+def _trajectory_info(info8):
+    return {"kernel_ms": float(info8[4]), "levels": int(info8[0]), "segment": int(info8[1]), "cg_iterations_total": int(info8[3]), "running_tracks": int(info8[2]),
+            "device_bytes": int(info8[6])}
+
+
+def refine_skeleton_trajectories(start, all_uvs, all_extrinsics, all_intrinsics, *, accel_std, bones, bone_length, bone_std, pixel_std=1.0, loss="linear", f_scale=3.0, weights=None,
+                                 max_iterations=30, xtol=1e-8, cg_tol=1e-6, cg_max=200, segment=None, device=0):
+    """Refine the K keypoint tracks of a recording together: `refine_trajectories`' fit of every track to its raw detections under the
+    second-difference prior, and `refine_skeleton`'s bones between the keypoints of a frame, in one problem.  Over
+    x_{t,k} of the running tracks, minimise
+
+        0.5 sum_t sum_k sum_{c sees (t,k)} f^2 [rho(ru^2 / f^2) + rho(rv^2 / f^2)] + 0.5 sum_k a_k^-2 sum_t |x_{t-1,k} - 2 x_{t,k} + x_{t+1,k}|^2
+          + 0.5 sum_t sum_{active bones (k, p)} ((|x_{t,k} - x_{t,p}| - L) / s)^2
+
+    Arguments as `refine_trajectories` (start, all_uvs, cameras, accel_std, pixel_std, loss -- linear, soft_l1 or huber --, f_scale, weights,
+    segment) and `refine_skeleton` (bones (E, 2), a forest over at most 64 keypoints, bone_length (E,), bone_std).  A track runs under
+    `refine_trajectories`' rule (two usable frames, a finite start; status as TRAJECTORY_REFINE_STATUS); a bone is active, in every frame, when
+    both its tracks run, and is dropped for the whole call otherwise (bone_residual NaN).  The bone term is always quadratic.
+
+    Gauss-Newton in step form on the call's objective.  The system of an iteration, (M + B) d = -G with M the tracks' block-pentadiagonal
+    matrices and B the bones' terms, is solved by conjugate gradients preconditioned with M: one elimination of the smoother per outer iteration,
+    one re-solve from its factors per CG iteration, until the residual (in the M^-1 norm) has fallen by cg_tol or after cg_max iterations.
+    Every iterate of that recurrence is a descent direction, so the objective never rises however early it ends.  The number of CG iterations
+    grows with the stiffness of the bones against what else holds a keypoint: a few where every keypoint is seen by two cameras, tens through
+    one-camera stretches and unseen gaps at bone_std of the order of the 3-D noise, hundreds for nearly rigid bones.
+    The largest alpha of 1, 1/2, 1/4, 1/8 whose objective is not above the current one is taken (none: the call stops where it is); the call
+    stops when alpha max |d| < xtol max |x| or at max_iterations.  An unseen stretch whose bone direction only the prior holds is a flat valley:
+    such a call can crawl at alpha = 1/8 to the iteration limit and returns converged = False, never worse than its start.  Two calls return the
+    same bits.
+
+    A start at which the objective is not finite (a bone of zero length) gives every running track status -3; a refused pivot of the
+    elimination ends the loop with status -2 on that track.
+
+    ValueError (before a device is touched): the errors of `refine_trajectories` and `refine_skeleton`, cg_tol outside (0, 1), cg_max < 1.  A call
+    that does not fit the device-memory budget MCBA_SMOOTH_BUDGET_MB whole is refused (ops.McbaError): bones couple the tracks, so it cannot run
+    in chunks.  Without a GPU: ops.McbaError -- there is no host path."""
+    pts, uvs, cam, dist, parent, child, L, s, pstd, w, acc, cg_max = _trajectory_arguments(start, all_uvs, all_extrinsics, all_intrinsics, accel_std, bones, bone_length, bone_std, pixel_std,
+                                                                                         loss, f_scale, weights, cg_tol, cg_max, segment)
+    C, T, K = uvs.shape[:3]
+    max_iterations = int(max_iterations)
+    if max_iterations < 1:
+        raise ValueError("max_iterations must be at least 1")
+    if not xtol >= 0:
+        raise ValueError("xtol must not be negative")
+    out, h6, bres, u3 = np.empty((T, K, 3)), np.empty((T, K, 6)), np.empty((T, K)), np.empty((T, K, 3))
+    status, nus, nsg = (np.empty(K, np.int32) for _ in range(3))
+    conv, nit = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    cost, cost0, hist, info = np.empty(1), np.empty(1), np.empty((max_iterations, 4)), np.zeros(8)
+    ms = ctypes.c_double(0.0)
+    p = lambda a: None if a is None else a.ctypes.data
+    ops.call("mcba_refine_skeleton_trajectories", T, K, C, p(uvs), p(cam), p(dist), p(w), p(pstd), p(pts), p(acc), p(parent), p(L), p(s), ops.LOSSES[loss], float(f_scale), max_iterations,
+             float(xtol), float(cg_tol), cg_max, 0 if segment is None else int(segment), int(device), p(out), p(h6), p(status), p(nus), p(nsg), p(conv), p(nit), p(cost), p(cost0), p(hist),
+             p(bres), p(u3), p(info), ctypes.addressof(ms))
+    return SkeletonTrajectoryRefinement(points=out, status=status, n_usable=nus, n_single=nsg, converged=bool(conv[0]), n_iterations=int(nit[0]), cost=float(cost[0]),
+                                        cost_start=float(cost0[0]), history=np.ascontiguousarray(hist[:int(nit[0])]), bone_residual=_per_bone_out(bres, child),
+                                        information=np.ascontiguousarray(h6[..., _SYM]), direction=_per_bone_out(u3, child), parent=parent, info=_trajectory_info(info))
+
+
+def refine_skeleton_trajectories_system(points, all_uvs, all_extrinsics, all_intrinsics, *, accel_std, bones, bone_length, bone_std, pixel_std=1.0, loss="linear", f_scale=3.0, weights=None,
+                                        cg_tol=1e-6, cg_max=200, segment=None, device=0, resolve_check=False):
+    """One evaluation of refine_skeleton_trajectories laid open, at `points` (T, K, 3) and before anything is accepted: the information blocks of
+    the data term, the gradient of the whole objective, the bones' directions, the step the preconditioned recurrence ended at with its
+    iteration count and final relative residual, the three terms of the objective at the points and the objective at x + alpha d for alpha = 1,
+    1/2, 1/4, 1/8 -- what a test holds against a dense oracle.  Arguments, statuses and errors as refine_skeleton_trajectories.
+    resolve_check=True (for tests): also (2, T, K, 3), the solution of M z = -G by the elimination and, after the right-hand-side halves of every
+    stored record were overwritten with NaN, by the re-solve from the stored factors; tracks that do not run are NaN."""
+    pts, uvs, cam, dist, parent, child, L, s, pstd, w, acc, cg_max = _trajectory_arguments(points, all_uvs, all_extrinsics, all_intrinsics, accel_std, bones, bone_length, bone_std, pixel_std,
+                                                                                         loss, f_scale, weights, cg_tol, cg_max, segment)
+    C, T, K = uvs.shape[:3]
+    h6, g, u3, d = np.empty((T, K, 6)), np.empty((T, K, 3)), np.empty((T, K, 3)), np.empty((T, K, 3))
+    status, nus, nsg = (np.empty(K, np.int32) for _ in range(3))
+    cgi, cgr, dc, pc, bc, tc, info = np.zeros(1, np.int32), np.empty(1), np.empty(1), np.empty(1), np.empty(1), np.empty(4), np.zeros(8)
+    if not any(resolve_check is v for v in (False, True)):
+        raise ValueError("resolve_check must be False or True")
+    rs = np.full((2, T, K, 3), np.nan) if resolve_check else None
+    ms = ctypes.c_double(0.0)
+    p = lambda a: None if a is None else a.ctypes.data
+    ops.call("mcba_refine_skeleton_trajectories_system", T, K, C, p(uvs), p(cam), p(dist), p(w), p(pstd), p(pts), p(acc), p(parent), p(L), p(s), ops.LOSSES[loss], float(f_scale),
+             float(cg_tol), cg_max, 0 if segment is None else int(segment), int(device), p(h6), p(g), p(u3), p(d), p(status), p(nus), p(nsg), p(cgi), p(cgr), p(dc), p(pc), p(bc), p(tc),
+             p(rs), p(info), ctypes.addressof(ms))
+    if rs is not None:
+        rs[:, :, status != 1] = np.nan
+    return SkeletonTrajectorySystem(information=np.ascontiguousarray(h6[..., _SYM]), gradient=g, direction=_per_bone_out(u3, child), step=d, cg_iterations=int(cgi[0]),
+                                    cg_residual=float(cgr[0]), data_cost=float(dc[0]), penalty_cost=float(pc[0]), bone_cost=float(bc[0]), trial_costs=tc, status=status, n_usable=nus,
+                                    n_single=nsg, parent=parent, info=_trajectory_info(info), resolve_check=rs)
