@@ -861,6 +861,35 @@ int mcba_smooth_trajectories(size_t n_frames, int n_tracks, const double* points
 int mcba_smooth_covariance(size_t n_frames, int n_tracks, const double* points, const double* cov6, const double* accel_std, const double* weights, int segment, int device,
                            double* out_cov6, double* out_lag9, int* status, int* n_usable, double* info8, double* kernel_ms);
 
+/* ---- The smoother's evidence (Python: trajectory.trajectory_evidence, trajectory.estimate_accel_std).  Stateless,
+ * additive to ABI 7.  Per track, with A(a) the matrix of mcba_smooth_covariance (same points, cov6, usable-frame rule, segment and weights) and
+ * x(a) = A(a)^-1 b its linear solve,
+ *   N(a) = sum_t w_t d_t^2(x) + a^-2 sum_t |x_{t-1} - 2 x_t + x_{t+1}|^2 + log det A(a) + 6 (T - 2) log a
+ * is -2 x the log restricted marginal likelihood of a = accel_std up to a constant in a (T the true frame count; the prior is improper on the
+ * motions linear in time).  log det A is summed from the Cholesky factors the elimination stores, one log per pivot, per-lane partials and a fixed
+ * tree per track: no atomics, the same bits from any chunking (MCBA_SMOOTH_BUDGET_MB).
+ * mcba_smooth_evidence: one evaluation at accel_std (K).  out4 (K, 4) = N, the data term, the penalty, log det A; status (K): 1, -1 fewer than
+ * two usable frames, -2 a refused pivot -- such a track is NaN throughout; n_usable (K); info8 = {levels, segment, tracks per chunk, chunks,
+ * kernel ms, 1, device bytes of a chunk, kernel ms of the per-level log-determinant kernels and the kernel of the final sums}.  MCBA_ERR_ARG as mcba_smooth_covariance. */
+int mcba_smooth_evidence(size_t n_frames, int n_tracks, const double* points, const double* cov6, const double* accel_std, const double* weights, int segment, int device, double* out4,
+                         int* status, int* n_usable, double* info8, double* kernel_ms);
+/* mcba_estimate_accel_std: the a that minimises N, per unit: pool NULL = every track its own unit; else pool (K) labels in 0 .. K - 1, the tracks of
+ * one label share one a and their unit's objective is the sum of its running tracks' N in track order (a NaN -- a pivot refused at that candidate
+ * -- counts as +infinity).  The rule: (1) grid (n_grid = G >= 3 values, u_g = log lo + g (log hi - log lo) / (G - 1), a_g = exp(u_g), a_0 = lo,
+ * a_{G-1} = hi) with g* the first argmin: every candidate NaN gives status -2; g* = 0 gives edge -1 and a = lo, g* = G - 1 edge +1 and a = hi, both
+ * with log_std NaN; (2) otherwise a golden-section search in u = log a on [u_{g*-1}, u_{g*+1}], two first evaluations and then one per round, the
+ * rounds -- the same for every unit -- ending when the bracket is narrower than rtol in [1e-6, 1); the estimate is the evaluated candidate with
+ * the lowest objective, the grid included, the first on a tie; (3) N at u + 0.2 and u - 0.2 gives kappa = (N+ - 2 N0 + N-) / 0.04 and log_std =
+ * sqrt(2 / kappa), NaN unless kappa > 0.  Every pass evaluates every track; n_evaluations (1) = G + 2 + rounds + 2 depends on the arguments alone.
+ * Outputs (K each unless said): out_accel, out_log_std, out_edge, status, n_usable, n_best = the track's N at its estimate; grid (G); n_grid_out
+ * (G, K); info8 as above with [5] = n_evaluations.  The detections are uploaded once per chunk, whatever the number of candidates.
+ * MCBA_ERR_ARG, before any device is touched and with nothing written: the checks of mcba_smooth_evidence, n_frames < 3, not 0 < lo < hi with
+ * finite inverse squares, n_grid < 3, rtol outside [1e-6, 1), a label outside 0 .. K - 1, and a pooled call that does not fit the budget
+ * MCBA_SMOOTH_BUDGET_MB whole (a pool couples the tracks: it cannot run in chunks). */
+int mcba_estimate_accel_std(size_t n_frames, int n_tracks, const double* points, const double* cov6, double accel_lo, double accel_hi, int n_grid, double rtol, const double* weights,
+                            const int* pool, int segment, int device, double* out_accel, double* out_log_std, int* out_edge, int* status, int* n_usable, double* grid, double* n_grid_out,
+                            double* n_best, int* n_evaluations, double* info8, double* kernel_ms);
+
 /* ---- Trajectory refinement (Python: trajectory.refine_trajectories).  Stateless, additive to ABI 7.  Per track k of
  * n_tracks (tracks are independent), frames t = 0 .. T - 1, unknowns x_t in R^3:
  *   minimise 0.5 sum_t sum_{c sees (t,k)} f^2 [rho(ru^2 / f^2) + rho(rv^2 / f^2)] + 0.5 / a_k^2 sum_{t=1}^{T-2} |x_{t-1} - 2 x_t + x_{t+1}|^2,

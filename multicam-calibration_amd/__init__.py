@@ -24,7 +24,8 @@ Only what the hot path needs lives here:
   trajectory.py  smooth_trajectories (the fixed-interval smoother of keypoint tracks: gaps filled, every frame trusted as its covariance says,
              gross errors discounted by a robust loss) -- SURVEY.md section 8f-19; trajectory_uncertainty (the covariance of every
              smoothed point and of neighbouring frames, by selected inversion) -- section 8f-20; refine_trajectories (the tracks refined on
-             the raw detections: Gauss-Newton on the reprojection cost plus the smoothness prior, single-camera frames used) -- section 8f-21
+             the raw detections: Gauss-Newton on the reprojection cost plus the smoothness prior, single-camera frames used) -- section 8f-21;
+             estimate_accel_std and trajectory_evidence (accel_std from the tracks themselves: the maximum of the smoother's evidence) -- section 8f-24
   skeleton.py  refine_skeleton (the keypoints of a frame refined together, joined by bones of known length: a keypoint one camera saw is located,
              the others get tighter) and estimate_bone_lengths (exact medians of the bone lengths and their spread) -- SURVEY.md section 8f-22; refine_skeleton_trajectories (the tracks of a recording refined together: the
              detections, the time prior and the bones in one fit, conjugate gradients preconditioned by the smoother's elimination) -- section 8f-23
@@ -47,6 +48,7 @@ from .detection import detect_chessboard, detect_chessboards, reorder_chessboard
 from .uncertainty import calibration_uncertainty, CalibrationUncertainty, triangulation_uncertainty, TriangulationUncertainty  # noqa: F401
 from . import trajectory  # noqa: F401
 from .trajectory import smooth_trajectories, TrajectorySmoothing, trajectory_uncertainty, TrajectoryUncertainty  # noqa: F401
+from .trajectory import estimate_accel_std, trajectory_evidence, AccelEstimate, TrajectoryEvidence  # noqa: F401
 from .trajectory import refine_trajectories, refine_trajectories_system, TrajectoryRefinement, TrajectoryRefinementSystem, TRAJECTORY_REFINE_STATUS  # noqa: F401
 from . import skeleton  # noqa: F401
 from .skeleton import refine_skeleton, refine_skeleton_system, estimate_bone_lengths, SkeletonRefinement, SkeletonSystem, BoneLengths  # noqa: F401
@@ -63,6 +65,7 @@ __all__ = ["bundle_adjust", "bundle_adjustment", "serialize_params", "deserializ
            "rodrigues", "rodrigues_inv", "get_transformation_matrix", "get_transformation_vector", "get_projection_matrix", "euclidean_to_homogenous", "homogeneous_to_euclidean",
            "calibration_uncertainty", "CalibrationUncertainty", "triangulation_uncertainty", "TriangulationUncertainty",
            "trajectory", "smooth_trajectories", "TrajectorySmoothing", "trajectory_uncertainty", "TrajectoryUncertainty",
+           "estimate_accel_std", "trajectory_evidence", "AccelEstimate", "TrajectoryEvidence",
            "refine_trajectories", "refine_trajectories_system", "TrajectoryRefinement", "TrajectoryRefinementSystem", "TRAJECTORY_REFINE_STATUS",
            "skeleton", "refine_skeleton", "refine_skeleton_system", "estimate_bone_lengths", "SkeletonRefinement", "SkeletonSystem", "BoneLengths",
            "refine_skeleton_trajectories", "refine_skeleton_trajectories_system", "SkeletonTrajectoryRefinement", "SkeletonTrajectorySystem"]

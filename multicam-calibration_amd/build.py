@@ -11,9 +11,9 @@ LIB = os.path.join(PKG, "libmcba.so")
 SOURCES = ["mcba_kernels.hip", "mcba_solve.hip", "mcba_triangulate.hip", "mcba_diag.hip", "mcba_calib.hip", "mcba_pnp.hip", "mcba_flat.hip", "mcba_api.hip", "mcba_lm_api.hip",
            "mcba_prefilter_api.hip", "mcba_calib_api.hip", "mcba_geom_api.hip", "mcba_comm_api.hip", "mcba_sparse.hip", "mcba_sparse_api.hip", "mcba_detect.hip", "mcba_keypoints.hip", "mcba_consensus.hip", "mcba_cov.hip", "mcba_cov_api.hip",
            "mcba_tricov.hip", "mcba_tricov_api.hip", "mcba_kpba.hip", "mcba_kpba_tiled.hip", "mcba_kpba_api.hip", "mcba_kpcam.hip", "mcba_kpcam_api.hip", "mcba_twoview.hip", "mcba_fivepoint.hip", "mcba_twoview_api.hip", "mcba_resect.hip", "mcba_resect_p3p.hip", "mcba_resect_api.hip",
-           "mcba_smooth.hip", "mcba_smooth_api.hip", "mcba_smooth_cov.hip", "mcba_smooth_cov_api.hip", "mcba_traj_refine.hip", "mcba_traj_refine_api.hip",
+           "mcba_smooth.hip", "mcba_smooth_api.hip", "mcba_smooth_cov.hip", "mcba_smooth_cov_api.hip", "mcba_smooth_evidence.hip", "mcba_smooth_evidence_api.hip", "mcba_traj_refine.hip", "mcba_traj_refine_api.hip",
            "mcba_skeleton.hip", "mcba_skeleton_api.hip", "mcba_skeltraj.hip", "mcba_skeltraj_api.hip"]
-DEPS = SOURCES + ["mcba_gram_finish.inc", "mcba_math.h", "mcba_geom_math.h", "mcba_pnp_math.h", "mcba_keypoint_math.h", "mcba_consensus_math.h", "mcba_cov_math.h", "mcba_tricov_math.h", "mcba_kpba_math.h", "mcba_kpcam_math.h", "mcba_detect_math.h", "mcba_twoview_math.h", "mcba_fivepoint_math.h", "mcba_resect_math.h", "mcba_resect_p3p_math.h", "mcba_smooth_math.h", "mcba_smooth_cov_math.h", "mcba_traj_refine_math.h", "mcba_skeleton_math.h", "mcba_skeltraj_math.h", "mcba_smooth_host.h", "mcba_hyp_score.h", "mcba_ransac_host.h", "mcba_device.h", "mcba_quadform.h", "mcba_backsub.h", "mcba_kernels.h", "mcba_gram_plan.h", "mcba_lm.h", "mcba_lm_state.h", "mcba_handle.h", os.path.join("..", "..", "include", "mcba.h")]
+DEPS = SOURCES + ["mcba_gram_finish.inc", "mcba_math.h", "mcba_geom_math.h", "mcba_pnp_math.h", "mcba_keypoint_math.h", "mcba_consensus_math.h", "mcba_cov_math.h", "mcba_tricov_math.h", "mcba_kpba_math.h", "mcba_kpcam_math.h", "mcba_detect_math.h", "mcba_twoview_math.h", "mcba_fivepoint_math.h", "mcba_resect_math.h", "mcba_resect_p3p_math.h", "mcba_smooth_math.h", "mcba_smooth_cov_math.h", "mcba_smooth_evidence_math.h", "mcba_traj_refine_math.h", "mcba_skeleton_math.h", "mcba_skeltraj_math.h", "mcba_smooth_host.h", "mcba_hyp_score.h", "mcba_ransac_host.h", "mcba_device.h", "mcba_quadform.h", "mcba_backsub.h", "mcba_kernels.h", "mcba_gram_plan.h", "mcba_lm.h", "mcba_lm_state.h", "mcba_handle.h", os.path.join("..", "..", "include", "mcba.h")]
 
 
 # Register-pressure-bound kernels (k_gram keeps 87 FP64 accumulators per lane): LLVM's "unclustered high register pressure"

@@ -371,6 +371,13 @@ int launch_smooth_solve(hipStream_t st, const SmLevel* lv, int levels, const SmD
 // down: z[l] = the SM_ZC planes of level l >= 1 (mcba_smooth_cov_math.h), cov6 (T, K, 6), lag9 (T - 1, K, 9) or null
 int launch_smooth_selinv(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, double* const* z, double* cov6, double* lag9, int K, const int* list, int nact);
 
+// ---- the smoother's evidence (mcba_smooth_evidence.hip).  After launch_smooth_reduce and launch_smooth_backsub of the nact
+// tracks of list: res (nact, 4) = sum w d^2, sum |second difference|^2, the sum of log over the stored pivot reciprocals of every factorised block,
+// and 1 where bad (launch_smooth_reduce's flags, K) is set.
+// part: 2 smooth_eval_blocks(T) nact doubles, lane: evidence_lanes() nact doubles of scratch; mark: null or an event recorded ahead of the
+// log-determinant kernels
+int launch_smooth_evidence(hipStream_t st, const SmLevel* lv, int levels, const SmData& td, int K, const int* list, int nact, const int* bad, double* part, double* lane, double* res, hipEvent_t mark);
+
 // ---- trajectory refinement (mcba_traj_refine.hip).  TrData: mcba_traj_refine_math.h, the planes of a chunk of K tracks;
 // cams: a KpCam table in device memory, 1 <= C <= kKpMaxCams; loss: linear, soft_l1 or huber.  Non-zero: arguments out of range
 struct TrData;

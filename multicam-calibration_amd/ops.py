@@ -157,6 +157,10 @@ SYMBOLS = [
                                                 _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     # trajectory uncertainty: every array by address; weights and out_lag9 may be NULL
     ("mcba_smooth_covariance", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    # the smoother's evidence and the estimate of accel_std from it: every array by address; weights and pool may be NULL
+    ("mcba_smooth_evidence", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
+    ("mcba_estimate_accel_std", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, _dp, _dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, _dp, _dp, ctypes.c_int, ctypes.c_int]
+     + [_dp] * 11),
     # trajectory refinement: every array by address; dist5, weights, out_cov6, out_lag9 may be NULL
     ("mcba_refine_trajectories", ctypes.c_int, [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double,
                                                 ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),

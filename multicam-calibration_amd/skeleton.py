@@ -355,7 +355,8 @@ def refine_skeleton_trajectories(start, all_uvs, all_extrinsics, all_intrinsics,
           + 0.5 sum_t sum_{active bones (k, p)} ((|x_{t,k} - x_{t,p}| - L) / s)^2
 
     Arguments as `refine_trajectories` (start, all_uvs, cameras, accel_std, pixel_std, loss -- linear, soft_l1 or huber --, f_scale, weights,
-    segment) and `refine_skeleton` (bones (E, 2), a forest over at most 64 keypoints, bone_length (E,), bone_std).  A track runs under
+    segment) and `refine_skeleton` (bones (E, 2), a forest over at most 64 keypoints, bone_length (E,), bone_std).  accel_std can be had from
+    triangulated tracks with `estimate_accel_std`, as bone_length and bone_std from `estimate_bone_lengths`.  A track runs under
     `refine_trajectories`' rule (two usable frames, a finite start; status as TRAJECTORY_REFINE_STATUS); a bone is active, in every frame, when
     both its tracks run, and is dropped for the whole call otherwise (bone_residual NaN).  The bone term is always quadratic.
 

@@ -1,7 +1,8 @@
 """smooth_trajectories -- the fixed-interval smoother of keypoint tracks: T frames x K keypoints of triangulated points and their per-frame
 covariances in, gap-free tracks out; trajectory_uncertainty -- the covariance of every smoothed point and, on request,
 of neighbouring frames (section 8f-20); refine_trajectories -- the same tracks refined on the raw detections, the maximum-likelihood fit of what
-was measured (section 8f-21).  The smoother fills the frames fewer than two cameras saw, trusts each frame exactly as much
+was measured (section 8f-21); estimate_accel_std and trajectory_evidence -- accel_std, which all of them require, from the tracks themselves:
+the maximum of the smoother's evidence (section 8f-24).  The smoother fills the frames fewer than two cameras saw, trusts each frame exactly as much
 as `triangulation_uncertainty` says, and with a robust loss discounts gross triangulation errors.
 
 The reference has no counterpart (its flatibration tutorial loads keypoints that an outside tool smoothed in time).  Everything runs on the GPU:
@@ -103,6 +104,7 @@ def smooth_trajectories(points, covariance, *, accel_std, loss="linear", f_scale
     points (T, K, 3): p, NaN = missing.  covariance (T, K, 3, 3): Sigma, for example
     `triangulation_uncertainty(...).covariance.reshape(T, K, 3, 3)`; a scalar, (K,) or (T, K) standard deviation means isotropic.
     accel_std: a, the standard deviation of the second difference in the points' unit per frame^2; a scalar or (K,), positive and finite.
+    estimate_accel_std() finds it from the tracks themselves.
     loss: scipy's "linear", "soft_l1" or "huber" rho; f = f_scale is in units of Mahalanobis distance.  "cauchy" and "arctan" are refused:
     the loop below is a majorise-minimise scheme only for a convex rho, and on a scene with 10 % gross errors it settled far from the truth
     (arctan) or did not settle in 30 iterations (cauchy).
@@ -182,7 +184,8 @@ def trajectory_uncertainty(points, covariance, *, accel_std, weights=None, lag=F
 
     For the linear loss (weights=None) Z is the exact posterior covariance under the second-difference prior.  For soft_l1 / huber pass
     weights = result.weights = rho'(d^2 / f^2): Z is then the weighted-least-squares covariance at those weights.  The rho'' term of a
-    Hessian-based covariance is out of scope.  covariance takes the three forms of smooth_trajectories.
+    Hessian-based covariance is out of scope.  covariance takes the three forms of smooth_trajectories.  Every Z is conditional on accel_std:
+    estimate_accel_std() finds it from the tracks themselves.
 
     Everything runs on the GPU: the elimination of the smoother once, then a selected inversion over the same separator tree.  Two calls return
     the same bits, whatever the chunking.  status as in smooth_trajectories; a track of status -1 or -2 is NaN throughout.
@@ -207,6 +210,123 @@ def _uncertainty(pts, cov6, acc, win, lag, segment, device):
     with np.errstate(invalid="ignore"):
         std = np.sqrt(full[..., (0, 1, 2), (0, 1, 2)])
     return TrajectoryUncertainty(covariance=full, std=std, lag_covariance=None if l9 is None else l9.reshape(T - 1, K, 3, 3), status=status, n_usable=nus, info=_info(info))
+
+
+@dataclass
+class TrajectoryEvidence:
+    neg2_log_evidence: np.ndarray  # (K,): N(a) = data + penalty + log_det + 6 (T - 2) log a; NaN unless the status is 1
+    data: np.ndarray               # (K,): sum_t w_t d_t^2 at the linear solve
+    penalty: np.ndarray            # (K,): a^-2 sum_t |x_{t-1} - 2 x_t + x_{t+1}|^2 there
+    log_det: np.ndarray            # (K,): log det A(a)
+    status: np.ndarray             # (K,): a key of TRAJECTORY_STATUS
+    n_usable: np.ndarray           # (K,)
+    info: dict                     # kernel_ms, levels, segment, tracks_per_chunk, chunks, device_bytes, log_det_ms (the log-determinant kernels and the final sums)
+
+
+@dataclass
+class AccelEstimate:
+    accel_std: np.ndarray               # (K,): the estimate, pooled tracks sharing their unit's; NaN unless the status is 1
+    log_std: np.ndarray                 # (K,): the standard deviation of log accel_std from the curvature of N; NaN on an edge or without curvature
+    edge: np.ndarray                    # (K,): -1 the minimum lies on accel_range[0], +1 on accel_range[1], 0 inside
+    status: np.ndarray                  # (K,): a key of TRAJECTORY_STATUS; -2: a pivot was refused at every candidate of the track's unit
+    n_usable: np.ndarray                # (K,)
+    grid: np.ndarray                    # (G,): the candidates of the grid
+    neg2_log_evidence_grid: np.ndarray  # (G, K): every track's N on the grid; NaN where a pivot was refused and for tracks that do not run
+    neg2_log_evidence: np.ndarray       # (K,): the track's N at accel_std
+    n_evaluations: int                  # linear solves per track: n_grid + 2 + rounds + 2
+    info: dict                          # as TrajectoryEvidence.info, and evaluations
+
+
+def _evidence_info(info8):
+    out = _info(info8)
+    out["log_det_ms"] = float(info8[7])
+    return out
+
+
+def trajectory_evidence(points, covariance, *, accel_std, weights=None, segment=None, device=0):
+    """One evaluation of the smoother's evidence laid open.  Per track, with A(a) exactly the matrix of
+    trajectory_uncertainty (same arguments, same usable-frame rule, w_t = weights, 1 by default and 0 on unusable frames), x(a) its linear solve
+    and a = accel_std,
+
+        N(a) = sum_t w_t d_t^2(x) + a^-2 sum_t |x_{t-1} - 2 x_t + x_{t+1}|^2 + log det A(a) + 6 (T - 2) log a
+
+    is -2 x the log restricted marginal likelihood of a, up to a constant in a: the exact evidence of the model of loss="linear", and with
+    weights from a robust run the evidence of the reweighted model.  Returned per track: N, its data term, its penalty and log det A, which is
+    summed on the GPU from the Cholesky factors the elimination stores.  Two calls return the same bits, whatever the chunking.
+    status as in smooth_trajectories; a track of status -1 or -2 is NaN throughout.  ValueError and ops.McbaError as trajectory_uncertainty."""
+    pts, cov6, acc = _track_arguments(points, covariance, accel_std)
+    T, K = pts.shape[:2]
+    win = _weights_argument(weights, "weights", T, K)
+    _check_segment(segment)
+    out4, status, nus, info = np.empty((K, 4)), np.empty(K, np.int32), np.empty(K, np.int32), np.zeros(8)
+    ms = ctypes.c_double(0.0)
+    ops.call("mcba_smooth_evidence", T, K, pts.ctypes.data, cov6.ctypes.data, acc.ctypes.data, None if win is None else win.ctypes.data, 0 if segment is None else int(segment), int(device),
+             out4.ctypes.data, status.ctypes.data, nus.ctypes.data, info.ctypes.data, ctypes.addressof(ms))
+    return TrajectoryEvidence(neg2_log_evidence=out4[:, 0].copy(), data=out4[:, 1].copy(), penalty=out4[:, 2].copy(), log_det=out4[:, 3].copy(), status=status, n_usable=nus,
+                              info=_evidence_info(info))
+
+
+def estimate_accel_std(points, covariance, *, accel_range, n_grid=17, rtol=1e-3, weights=None, pool=None, segment=None, device=0):
+    """Estimate accel_std from the tracks themselves: the value that maximises the smoother's evidence, that is,
+    minimises N(a) of trajectory_evidence.  points, covariance, weights, segment as there.  accel_range = (lo, hi), 0 < lo < hi: the search
+    stays inside it.  pool: None -- every track gets its own estimate; "all" -- one value for every running track; a (K,) array of integer
+    labels -- one value per label; a unit's objective is the sum of its running tracks' N.
+
+    The rule is deterministic: N on a grid of n_grid >= 3 values spaced evenly in log a, its first argmin g*; a golden-section search in log a
+    on the two grid steps around g* until the bracket is narrower than rtol (in [1e-6, 1)); the estimate is the evaluated candidate with the
+    lowest N.  log_std = sqrt(2 / kappa) with kappa the second difference of N at log a +- 0.2: the standard deviation of log accel_std in
+    the Laplace approximation.  A minimum on the first or the last grid value is reported as edge = -1 or +1 with accel_std = lo or hi and
+    log_std NaN: widen the range.  With the defaults that is 17 + 16 + 2 linear solves per track; the detections cross to the GPU once.
+
+    The model is the weighted Gaussian one: no robust loss runs inside the estimator.  For outlier-laden tracks pass
+    weights = smooth_trajectories(..., loss="soft_l1", accel_std=provisional).weights.  The estimate carries over to refine_trajectories and
+    refine_skeleton_trajectories, whose prior is the same.
+
+    status (TRAJECTORY_STATUS): -1 fewer than two usable frames; -2 a pivot was refused at every candidate.  Such a track is NaN.  Two calls
+    return the same bits; an unpooled call also whatever the chunking.  A pooled call runs as one chunk and is refused (ops.McbaError naming
+    MCBA_SMOOTH_BUDGET_MB) when it does not fit the device-memory budget.
+    ValueError (before a device is touched): the errors of trajectory_uncertainty, T < 3 (with two frames the evidence does not depend on
+    accel_std), accel_range not 0 < lo < hi with finite inverse squares, n_grid < 3, rtol outside [1e-6, 1), a pool that is none of the three
+    forms.  Without a GPU: ops.McbaError -- there is no host path."""
+    rng = np.asarray(accel_range, dtype=np.float64)
+    if rng.shape != (2,):
+        raise ValueError("accel_range must be (lo, hi)")
+    lo, hi = float(rng[0]), float(rng[1])
+    with np.errstate(over="ignore", divide="ignore"):
+        if not (np.isfinite(rng).all() and 0 < lo < hi and np.isfinite(1.0 / (rng * rng)).all() and (1.0 / (rng * rng) > 0).all()):
+            raise ValueError("accel_range must be 0 < lo < hi, finite, with finite inverse squares")
+    pts, cov6, _ = _track_arguments(points, covariance, lo)
+    T, K = pts.shape[:2]
+    if T < 3:
+        raise ValueError("estimate_accel_std needs at least 3 frames: with 2 the evidence does not depend on accel_std")
+    n_grid = int(n_grid)
+    if n_grid < 3:
+        raise ValueError("n_grid must be at least 3")
+    if not 1e-6 <= rtol < 1:
+        raise ValueError("rtol must lie in [1e-6, 1)")
+    win = _weights_argument(weights, "weights", T, K)
+    _check_segment(segment)
+    if pool is None:
+        units = None
+    elif isinstance(pool, str):
+        if pool != "all":
+            raise ValueError('pool must be None, "all" or a (K,) array of integer labels')
+        units = np.zeros(K, np.int32)
+    else:
+        lab = np.asarray(pool)
+        if lab.shape != (K,) or lab.dtype.kind not in "iu":
+            raise ValueError(f'pool must be None, "all" or a ({K},) array of integer labels')
+        units = np.ascontiguousarray(np.unique(lab, return_inverse=True)[1].reshape(K), dtype=np.int32)
+    acc, ls, nb = np.empty(K), np.empty(K), np.empty(K)
+    edge, status, nus, nev = np.empty(K, np.int32), np.empty(K, np.int32), np.empty(K, np.int32), np.zeros(1, np.int32)
+    grid, ng, info = np.empty(n_grid), np.empty((n_grid, K)), np.zeros(8)
+    ms = ctypes.c_double(0.0)
+    ops.call("mcba_estimate_accel_std", T, K, pts.ctypes.data, cov6.ctypes.data, lo, hi, n_grid, float(rtol), None if win is None else win.ctypes.data,
+             None if units is None else units.ctypes.data, 0 if segment is None else int(segment), int(device), acc.ctypes.data, ls.ctypes.data, edge.ctypes.data, status.ctypes.data,
+             nus.ctypes.data, grid.ctypes.data, ng.ctypes.data, nb.ctypes.data, nev.ctypes.data, info.ctypes.data, ctypes.addressof(ms))
+    inf = _evidence_info(info)
+    inf["evaluations"] = int(info[5])
+    return AccelEstimate(accel_std=acc, log_std=ls, edge=edge, status=status, n_usable=nus, grid=grid, neg2_log_evidence_grid=ng, neg2_log_evidence=nb, n_evaluations=int(nev[0]), info=inf)
 
 
 @dataclass
@@ -299,7 +419,8 @@ def refine_trajectories(start, all_uvs, all_extrinsics, all_intrinsics, *, accel
 
     start (T, K, 3): where the iteration begins -- the intended start is `smooth_trajectories(...).points`, which has every frame filled.
     all_uvs (C, T, K, 2) or a list of C arrays (T, K, 2): raw detections, NaN = unseen.  all_extrinsics, all_intrinsics: the cameras as
-    `refine_triangulation` takes them (the five-coefficient forward model), at most 64.  accel_std: a, a scalar or (K,).  pixel_std: the
+    `refine_triangulation` takes them (the five-coefficient forward model), at most 64.  accel_std: a, a scalar or (K,); estimate_accel_std()
+    finds it from triangulated tracks, and the estimate carries over because the prior is the same.  pixel_std: the
     detection noise in pixels, a scalar or (C,).  loss: scipy's "linear", "soft_l1" or "huber" rho per scalar residual, f = f_scale in units
     of pixel_std; "cauchy" and "arctan" are refused.  weights: None or (C, T, K) per-detection weights as `refine_triangulation` takes them
     (0 or NaN: the detection is unseen).
