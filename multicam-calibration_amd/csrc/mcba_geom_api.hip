@@ -5,6 +5,13 @@
 
 using namespace mcba_internal;
 
+// the camera table of the keypoint kernels in device memory: for the calls of this file and every other stateless call on keypoints (mcba_handle.h)
+int mcba_internal::upload_kp_cams(StatelessCall& call, int n_cameras, const double* cam12, const double* dist5, mcba::KpCam** d_cams) {
+  std::vector<mcba::KpCam> tab((size_t)n_cameras);
+  for (int c = 0; c < n_cameras; ++c) mcba::make_kp_cam(cam12 + 12 * c, dist5 ? dist5 + 5 * c : nullptr, tab[c]);
+  return call.upload(d_cams, tab.data(), tab.size());
+}
+
 extern "C" {
 
 // undistort_points (reference geometry.py:328-358): stateless; host arrays in, host array out
@@ -85,12 +92,7 @@ int mcba_triangulate(int n_cameras, size_t n_points, const double* uvs, const do
 
 // ---------------------------------------------------------------------------------------------------------
 // Keypoints through a calibration (reference geometry.py:128-152 apply_rigid_transform, :277-325 project_points): stateless; host arrays in and out.
-// the camera table of the keypoint kernels (mcba_keypoint_math.h: KpCam) in device memory
-static int kp_table(StatelessCall& call, int n_cameras, const double* cam12, const double* dist5, mcba::KpCam** d_cams) {
-  std::vector<mcba::KpCam> tab((size_t)n_cameras);
-  for (int c = 0; c < n_cameras; ++c) mcba::make_kp_cam(cam12 + 12 * c, dist5 ? dist5 + 5 * c : nullptr, tab[c]);
-  return call.upload(d_cams, tab.data(), tab.size());
-}
+// (the camera table of the keypoint kernels: upload_kp_cams, above)
 
 int mcba_project_points(int n_cameras, size_t n_points, const double* points, const double* cam12, const double* dist5, int device, double* uvs_out, double* kernel_ms) {
   if (n_cameras < 1 || !points || !cam12 || !uvs_out) return fail(MCBA_ERR_ARG, "mcba_project_points: cameras >= 1, non-NULL arrays required");
@@ -102,7 +104,7 @@ int mcba_project_points(int n_cameras, size_t n_points, const double* points, co
   const size_t nout = (size_t)2 * n_cameras * n_points;
   if (int rc = call.upload(&d_pts, points, 3 * n_points)) return rc;
   if (int rc = call.scratch(&d_out, nout)) return rc;
-  if (int rc = kp_table(call, n_cameras, cam12, dist5, &d_cams)) return rc;
+  if (int rc = upload_kp_cams(call, n_cameras, cam12, dist5, &d_cams)) return rc;
   HIPCHK(call.start());
   for (int c0 = 0; c0 < n_cameras; c0 += mcba::kKpMaxCams) {   // the table of one launch holds kKpMaxCams cameras
     const int nc = std::min(mcba::kKpMaxCams, n_cameras - c0);
@@ -150,7 +152,7 @@ int mcba_keypoint_errors(int n_cameras, size_t n_points, const double* points, c
   if (int rc = call.upload(&d_uv, uvs, nuv)) return rc;
   if (int rc = call.scratch(&d_err, (size_t)n_cameras * npad)) return rc;
   if (int rc = call.scratch(&d_sel, sel.size())) return rc;
-  if (int rc = kp_table(call, n_cameras, cam12, dist5, &d_cams)) return rc;
+  if (int rc = upload_kp_cams(call, n_cameras, cam12, dist5, &d_cams)) return rc;
   HIPCHK(call.start());
   for (int c0 = 0; c0 < n_cameras; c0 += mcba::kKpMaxCams) {
     const int nc = std::min(mcba::kKpMaxCams, n_cameras - c0);
@@ -200,7 +202,7 @@ int mcba_triangulate_refine_weighted(int n_cameras, size_t n_points, const doubl
   if (int rc = call.scratch(&d_out, 3 * n_points)) return rc;
   if (info_out)
     if (int rc = call.scratch(&d_info, 4 * n_points)) return rc;
-  if (int rc = kp_table(call, n_cameras, cam12, dist5, &d_cams)) return rc;
+  if (int rc = upload_kp_cams(call, n_cameras, cam12, dist5, &d_cams)) return rc;
   TriOperands op;
   if (!points_in)
     if (int rc = tri_operands(call, n_cameras, cam12, dist5, op)) return rc;
@@ -217,7 +219,7 @@ int mcba_triangulate_refine_weighted(int n_cameras, size_t n_points, const doubl
 }
 
 // Consensus triangulation (csrc/mcba_consensus.hip): the detections go up once; the search, the refit and the optional errors at the
-// final point run on that copy.  The projection matrices of the hypotheses are derived on the device from the one camera table (kp_table).
+// final point run on that copy.  The projection matrices of the hypotheses are derived on the device from the one camera table (upload_kp_cams).
 int mcba_triangulate_consensus(int n_cameras, size_t n_points, const double* uvs, const double* cam12, const double* dist5, double threshold, int min_views, int undistort_iterations, int loss,
                                double f_scale, int max_iterations, int device, double* points_out, unsigned long long* inliers_out, double* info_out, double* errors_out, double* kernel_ms) {
   if (n_cameras < 2 || n_cameras > 64 || !uvs || !cam12 || !points_out || !inliers_out || undistort_iterations < 0 || max_iterations < 0)
@@ -241,7 +243,7 @@ int mcba_triangulate_consensus(int n_cameras, size_t n_points, const double* uvs
     if (int rc = call.scratch(&d_info, 8 * n_points)) return rc;
   if (errors_out)
     if (int rc = call.scratch(&d_err, (size_t)n_cameras * n_points)) return rc;
-  if (int rc = kp_table(call, n_cameras, cam12, dist5, &d_cams)) return rc;
+  if (int rc = upload_kp_cams(call, n_cameras, cam12, dist5, &d_cams)) return rc;
   HIPCHK(call.start());
   if (mcba::launch_consensus(nullptr, mcba::CONSENSUS_AUTO, loss, d_uv, n_points, d_cams, n_cameras, threshold, min_views, undistort_iterations, f_scale, max_iterations, d_out, d_mask, d_hyp, d_info) != 0)
     return fail(MCBA_ERR_ARG, "mcba_triangulate_consensus: bad launch (MCBA_CONSENSUS_FORM, if set, must be lane, wave or lane2)");

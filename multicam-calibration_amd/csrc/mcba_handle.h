@@ -233,11 +233,11 @@ inline int lds_optin_of(int device) {
 // an MCBA_* code with g_err set; counts are elements of T, the type of both the host and the device side; start / stop time the call's kernels
 struct StatelessCall {
   std::vector<void*> bufs;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   ~StatelessCall() {
     for (void* b : bufs) (void)hipFree(b);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    for (hipEvent_t e : {e0, e1, e2})
+      if (e) (void)hipEventDestroy(e);
   }
   template <class T>
   int alloc(T** p, size_t count, bool poison) {
@@ -270,6 +270,25 @@ struct StatelessCall {
     HIPCHK(hipMemcpy(host, src, count * sizeof(T), hipMemcpyDeviceToHost));
     return MCBA_OK;
   }
+  // ---- timed brackets of a call with many of them (e0 and e1 created by the call): open() before the launches; close() checks them, waits for
+  // them and adds their time to sum.  A bracket whose last part is timed on its own has mark() between the parts -- or a launcher that records
+  // e1 there itself -- and closes with close_split(), which adds the time after the mark to part as well; e2, its end, is made by the first
+  // open(true), ahead of the bracket, so that nothing but the launches lies between its events
+  int open(bool split = false) {
+    if (split && !e2) HIPCHK(hipEventCreate(&e2));
+    HIPCHK(hipEventRecord(e0, nullptr));
+    return MCBA_OK;
+  }
+  int mark() { HIPCHK(hipEventRecord(e1, nullptr)); return MCBA_OK; }
+  int close(double& sum) {
+    if (int rc = mark_launches(e1)) return rc;
+    return add_ms(e0, e1, sum);
+  }
+  int close_split(double& sum, double& part) {
+    if (int rc = mark_launches(e2)) return rc;
+    if (int rc = add_ms(e0, e2, sum)) return rc;
+    return add_ms(e1, e2, part);
+  }
   hipError_t start() {
     hipError_t e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
@@ -285,6 +304,20 @@ struct StatelessCall {
       *kernel_ms = ms;
     }
     return e;
+  }
+
+ private:
+  int mark_launches(hipEvent_t end) {
+    if (int rc = check_launch()) return rc;
+    HIPCHK(hipEventRecord(end, nullptr));
+    HIPCHK(hipEventSynchronize(end));
+    return MCBA_OK;
+  }
+  int add_ms(hipEvent_t from, hipEvent_t to, double& sum) {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, from, to));
+    sum += ms;
+    return MCBA_OK;
   }
 };
 
@@ -333,6 +366,61 @@ inline int upload_sqrt_weights(StatelessCall& call, const double* weights, size_
   std::vector<double> sq(count);
   for (size_t i = 0; i < count; ++i) sq[i] = weights[i] > 0.0 ? sqrt(weights[i]) : 0.0;
   return call.upload(d_sw, sq.data(), count);
+}
+
+// the camera table of the keypoint kernels (mcba_keypoint_math.h: KpCam, one per camera of cam12 and dist5 or NULL) in device memory (mcba_geom_api.hip)
+int upload_kp_cams(StatelessCall& call, int n_cameras, const double* cam12, const double* dist5, mcba::KpCam** d_cams);
+
+// The argument checks that the calls on detections of tracks and skeletons (mcba_traj_refine_api.hip, mcba_skeltraj_api.hip,
+// mcba_skeleton_api.hip) make alike.  Each is a run of checks that stands at the same place in every caller's order, so the message of the
+// first thing wrong is the same as if the caller had written them out; what differs between the callers is checked by them, through bad()
+struct DetectionChecks {
+  const char* who;
+  int bad(const char* what) const { g_err = std::string(who) + ": " + what; return MCBA_ERR_ARG; }
+  static bool finite(double v) { return v - v == 0.0; }
+  // k_max, c_max: SK_MAX_K and kKpMaxCams, the 64 of the messages
+  int frames_keypoints(size_t T, int K, int k_max) const {
+    if (T < 1 || T > ((size_t)1 << 31)) return bad("1 .. 2^31 frames required");
+    if (K < 1 || K > k_max) return bad("1 .. 64 keypoints required");
+    return MCBA_OK;
+  }
+  // arrays: every input array that may not be NULL is there
+  int cameras_arrays(int C, int c_max, bool arrays) const {
+    if (C < 1 || C > c_max) return bad("1 .. 64 cameras required");
+    if (!arrays) return bad("non-NULL arrays (but dist5 and weights) required");
+    return MCBA_OK;
+  }
+  int convex_loss(int loss) const {
+    if (loss < mcba::LOSS_LINEAR || loss > mcba::LOSS_HUBER) return bad("loss must be linear, soft_l1 or huber (0 .. 2)");
+    return MCBA_OK;
+  }
+  int loop(double f_scale, int max_iterations, double xtol) const {
+    if (!(f_scale > 0.0) || !finite(f_scale)) return bad("f_scale must be positive and finite");
+    if (max_iterations < 1) return bad("max_iterations >= 1");
+    if (!(xtol >= 0.0)) return bad("xtol >= 0");
+    return MCBA_OK;
+  }
+  int pixel_std(const double* std, int C) const {
+    for (int c = 0; c < C; ++c)
+      if (!(std[c] > 0.0) || !finite(std[c]) || !finite(1.0 / std[c])) return bad("pixel_std must be positive and finite (and its inverse too)");
+    return MCBA_OK;
+  }
+  // rc: what skel_plan (mcba_skeleton_math.h) returned for the forest
+  int forest(int rc) const {
+    switch (rc) {
+      case 0: return MCBA_OK;
+      case 2: return bad("a parent outside -1 .. K - 1, or a keypoint that is its own parent");
+      case 3: return bad("the parents form a cycle: the skeleton must be a forest");
+      default: return bad("bone_length and bone_std must be positive and finite for every keypoint with a parent");
+    }
+  }
+};
+
+// info8 and *kernel_ms (or NULL) of a trajectory or skeleton call, slot by slot
+inline void fill_info8(double* info8, double* kernel_ms, double levels, double width, double s2, double s3, double ms, double s5, double device_bytes, double s7) {
+  const double v[8] = {levels, width, s2, s3, ms, s5, device_bytes, s7};
+  for (int i = 0; i < 8; ++i) info8[i] = v[i];
+  if (kernel_ms) *kernel_ms = ms;
 }
 
 inline int slot_ok(const mcba_handle* h, int slot) { return h && (slot == 0 || slot == 1); }

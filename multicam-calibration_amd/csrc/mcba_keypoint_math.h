@@ -114,6 +114,20 @@ MCBA_HD void kp_scale_pair(double s, double& a, double& b) {
   if (WEIGHTED) { a *= s; b *= s; }
 }
 
+// The weight plane of the calls that take a pixel_std per camera (host only): what those kernels read as sw beside a detection is
+// sqrt(w) / pixel_std[c], 0 for a zero or NaN weight (unseen).  One sub-box of the (C, T, K) array weights (NULL: every w = 1) -- frames
+// t0 .. t0 + tc - 1, tracks k0 .. k0 + kc - 1 -- into out (C, tc, kc).  1 / pixel_std[c] is formed first and then multiplied
+inline void kp_weight_box(const double* weights, const double* pixel_std, int C, size_t T, size_t K, size_t t0, size_t tc, size_t k0, size_t kc, double* out) {
+  for (int c = 0; c < C; ++c) {
+    const double ips = 1.0 / pixel_std[c];
+    for (size_t t = 0; t < tc; ++t)
+      for (size_t k = 0; k < kc; ++k) {
+        const double w = weights ? weights[((size_t)c * T + t0 + t) * K + k0 + k] : 1.0;
+        out[((size_t)c * tc + t) * kc + k] = w > 0.0 ? sqrt(w) * ips : 0.0;
+      }
+  }
+}
+
 // ---- refinement of one point: minimise 0.5 sum rho(f^2) over X, f = the 2 (cameras that see it) scalars detection - projection (pixels), rho and
 // f_scale scipy's (loss_weights).  observation(c, ou, ov) hands out the point's detection in camera c (with a fourth argument: and sqrt(w)).
 // One linearisation at X: packed Gauss-Newton matrix H (00 01 02 11 12 22) with the curvature weights of the bundle-adjustment tick

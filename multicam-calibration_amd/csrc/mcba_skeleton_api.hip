@@ -1,7 +1,8 @@
 // mcba_skeleton_api.hip -- the stateless skeleton calls of include/mcba.h (host arrays in, host arrays out, a device ordinal, no handle), in the
 // idiom of mcba_traj_refine_api.hip.  Frames are independent, so a call runs them in chunks of whole frames under a device-memory budget; the
 // forest plan (order, levels, child lists) is derived and checked here, before a device is touched, by skel_plan (mcba_skeleton_math.h).  One
-// launch per chunk: the whole Levenberg-Marquardt loop of a frame runs inside k_skel_refine.
+// launch per chunk: the whole Levenberg-Marquardt loop of a frame runs inside k_skel_refine.  The argument checks it has in common with the
+// trajectory calls, the camera table and the timed bracket are those of mcba_handle.h; the weight plane is kp_weight_box (mcba_keypoint_math.h).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -39,24 +40,14 @@ struct SkelOut {
 };
 
 int skel_check(const char* who, const SkelIn& in, mcba::SkPlan& plan) {
-  auto bad = [&](const char* what) { g_err = std::string(who) + ": " + what; return MCBA_ERR_ARG; };
-  if (in.T < 1 || in.T > ((size_t)1 << 31)) return bad("1 .. 2^31 frames required");
-  if (in.K < 1 || in.K > mcba::SK_MAX_K) return bad("1 .. 64 keypoints required");
-  if (in.C < 1 || in.C > mcba::kKpMaxCams) return bad("1 .. 64 cameras required");
-  if (!in.uvs || !in.cam12 || !in.pixel_std || !in.start || !in.parent || !in.bone_length || !in.bone_std) return bad("non-NULL arrays (but dist5 and weights) required");
-  if (in.loss < mcba::LOSS_LINEAR || in.loss > mcba::LOSS_ARCTAN) return bad("loss must be one of linear, soft_l1, huber, cauchy, arctan (0 .. 4)");
-  if (!(in.f_scale > 0.0) || !mcba::sk_finite(in.f_scale)) return bad("f_scale must be positive and finite");
-  if (in.max_iterations < 1) return bad("max_iterations >= 1");
-  if (!(in.xtol >= 0.0)) return bad("xtol >= 0");
-  if (!(in.lam >= 0.0) || !mcba::sk_finite(in.lam)) return bad("the damping must be finite and not negative");
-  for (int c = 0; c < in.C; ++c)
-    if (!(in.pixel_std[c] > 0.0) || !mcba::sk_finite(in.pixel_std[c]) || !mcba::sk_finite(1.0 / in.pixel_std[c])) return bad("pixel_std must be positive and finite (and its inverse too)");
-  switch (mcba::skel_plan(in.K, in.parent, in.bone_length, in.bone_std, plan)) {
-    case 0: break;
-    case 2: return bad("a parent outside -1 .. K - 1, or a keypoint that is its own parent");
-    case 3: return bad("the parents form a cycle: the skeleton must be a forest");
-    default: return bad("bone_length and bone_std must be positive and finite for every keypoint with a parent");
-  }
+  const DetectionChecks ck{who};
+  if (int rc = ck.frames_keypoints(in.T, in.K, mcba::SK_MAX_K)) return rc;
+  if (int rc = ck.cameras_arrays(in.C, mcba::kKpMaxCams, in.uvs && in.cam12 && in.pixel_std && in.start && in.parent && in.bone_length && in.bone_std)) return rc;
+  if (in.loss < mcba::LOSS_LINEAR || in.loss > mcba::LOSS_ARCTAN) return ck.bad("loss must be one of linear, soft_l1, huber, cauchy, arctan (0 .. 4)");
+  if (int rc = ck.loop(in.f_scale, in.max_iterations, in.xtol)) return rc;
+  if (!(in.lam >= 0.0) || !mcba::sk_finite(in.lam)) return ck.bad("the damping must be finite and not negative");
+  if (int rc = ck.pixel_std(in.pixel_std, in.C)) return rc;
+  if (int rc = ck.forest(mcba::skel_plan(in.K, in.parent, in.bone_length, in.bone_std, plan))) return rc;
   return check_weights(who, in.weights, (size_t)in.C * in.T * in.K);
 }
 
@@ -77,9 +68,7 @@ int skel_run(const char* who, const SkelIn& in, const SkelOut& out, const mcba::
   StatelessCall call;
   mcba::KpCam* d_cams = nullptr;
   mcba::SkPlan* d_plan = nullptr;
-  std::vector<mcba::KpCam> tab((size_t)C);
-  for (int c = 0; c < C; ++c) mcba::make_kp_cam(in.cam12 + 12 * c, in.dist5 ? in.dist5 + 5 * c : nullptr, tab[c]);
-  if (int rc = call.upload(&d_cams, tab.data(), tab.size())) return rc;
+  if (int rc = upload_kp_cams(call, C, in.cam12, in.dist5, &d_cams)) return rc;
   if (int rc = call.upload(&d_plan, &plan, 1)) return rc;
   double *d_det = nullptr, *d_sw = nullptr, *d_x = nullptr, *d_pts = nullptr, *d_cost = nullptr, *d_cost0 = nullptr, *d_bres = nullptr, *d_cov = nullptr, *d_info = nullptr, *d_dir = nullptr,
          *d_grad = nullptr, *d_step = nullptr, *d_dc = nullptr, *d_bc = nullptr, *d_tc = nullptr;
@@ -117,13 +106,7 @@ int skel_run(const char* who, const SkelIn& in, const SkelOut& out, const mcba::
     const size_t t0 = c0 * Tc, tc = std::min(Tc, T - t0), tk = tc * K;
     // the chunk's planes: detections (C, tc K) pairs, sqrt(w) / pixel_std beside them, the start
     h_sw.resize(C * tk);
-    for (int cc = 0; cc < C; ++cc) {
-      const double ips = 1.0 / in.pixel_std[cc];
-      for (size_t i = 0; i < tk; ++i) {
-        const double w = in.weights ? in.weights[(cc * T + t0) * K + i] : 1.0;
-        h_sw[cc * tk + i] = w > 0.0 ? sqrt(w) * ips : 0.0;   // (a zero or NaN weight: unseen)
-      }
-    }
+    mcba::kp_weight_box(in.weights, in.pixel_std, C, T, K, t0, tc, 0, K, h_sw.data());
     HIPCHK(hipMemcpy2D(d_det, 2 * tk * sizeof(double), in.uvs + 2 * t0 * K, 2 * T * K * sizeof(double), 2 * tk * sizeof(double), (size_t)C, hipMemcpyHostToDevice));
     if (int rc = call.put(d_sw, h_sw.data(), C * tk)) return rc;
     if (int rc = call.put(d_x, in.start + 3 * t0 * K, 3 * tk)) return rc;
@@ -133,14 +116,9 @@ int skel_run(const char* who, const SkelIn& in, const SkelOut& out, const mcba::
     a.max_iterations = out.system ? 1 : in.max_iterations; a.system = out.system ? 1 : 0; a.cov = cov ? 1 : 0;
     a.points = d_pts; a.kstatus = d_kst; a.fstatus = d_fst; a.nit = d_nit; a.cost = d_cost; a.cost0 = d_cost0; a.bone_res = d_bres; a.info6 = d_info; a.dir = d_dir; a.cov6 = d_cov;
     a.grad = d_grad; a.step = d_step; a.data_cost = d_dc; a.bone_cost = d_bc; a.trial_cost = d_tc;
-    HIPCHK(hipEventRecord(call.e0, nullptr));
+    if (int rc = call.open()) return rc;
     if (mcba::launch_skel_refine(nullptr, in.loss, a, d_plan, in.K, d_cams, C) != 0) return fail(MCBA_ERR_ARG, "skeleton refinement: bad launch");
-    if (int rc = check_launch()) return rc;
-    HIPCHK(hipEventRecord(call.e1, nullptr));
-    HIPCHK(hipEventSynchronize(call.e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, call.e0, call.e1));
-    ms_total += ms;
+    if (int rc = call.close(ms_total)) return rc;
     if (int rc = call.download(out.kstatus + t0 * K, d_kst, tk)) return rc;
     if (int rc = call.download(out.fstatus + t0, d_fst, tc)) return rc;
     if (out.system) {
@@ -163,10 +141,7 @@ int skel_run(const char* who, const SkelIn& in, const SkelOut& out, const mcba::
       if (int rc = call.download(out.dir + 3 * t0 * K, d_dir, 3 * tk)) return rc;
     }
   }
-  double* info8 = out.info8;
-  info8[0] = plan.levels; info8[1] = mcba::skel_frames_per_group(in.K); info8[2] = (double)Tc; info8[3] = (double)nchunks; info8[4] = ms_total; info8[5] = out.system ? 1 : most;
-  info8[6] = (double)per_frame * (double)Tc; info8[7] = 0.0;
-  if (out.kernel_ms) *out.kernel_ms = ms_total;
+  fill_info8(out.info8, out.kernel_ms, plan.levels, mcba::skel_frames_per_group(in.K), (double)Tc, (double)nchunks, ms_total, out.system ? 1 : most, (double)per_frame * (double)Tc, 0.0);
   return MCBA_OK;
 }
 

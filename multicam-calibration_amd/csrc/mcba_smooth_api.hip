@@ -1,7 +1,7 @@
 // mcba_smooth_api.hip -- the stateless trajectory-smoothing call of include/mcba.h (host arrays in, host arrays out, a device ordinal, no handle),
-// in the idiom of mcba_tricov_api.hip.  The walk over chunks of tracks is SmoothChunks of mcba_smooth_host.h.  The IRLS loop is here: per
-// iteration the kernels of mcba_smooth.hip back to back and one small download (four doubles and a flag per running track), as
-// mcba_refine_extrinsics does.
+// in the idiom of mcba_tricov_api.hip.  The walk over chunks of tracks and the timed brackets are SmoothChunks of mcba_smooth_host.h.  The
+// IRLS loop is here: per iteration the kernels of mcba_smooth.hip back to back and one small download (four doubles and a flag per running
+// track), as mcba_refine_extrinsics does.
 #include "mcba_smooth_host.h"
 
 using namespace mcba_internal;
@@ -57,12 +57,9 @@ int mcba_smooth_trajectories(size_t n_frames, int n_tracks, const double* points
     for (int it = 0; it < max_iterations && !h_list.empty(); ++it) {
       const int nact = (int)h_list.size();
       if (int rc = call.put(ch.d_list, h_list.data(), (size_t)nact)) return rc;
-      HIPCHK(hipEventRecord(call.e0, nullptr));
+      if (int rc = ch.open()) return rc;
       if (mcba::launch_smooth_solve(nullptr, ch.lv, ch.levels, td, kc, ch.d_list, nact, ch.d_bad, d_part, d_res) != 0) return fail(MCBA_ERR_ARG, "mcba_smooth_trajectories: bad launch");
-      if (int rc = check_launch()) return rc;
-      HIPCHK(hipEventRecord(call.e1, nullptr));
-      HIPCHK(hipEventSynchronize(call.e1));
-      if (int rc = ch.add_ms(call.e0, call.e1, ch.ms_total)) return rc;
+      if (int rc = ch.close()) return rc;
       if (int rc = call.download(h_res.data(), d_res, (size_t)4 * nact)) return rc;
       if (int rc = call.download(h_bad.data(), ch.d_bad, (size_t)kc)) return rc;
       most_solves = std::max(most_solves, it + 1);
@@ -92,9 +89,7 @@ int mcba_smooth_trajectories(size_t n_frames, int n_tracks, const double* points
       ch.scatter(k, ok, h_d2.data(), 1, out_d2, nan);
     }
   }
-  info8[0] = ch.levels; info8[1] = segment; info8[2] = Kc; info8[3] = ch.nchunks; info8[4] = ch.ms_total; info8[5] = most_solves;
-  info8[6] = (double)mcba::smooth_chunk_doubles(T, Kc, segment) * sizeof(double); info8[7] = 0.0;
-  if (kernel_ms) *kernel_ms = ch.ms_total;
+  ch.info(info8, kernel_ms, Kc, ch.nchunks, most_solves, (double)mcba::smooth_chunk_doubles(T, Kc, segment) * sizeof(double), 0.0);
   return MCBA_OK;
 }
 

@@ -30,7 +30,6 @@ int mcba_smooth_covariance(size_t n_frames, int n_tracks, const double* points, 
   double *d_oc = nullptr, *d_ol = nullptr;
   if (int rc = call.scratch(&d_oc, 6 * T * Kc)) return rc;
   if (lag) if (int rc = call.scratch(&d_ol, 9 * (T - 1) * Kc)) return rc;
-  HIPCHK(hipEventCreate(&ch.e2));
 
   std::vector<double> h_oc, h_ol;
   std::vector<int> h_bad;
@@ -45,16 +44,12 @@ int mcba_smooth_covariance(size_t n_frames, int n_tracks, const double* points, 
     if (!ch.h_list.empty()) {
       const int nact = (int)ch.h_list.size();
       if (int rc = call.put(ch.d_list, ch.h_list.data(), (size_t)nact)) return rc;
-      HIPCHK(hipEventRecord(call.e0, nullptr));
+      if (int rc = ch.open(true)) return rc;
       if (mcba::launch_smooth_reduce(nullptr, ch.lv, ch.levels, ch.td, kc, ch.d_list, nact, ch.d_bad) != 0) return fail(MCBA_ERR_ARG, "mcba_smooth_covariance: bad launch");
       if (int rc = check_launch()) return rc;
-      HIPCHK(hipEventRecord(call.e1, nullptr));
+      if (int rc = ch.mark()) return rc;
       if (mcba::launch_smooth_selinv(nullptr, ch.lv, ch.levels, ch.td, ch.aux, d_oc, lag ? d_ol : nullptr, kc, ch.d_list, nact) != 0) return fail(MCBA_ERR_ARG, "mcba_smooth_covariance: bad launch");
-      if (int rc = check_launch()) return rc;
-      HIPCHK(hipEventRecord(ch.e2, nullptr));
-      HIPCHK(hipEventSynchronize(ch.e2));
-      if (int rc = ch.add_ms(call.e0, ch.e2, ch.ms_total)) return rc;
-      if (int rc = ch.add_ms(call.e1, ch.e2, ms_selinv)) return rc;
+      if (int rc = ch.close_split(ms_selinv)) return rc;
       if (int rc = call.download(h_bad.data(), ch.d_bad, (size_t)kc)) return rc;
       if (int rc = call.download(h_oc.data(), d_oc, 6 * tk)) return rc;
       if (lag && lk) if (int rc = call.download(h_ol.data(), d_ol, 9 * lk)) return rc;
@@ -67,9 +62,7 @@ int mcba_smooth_covariance(size_t n_frames, int n_tracks, const double* points, 
       if (lag) ch.scatter(k, st == mcba::SM_OK, h_ol.data(), 9, out_lag9, nan, T - 1);
     }
   }
-  info8[0] = ch.levels; info8[1] = segment; info8[2] = Kc; info8[3] = ch.nchunks; info8[4] = ch.ms_total; info8[5] = 1.0;
-  info8[6] = (double)mcba::smooth_cov_chunk_doubles(T, Kc, segment, lag) * sizeof(double); info8[7] = ms_selinv;
-  if (kernel_ms) *kernel_ms = ch.ms_total;
+  ch.info(info8, kernel_ms, Kc, ch.nchunks, 1.0, (double)mcba::smooth_cov_chunk_doubles(T, Kc, segment, lag) * sizeof(double), ms_selinv);
   return MCBA_OK;
 }
 

@@ -1,9 +1,10 @@
 // mcba_smooth_evidence_api.hip -- the stateless evidence calls of include/mcba.h (host arrays in, host arrays out, a device
 // ordinal, no handle), in the idiom of mcba_smooth_api.hip: tracks run in chunks under the same device-memory budget (SmoothChunks of
-// mcba_smooth_host.h).  Per chunk the detections are uploaded and prepared once; per candidate accel_std the chunk gets its 1 / a^2, the smoother's
-// elimination and back-substitution, the kernels of mcba_smooth_evidence.hip and one small download (four doubles per running track).  The
-// search of mcba_estimate_accel_std is evidence_search of mcba_smooth_evidence_math.h, decided on the host between candidates.  A pooled call
-// couples its tracks: it is one chunk and is refused, before anything is allocated, when it does not fit the budget.
+// mcba_smooth_host.h).  Per chunk the detections are uploaded and prepared once; per candidate accel_std the chunk gets its 1 / a^2
+// (SmoothChunks::set_accel: the walk itself is given no accel_std), the smoother's elimination and back-substitution, the kernels of
+// mcba_smooth_evidence.hip and one small download (four doubles per running track).  The search of mcba_estimate_accel_std is evidence_search
+// of mcba_smooth_evidence_math.h, decided on the host between candidates.  A pooled call couples its tracks: it is one chunk and is refused,
+// before anything is allocated, when it does not fit the budget.
 #include "mcba_smooth_host.h"
 #include "mcba_smooth_evidence_math.h"
 
@@ -15,17 +16,16 @@ namespace {
 struct EvidenceChunks {
   SmoothChunks ch;
   size_t T = 0;
-  int nblk = 0, evaluations = 0;
+  int nblk = 0;
   size_t lanes = 0;
   double *d_x = nullptr, *d_d2 = nullptr, *d_dx = nullptr, *d_w2 = nullptr, *d_part = nullptr, *d_lane = nullptr, *d_res = nullptr;
   double ms_logdet = 0.0;
   mcba::SmData td{}, tdb{};   // the elimination's and the evaluation's view (w = the weights given), the back-substitution's (w = a plane to overwrite)
-  std::vector<double> h_res, ones;
+  std::vector<double> h_res;
 
   int setup(const char* who, size_t T_, size_t K, int segment, const double* points, const double* cov6, const double* weights) {
     T = T_;
-    ones.assign(K, 1.0);   // (SmoothChunks uploads 1 / a^2 of an array per chunk: every candidate replaces it)
-    if (int rc = ch.setup(who, T, K, segment, points, cov6, ones.data(), weights, mcba::evidence_chunk_doubles(T, 1, segment), 6)) return rc;
+    if (int rc = ch.setup(who, T, K, segment, points, cov6, nullptr, weights, mcba::evidence_chunk_doubles(T, 1, segment), 6)) return rc;
     const size_t TK = T * ch.Kc;
     nblk = mcba::smooth_eval_blocks(T);
     lanes = mcba::evidence_lanes(ch.lv, mcba::smooth_plan(T, segment, ch.Kc, ch.lv));
@@ -37,7 +37,6 @@ struct EvidenceChunks {
     if (int rc = call.scratch(&d_part, (size_t)2 * nblk * ch.Kc)) return rc;
     if (int rc = call.scratch(&d_lane, lanes * ch.Kc)) return rc;
     if (int rc = call.scratch(&d_res, (size_t)mcba::EV_RES * ch.Kc)) return rc;
-    HIPCHK(hipEventCreate(&ch.e2));
     return MCBA_OK;
   }
 
@@ -54,8 +53,8 @@ struct EvidenceChunks {
     return MCBA_OK;
   }
 
-  // one candidate of the chunk begin() left: a (kc) -> out4 (kc, 4) = N, data, penalty, log det; NaN for a track that does not run or whose
-  // pivot was refused at this candidate (refused[k] = 1)
+  // one candidate of the chunk begin() left: a (kc, positive at every track) -> out4 (kc, 4) = N, data, penalty, log det; NaN for a track
+  // that does not run or whose pivot was refused at this candidate (refused[k] = 1)
   int evaluate(const double* a, double* out4, int* refused) {
     const int kc = ch.kc, nact = (int)ch.h_list.size();
     const double nan = __builtin_nan("");
@@ -63,22 +62,14 @@ struct EvidenceChunks {
     for (int k = 0; k < kc; ++k) refused[k] = 0;
     if (nact == 0) return MCBA_OK;
     StatelessCall& call = ch.call;
-    ch.h_ia2.assign(kc, 1.0);
-    for (int kk = 0; kk < nact; ++kk) ch.h_ia2[ch.h_list[kk]] = 1.0 / (a[ch.h_list[kk]] * a[ch.h_list[kk]]);
-    if (int rc = call.put(ch.d_ia2, ch.h_ia2.data(), (size_t)kc)) return rc;
-    HIPCHK(hipMemset(ch.d_bad, 0, kc * sizeof(int)));
-    HIPCHK(hipEventRecord(call.e0, nullptr));
+    if (int rc = ch.set_accel(a)) return rc;
+    if (int rc = ch.open(true)) return rc;
     if (mcba::launch_smooth_reduce(nullptr, ch.lv, ch.levels, td, kc, ch.d_list, nact, ch.d_bad) != 0) return fail(MCBA_ERR_ARG, "smoother evidence: bad launch");
     if (mcba::launch_smooth_backsub(nullptr, ch.lv, ch.levels, tdb, kc, ch.d_list, nact) != 0) return fail(MCBA_ERR_ARG, "smoother evidence: bad launch");
     if (mcba::launch_smooth_evidence(nullptr, ch.lv, ch.levels, td, kc, ch.d_list, nact, ch.d_bad, d_part, d_lane, d_res, call.e1) != 0) return fail(MCBA_ERR_ARG, "smoother evidence: bad launch");
-    if (int rc = check_launch()) return rc;
-    HIPCHK(hipEventRecord(ch.e2, nullptr));
-    HIPCHK(hipEventSynchronize(ch.e2));
-    if (int rc = ch.add_ms(call.e0, ch.e2, ch.ms_total)) return rc;
-    if (int rc = ch.add_ms(call.e1, ch.e2, ms_logdet)) return rc;
+    if (int rc = ch.close_split(ms_logdet)) return rc;   // (the mark: launch_smooth_evidence records e1 ahead of the log-determinant)
     h_res.resize((size_t)mcba::EV_RES * nact);
     if (int rc = call.download(h_res.data(), d_res, (size_t)mcba::EV_RES * nact)) return rc;
-    ++evaluations;
     for (int kk = 0; kk < nact; ++kk) {
       const int k = ch.h_list[kk];
       if (h_res[(size_t)mcba::EV_RES * kk + 3] != 0.0) { refused[k] = 1; continue; }
@@ -87,9 +78,9 @@ struct EvidenceChunks {
     return MCBA_OK;
   }
 
-  void info(double* info8, int segment) const {
-    info8[0] = ch.levels; info8[1] = segment; info8[2] = ch.Kc; info8[3] = ch.nchunks; info8[4] = ch.ms_total; info8[5] = evaluations;
-    info8[6] = (double)mcba::evidence_chunk_doubles(T, ch.Kc, segment) * sizeof(double); info8[7] = ms_logdet;
+  // n_eval: the evaluations of one track, as the entry counts them
+  void info(double* info8, double* kernel_ms, int n_eval) const {
+    ch.info(info8, kernel_ms, ch.Kc, ch.nchunks, n_eval, (double)mcba::evidence_chunk_doubles(T, ch.Kc, ch.segment) * sizeof(double), ms_logdet);
   }
 };
 
@@ -122,9 +113,7 @@ int mcba_smooth_evidence(size_t n_frames, int n_tracks, const double* points, co
       for (int e = 0; e < 4; ++e) out4[4 * (ev.ch.k0 + k) + e] = o4[4 * k + e];
     }
   }
-  ev.info(info8, segment);
-  info8[5] = 1.0;
-  if (kernel_ms) *kernel_ms = ev.ch.ms_total;
+  ev.info(info8, kernel_ms, 1);
   return MCBA_OK;
 }
 
@@ -142,9 +131,7 @@ int mcba_estimate_accel_std(size_t n_frames, int n_tracks, const double* points,
   if (!(rtol >= mcba::EV_RTOL_MIN) || !(rtol < 1.0)) return fail(MCBA_ERR_ARG, "mcba_estimate_accel_std: rtol must lie in [1e-6, 1)");
   const size_t T = n_frames, K = (size_t)n_tracks;
   if (int rc = smooth_check_common(who, "weights", T, 2, range, nullptr, segment)) return rc;   // (the range as two values of accel_std)
-  if (weights)
-    for (size_t i = 0; i < T * K; ++i)
-      if (!(weights[i] >= 0.0) || !mcba::sm_finite(weights[i])) return fail(MCBA_ERR_ARG, "mcba_estimate_accel_std: weights must be finite and not negative");
+  if (int rc = smooth_check_weights(who, "weights", weights, T * K)) return rc;
   if (pool)
     for (size_t k = 0; k < K; ++k)
       if (pool[k] < 0 || (size_t)pool[k] >= K) return fail(MCBA_ERR_ARG, "mcba_estimate_accel_std: pool labels must lie in 0 .. n_tracks - 1");
@@ -192,9 +179,7 @@ int mcba_estimate_accel_std(size_t n_frames, int n_tracks, const double* points,
       for (int g = 0; g < G; ++g) n_grid_out[(size_t)g * K + k] = ng[(size_t)g * nt + i];
     }
   }
-  ev.info(info8, segment);
-  info8[5] = *n_evaluations;
-  if (kernel_ms) *kernel_ms = ev.ch.ms_total;
+  ev.info(info8, kernel_ms, *n_evaluations);
   return MCBA_OK;
 }
 

@@ -1,10 +1,10 @@
 // mcba_traj_refine_api.hip -- the stateless trajectory-refinement calls of include/mcba.h (host arrays in, host arrays out, a device ordinal, no
 // handle), in the idiom of mcba_smooth_api.hip: tracks run in chunks under the same device-memory budget (the shared part of SmoothChunks,
-// mcba_smooth_host.h); the data planes of a chunk -- detections, sqrt(w) / pixel_std, the points -- are this file's own.  The Gauss-Newton loop is
-// here: per iteration the kernels of mcba_traj_refine.hip and the smoother's elimination back to back and one small download (TR_SUMS doubles and a
-// flag per running track).  mcba_refine_trajectories_system is the first iteration of that loop laid open, before anything is accepted.
-#include "mcba_smooth_host.h"
-#include "mcba_traj_refine_math.h"
+// mcba_smooth_host.h); the data planes of a chunk -- detections, sqrt(w) / pixel_std, the points --, its count and the opening of an iteration
+// are TrackFit's (mcba_traj_host.h), shared with mcba_skeltraj_api.hip.  The Gauss-Newton loop is here: per iteration the kernels of
+// mcba_traj_refine.hip and the smoother's elimination back to back and one small download (TR_SUMS doubles and a flag per running track).
+// mcba_refine_trajectories_system is the first iteration of that loop laid open, before anything is accepted.
+#include "mcba_traj_host.h"
 
 using namespace mcba_internal;
 
@@ -31,16 +31,12 @@ struct TrajOut {
 };
 
 int traj_check(const char* who, const TrajIn& in) {
-  auto bad = [&](const char* what) { g_err = std::string(who) + ": " + what; return MCBA_ERR_ARG; };
-  if (in.T < 1 || in.T > ((size_t)1 << 31) || in.K < 1) return bad("1 .. 2^31 frames and at least one track required");
-  if (in.C < 1 || in.C > mcba::kKpMaxCams) return bad("1 .. 64 cameras required");
-  if (!in.uvs || !in.cam12 || !in.pixel_std || !in.start || !in.accel_std) return bad("non-NULL arrays (but dist5 and weights) required");
-  if (in.loss < mcba::SM_LOSS_LINEAR || in.loss > mcba::SM_LOSS_HUBER) return bad("loss must be linear, soft_l1 or huber (0 .. 2)");
-  if (!(in.f_scale > 0.0) || !mcba::sm_finite(in.f_scale)) return bad("f_scale must be positive and finite");
-  if (in.max_iterations < 1) return bad("max_iterations >= 1");
-  if (!(in.xtol >= 0.0)) return bad("xtol >= 0");
-  for (int c = 0; c < in.C; ++c)
-    if (!(in.pixel_std[c] > 0.0) || !mcba::sm_finite(in.pixel_std[c]) || !mcba::sm_finite(1.0 / in.pixel_std[c])) return bad("pixel_std must be positive and finite (and its inverse too)");
+  const DetectionChecks ck{who};
+  if (in.T < 1 || in.T > ((size_t)1 << 31) || in.K < 1) return ck.bad("1 .. 2^31 frames and at least one track required");
+  if (int rc = ck.cameras_arrays(in.C, mcba::kKpMaxCams, in.uvs && in.cam12 && in.pixel_std && in.start && in.accel_std)) return rc;
+  if (int rc = ck.convex_loss(in.loss)) return rc;
+  if (int rc = ck.loop(in.f_scale, in.max_iterations, in.xtol)) return rc;
+  if (int rc = ck.pixel_std(in.pixel_std, in.C)) return rc;
   if (int rc = check_weights(who, in.weights, (size_t)in.C * in.T * in.K)) return rc;
   return smooth_check_common(who, "weights", in.T, in.K, in.accel_std, nullptr, in.segment);
 }
@@ -61,77 +57,31 @@ int traj_run(const char* who, const TrajIn& in, const TrajOut& out) {
   if (int rc = ch.setup_shared(who, T, K, segment, in.accel_std, mcba::traj_refine_chunk_doubles(T, 1, C, segment, cov, lag), cov ? mcba::SM_ZC : 6)) return rc;
   const int Kc = ch.Kc, nblk = mcba::smooth_eval_blocks(T);
   const size_t TK = T * Kc;
-  double *d_det = nullptr, *d_sw = nullptr, *d_x = nullptr, *d_d = nullptr, *d_H = nullptr, *d_G = nullptr, *d_part = nullptr, *d_res = nullptr, *d_alpha = nullptr, *d_oc = nullptr, *d_ol = nullptr;
-  int *d_nsg = nullptr, *d_nbs = nullptr, *d_run = nullptr;
-  mcba::KpCam* d_cams = nullptr;
-  std::vector<mcba::KpCam> tab((size_t)C);
-  for (int c = 0; c < C; ++c) mcba::make_kp_cam(in.cam12 + 12 * c, in.dist5 ? in.dist5 + 5 * c : nullptr, tab[c]);
-  if (int rc = call.upload(&d_cams, tab.data(), tab.size())) return rc;
-  if (int rc = call.scratch(&d_det, 2 * C * TK)) return rc;
-  if (int rc = call.scratch(&d_sw, C * TK)) return rc;
-  if (int rc = call.scratch(&d_x, 3 * TK)) return rc;
-  if (int rc = call.scratch(&d_d, 3 * TK)) return rc;
-  if (int rc = call.scratch(&d_H, 6 * TK)) return rc;
-  if (int rc = call.scratch(&d_G, 3 * TK)) return rc;
+  TrackFit fit{ch, "trajectory refinement", C, in.uvs, in.weights, in.pixel_std, in.start, in.f_scale};
+  if (int rc = fit.setup(in.cam12, in.dist5)) return rc;
+  double *d_part = nullptr, *d_res = nullptr, *d_oc = nullptr, *d_ol = nullptr;
   if (int rc = call.scratch(&d_part, (size_t)mcba::TR_SUMS * nblk * Kc)) return rc;
   if (int rc = call.scratch(&d_res, (size_t)mcba::TR_SUMS * Kc)) return rc;
-  if (int rc = call.scratch(&d_alpha, (size_t)Kc)) return rc;
-  if (int rc = call.scratch(&d_nsg, (size_t)Kc)) return rc;
-  if (int rc = call.scratch(&d_nbs, (size_t)Kc)) return rc;
-  if (int rc = call.scratch(&d_run, (size_t)Kc)) return rc;
   if (cov) if (int rc = call.scratch(&d_oc, 6 * TK)) return rc;
   if (lag) if (int rc = call.scratch(&d_ol, 9 * (T - 1) * Kc)) return rc;
-  HIPCHK(hipEventCreate(&ch.e2));
+  mcba::KpCam* const d_cams = fit.d_cams;
+  double *const d_x = fit.d_x, *const d_d = fit.d_d, *const d_H = fit.d_H, *const d_G = fit.d_G;
+  int* const d_run = fit.d_run;
 
-  std::vector<double> h_det, h_sw, h_x, h_H, h_G, h_d, h_res, h_alpha, h_cost, h_oc, h_ol;
-  std::vector<int> h_nus, h_nsg, h_nbs, h_bad, h_stat, h_nit, h_run;
+  std::vector<double> h_x, h_H, h_G, h_d, h_res, h_alpha, h_cost, h_oc, h_ol;
+  std::vector<int> h_bad, h_nit;
+  std::vector<int>&h_stat = fit.h_stat, &h_run = fit.h_run, &h_nus = fit.h_nus, &h_nsg = fit.h_nsg;
   for (int c = 0; c < ch.nchunks; ++c) {
     if (int rc = ch.begin_shared(c)) return rc;
+    if (int rc = fit.begin()) return rc;
     const int kc = ch.kc;
     const size_t k0 = ch.k0, tk = ch.tk;
-    // gather the chunk's planes: detections (C, T kc) pairs, sqrt(w) / pixel_std beside them, the start
-    h_sw.resize(C * tk);
-    const double *s_det = in.uvs, *s_x = in.start;
-    if (kc != (int)K) {
-      h_det.resize(2 * C * tk); h_x.resize(3 * tk);
-      for (int cc = 0; cc < C; ++cc)
-        for (size_t t = 0; t < T; ++t) memcpy(h_det.data() + 2 * (cc * tk + t * kc), in.uvs + 2 * ((cc * T + t) * K + k0), 2 * kc * sizeof(double));
-      for (size_t t = 0; t < T; ++t) memcpy(h_x.data() + 3 * t * kc, in.start + 3 * (t * K + k0), 3 * kc * sizeof(double));
-      s_det = h_det.data(); s_x = h_x.data();
-    }
-    for (int cc = 0; cc < C; ++cc) {
-      const double ips = 1.0 / in.pixel_std[cc];
-      for (size_t t = 0; t < T; ++t)
-        for (int k = 0; k < kc; ++k) {
-          const double w = in.weights ? in.weights[(cc * T + t) * K + k0 + k] : 1.0;
-          h_sw[cc * tk + t * kc + k] = w > 0.0 ? sqrt(w) * ips : 0.0;   // (a zero or NaN weight: unseen)
-        }
-    }
-    if (int rc = call.put(d_det, s_det, 2 * C * tk)) return rc;
-    if (int rc = call.put(d_sw, h_sw.data(), C * tk)) return rc;
-    if (int rc = call.put(d_x, s_x, 3 * tk)) return rc;
     for (int l = 1; l < ch.levels; ++l) ch.lv[l].x = ch.aux[l];   // (with cov: the first six of the SM_ZC planes)
-    const mcba::TrData rd{T, d_det, d_sw, d_x, d_d, d_H, d_G, ch.d_ia2, in.f_scale * in.f_scale, 1.0 / (in.f_scale * in.f_scale)};
+    const mcba::TrData& rd = fit.rd;
     // level 0 of the elimination: H as the diagonal blocks, -G as the right-hand side, d as the solution
     mcba::SmData td{T, nullptr, d_H, nullptr, ch.d_ia2, d_d, nullptr, nullptr, mcba::SM_LOSS_LINEAR, 1.0, 1.0, d_G};
-
-    HIPCHK(hipEventRecord(call.e0, nullptr));
-    if (mcba::launch_traj_count(nullptr, rd, C, kc, ch.d_nus, d_nsg, d_nbs) != 0) return fail(MCBA_ERR_ARG, "trajectory refinement: bad launch");
-    if (int rc = check_launch()) return rc;
-    HIPCHK(hipEventRecord(call.e1, nullptr));
-    HIPCHK(hipEventSynchronize(call.e1));
-    if (int rc = ch.add_ms(call.e0, call.e1, ch.ms_total)) return rc;
-    h_nus.resize(kc); h_nsg.resize(kc); h_nbs.resize(kc);
-    if (int rc = call.download(h_nus.data(), ch.d_nus, (size_t)kc)) return rc;
-    if (int rc = call.download(h_nsg.data(), d_nsg, (size_t)kc)) return rc;
-    if (int rc = call.download(h_nbs.data(), d_nbs, (size_t)kc)) return rc;
-    h_stat.resize(kc); h_nit.assign(kc, 0); h_bad.assign(kc, 0); h_res.assign((size_t)mcba::TR_SUMS * kc, nan); h_alpha.assign(kc, 0.0); h_cost.assign(kc, nan); h_run.assign(kc, 0);
+    h_nit.assign(kc, 0); h_bad.assign(kc, 0); h_res.assign((size_t)mcba::TR_SUMS * kc, nan); h_alpha.assign(kc, 0.0); h_cost.assign(kc, nan);
     std::vector<int>& h_list = ch.h_list;
-    h_list.clear();
-    for (int k = 0; k < kc; ++k) {
-      h_stat[k] = h_nus[k] < 2 ? mcba::TR_TOO_FEW_FRAMES : h_nbs[k] ? mcba::TR_BAD_START : mcba::TR_OK;   // (neither is ever launched)
-      if (h_stat[k] == mcba::TR_OK) h_list.push_back(k);
-    }
     std::vector<int> ran = h_list, sys_pos(kc, -1);
     bool pending = false;   // accepted steps not yet applied: the next bracket starts with them
     for (int it = 0; it < max_iterations && !h_list.empty(); ++it) {
@@ -140,18 +90,12 @@ int traj_run(const char* who, const TrajIn& in, const TrajOut& out) {
       for (int k : h_list) h_run[k] = 1;
       if (int rc = call.put(ch.d_list, h_list.data(), (size_t)nact)) return rc;
       if (int rc = call.put(d_run, h_run.data(), (size_t)kc)) return rc;
-      if (pending) if (int rc = call.put(d_alpha, h_alpha.data(), (size_t)kc)) return rc;
-      HIPCHK(hipEventRecord(call.e0, nullptr));
-      int lrc = pending ? mcba::launch_traj_apply(nullptr, rd, kc, d_alpha) : 0;
-      lrc = lrc || mcba::launch_traj_linearise(nullptr, loss, rd, d_cams, C, kc, d_run);
-      lrc = lrc || mcba::launch_smooth_reduce(nullptr, ch.lv, ch.levels, td, kc, ch.d_list, nact, ch.d_bad, true);
+      if (int rc = fit.open_linearised(loss, pending, h_alpha)) return rc;
+      int lrc = mcba::launch_smooth_reduce(nullptr, ch.lv, ch.levels, td, kc, ch.d_list, nact, ch.d_bad, true);
       lrc = lrc || mcba::launch_smooth_backsub(nullptr, ch.lv, ch.levels, td, kc, ch.d_list, nact, true);
       lrc = lrc || mcba::launch_traj_trial(nullptr, loss, rd, d_cams, C, kc, ch.d_list, nact, d_part, d_res);
-      if (lrc) return fail(MCBA_ERR_ARG, "trajectory refinement: bad launch");
-      if (int rc = check_launch()) return rc;
-      HIPCHK(hipEventRecord(call.e1, nullptr));
-      HIPCHK(hipEventSynchronize(call.e1));
-      if (int rc = ch.add_ms(call.e0, call.e1, ch.ms_total)) return rc;
+      if (lrc) return fit.bad_launch();
+      if (int rc = ch.close()) return rc;
       if (int rc = call.download(h_res.data(), d_res, (size_t)mcba::TR_SUMS * nact)) return rc;
       if (int rc = call.download(h_bad.data(), ch.d_bad, (size_t)kc)) return rc;
       most = std::max(most, it + 1);
@@ -194,21 +138,14 @@ int traj_run(const char* who, const TrajIn& in, const TrajOut& out) {
         const int nact = (int)h_list.size();
         if (int rc = call.put(ch.d_list, h_list.data(), (size_t)nact)) return rc;
         if (int rc = call.put(d_run, h_run.data(), (size_t)kc)) return rc;
-        if (pending) if (int rc = call.put(d_alpha, h_alpha.data(), (size_t)kc)) return rc;
-        HIPCHK(hipEventRecord(call.e0, nullptr));
-        int lrc = pending ? mcba::launch_traj_apply(nullptr, rd, kc, d_alpha) : 0;
-        lrc = lrc || mcba::launch_traj_linearise(nullptr, loss, rd, d_cams, C, kc, d_run);
-        HIPCHK(hipEventRecord(call.e1, nullptr));
+        if (int rc = fit.open_linearised(loss, pending, h_alpha, true)) return rc;
+        if (int rc = ch.mark()) return rc;
         if (cov) {
-          lrc = lrc || mcba::launch_smooth_reduce(nullptr, ch.lv, ch.levels, td, kc, ch.d_list, nact, ch.d_bad, true);
+          int lrc = mcba::launch_smooth_reduce(nullptr, ch.lv, ch.levels, td, kc, ch.d_list, nact, ch.d_bad, true);
           lrc = lrc || mcba::launch_smooth_selinv(nullptr, ch.lv, ch.levels, td, ch.aux, d_oc, d_ol, kc, ch.d_list, nact);
+          if (lrc) return fit.bad_launch();
         }
-        if (lrc) return fail(MCBA_ERR_ARG, "trajectory refinement: bad launch");
-        if (int rc = check_launch()) return rc;
-        HIPCHK(hipEventRecord(ch.e2, nullptr));
-        HIPCHK(hipEventSynchronize(ch.e2));
-        if (int rc = ch.add_ms(call.e0, ch.e2, ch.ms_total)) return rc;
-        if (int rc = ch.add_ms(call.e1, ch.e2, ms_cov)) return rc;
+        if (int rc = ch.close_split(ms_cov)) return rc;
         if (cov) {
           if (int rc = call.download(h_bad.data(), ch.d_bad, (size_t)kc)) return rc;
           for (int k : h_list)
@@ -248,10 +185,7 @@ int traj_run(const char* who, const TrajIn& in, const TrajOut& out) {
       }
     }
   }
-  double* info8 = out.info8;
-  info8[0] = ch.levels; info8[1] = segment; info8[2] = Kc; info8[3] = ch.nchunks; info8[4] = ch.ms_total; info8[5] = most;
-  info8[6] = (double)mcba::traj_refine_chunk_doubles(T, Kc, C, segment, cov, lag) * sizeof(double); info8[7] = ms_cov;
-  if (out.kernel_ms) *out.kernel_ms = ch.ms_total;
+  ch.info(out.info8, out.kernel_ms, Kc, ch.nchunks, most, (double)mcba::traj_refine_chunk_doubles(T, Kc, C, segment, cov, lag) * sizeof(double), ms_cov);
   return MCBA_OK;
 }
 

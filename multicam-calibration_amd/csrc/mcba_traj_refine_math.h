@@ -162,6 +162,9 @@ MCBA_HD void traj_apply_lane(const TrData& rd, size_t idx, double alpha) {
   for (int e = 0; e < 3; ++e) rd.x[3 * idx + e] = fma(alpha, rd.d[3 * idx + e], rd.x[3 * idx + e]);
 }
 
+// ---- the status a track starts with, from its counts (traj_count_frame): one that is not TR_OK is never launched
+MCBA_HD int traj_start_status(int n_usable, bool bad_start) { return n_usable < 2 ? TR_TOO_FEW_FRAMES : bad_start ? TR_BAD_START : TR_OK; }
+
 // ---- the loop's decision for one track after iteration `it` (0-based) from its sums res (TR_SUMS): the accepted alpha -- the largest trial
 // whose objective is not above the one at x, 0 when there is none -- the objective after it, and true = the track stops: nothing accepted (the
 // minimiser to the cost's resolution), the last iteration, or a step alpha max |d| below xtol max |x|

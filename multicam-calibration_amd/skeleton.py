@@ -11,11 +11,11 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import ops
-from .triangulation import _cam_blocks
+from .trajectory import _accel_argument, _check_loss, _check_segment, _detection_arguments, _loop_arguments
 
 KEYPOINT_STATUS = {2: "fitted, two views or more", 1: "fitted, one view", -1: "no view or a non-finite start", -2: "in a piece without a keypoint of two views"}
 FRAME_STATUS = {1: "converged", 0: "iteration limit", -1: "nothing to fit"}
-MAX_KEYPOINTS, MAX_CAMERAS = 64, 64
+MAX_KEYPOINTS = 64
 _SYM = np.array([[0, 1, 2], [1, 3, 4], [2, 4, 5]])
 
 
@@ -117,26 +117,8 @@ def _arguments(start, all_uvs, all_extrinsics, all_intrinsics, bones, bone_lengt
     """the checked arrays both calls take: pts (T, K, 3), uvs (C, T, K, 2), cam (C, 12), dist (C, 5), parent (K), child (E), L (K), s (K), pstd (C), w (C, T, K) or None"""
     if callable(loss) or loss not in ops.LOSSES:
         raise ValueError(f"loss must be one of {sorted(ops.LOSSES)}")
-    pts = np.ascontiguousarray(start, dtype=np.float64)
-    if pts.ndim != 3 or pts.shape[2] != 3:
-        raise ValueError("start must be (T, K, 3)")
-    T, K = pts.shape[:2]
-    if T == 0 or K == 0:
-        raise ValueError("start must hold at least one frame and one keypoint")
-    if K > MAX_KEYPOINTS:
-        raise ValueError(f"refine_skeleton supports at most {MAX_KEYPOINTS} keypoints")
-    if len(all_extrinsics) != len(all_intrinsics) or len(all_extrinsics) < 1:
-        raise ValueError("one (camera_matrix, dist_coefs) per entry of all_extrinsics, at least one camera")
-    C = len(all_extrinsics)
-    if C > MAX_CAMERAS:
-        raise ValueError(f"refine_skeleton supports at most {MAX_CAMERAS} cameras")
-    if len(all_uvs) != C:
-        raise ValueError(f"all_uvs must be ({C}, {T}, {K}, 2), or a list of {C} arrays ({T}, {K}, 2)")
-    uvs = [np.asarray(u, dtype=np.float64) for u in all_uvs]
-    if any(u.shape != (T, K, 2) for u in uvs):
-        raise ValueError(f"all_uvs must be ({C}, {T}, {K}, 2), or a list of {C} arrays ({T}, {K}, 2)")
-    uvs = np.ascontiguousarray(np.stack(uvs))
-    cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
+    pts, uvs, cam, dist, pstd, w = _detection_arguments("refine_skeleton", "keypoint", start, all_uvs, all_extrinsics, all_intrinsics, pixel_std, f_scale, weights, MAX_KEYPOINTS)
+    K = pts.shape[1]
     parent, child = forest_parents(bones, K)
     E = len(child)
     if np.asarray(bone_length).shape != (E,):
@@ -144,22 +126,6 @@ def _arguments(start, all_uvs, all_extrinsics, all_intrinsics, bones, bone_lengt
     Lb, sb = _per_bone(bone_length, "bone_length", E), _per_bone(bone_std, "bone_std", E)
     L, s = np.ones(K), np.ones(K)
     L[child], s[child] = Lb, sb
-    pstd = np.asarray(pixel_std, dtype=np.float64)
-    if pstd.shape not in ((), (C,)):
-        raise ValueError(f"pixel_std must be a scalar or ({C},)")
-    pstd = np.ascontiguousarray(np.broadcast_to(pstd, (C,)))
-    with np.errstate(over="ignore", divide="ignore"):
-        if not (np.isfinite(pstd).all() and (pstd > 0).all() and np.isfinite(1.0 / pstd).all()):
-            raise ValueError("pixel_std must be positive and finite")
-    if not (np.isfinite(f_scale) and f_scale > 0):
-        raise ValueError("`f_scale` must be positive.")
-    w = None
-    if weights is not None:
-        w = np.ascontiguousarray(weights, dtype=np.float64)
-        if w.shape != (C, T, K):
-            raise ValueError(f"weights must be ({C}, {T}, {K}): one per camera, frame and keypoint, got {w.shape}")
-        if (w < 0).any() or np.isinf(w).any():
-            raise ValueError("weights must be finite and not negative (0 or NaN: the detection is unseen)")
     return pts, uvs, cam, dist, parent, child, L, s, pstd, w
 
 
@@ -234,11 +200,7 @@ def refine_skeleton(start, all_uvs, all_extrinsics, all_intrinsics, *, bones, bo
     infinite weight, max_iterations < 1, xtol < 0.  Without a GPU: ops.McbaError -- there is no host path."""
     pts, uvs, cam, dist, parent, child, L, s, pstd, w = _arguments(start, all_uvs, all_extrinsics, all_intrinsics, bones, bone_length, bone_std, pixel_std, loss, f_scale, weights)
     C, T, K = uvs.shape[:3]
-    max_iterations = int(max_iterations)
-    if max_iterations < 1:
-        raise ValueError("max_iterations must be at least 1")
-    if not xtol >= 0:
-        raise ValueError("xtol must not be negative")
+    max_iterations = _loop_arguments(max_iterations, xtol)
     if not any(covariance is v for v in (False, True)):
         raise ValueError("covariance must be False or True")
     out, kst, fst, nit = np.empty((T, K, 3)), np.empty((T, K), np.int32), np.empty(T, np.int32), np.empty(T, np.int32)
@@ -319,18 +281,9 @@ class SkeletonTrajectorySystem:
 
 def _trajectory_arguments(start, all_uvs, all_extrinsics, all_intrinsics, accel_std, bones, bone_length, bone_std, pixel_std, loss, f_scale, weights, cg_tol, cg_max, segment):
     """_arguments plus what the time prior and the inner solve take: acc (K,), cg_max"""
-    from .trajectory import _check_segment
-    if not callable(loss) and loss in ("cauchy", "arctan"):
-        raise ValueError(f"refine_skeleton_trajectories: loss {loss!r} is not convex -- the backtracking Gauss-Newton loop is for linear, soft_l1 and huber")
+    _check_loss(loss, "refine_skeleton_trajectories", known=ops.LOSSES)
     args = _arguments(start, all_uvs, all_extrinsics, all_intrinsics, bones, bone_length, bone_std, pixel_std, loss, f_scale, weights)
-    K = args[0].shape[1]
-    acc = np.asarray(accel_std, dtype=np.float64)
-    if acc.shape not in ((), (K,)):
-        raise ValueError(f"accel_std must be a scalar or ({K},)")
-    acc = np.ascontiguousarray(np.broadcast_to(acc, (K,)))
-    with np.errstate(over="ignore", divide="ignore"):
-        if not (np.isfinite(acc).all() and (acc > 0).all() and np.isfinite(1.0 / (acc * acc)).all()):
-            raise ValueError("accel_std must be positive and finite")
+    acc = _accel_argument(accel_std, args[0].shape[1])
     if not 0.0 < cg_tol < 1.0:
         raise ValueError("cg_tol must lie inside (0, 1)")
     cg_max = int(cg_max)
@@ -380,11 +333,7 @@ def refine_skeleton_trajectories(start, all_uvs, all_extrinsics, all_intrinsics,
     pts, uvs, cam, dist, parent, child, L, s, pstd, w, acc, cg_max = _trajectory_arguments(start, all_uvs, all_extrinsics, all_intrinsics, accel_std, bones, bone_length, bone_std, pixel_std,
                                                                                          loss, f_scale, weights, cg_tol, cg_max, segment)
     C, T, K = uvs.shape[:3]
-    max_iterations = int(max_iterations)
-    if max_iterations < 1:
-        raise ValueError("max_iterations must be at least 1")
-    if not xtol >= 0:
-        raise ValueError("xtol must not be negative")
+    max_iterations = _loop_arguments(max_iterations, xtol)
     out, h6, bres, u3 = np.empty((T, K, 3)), np.empty((T, K, 6)), np.empty((T, K)), np.empty((T, K, 3))
     status, nus, nsg = (np.empty(K, np.int32) for _ in range(3))
     conv, nit = np.zeros(1, np.int32), np.zeros(1, np.int32)

@@ -19,6 +19,7 @@ TRAJECTORY_STATUS = {1: "ok", -1: "fewer than two usable frames", -2: "a block p
 TRAJECTORY_REFINE_STATUS = {1: "ok", -1: "fewer than two usable frames", -2: "a block pivot below the threshold", -3: "a non-finite start"}
 LOSSES = {"linear": 0, "soft_l1": 1, "huber": 2}
 SEGMENT_MIN, SEGMENT_MAX = 2, 64
+MAX_CAMERAS = 64   # of the calls on raw detections: the camera table of one launch
 
 
 @dataclass
@@ -68,7 +69,11 @@ def _track_arguments(points, covariance, accel_std):
     T, K = pts.shape[:2]
     if T == 0 or K == 0:
         raise ValueError("points must hold at least one frame and one track")
-    cov6 = _covariance_planes(covariance, T, K)
+    return pts, _covariance_planes(covariance, T, K), _accel_argument(accel_std, K)
+
+
+def _accel_argument(accel_std, K):
+    """accel_std, a scalar or (K,), as (K,), checked"""
     acc = np.asarray(accel_std, dtype=np.float64)
     if acc.shape not in ((), (K,)):
         raise ValueError(f"accel_std must be a scalar or ({K},)")
@@ -76,7 +81,7 @@ def _track_arguments(points, covariance, accel_std):
     with np.errstate(over="ignore", divide="ignore"):
         if not (np.isfinite(acc).all() and (acc > 0).all() and np.isfinite(1.0 / (acc * acc)).all()):
             raise ValueError("accel_std must be positive and finite")
-    return pts, cov6, acc
+    return acc
 
 
 def _weights_argument(weights, name, T, K):
@@ -94,6 +99,68 @@ def _weights_argument(weights, name, T, K):
 def _check_segment(segment):
     if segment is not None and not SEGMENT_MIN <= int(segment) <= SEGMENT_MAX:
         raise ValueError(f"segment must be None or {SEGMENT_MIN} .. {SEGMENT_MAX}")
+
+
+def _check_loss(loss, caller, loop="the backtracking Gauss-Newton loop is for", known=LOSSES):
+    """the loops of this module and of refine_skeleton_trajectories take the three convex losses; known: what an unknown loss is told the choice is"""
+    if callable(loss) or loss not in LOSSES:
+        if not callable(loss) and loss in ("cauchy", "arctan"):
+            raise ValueError(f"{caller}: loss {loss!r} is not convex -- {loop} linear, soft_l1 and huber")
+        raise ValueError(f"loss must be one of {sorted(known)}")
+
+
+def _loop_arguments(max_iterations, xtol):
+    """max_iterations as an int, both checked"""
+    max_iterations = int(max_iterations)
+    if max_iterations < 1:
+        raise ValueError("max_iterations must be at least 1")
+    if not xtol >= 0:
+        raise ValueError("xtol must not be negative")
+    return max_iterations
+
+
+def _detection_arguments(caller, noun, start, all_uvs, all_extrinsics, all_intrinsics, pixel_std, f_scale, weights, max_keypoints=None):
+    """the checked arrays every call on raw detections takes: pts (T, K, 3), uvs (C, T, K, 2), cam (C, 12), dist (C, 5), pstd (C,), w (C, T, K) or
+    None.  caller and noun ("track" or "keypoint") go into the messages; max_keypoints: the caller's limit on K, if it has one.  The order of
+    the checks is the order in which a call reports what is wrong: the loss first (the caller's), then these -- start, the cameras, all_uvs,
+    pixel_std, f_scale, weights -- then the caller's further arguments (accel_std, the bones, cg_tol, cg_max, segment)"""
+    pts = np.ascontiguousarray(start, dtype=np.float64)
+    if pts.ndim != 3 or pts.shape[2] != 3:
+        raise ValueError("start must be (T, K, 3)")
+    T, K = pts.shape[:2]
+    if T == 0 or K == 0:
+        raise ValueError(f"start must hold at least one frame and one {noun}")
+    if max_keypoints is not None and K > max_keypoints:
+        raise ValueError(f"{caller} supports at most {max_keypoints} keypoints")
+    if len(all_extrinsics) != len(all_intrinsics) or len(all_extrinsics) < 1:
+        raise ValueError("one (camera_matrix, dist_coefs) per entry of all_extrinsics, at least one camera")
+    C = len(all_extrinsics)
+    if C > MAX_CAMERAS:
+        raise ValueError(f"{caller} supports at most {MAX_CAMERAS} cameras")
+    if len(all_uvs) != C:
+        raise ValueError(f"all_uvs must be ({C}, {T}, {K}, 2), or a list of {C} arrays ({T}, {K}, 2)")
+    uvs = [np.asarray(u, dtype=np.float64) for u in all_uvs]
+    if any(u.shape != (T, K, 2) for u in uvs):
+        raise ValueError(f"all_uvs must be ({C}, {T}, {K}, 2), or a list of {C} arrays ({T}, {K}, 2)")
+    uvs = np.ascontiguousarray(np.stack(uvs))
+    cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
+    pstd = np.asarray(pixel_std, dtype=np.float64)
+    if pstd.shape not in ((), (C,)):
+        raise ValueError(f"pixel_std must be a scalar or ({C},)")
+    pstd = np.ascontiguousarray(np.broadcast_to(pstd, (C,)))
+    with np.errstate(over="ignore", divide="ignore"):
+        if not (np.isfinite(pstd).all() and (pstd > 0).all() and np.isfinite(1.0 / pstd).all()):
+            raise ValueError("pixel_std must be positive and finite")
+    if not (np.isfinite(f_scale) and f_scale > 0):
+        raise ValueError("`f_scale` must be positive.")
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (C, T, K):
+            raise ValueError(f"weights must be ({C}, {T}, {K}): one per camera, frame and {noun}, got {w.shape}")
+        if (w < 0).any() or np.isinf(w).any():
+            raise ValueError("weights must be finite and not negative (0 or NaN: the detection is unseen)")
+    return pts, uvs, cam, dist, pstd, w
 
 
 def smooth_trajectories(points, covariance, *, accel_std, loss="linear", f_scale=3.0, weights_in=None, max_iterations=50, xtol=1e-8, segment=None, device=0, uncertainty=False):
@@ -129,20 +196,13 @@ def smooth_trajectories(points, covariance, *, accel_std, loss="linear", f_scale
     Without a GPU: ops.McbaError -- there is no host path."""
     if not any(uncertainty is u for u in (False, True)) and uncertainty != "lag":
         raise ValueError('uncertainty must be False, True or "lag"')
-    if callable(loss) or loss not in LOSSES:
-        if loss in ("cauchy", "arctan"):
-            raise ValueError(f"smooth_trajectories: loss {loss!r} is not convex -- the reweighting loop is a majorise-minimise scheme only for linear, soft_l1 and huber")
-        raise ValueError(f"loss must be one of {sorted(LOSSES)}")
+    _check_loss(loss, "smooth_trajectories", "the reweighting loop is a majorise-minimise scheme only for")
     pts, cov6, acc = _track_arguments(points, covariance, accel_std)
     T, K = pts.shape[:2]
     if not (np.isfinite(f_scale) and f_scale > 0):
         raise ValueError("`f_scale` must be positive.")
     win = _weights_argument(weights_in, "weights_in", T, K)
-    max_iterations = int(max_iterations)
-    if max_iterations < 1:
-        raise ValueError("max_iterations must be at least 1")
-    if not xtol >= 0:
-        raise ValueError("xtol must not be negative")
+    max_iterations = _loop_arguments(max_iterations, xtol)
     _check_segment(segment)
 
     out, w, d2 = np.empty((T, K, 3)), np.empty((T, K)), np.empty((T, K))
@@ -361,50 +421,9 @@ class TrajectoryRefinementSystem:
 
 def _refine_arguments(start, all_uvs, all_extrinsics, all_intrinsics, accel_std, pixel_std, loss, f_scale, weights, segment):
     """the checked arrays both refinement calls take: start (T, K, 3), uvs (C, T, K, 2), cam (C, 12), dist (C, 5), acc (K,), pstd (C,), w (C, T, K) or None"""
-    if callable(loss) or loss not in LOSSES:
-        if loss in ("cauchy", "arctan"):
-            raise ValueError(f"refine_trajectories: loss {loss!r} is not convex -- the backtracking Gauss-Newton loop is for linear, soft_l1 and huber")
-        raise ValueError(f"loss must be one of {sorted(LOSSES)}")
-    pts = np.ascontiguousarray(start, dtype=np.float64)
-    if pts.ndim != 3 or pts.shape[2] != 3:
-        raise ValueError("start must be (T, K, 3)")
-    T, K = pts.shape[:2]
-    if T == 0 or K == 0:
-        raise ValueError("start must hold at least one frame and one track")
-    if len(all_extrinsics) != len(all_intrinsics) or len(all_extrinsics) < 1:
-        raise ValueError("one (camera_matrix, dist_coefs) per entry of all_extrinsics, at least one camera")
-    C = len(all_extrinsics)
-    if C > 64:
-        raise ValueError("refine_trajectories supports at most 64 cameras")
-    if len(all_uvs) != C:
-        raise ValueError(f"all_uvs must be ({C}, {T}, {K}, 2), or a list of {C} arrays ({T}, {K}, 2)")
-    uvs = [np.asarray(u, dtype=np.float64) for u in all_uvs]
-    if any(u.shape != (T, K, 2) for u in uvs):
-        raise ValueError(f"all_uvs must be ({C}, {T}, {K}, 2), or a list of {C} arrays ({T}, {K}, 2)")
-    uvs = np.ascontiguousarray(np.stack(uvs))
-    cam, dist = _cam_blocks(all_extrinsics, all_intrinsics)
-    acc = np.asarray(accel_std, dtype=np.float64)
-    if acc.shape not in ((), (K,)):
-        raise ValueError(f"accel_std must be a scalar or ({K},)")
-    acc = np.ascontiguousarray(np.broadcast_to(acc, (K,)))
-    pstd = np.asarray(pixel_std, dtype=np.float64)
-    if pstd.shape not in ((), (C,)):
-        raise ValueError(f"pixel_std must be a scalar or ({C},)")
-    pstd = np.ascontiguousarray(np.broadcast_to(pstd, (C,)))
-    with np.errstate(over="ignore", divide="ignore"):
-        if not (np.isfinite(acc).all() and (acc > 0).all() and np.isfinite(1.0 / (acc * acc)).all()):
-            raise ValueError("accel_std must be positive and finite")
-        if not (np.isfinite(pstd).all() and (pstd > 0).all() and np.isfinite(1.0 / pstd).all()):
-            raise ValueError("pixel_std must be positive and finite")
-    if not (np.isfinite(f_scale) and f_scale > 0):
-        raise ValueError("`f_scale` must be positive.")
-    w = None
-    if weights is not None:
-        w = np.ascontiguousarray(weights, dtype=np.float64)
-        if w.shape != (C, T, K):
-            raise ValueError(f"weights must be ({C}, {T}, {K}): one per camera, frame and track, got {w.shape}")
-        if (w < 0).any() or np.isinf(w).any():
-            raise ValueError("weights must be finite and not negative (0 or NaN: the detection is unseen)")
+    _check_loss(loss, "refine_trajectories")
+    pts, uvs, cam, dist, pstd, w = _detection_arguments("refine_trajectories", "track", start, all_uvs, all_extrinsics, all_intrinsics, pixel_std, f_scale, weights)
+    acc = _accel_argument(accel_std, pts.shape[1])
     _check_segment(segment)
     return pts, uvs, cam, dist, acc, pstd, w
 
@@ -446,11 +465,7 @@ def refine_trajectories(start, all_uvs, all_extrinsics, all_intrinsics, *, accel
         raise ValueError('uncertainty must be False, True or "lag"')
     pts, uvs, cam, dist, acc, pstd, w = _refine_arguments(start, all_uvs, all_extrinsics, all_intrinsics, accel_std, pixel_std, loss, f_scale, weights, segment)
     C, T, K = uvs.shape[:3]
-    max_iterations = int(max_iterations)
-    if max_iterations < 1:
-        raise ValueError("max_iterations must be at least 1")
-    if not xtol >= 0:
-        raise ValueError("xtol must not be negative")
+    max_iterations = _loop_arguments(max_iterations, xtol)
     out, h6 = np.empty((T, K, 3)), np.empty((T, K, 6))
     status, nus, nsg, nit = (np.empty(K, np.int32) for _ in range(4))
     cost, hist, info = np.empty(K), np.empty((max_iterations, K, 3)), np.zeros(8)

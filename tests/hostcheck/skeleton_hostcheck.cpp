@@ -63,11 +63,7 @@ extern "C" int hc_refine_skeleton(int system, size_t T, int K, int C, const doub
   std::vector<KpCam> cams(C);
   for (int c = 0; c < C; ++c) make_kp_cam(cam12 + 12 * c, dist5 ? dist5 + 5 * c : nullptr, cams[c]);
   std::vector<double> sw((size_t)C * TK);
-  for (int c = 0; c < C; ++c)
-    for (size_t i = 0; i < TK; ++i) {
-      const double w = weights ? weights[c * TK + i] : 1.0;
-      sw[c * TK + i] = w > 0.0 ? sqrt(w) * (1.0 / pixel_std[c]) : 0.0;
-    }
+  kp_weight_box(weights, pixel_std, C, T, K, 0, T, 0, K, sw.data());
   SkArgs a{};
   a.T = T; a.det = uvs; a.sw = sw.data(); a.start = start;
   a.fs2 = f_scale * f_scale; a.inv_fs2 = 1.0 / a.fs2; a.lam0 = system ? lam : SK_LAM_START; a.xtol = xtol;

@@ -111,11 +111,7 @@ extern "C" int hc_refine_skeleton_trajectories(int system, size_t T, int K, int 
   for (int c = 0; c < C; ++c) make_kp_cam(cam12 + 12 * c, dist5 ? dist5 + 5 * c : nullptr, cams[c]);
   std::vector<double> sw((size_t)C * TK), x(start, start + 3 * TK), d(3 * TK, nan), H(6 * TK, nan), G(3 * TK, nan), q(3 * TK, nan), p(3 * TK, nan), y(3 * TK, nan), z(3 * TK, nan), dir(3 * TK, nan),
       bres(TK, nan), ia2(K);
-  for (int c = 0; c < C; ++c)
-    for (size_t i = 0; i < TK; ++i) {
-      const double w = weights ? weights[c * TK + i] : 1.0;
-      sw[c * TK + i] = w > 0.0 ? sqrt(w) * (1.0 / pixel_std[c]) : 0.0;
-    }
+  kp_weight_box(weights, pixel_std, C, T, K, 0, T, 0, K, sw.data());
   for (int k = 0; k < K; ++k) ia2[k] = 1.0 / (accel_std[k] * accel_std[k]);
   const TrData rd{T, uvs, sw.data(), x.data(), d.data(), H.data(), G.data(), ia2.data(), f_scale * f_scale, 1.0 / (f_scale * f_scale)};
   const SmData td{T, nullptr, H.data(), nullptr, ia2.data(), z.data(), nullptr, nullptr, SM_LOSS_LINEAR, 1.0, 1.0, q.data()};
@@ -124,7 +120,7 @@ extern "C" int hc_refine_skeleton_trajectories(int system, size_t T, int K, int 
     double acc[3] = {0.0, 0.0, 0.0};
     for (size_t t = 0; t < T; ++t) traj_count_frame(rd, C, K, k, t, acc);
     n_usable[k] = (int)acc[0]; n_single[k] = (int)acc[1];
-    stat[k] = n_usable[k] < 2 ? TR_TOO_FEW_FRAMES : acc[2] != 0.0 ? TR_BAD_START : TR_OK;
+    stat[k] = traj_start_status(n_usable[k], acc[2] != 0.0);
     if (stat[k] == TR_OK) { list.push_back(k); run[k] = 1; }
   }
   for (int k = 0; k < K; ++k) par[k] = run[k] && parent[k] >= 0 && run[parent[k]] ? parent[k] : -1;

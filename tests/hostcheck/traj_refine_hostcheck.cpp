@@ -86,11 +86,7 @@ extern "C" int hc_refine_trajectories(int system, size_t T, int K, int C, const 
   std::vector<KpCam> cams(C);
   for (int c = 0; c < C; ++c) make_kp_cam(cam12 + 12 * c, dist5 ? dist5 + 5 * c : nullptr, cams[c]);
   std::vector<double> sw((size_t)C * TK), x(start, start + 3 * TK), d(3 * TK, nan), H(6 * TK, nan), G(3 * TK, nan), ia2(K), oc(cov ? 6 * TK : 0, nan), ol(out_lag9 ? 9 * (T - 1) * K : 0, nan);
-  for (int c = 0; c < C; ++c)
-    for (size_t i = 0; i < TK; ++i) {
-      const double w = weights ? weights[c * TK + i] : 1.0;
-      sw[c * TK + i] = w > 0.0 ? sqrt(w) * (1.0 / pixel_std[c]) : 0.0;
-    }
+  kp_weight_box(weights, pixel_std, C, T, K, 0, T, 0, K, sw.data());
   for (int k = 0; k < K; ++k) ia2[k] = 1.0 / (accel_std[k] * accel_std[k]);
   const TrData rd{T, uvs, sw.data(), x.data(), d.data(), H.data(), G.data(), ia2.data(), f_scale * f_scale, 1.0 / (f_scale * f_scale)};
   SmData td{T, nullptr, H.data(), nullptr, ia2.data(), d.data(), nullptr, nullptr, SM_LOSS_LINEAR, 1.0, 1.0, G.data()};
@@ -100,7 +96,7 @@ extern "C" int hc_refine_trajectories(int system, size_t T, int K, int C, const 
     double acc[3] = {0.0, 0.0, 0.0};
     for (size_t t = 0; t < T; ++t) traj_count_frame(rd, C, K, k, t, acc);
     n_usable[k] = (int)acc[0]; n_single[k] = (int)acc[1];
-    stat[k] = n_usable[k] < 2 ? TR_TOO_FEW_FRAMES : acc[2] != 0.0 ? TR_BAD_START : TR_OK;
+    stat[k] = traj_start_status(n_usable[k], acc[2] != 0.0);
     if (stat[k] == TR_OK) list.push_back(k);
   }
   const std::vector<int> ran = list;
@@ -220,6 +216,11 @@ extern "C" int hc_refine_trajectories(int system, size_t T, int K, int C, const 
   for (int i = 0; i < 8; ++i) info8[i] = 0.0;
   info8[0] = levels; info8[1] = segment; info8[2] = K; info8[3] = 1; info8[5] = most;
   return 0;
+}
+
+// the weight plane of the detection calls, one sub-box of it: kp_weight_box (mcba_keypoint_math.h) as the C calls use it
+extern "C" void hc_weight_box(const double* weights, const double* pixel_std, int C, size_t T, size_t K, size_t t0, size_t tc, size_t k0, size_t kc, double* out) {
+  kp_weight_box(weights, pixel_std, C, T, K, t0, tc, k0, kc, out);
 }
 
 // the chunk rule of the C call: out4 = tracks per chunk, chunks, device bytes, levels

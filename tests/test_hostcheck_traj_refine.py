@@ -25,6 +25,8 @@ def build(tmp_path_factory):
     h = ctypes.CDLL(lib)
     h.hc_refine_trajectories.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, V, V, V, V, V, V, V, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int] + [V] * 16
     h.hc_refine_chunks.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, V]
+    h.hc_weight_box.argtypes = [V, V, ctypes.c_int] + [ctypes.c_size_t] * 6 + [V]
+    h.hc_weight_box.restype = None
     return h
 
 
@@ -115,3 +117,26 @@ def check_chunk_rule(hc, T, segment):
                     assert tuple(int(v) for v in out4) == want, (K, C, budget, out4, want)
     a, b = tro.chunk_doubles(T, 1, 6, segment or 16), tro.chunk_doubles(T, 1, 7, segment or 16)
     assert b - a == 3 * T
+
+
+WEIGHT_BOXES = {"last track chunk": (0, 3, 3, 2), "frame chunk": (1, 2, 0, 5), "whole": (0, 3, 0, 5), "one element": (2, 1, 4, 1)}   # t0, tc, k0, kc
+
+
+@pytest.mark.parametrize("box", sorted(WEIGHT_BOXES))
+@pytest.mark.parametrize("weighted", [False, True])
+def test_weight_box_against_numpy_slicing(hc, box, weighted):
+    """kp_weight_box (mcba_keypoint_math.h), the one place the C calls form sqrt(w) / pixel_std: every sub-box they ask for -- a block of tracks
+    (the narrower last chunk of a chunking by two), a block of frames, everything, one element -- is the numpy slice of the whole plane, bit for
+    bit; a zero or NaN weight gives 0, no weights means w = 1"""
+    C, T, K = 2, 3, 5
+    t0, tc, k0, kc = WEIGHT_BOXES[box]
+    ps = np.array([0.7, 3.0])
+    w = None
+    if weighted:
+        w = np.resize(np.array([0.0, np.nan, 0.25, 4.0, 1.3, 0.6, 2.0]), (C, T, K))   # (30 of them: each value four times or more)
+    ww = np.ones((C, T, K)) if w is None else w
+    with np.errstate(invalid="ignore"):
+        want = np.where(ww > 0, np.sqrt(ww) * (1.0 / ps)[:, None, None], 0.0)[:, t0:t0 + tc, k0:k0 + kc]
+    out = np.full((C, tc, kc), 7.0)
+    hc.hc_weight_box(None if w is None else w.ctypes.data, ps.ctypes.data, C, T, K, t0, tc, k0, kc, out.ctypes.data)
+    assert np.array_equal(out, want)
